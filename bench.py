@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X batched MPC-QP hot path (MPC.py formulation + OSQP solve).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -18,13 +18,20 @@ synthetic (xref, fsteps) instances, inputs resident in HBM.  Ranks shard the
 instances (no data-path collective): value = instances solved by all ranks /
 max-over-ranks wall time of the K timed steps.
 
+A plain run does only what the headline needs: set-up, the W warm-up steps, the
+K timed steps, the result line.  --dump-outputs DIR also writes what the last
+timed step computed (DIR/<name>.npy, float64; the inputs are seeded, so two
+builds can be compared output for output).
+
 The headline runs OSQP as MPC.py configures it (--headline reference, the
 default: polish off, MPC.py:414-416), so "f_osqp" of the metric is that
-solver's output; on one GPU the line also carries a "companion" object with
-the engine's accuracy extension (polish=2: forces on the certified optimum x*)
-timed the same way, and "parity" reports each mode against both readings of
-f_osqp (the restated OSQP with MPC.py's settings, and x*) with which of them
-meets 1e-4.
+solver's output.  With --full the run goes on after the headline: a repeated
+launch (bitwise repeatability) and the host-buffer end-to-end path; on one GPU
+a "companion" object with the engine's accuracy extension (polish=2: forces on
+the certified optimum x*) and OSQP at adaptive-rho interval 25, timed the same
+way, the CPU baseline, and "parity", which reports each mode against both
+readings of f_osqp (the restated OSQP with MPC.py's settings, and x*) with
+which of them meets 1e-4.
 
 Workloads (BASELINE.json configs):
   c1            1 instance per GPU, N=16, static trot    -> latency of one tick
@@ -71,6 +78,14 @@ def parse():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run everything else the benchmark measures or checks: the "
+                         "repeated launch and the host-buffer end-to-end path, the companion and reference25 "
+                         "modes, the CPU baseline, the certificate and the restatement parity (--companion, "
+                         "--reference25, --cpu-sample, --certify, --restatement size them and apply only here)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last of them computed as DIR/<name>.npy (float64; "
+                         f"beyond {DUMP_LIMIT >> 20} MB in all a fixed seeded sample of the instances)")
     ap.add_argument("--batch", type=int, default=0, help="override instances per GPU")
     ap.add_argument("--headline", default="reference", choices=("reference", "accuracy"),
                     help="reference (default): OSQP as MPC.py configures it (eps 1e-7, every other setting at "
@@ -82,10 +97,10 @@ def parse():
     ap.add_argument("--no-polish", dest="headline", action="store_const", const="reference",
                     help="= --headline reference")
     ap.add_argument("--companion", type=int, default=1,
-                    help="1 (default, one GPU): after the headline, time the other mode on the same batch and "
+                    help="--full: 1 (default, one GPU): after the headline, time the other mode on the same batch and "
                          "report it in the line's 'companion' object; 0 = skip")
     ap.add_argument("--reference25", type=int, default=1,
-                    help="1 (default, one GPU, reference headline): also time OSQP at MPC.py's settings with "
+                    help="--full: 1 (default, one GPU, reference headline): also time OSQP at MPC.py's settings with "
                          "adaptive_rho_interval 25 (the timing-derived interval of a PROFILING osqp build on a fast "
                          "host) on the same batch, with its own parity against the restatement at 25; 0 = skip")
     ap.add_argument("--order-by-class", type=int, default=1,
@@ -103,14 +118,14 @@ def parse():
     ap.add_argument("--rho-interval", type=int, default=0,
                     help="override adaptive_rho_interval (0 = the library default)")
     ap.add_argument("--cpu-sample", type=float, default=1.5,
-                    help="seconds of CPU work per CPU-baseline run (3 warm-up + 10 timed runs, each over "
+                    help="--full: seconds of CPU work per CPU-baseline run (3 warm-up + 10 timed runs, each over "
                          "instances cycling through the rank-0 batch; 0 = skip)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = every CPU this process may use")
     ap.add_argument("--certify", type=int, default=1024,
-                    help="instances (the first ones of rank 0) whose forces are checked against the "
+                    help="--full: instances (the first ones of rank 0) whose forces are checked against the "
                          "KKT-certified optimum (-1 = all, 0 = skip)")
     ap.add_argument("--restatement", type=int, default=1024,
-                    help="instances (the first ones of rank 0) solved again by the oracle's restatement of "
+                    help="--full: instances (the first ones of rank 0) solved again by the oracle's restatement of "
                          "each mode, and at adaptive_rho_interval 25 and 100 for the OSQP band (0 = skip)")
     ap.add_argument("--gather", action="store_true", help="include an RCCL all-gather of f0 in the timed region")
     ap.add_argument("--seed", type=int, default=2)
@@ -122,6 +137,24 @@ def parse():
 
 
 AUTO_SLICE = 1000  # bench.py --slice -1 beyond 16 stages (C3: r06y / r06z)
+DUMP_LIMIT = 64 << 20  # --dump-outputs: bytes in all
+
+
+def dump_outputs(path, arrays, rank=0):
+    """--dump-outputs: each array of ``arrays`` (name -> one row per instance of this rank) as
+    DIR/<name>.npy in float64 (rank r > 0 of a multi-GPU run: <name>_rank<r>.npy).  Beyond
+    DUMP_LIMIT bytes in all, the same fixed seeded sample of the rows of every array, with
+    their indices in rows.npy."""
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    n = next(iter(arrays.values())).shape[0]
+    row = sum(a[0].size for a in arrays.values()) * 8 if n else 0
+    if n * row > DUMP_LIMIT:
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_LIMIT // (row + 8), replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + (f"_rank{rank}" if rank else "") + ".npy"), np.ascontiguousarray(a))
 
 
 def load_pmc(tag: str, src_sha: str | None = None, path: str | None = None) -> dict:
@@ -295,6 +328,8 @@ def main_plan(args):
 
     wall, ms = _timed(torch, dist, dev, coll, world, stream, step, args.steps, args.warmup)
     ok = int((d["status"] == 0).sum().item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {k: d[k].cpu().numpy() for k in ("xref", "fsteps", "status", "red")}, rank)
     if rank == 0:
         by = model.planner_bytes_per_instance(N) * per
         ach = by / (ms * 1e-3) / 1e9
@@ -358,6 +393,8 @@ def main_tick(args):
     plan_ms, solve_ms = eng.last_kernel_ms()
     st = sess.read(mpcq.SV_STATUS)
     it = sess.read(mpcq.SV_ITERS)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"f0": sess.read(mpcq.SV_F0), "status": st, "iters": it}, rank)
     if rank == 0:
         fl = model.flops(N, it, np.zeros_like(it)).sum()
         ach = fl / (solve_ms * 1e-3) / 1e12
@@ -487,6 +524,9 @@ def launch_or_check(args):
 
 def main():
     args = parse()
+    if not args.full:  # a plain run: the headline alone
+        args.companion = args.reference25 = args.certify = args.restatement = 0
+        args.cpu_sample = 0.0
     launch_or_check(args)
     if args.mode == "plan":
         return main_plan(args)
@@ -525,7 +565,8 @@ def main():
 
     def run_mode(mode, timed_steps, warmup, gather):
         """W untimed + K timed launches of one mode (barrier + synchronisation on both sides
-        of the timed region), then one more launch that also returns x and y."""
+        of the timed region); with --full then one more launch that also returns x and y,
+        and the host-buffer path."""
         over = dict(MODES[mode])
         if args.rho_interval > 0:
             over["adaptive_rho_interval"] = args.rho_interval
@@ -570,6 +611,9 @@ def main():
         r = dict(mode=mode, over=over, params=eng.params, wall=wall, launch_ms=launch_ms,
                  kern_ms=float(launch_ms.mean()), status=st_d.cpu().numpy(), iters=it_d.cpu().numpy(),
                  info=info_d.cpu().numpy(), f0=f0_d.cpu().numpy())
+        if not args.full:
+            eng.close()
+            return r
         # after the timed region: one more launch that also returns x and y (the certificate's
         # active-set seed), and the host-buffer end-to-end path
         x_d = torch.empty((per, 24 * N), dtype=torch.float64, device=dev)
@@ -590,6 +634,8 @@ def main():
         return r
 
     head = run_mode(args.headline, args.steps, args.warmup, args.gather)
+    if args.dump_outputs:  # the last timed step's results, as solve_device's caller receives them
+        dump_outputs(args.dump_outputs, {k: head[k] for k in ("f0", "status", "iters", "info")}, rank)
     wall_max = shard.max_over_ranks(dist, head["wall"], coll, world)
     kern_ms = head["kern_ms"]
     status, iters, info, f0 = head["status"], head["iters"], head["info"], head["f0"]
@@ -688,14 +734,15 @@ def main():
             "kernel_ms_per_launch": kern_ms,
             "kernel_ms_launches": {"median": float(np.median(launch_ms)), "min": float(launch_ms.min()),
                                    "max": float(launch_ms.max())},
-            "end_to_end_host_ms": head["e2e_ms"],
-            "end_to_end_host_value": per / (head["e2e_ms"] * 1e-3),
             "solved_fraction": float(allst[:, 0].sum() / allst[:, 1].sum()),
             "status_hist": hist_of(head),
             "iters": {"median": float(np.median(iters)), "p90": float(np.percentile(iters, 90)),
                       "max": int(iters.max()), "rho_updates_mean": float(info[:, 0].mean()),
                       "hist_edges_step": 250, "hist": hist.tolist()},
         }
+        if args.full:
+            out["end_to_end_host_ms"] = head["e2e_ms"]
+            out["end_to_end_host_value"] = per / (head["e2e_ms"] * 1e-3)
         if pol:
             out["polish"] = {"accepted_fraction": float((info[:, 1] == 1).mean()),
                              "rounds_mean": float(info[:, 2].mean()), "rounds_max": int(info[:, 2].max()),
@@ -732,7 +779,7 @@ def main():
         if world == 1 and (args.cpu_sample > 0 or args.certify != 0 or args.restatement > 0):
             from oracle import oracle as O
             O.build()
-        par = {"repeat_launch_bitwise_equal": head["same"] and (comp is None or comp["same"])}
+        par = {"repeat_launch_bitwise_equal": head["same"] and (comp is None or comp["same"])} if args.full else {}
         runs = {args.headline: head}
         if comp is not None:
             runs[other] = comp
@@ -826,7 +873,8 @@ def main():
             meets[name] = mm
         if any(meets.values()):
             par["meets_1e-4"] = meets
-        out["parity"] = par
+        if args.full:
+            out["parity"] = par
         print(json.dumps(out), flush=True)
 
     if _distributed(dist):
