@@ -6,6 +6,8 @@
     python tests/golden/gen_golden.py horizons_r3  # golden_horizons_r3.npz: N = 5, 6, 10, 13, 33,
                                                    # 36, 40, 57, 64
     python tests/golden/gen_golden.py horizons_r4  # golden_horizons_r4.npz: N = 49, 50
+    python tests/golden/gen_golden.py params       # golden_params.npz: formulation only, under
+                                                   # non-default mass / mu / gI / dt / footholds
 
 What it does, per instance:
 1. Inputs: seeded synthetic (xref, fsteps) from mpcq.synth (trot / bound /
@@ -91,11 +93,15 @@ def import_reference_mpc():
     return MPC
 
 
-def reference_qps(MPC, xref, fsteps, dt=0.02):
+def reference_qps(MPC, xref, fsteps, dt=0.02, attrs=None):
     """run(0) then run(1) as MPC_Wrapper.run_MPC_synchronous does; return the
-    setup-mode and update-mode QP data handed to osqp."""
+    setup-mode and update-mode QP data handed to osqp.  ``attrs``: attributes set
+    on the constructed object before the first run (mass, mu, gI, footholds)."""
     N = xref.shape[1] - 1
     mpc = MPC.MPC(dt, N, 0.32)
+    for k, v in (attrs or {}).items():
+        assert hasattr(mpc, k), k
+        setattr(mpc, k, v)
     mpc.run(0, xref.copy(), fsteps.copy())
     mpc.run(1, xref.copy(), fsteps.copy())
     calls = mpc.prob.calls
@@ -318,7 +324,52 @@ def main_horizons_r4():
     print("wrote", path, os.path.getsize(path), "bytes")
 
 
+# non-default formulation constants: the attributes MPC.py keeps on the object (mass, mu, gI,
+# footholds) and its constructor's dt.  gravity, fz_max and the weights are literals in the
+# reference, so no fixture can cover them.
+PARAMS_GI = np.array([[0.05, 0.004, -0.003], [0.002, 0.03, 0.001], [-0.001, 0.006, 0.08]])   # not symmetric
+PARAMS_FOOTHOLDS_SHIFT = np.array([[0.03, -0.02, 0.04, -0.01], [-0.02, 0.03, 0.01, -0.04], [0.0, 0.0, 0.0, 0.0]])
+PARAMS_SET = dict(mass=3.3, mu=0.55, gI=PARAMS_GI, dt=0.025, footholds=PARAMS_FOOTHOLDS_SHIFT)
+PARAMS_ENTRIES = (tuple(("all", N, tuple(PARAMS_SET)) for N in (5, 16, 20, 50))
+                  + tuple((k, 16, (k,)) for k in PARAMS_SET))
+
+
+def main_params():
+    """golden_params.npz: A.data / l / u of the unmodified reference in both modes under
+    non-default mass / mu / gI / dt / footholds, 3 synthetic instances (one per gait) per
+    entry.  Keys e<i>_<field>; the parameter values of each entry are stored with it (gI and
+    footholds row-major, as struct mpcq_params keeps them)."""
+    MPC = import_reference_mpc()
+    out = {}
+    for i, (name, N, which) in enumerate(PARAMS_ENTRIES):
+        b = synth.make_batch(3, N, gaits=synth.GAITS, seed=7000 + 10 * i + N)
+        default = MPC.MPC(0.02, N, 0.32)
+        dt = PARAMS_SET["dt"] if "dt" in which else default.dt
+        attrs = {k: PARAMS_SET[k] for k in which if k not in ("dt", "footholds")}
+        if "footholds" in which:
+            attrs["footholds"] = default.footholds + PARAMS_SET["footholds"]
+        qs = [reference_qps(MPC, b["xref"][j], b["fsteps"][j], dt=dt,
+                            attrs={k: np.array(v, copy=True) for k, v in attrs.items()}) for j in range(3)]
+        pre = f"e{i}_"
+        out[pre + "name"] = np.array(name)
+        out[pre + "N"] = np.array(N)
+        out[pre + "xref"] = b["xref"]
+        out[pre + "fsteps"] = b["fsteps"]
+        for k in ("Ax", "l", "u", "Ax_setup", "l_setup", "u_setup"):
+            out[pre + k] = np.array([q[k] for q in qs])
+        out[pre + "dt"] = np.array(float(dt))
+        for k in ("mass", "mu", "gI", "footholds"):
+            out[pre + k] = np.asarray(attrs.get(k, getattr(default, k)), np.float64).ravel().squeeze()
+        print(f"params entry {i}: {name} N={N}", flush=True)
+    path = os.path.join(HERE, "golden_params.npz")
+    np.savez_compressed(path, entries=np.array(len(PARAMS_ENTRIES)), **out)
+    print("wrote", path, os.path.getsize(path), "bytes")
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "params":
+        main_params()
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "horizons_r4":
         main_horizons_r4()
         return
