@@ -36,7 +36,11 @@ extern "C" {
 /* ABI changelog:
  *   2: eps_prim_inf / eps_dual_inf, dual_warm, infeasibility statuses
  *   3: info[b][3] = the ADMM's own exit status (before polish; was always 0),
- *      MPCQ_SV_ORDER added (MPCQ_SV_COUNT 16 -> 17), initialised to the identity */
+ *      MPCQ_SV_ORDER added (MPCQ_SV_COUNT 16 -> 17), initialised to the identity
+ *   3 (additions, no bump): mpcq_debug_class_table_slots / _read / _write, mpcq_debug_class_order,
+ *      mpcq_debug_class_learn, mpcq_debug_suspended_status, mpcq_debug_suspended,
+ *      mpcq_debug_session_order, mpcq_debug_last_dispatch (diagnostics);
+ *      MPCQ_SLICE16 in the environment no longer slices a library compiled without it */
 #define MPCQ_ABI_VERSION 3
 
 /* error codes (return values) */
@@ -338,6 +342,44 @@ int mpcq_session_device_ptr(mpcq_session* s, int what, void** out);
  * (compiled with -DMPCQ_STAMPS, libmpcq_stamps.so) fills with per-phase
  * s_memtime cycle counts of thread 0; ignored by the shipped build. */
 int mpcq_debug_set_stamps(mpcq_ctx* ctx, void* device_buffer);
+
+/* The dispatch-order layer on its own (no reference counterpart; tests/test_gpu_dispatch.py
+ * pins these kernels to a host model).  Every pointer is a host pointer, every call blocks,
+ * none launches the engine or adds work to a solve.
+ *
+ * The class table of MPCQ_FLAG_ORDER_BY_CLASS: mpcq_debug_class_table_slots() slots, per slot
+ * the sum of the iteration counts learned and their number (uint64 each).  A context that has
+ * not solved with the flag yet holds the all-zero table. */
+int mpcq_debug_class_table_slots(void);
+int mpcq_debug_class_table_read(mpcq_ctx* ctx, uint64_t* sum, uint64_t* cnt);
+int mpcq_debug_class_table_write(mpcq_ctx* ctx, const uint64_t* sum, const uint64_t* cnt);
+/* The class order of fsteps [B][20][13] on ctx's table as it stands: cls [B] = each instance's
+ * slot, order [B] = the dispatch order (what a solve with the flag would use now). */
+int mpcq_debug_class_order(mpcq_ctx* ctx, int64_t batch, const double* fsteps, int32_t* cls,
+                           int32_t* order);
+/* Adds iters [B] to the slots cls [B] of ctx's table (entries with iters <= 0 are not counted);
+ * a slot outside the table is MPCQ_E_INVALID. */
+int mpcq_debug_class_learn(mpcq_ctx* ctx, int64_t batch, const int32_t* cls, const int32_t* iters);
+/* The status value a sliced solve's first launch leaves on a suspended instance (internal:
+ * no caller of a solve ever sees it). */
+int mpcq_debug_suspended_status(void);
+/* The resumed launch's list: of prev [n] (NULL: 0..n-1; instance indices below n_inst, else
+ * MPCQ_E_INVALID) the instances whose status [n_inst] is the suspended one, the largest
+ * key [n_inst][2] (element 0) first in buckets of 1/8 octave, prev's order inside a bucket.
+ * list [n]: *count entries are written. */
+int mpcq_debug_suspended(mpcq_ctx* ctx, int64_t n, int64_t n_inst, const int32_t* prev,
+                         const int32_t* status, const double* key, int32_t* list, int32_t* count);
+/* The session's order of its next tick (MPCQ_SV_ORDER) from iters [B]. */
+int mpcq_debug_session_order(mpcq_ctx* ctx, int64_t batch, const int32_t* iters, int32_t* order);
+/* What the last mpcq_solve_batch / mpcq_qp_solve_batch of ctx dispatched by, read from the
+ * scratch the context keeps (so before the next solve).  Every output is optional (NULL).
+ * batch: its batch B (0: no solve yet); sliced: whether it ran as two launches; by_class:
+ * whether it used the class order; cls [B], order [B]: the slots and the first launch's order
+ * (by_class only; otherwise untouched); list [B], count: the resumed launch's instances, in its
+ * order (list[*count..B) = -1; sliced only, otherwise *count = 0); key [B][2]: element 0 of a
+ * listed instance is the key it was ranked by (sliced only; otherwise untouched). */
+int mpcq_debug_last_dispatch(mpcq_ctx* ctx, int64_t* batch, int32_t* sliced, int32_t* by_class,
+                             int32_t* cls, int32_t* order, int32_t* list, int32_t* count, double* key);
 
 #ifdef __cplusplus
 }

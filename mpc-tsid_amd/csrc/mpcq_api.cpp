@@ -31,9 +31,12 @@ struct mpcq_ctx {
   // per-instance scratch (class slot, dispatch order, iteration counts when the caller
   // passes none)
   uint64_t* cls_sum = nullptr;
-  uint32_t* cls_cnt = nullptr;
+  uint64_t* cls_cnt = nullptr;
   int32_t* ord_buf = nullptr;
   int64_t ord_cap = 0;
+  // what the last batch solve dispatched by (mpcq_debug_last_dispatch): host bookkeeping only
+  int64_t last_B = 0;
+  bool last_by_class = false, last_sliced = false;
   // sliced solves (mpcq_set_slice): the slice length (0: off), the suspended instances'
   // iterates (mpcq::res_lanes(N) x 8 doubles, rho, key, 4 counters each), the resumed launch's
   // dispatch list (B int32, of 3 B: two once held alternating lists) and a status scratch, the
@@ -153,16 +156,22 @@ int ensure_work(mpcq_ctx* c, int64_t B, double** out) {
 
 // MPCQ_FLAG_ORDER_BY_CLASS scratch: the class table (zeroed once, kept for the context's
 // life) and 3 B int32 (class slots, order, iteration counts)
-int ensure_order(mpcq_ctx* c, int64_t B) {
+int ensure_class_table(mpcq_ctx* c) {
   const int slots = mpcq::class_table_slots();
   if (!c->cls_sum) {
     void* tab = nullptr;
-    const size_t tb = (size_t)slots * (8 + 4);
+    const size_t tb = (size_t)slots * (8 + 8);
     if (hipMalloc(&tab, tb) != hipSuccess) return fail(MPCQ_E_NOMEM, "hipMalloc(%zu) for the class table failed", tb);
     c->cls_sum = (uint64_t*)tab;
-    c->cls_cnt = (uint32_t*)((char*)tab + (size_t)slots * 8);
+    c->cls_cnt = c->cls_sum + slots;
     HIP_TRY(hipMemsetAsync(tab, 0, tb, c->stream));
   }
+  return MPCQ_OK;
+}
+
+int ensure_order(mpcq_ctx* c, int64_t B) {
+  const int trc = ensure_class_table(c);
+  if (trc) return trc;
   if (B > c->ord_cap) {
     if (c->ord_buf) {
       HIP_TRY(hipStreamSynchronize(c->stream));
@@ -241,6 +250,12 @@ int ensure_slice(mpcq_ctx* c, int64_t B) {
     c->res_key = c->res_rho + B;
     c->res_i = (int32_t*)(c->res_key + 2 * B);
     c->sl_cap = B;
+    // no half-way sample yet (res_i[8 b + 4] = 0): an instance suspended before its first one
+    // -- a slice shorter than two segments -- then takes the key's fallback, not unwritten
+    // memory.  Zeroed here once; every call's launch_suspended clears what its first launch
+    // sampled, so each first launch starts without one.  (The other counters are written at
+    // suspension, before the resumed launch reads them.)
+    HIP_TRY(hipMemsetAsync(c->res_i, 0, (size_t)B * 32, c->stream));
   }
   return MPCQ_OK;
 }
@@ -519,7 +534,13 @@ static int solve_common(mpcq_ctx* c, int64_t B, bool fused, const double* xref, 
   // farthest from convergence (the iterations left, extrapolated from the residuals' decay)
   // first, and runs them to their end.  (Re-slicing the second launch too was slower: C3 39.0 k
   // against 44.1 k QP/s at 1200, profiles/r06r_*.)
-  const bool sliced = c->slice_iters > 0 && c->slice_iters < c->p.max_iter && (N > 16 || getenv("MPCQ_SLICE16"));
+  // Only where the engine unit of this horizon holds the suspend / resume code (slice_supported:
+  // beyond 16 stages, or a -DMPCQ_SLICE16 build): a unit without it ignores the count on the
+  // device and would take the resumed launch's unwritten list for instance indices.
+  const bool sliced = c->slice_iters > 0 && c->slice_iters < c->p.max_iter && mpcq::slice_supported(N);
+  c->last_B = B;
+  c->last_by_class = by_class;
+  c->last_sliced = sliced;
   if (sliced) {
     rc = ensure_slice(c, B);
     if (rc) return rc;
@@ -536,7 +557,7 @@ static int solve_common(mpcq_ctx* c, int64_t B, bool fused, const double* xref, 
     // (the resumed launch is sized for the whole batch and reads the count from the device:
     // workgroups past it return at once -- no host round trip, the call stays asynchronous)
     int32_t* list = c->sl_buf;
-    HIP_TRY(mpcq::launch_suspended(a.order, B, a.status, c->res_key, list, c->sl_count, c->stream));
+    HIP_TRY(mpcq::launch_suspended(a.order, B, a.status, c->res_key, list, c->sl_count, c->res_i, c->stream));
     mpcq::LaunchArgs r = a;
     r.order = list;
     r.batch_dev = c->sl_count;
@@ -975,6 +996,137 @@ int mpcq_session_device_ptr(mpcq_session* s, int what, void** out) {
 int mpcq_debug_set_stamps(mpcq_ctx* c, void* buf) {
   if (!c) return fail(MPCQ_E_INVALID, "ctx is NULL");
   c->stamps = (uint64_t*)buf;
+  return MPCQ_OK;
+}
+
+// The dispatch-order kernels on their own (include/mpcq.h "diagnostics"): host arrays staged
+// through the arena, one launch, blocking.  None touches the scratch of the last solve.
+
+int mpcq_debug_class_table_slots(void) { return mpcq::class_table_slots(); }
+
+int mpcq_debug_suspended_status(void) { return mpcq::kStatusSuspended; }
+
+int mpcq_debug_class_table_read(mpcq_ctx* c, uint64_t* sum, uint64_t* cnt) {
+  if (!c || !sum || !cnt) return fail(MPCQ_E_INVALID, "NULL argument");
+  DeviceGuard g(c->device);
+  int rc = ensure_class_table(c);
+  if (rc) return rc;
+  const size_t tb = (size_t)mpcq::class_table_slots() * 8;
+  HIP_TRY(hipMemcpyAsync(sum, c->cls_sum, tb, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(cnt, c->cls_cnt, tb, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return MPCQ_OK;
+}
+
+int mpcq_debug_class_table_write(mpcq_ctx* c, const uint64_t* sum, const uint64_t* cnt) {
+  if (!c || !sum || !cnt) return fail(MPCQ_E_INVALID, "NULL argument");
+  DeviceGuard g(c->device);
+  int rc = ensure_class_table(c);
+  if (rc) return rc;
+  const size_t tb = (size_t)mpcq::class_table_slots() * 8;
+  HIP_TRY(hipMemcpyAsync(c->cls_sum, sum, tb, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->cls_cnt, cnt, tb, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return MPCQ_OK;
+}
+
+int mpcq_debug_class_order(mpcq_ctx* c, int64_t B, const double* fsteps, int32_t* cls, int32_t* order) {
+  int rc = check_ctx(c, B);
+  if (rc) return rc;
+  if (B < 1 || !fsteps || !cls || !order) return fail(MPCQ_E_INVALID, "batch >= 1 and every array are required");
+  DeviceGuard g(c->device);
+  rc = ensure_class_table(c);
+  if (rc) return rc;
+  Xfer xs[3] = {{fsteps, nullptr, (size_t)B * 260 * 8, nullptr}, {nullptr, cls, (size_t)B * 4, nullptr},
+                {nullptr, order, (size_t)B * 4, nullptr}};
+  rc = stage(c, xs, 3);
+  if (rc) return rc;
+  HIP_TRY(mpcq::launch_class_order((const double*)xs[0].dev, B, (int32_t*)xs[1].dev, c->cls_sum, c->cls_cnt,
+                                   (int32_t*)xs[2].dev, c->stream));
+  return unstage(c, xs, 3);
+}
+
+int mpcq_debug_class_learn(mpcq_ctx* c, int64_t B, const int32_t* cls, const int32_t* iters) {
+  int rc = check_ctx(c, B);
+  if (rc) return rc;
+  if (B < 1 || !cls || !iters) return fail(MPCQ_E_INVALID, "batch >= 1 and every array are required");
+  const int slots = mpcq::class_table_slots();
+  for (int64_t i = 0; i < B; ++i)  // (the kernel indexes its LDS table by them)
+    if (cls[i] < 0 || cls[i] >= slots) return fail(MPCQ_E_INVALID, "cls[%lld] = %d is no slot", (long long)i, cls[i]);
+  DeviceGuard g(c->device);
+  rc = ensure_class_table(c);
+  if (rc) return rc;
+  Xfer xs[2] = {{cls, nullptr, (size_t)B * 4, nullptr}, {iters, nullptr, (size_t)B * 4, nullptr}};
+  rc = stage(c, xs, 2);
+  if (rc) return rc;
+  HIP_TRY(mpcq::launch_class_learn((const int32_t*)xs[0].dev, (const int32_t*)xs[1].dev, B, c->cls_sum, c->cls_cnt,
+                                   c->stream));
+  return unstage(c, xs, 2);
+}
+
+int mpcq_debug_suspended(mpcq_ctx* c, int64_t n, int64_t n_inst, const int32_t* prev, const int32_t* status,
+                         const double* key, int32_t* list, int32_t* count) {
+  int rc = check_ctx(c, n);
+  if (!rc) rc = check_ctx(c, n_inst);
+  if (rc) return rc;
+  if (n < 1 || !status || !key || !list || !count) return fail(MPCQ_E_INVALID, "n >= 1 and every array but prev are required");
+  if (!prev && n_inst < n) return fail(MPCQ_E_INVALID, "n_inst < n without prev");
+  if (prev)  // (the kernel indexes status and key by them)
+    for (int64_t i = 0; i < n; ++i)
+      if (prev[i] < 0 || prev[i] >= n_inst) return fail(MPCQ_E_INVALID, "prev[%lld] = %d is no instance", (long long)i, prev[i]);
+  DeviceGuard g(c->device);
+  Xfer xs[5] = {{prev, nullptr, (size_t)n * 4, nullptr},
+                {status, nullptr, (size_t)n_inst * 4, nullptr},
+                {key, nullptr, (size_t)n_inst * 16, nullptr},
+                {nullptr, list, (size_t)n * 4, nullptr},
+                {nullptr, count, 4, nullptr}};
+  rc = stage(c, xs, 5);
+  if (rc) return rc;
+  HIP_TRY(hipMemsetAsync(xs[3].dev, 0xff, (size_t)n * 4, c->stream));  // (entries past the count: -1)
+  HIP_TRY(mpcq::launch_suspended((const int32_t*)xs[0].dev, n, (const int32_t*)xs[1].dev, (const double*)xs[2].dev,
+                                 (int32_t*)xs[3].dev, (int32_t*)xs[4].dev, nullptr, c->stream));
+  return unstage(c, xs, 5);
+}
+
+int mpcq_debug_session_order(mpcq_ctx* c, int64_t B, const int32_t* iters, int32_t* order) {
+  int rc = check_ctx(c, B);
+  if (rc) return rc;
+  if (B < 1 || !iters || !order) return fail(MPCQ_E_INVALID, "batch >= 1 and every array are required");
+  DeviceGuard g(c->device);
+  Xfer xs[2] = {{iters, nullptr, (size_t)B * 4, nullptr}, {nullptr, order, (size_t)B * 4, nullptr}};
+  rc = stage(c, xs, 2);
+  if (rc) return rc;
+  HIP_TRY(mpcq::launch_order((const int32_t*)xs[0].dev, B, (int32_t*)xs[1].dev, c->stream));
+  return unstage(c, xs, 2);
+}
+
+int mpcq_debug_last_dispatch(mpcq_ctx* c, int64_t* batch, int32_t* sliced, int32_t* by_class, int32_t* cls,
+                             int32_t* order, int32_t* list, int32_t* count, double* key) {
+  if (!c) return fail(MPCQ_E_INVALID, "ctx is NULL");
+  DeviceGuard g(c->device);
+  const int64_t B = c->last_B;
+  if (batch) *batch = B;
+  if (sliced) *sliced = c->last_sliced;
+  if (by_class) *by_class = c->last_by_class;
+  if (count) *count = 0;
+  if (B < 1) return MPCQ_OK;
+  const hipMemcpyKind d2h = hipMemcpyDeviceToHost;
+  if (c->last_by_class) {  // (solve_common: ord_buf = the slots, then the order)
+    if (cls) HIP_TRY(hipMemcpyAsync(cls, c->ord_buf, (size_t)B * 4, d2h, c->stream));
+    if (order) HIP_TRY(hipMemcpyAsync(order, c->ord_buf + B, (size_t)B * 4, d2h, c->stream));
+  }
+  int32_t cnt = 0;
+  if (c->last_sliced) {
+    HIP_TRY(hipMemcpyAsync(&cnt, c->sl_count, 4, d2h, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (cnt < 0 || cnt > B) return fail(MPCQ_E_DEVICE, "the suspended count %d is outside 0..%lld", cnt, (long long)B);
+    if (list && cnt) HIP_TRY(hipMemcpyAsync(list, c->sl_buf, (size_t)cnt * 4, d2h, c->stream));
+    if (key) HIP_TRY(hipMemcpyAsync(key, c->res_key, (size_t)B * 16, d2h, c->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (list)
+    for (int64_t i = cnt; i < B; ++i) list[i] = -1;
+  if (count) *count = cnt;
   return MPCQ_OK;
 }
 

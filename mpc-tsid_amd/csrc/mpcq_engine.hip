@@ -3931,5 +3931,8 @@ hipError_t MPCQ_CAT(engine_launch_n, MPCQ_ENGINE_N)(bool fused, bool solve, cons
                                                    const LaunchArgs& a, hipStream_t s) {
   return launch_t<MPCQ_ENGINE_N>(fused, solve, p, a, s);
 }
+// whether this unit holds the sliced-solve code (mpcq_dispatch.cpp slice_supported: the host
+// slices a solve only where the engine can suspend and resume)
+bool MPCQ_CAT(engine_slice_n, MPCQ_ENGINE_N)() { return kSlice<MPCQ_ENGINE_N>; }
 
 }  // namespace mpcq

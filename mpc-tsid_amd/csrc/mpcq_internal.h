@@ -147,14 +147,16 @@ hipError_t launch_order(const int32_t* iters, int64_t batch, int32_t* order, hip
 // iteration counts to the table.
 int class_table_slots();
 hipError_t launch_class_order(const double* fsteps, int64_t batch, int32_t* cls, const uint64_t* sum,
-                              const uint32_t* cnt, int32_t* order, hipStream_t s);
+                              const uint64_t* cnt, int32_t* order, hipStream_t s);
 hipError_t launch_class_learn(const int32_t* cls, const int32_t* iters, int64_t batch, uint64_t* sum,
-                              uint32_t* cnt, hipStream_t s);
+                              uint64_t* cnt, hipStream_t s);
 // Sliced solves: list[*count] = the instances of prev[0..n) (null: 0..n-1) whose status is
 // kStatusSuspended, the largest key (key[2 id]: the iterations left, extrapolated) first, in
-// prev's order inside a key bucket (one workgroup; buckets of 1/8 octave).
+// prev's order inside a key bucket (one workgroup; buckets of 1/8 octave).  res_i (LaunchArgs::res_i
+// of the launch just ended, or null): the half-way sample's iteration of every instance of prev
+// is reset to 0 (none) for the next sliced call.
 hipError_t launch_suspended(const int32_t* prev, int64_t n, const int32_t* status, const double* key,
-                            int32_t* list, int32_t* count, hipStream_t s);
+                            int32_t* list, int32_t* count, int32_t* res_i, hipStream_t s);
 
 // Launchers (mpcq_engine.hip).  Return hipError_t.
 hipError_t launch_formulate(int N, const mpcq_params& p, const LaunchArgs& a, hipStream_t s);
@@ -166,6 +168,8 @@ hipError_t launch_solve(int N, bool fused, const mpcq_params& p, const LaunchArg
   X(41) X(42) X(43) X(44) X(45) X(46) X(47) X(48) X(49) X(50) X(51) X(52) X(53) X(54) X(55) X(56) X(57) X(58)  \
   X(59) X(60) X(61) X(62) X(63) X(64)
 bool horizon_supported(int N);
+// whether horizon N's engine unit was compiled with the sliced-solve code (its kSlice<N>)
+bool slice_supported(int N);
 int supported_horizons(int32_t* out, int cap);
 
 }  // namespace mpcq

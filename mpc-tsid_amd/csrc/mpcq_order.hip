@@ -56,7 +56,7 @@ __global__ __launch_bounds__(256) void class_kernel(const double* __restrict__ f
 
 __global__ __launch_bounds__(1024) void class_order_kernel(const int32_t* __restrict__ cls, int64_t B,
                                                            const unsigned long long* __restrict__ sum,
-                                                           const unsigned* __restrict__ cnt,
+                                                           const unsigned long long* __restrict__ cnt,
                                                            int32_t* __restrict__ order) {
   __shared__ int cost[kSlots];          // bucket of each slot
   __shared__ int base[kBuckets];        // next free position of each bucket
@@ -137,8 +137,10 @@ __global__ __launch_bounds__(1024) void class_order_kernel(const int32_t* __rest
 __global__ __launch_bounds__(256) void class_learn_kernel(const int32_t* __restrict__ cls,
                                                           const int32_t* __restrict__ iters, int64_t B,
                                                           unsigned long long* __restrict__ sum,
-                                                          unsigned* __restrict__ cnt) {
+                                                          unsigned long long* __restrict__ cnt) {
   // a batch holds few classes: sum in LDS per block, then one global atomic per class and block
+  // (the table's count is 64 bits wide: a 32-bit one wraps within hours on a busy context, and
+  // sum / cnt then pins the class to the last bucket)
   __shared__ unsigned long long bs[kSlots];
   __shared__ unsigned bn[kSlots];
   const int t = threadIdx.x;
@@ -156,7 +158,7 @@ __global__ __launch_bounds__(256) void class_learn_kernel(const int32_t* __restr
   for (int q = t; q < kSlots; q += blockDim.x)
     if (bn[q]) {
       atomicAdd(&sum[q], bs[q]);
-      atomicAdd(&cnt[q], bn[q]);
+      atomicAdd(&cnt[q], (unsigned long long)bn[q]);
     }
 }
 
@@ -165,7 +167,11 @@ __global__ __launch_bounds__(256) void class_learn_kernel(const int32_t* __restr
 // second half of the slice (Spearman +0.995 with the final iteration count over C3's instances
 // suspended at 1200 iterations, tools/resume_predictors.py) -- in buckets of 1/8 octave, the last
 // launch's order inside a bucket: a stable counting sort in one workgroup (the class order's
-// scheme)
+// scheme).  The key is formed at suspension from the half-way residual sample of the launch just
+// ended (res_i[8 b + 4]: its iteration); this kernel, which runs after every sliced first launch
+// over the whole batch, clears the samples (`sample`, null: none to clear) so that the next
+// call's first launch starts without one: an instance suspended before its first sample then
+// takes the key's fallback, not an earlier call's sample.
 __device__ __forceinline__ int key_bucket(double v) {
   if (!(v > 0.0)) return 0;
   const double e = floor(8.0 * log2(v)) + 128.0;  // (1/8 octave; keys from 2^-16 to 2^16)
@@ -175,7 +181,8 @@ __device__ __forceinline__ int key_bucket(double v) {
 __global__ __launch_bounds__(1024) void suspended_kernel(const int32_t* __restrict__ prev, int64_t n,
                                                          const int32_t* __restrict__ status,
                                                          const double* __restrict__ key,
-                                                         int32_t* __restrict__ list, int32_t* __restrict__ count) {
+                                                         int32_t* __restrict__ list, int32_t* __restrict__ count,
+                                                         int32_t* __restrict__ sample) {
   __shared__ int base[kBuckets];
   __shared__ int wcnt[kWaves][kBuckets];
   const int t = threadIdx.x, w = t >> 6, lane = t & 63;
@@ -184,6 +191,7 @@ __global__ __launch_bounds__(1024) void suspended_kernel(const int32_t* __restri
   __syncthreads();
   for (int64_t i = t; i < n; i += blockDim.x) {
     const int32_t id = prev ? prev[i] : (int32_t)i;
+    if (sample) sample[8 * (int64_t)id + 4] = 0;
     if (status[id] == kStatusSuspended) atomicAdd(&base[key_bucket(key[2 * id])], 1);
   }
   __syncthreads();
@@ -249,27 +257,27 @@ __global__ __launch_bounds__(1024) void suspended_kernel(const int32_t* __restri
 int class_table_slots() { return kSlots; }
 
 hipError_t launch_suspended(const int32_t* prev, int64_t n, const int32_t* status, const double* key,
-                            int32_t* list, int32_t* count, hipStream_t s) {
+                            int32_t* list, int32_t* count, int32_t* res_i, hipStream_t s) {
   if (n <= 0 || n > INT32_MAX) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(suspended_kernel, dim3(1), dim3(1024), 0, s, prev, n, status, key, list, count);
+  hipLaunchKernelGGL(suspended_kernel, dim3(1), dim3(1024), 0, s, prev, n, status, key, list, count, res_i);
   return hipGetLastError();
 }
 
 hipError_t launch_class_order(const double* fsteps, int64_t B, int32_t* cls, const uint64_t* sum,
-                              const uint32_t* cnt, int32_t* order, hipStream_t s) {
+                              const uint64_t* cnt, int32_t* order, hipStream_t s) {
   if (B <= 0) return hipSuccess;
   if (B > INT32_MAX) return hipErrorInvalidValue;
   hipLaunchKernelGGL(class_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, fsteps, B, cls);
   hipLaunchKernelGGL(class_order_kernel, dim3(1), dim3(1024), 0, s, (const int32_t*)cls, B,
-                     (const unsigned long long*)sum, (const unsigned*)cnt, order);
+                     (const unsigned long long*)sum, (const unsigned long long*)cnt, order);
   return hipGetLastError();
 }
 
-hipError_t launch_class_learn(const int32_t* cls, const int32_t* iters, int64_t B, uint64_t* sum, uint32_t* cnt,
+hipError_t launch_class_learn(const int32_t* cls, const int32_t* iters, int64_t B, uint64_t* sum, uint64_t* cnt,
                               hipStream_t s) {
   if (B <= 0) return hipSuccess;
   hipLaunchKernelGGL(class_learn_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, cls, iters, B,
-                     (unsigned long long*)sum, (unsigned*)cnt);
+                     (unsigned long long*)sum, (unsigned long long*)cnt);
   return hipGetLastError();
 }
 

@@ -67,7 +67,10 @@ EXPORTS = ("mpcq_abi_version", "mpcq_default_params", "mpcq_dims", "mpcq_pattern
            "mpcq_qp_solve_batch", "mpcq_solve_batch", "mpcq_default_planner_params",
            "mpcq_plan_batch", "mpcq_session_create", "mpcq_session_destroy", "mpcq_session_tick",
            "mpcq_session_read", "mpcq_session_write", "mpcq_session_device_ptr", "mpcq_debug_set_stamps",
-           "mpcq_build_info")
+           "mpcq_build_info",
+           "mpcq_debug_class_table_slots", "mpcq_debug_class_table_read", "mpcq_debug_class_table_write",
+           "mpcq_debug_class_order", "mpcq_debug_class_learn", "mpcq_debug_suspended_status",
+           "mpcq_debug_suspended", "mpcq_debug_session_order", "mpcq_debug_last_dispatch")
 
 
 class MpcqError(RuntimeError):
@@ -211,6 +214,19 @@ def lib():
     L.mpcq_session_write.argtypes = [vp, C.c_int, vp, C.c_uint32]
     L.mpcq_session_device_ptr.argtypes = [vp, C.c_int, C.POINTER(vp)]
     L.mpcq_plan_batch.argtypes = [vp, C.POINTER(PlannerParams), C.c_int64, C.c_uint32, C.c_int] + [vp] * 12 + [C.c_uint32]
+    L.mpcq_debug_class_table_slots.restype = C.c_int
+    L.mpcq_debug_suspended_status.restype = C.c_int
+    L.mpcq_debug_class_table_read.argtypes = [vp, vp, vp]
+    L.mpcq_debug_class_table_write.argtypes = [vp, vp, vp]
+    L.mpcq_debug_class_order.argtypes = [vp, C.c_int64, vp, vp, vp]
+    L.mpcq_debug_class_learn.argtypes = [vp, C.c_int64, vp, vp]
+    L.mpcq_debug_suspended.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp]
+    L.mpcq_debug_session_order.argtypes = [vp, C.c_int64, vp, vp]
+    L.mpcq_debug_last_dispatch.argtypes = [vp, C.POINTER(C.c_int64), ip, ip, vp, vp, vp, ip, vp]
+    for name in ("mpcq_debug_class_table_read", "mpcq_debug_class_table_write", "mpcq_debug_class_order",
+                 "mpcq_debug_class_learn", "mpcq_debug_suspended", "mpcq_debug_session_order",
+                 "mpcq_debug_last_dispatch"):
+        getattr(L, name).restype = C.c_int
     for name in ("mpcq_dims", "mpcq_pattern", "mpcq_supported_horizons", "mpcq_create",
                  "mpcq_destroy", "mpcq_set_stream", "mpcq_set_slice", "mpcq_last_kernel_ms", "mpcq_formulate_batch",
                  "mpcq_qp_solve_batch", "mpcq_solve_batch", "mpcq_default_planner_params",

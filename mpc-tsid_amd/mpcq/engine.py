@@ -221,6 +221,84 @@ class Engine:
                                          v(warm_y_ptr), None, v(f0_ptr), v(x_ptr), v(y_ptr), None, v(status_ptr),
                                          v(iters_ptr), v(info_ptr), flags)
 
+    # ------------------------------------------------------------------ diagnostics
+    # The dispatch-order kernels on their own (mpcq_debug_*, include/mpcq.h): no engine launch.
+    @staticmethod
+    def class_table_slots() -> int:
+        return L.lib().mpcq_debug_class_table_slots()
+
+    @staticmethod
+    def suspended_status() -> int:
+        return L.lib().mpcq_debug_suspended_status()
+
+    def class_table(self):
+        """(sum, cnt): this engine's class table, uint64 per slot."""
+        k = self.class_table_slots()
+        s, n = np.empty(k, np.uint64), np.empty(k, np.uint64)
+        self._call("mpcq_debug_class_table_read", self._h, _p(s), _p(n))
+        return s, n
+
+    def set_class_table(self, sum, cnt):  # noqa: A002
+        k = self.class_table_slots()
+        s = np.ascontiguousarray(sum, dtype=np.uint64)
+        n = np.ascontiguousarray(cnt, dtype=np.uint64)
+        if s.shape != (k,) or n.shape != (k,):
+            raise ValueError(f"the class table has {k} slots")
+        self._call("mpcq_debug_class_table_write", self._h, _p(s), _p(n))
+
+    def class_order(self, fsteps):
+        """(cls, order) of fsteps (B,20,13) on the table as it stands."""
+        fsteps = np.ascontiguousarray(fsteps, dtype=np.float64)
+        B = fsteps.shape[0]
+        if fsteps.shape != (B, 20, 13):
+            raise ValueError(f"fsteps must be (B,20,13); got {fsteps.shape}")
+        cls, order = np.empty(B, np.int32), np.empty(B, np.int32)
+        self._call("mpcq_debug_class_order", self._h, B, _p(fsteps), _p(cls), _p(order))
+        return cls, order
+
+    def class_learn(self, cls, iters):
+        cls = np.ascontiguousarray(cls, dtype=np.int32)
+        iters = np.ascontiguousarray(iters, dtype=np.int32)
+        if cls.ndim != 1 or cls.shape != iters.shape:
+            raise ValueError("cls and iters must be 1-d arrays of one length")
+        self._call("mpcq_debug_class_learn", self._h, cls.shape[0], _p(cls), _p(iters))
+
+    def suspended_list(self, prev, n: int, status, key):
+        """(list[:count], count): the resumed launch's list from prev (n,) or None, status (M,)
+        and key (M,2)."""
+        prev = None if prev is None else np.ascontiguousarray(prev, dtype=np.int32)
+        status = np.ascontiguousarray(status, dtype=np.int32)
+        key = np.ascontiguousarray(key, dtype=np.float64)
+        M = status.shape[0]
+        if key.shape != (M, 2) or (prev is not None and prev.shape != (n,)):
+            raise ValueError("status (M,), key (M,2), prev (n,) or None")
+        lst = np.empty(n, np.int32)
+        cnt = C.c_int32()
+        self._call("mpcq_debug_suspended", self._h, int(n), M, _p(prev), _p(status), _p(key), _p(lst), C.byref(cnt))
+        return lst[:cnt.value], cnt.value
+
+    def session_order(self, iters):
+        iters = np.ascontiguousarray(iters, dtype=np.int32)
+        order = np.empty(iters.shape[0], np.int32)
+        self._call("mpcq_debug_session_order", self._h, iters.shape[0], _p(iters), _p(order))
+        return order
+
+    def last_dispatch(self):
+        """What the last solve / qp_solve dispatched by: dict(batch, sliced, by_class, cls, order
+        (None unless by_class), list (the resumed launch's instances in its order; empty unless
+        sliced), count, key (B,2), None unless sliced)."""
+        B = C.c_int64()
+        self._call("mpcq_debug_last_dispatch", self._h, C.byref(B), None, None, None, None, None, None, None)
+        B = B.value
+        sl, bc, cnt = C.c_int32(), C.c_int32(), C.c_int32()
+        cls, order, lst = np.empty(B, np.int32), np.empty(B, np.int32), np.empty(B, np.int32)
+        key = np.empty((B, 2))
+        self._call("mpcq_debug_last_dispatch", self._h, None, C.byref(sl), C.byref(bc), _p(cls), _p(order),
+                   _p(lst), C.byref(cnt), _p(key))
+        return dict(batch=B, sliced=bool(sl.value), by_class=bool(bc.value),
+                    cls=cls if bc.value else None, order=order if bc.value else None,
+                    list=lst[:cnt.value].copy(), count=cnt.value, key=key if sl.value else None)
+
     def last_kernel_ms(self):
         f = C.c_double()
         s = C.c_double()
