@@ -40,7 +40,10 @@ extern "C" {
  *   3 (additions, no bump): mpcq_debug_class_table_slots / _read / _write, mpcq_debug_class_order,
  *      mpcq_debug_class_learn, mpcq_debug_suspended_status, mpcq_debug_suspended,
  *      mpcq_debug_session_order, mpcq_debug_last_dispatch (diagnostics);
- *      MPCQ_SLICE16 in the environment no longer slices a library compiled without it */
+ *      MPCQ_SLICE16 in the environment no longer slices a library compiled without it
+ *   3 (additions, no bump): mpcq_default_swing_params, mpcq_swing_step_batch, mpcq_swing_batch,
+ *      mpcq_session_enable_swing; MPCQ_SV_SWING_REF / _SWING_STATE / _FRAME (MPCQ_SV_COUNT
+ *      17 -> 20; MPCQ_E_INVALID on a session that has not enabled swing) */
 #define MPCQ_ABI_VERSION 3
 
 /* error codes (return values) */
@@ -326,7 +329,12 @@ int mpcq_session_tick(mpcq_session* s, int k, const double* state, const double*
 #define MPCQ_SV_ORDER 16    /* [B] int32: the next tick's dispatch order (read-only: a permutation of
                                0..B-1, longest previous solve first, buckets of 16 iterations; the
                                identity until the first tick) */
-#define MPCQ_SV_COUNT 17
+/* Only on a session with mpcq_session_enable_swing (otherwise MPCQ_E_INVALID): */
+#define MPCQ_SV_SWING_REF 17   /* [B][k_mpc][4][9] the tick's swing-foot references (read-only) */
+#define MPCQ_SV_SWING_STATE 18 /* [B][4][MPCQ_SWING_STATE] the foot trajectory generators */
+#define MPCQ_SV_FRAME 19    /* [B][3] x, y, yaw of MPCQ_SV_Q_W as they stood before this tick's
+                               update: the frame of the tick's fsteps (read-only) */
+#define MPCQ_SV_COUNT 20
 /* Copy array `what` to dst (host, or device with MPCQ_FLAG_DEVICE_PTRS); blocking. */
 int mpcq_session_read(mpcq_session* s, int what, void* dst, uint32_t flags);
 /* Overwrite array `what` from src (host, or device with MPCQ_FLAG_DEVICE_PTRS); blocking.
@@ -336,6 +344,71 @@ int mpcq_session_write(mpcq_session* s, int what, const void* src, uint32_t flag
  * MPCQ_SV_ORDER as its workgroup -> robot map: writing through its device address is not
  * allowed (a non-permutation would solve some robots twice and others not at all). */
 int mpcq_session_device_ptr(mpcq_session* s, int what, void** out);
+
+/* ---- swing-foot trajectories ----------------------------------------------
+ * The consumer of (gait, fsteps) between two MPC ticks: the position, velocity and
+ * acceleration references of the swing feet that the reference's whole-body controller
+ * derives every dt (update_feet_tasks / update_footsteps,
+ * TSID_Debug_controller_four_legs_fb_vel.py:247-327, 471-487) with
+ * Foot_trajectory_generator.get_next_foot (FootTrajectoryGenerator.py:184-380): a 5th-order
+ * polynomial in x and y, a 6th-order one in z, re-targeted every step until t_lock before
+ * touchdown.  pinocchio and the TSID solver stay out of scope. */
+typedef struct mpcq_swing_params {
+  double dt;          /* 0.001  TSID:107 */
+  double max_height;  /* 0.05   TSID:96  */
+  double t_lock;      /* 0.05   TSID:97  */
+  double feet_z;      /* 0.0    Interface.py:91 */
+  int32_t k_mpc;      /* 20     main.py:21 */
+  int32_t reserved[7];
+} mpcq_swing_params;
+void mpcq_default_swing_params(mpcq_swing_params* sp);
+/* doubles per foot; a generator's state is [B][4][MPCQ_SWING_STATE], all-zero = a new generator:
+ *   0..23  lastCoeffs in the reference's order (cx5..cx0, dx5..dx0, cy5..cy0, dy5..dy0,
+ *          FootTrajectoryGenerator.py:308-309)
+ *   24,25  x1, y1         26..31  mgoals (x, dx, ddx, y, dy, ddy)
+ *   32     t_swing         33      the last t0
+ *   34     the last mode (1 adaptive, 0 locked)
+ *   35,36  the foot's last world x, y            37..39  zero */
+#define MPCQ_SWING_STATE 40
+
+/* One get_next_foot(x0, dx0, ddx0, y0, dy0, ddy0, x1, y1, t0, t1, dt) per (robot, foot).
+ *   in    [B][4][10]  the ten arguments above (dt from sp)
+ *   state [B][4][MPCQ_SWING_STATE] in/out (slots 0..25 and 34 are used)
+ *   out   [B][4][11]  the reference's return list: x0, dx0, ddx0, y0, dy0, ddy0, z0, dz0,
+ *                     ddz0, gx1, gy1
+ * A foot whose t0 is NaN is skipped: its outputs are NaN and its state is untouched. */
+int mpcq_swing_step_batch(mpcq_ctx* ctx, const mpcq_swing_params* sp, int64_t batch,
+                          const double* in, double* state, double* out, uint32_t flags);
+
+/* Substeps k_sub0 .. k_sub0 + n_sub - 1 (k_loop % k_mpc in the reference) of
+ * update_footsteps + update_feet_tasks for a batch.
+ *   gait    [B][20][5], fsteps [B][20][13]   the tick's tables
+ *   frame   [B][3]  x, y, yaw of the local frame in the world (the reference's oMl), held
+ *                   for the whole call.  The reference moves oMl every substep: a call with
+ *                   n_sub = 1 reproduces that exactly; a call over a whole tick holds the
+ *                   frame, which is exact for the session's virtual robot.
+ *   feet0   [B][4][6] or NULL: the measured foot (x, dx, ddx, y, dy, ddy, world frame) a
+ *                   swing starts from at lift-off (t0 == 0, TSID:290-295).  NULL: the
+ *                   foot's last world position kept in the state, at rest (the virtual
+ *                   robot's rule; no reference counterpart).
+ *   state   [B][4][MPCQ_SWING_STATE] in/out
+ *   ref     [B][n_sub][4][9] out: pos xyz, vel xyz, acc xyz (feet_z added to z); NaN for a
+ *                   stance foot (no tracking task, TSID:524-549)
+ *   t0_out  [B][n_sub][4] out, optional; NaN for stance feet
+ *   status  [B] out, optional: 0, or MPCQ_STATUS_BAD_GAIT for a robot with a swing foot that
+ *                   has no stance row in its gait column (the reference raises IndexError);
+ *                   its state is left unchanged and its outputs are NaN.
+ * k_sub0 < 0, n_sub < 1, k_sub0 + n_sub > k_mpc or a NULL required pointer: MPCQ_E_INVALID. */
+int mpcq_swing_batch(mpcq_ctx* ctx, const mpcq_swing_params* sp, int64_t batch, int k_sub0,
+                     int n_sub, const double* gait, const double* fsteps, const double* frame,
+                     const double* feet0, double* state, double* ref, double* t0_out,
+                     int32_t* status, uint32_t flags);
+
+/* Opt-in (sp NULL = mpcq_default_swing_params): every later mpcq_session_tick appends one
+ * swing launch after its last launch, over substeps 0..k_mpc-1 of the tick's resident gait /
+ * fsteps with feet0 = NULL and the frame MPCQ_SV_FRAME.  A session that never calls it
+ * launches exactly what it did before. */
+int mpcq_session_enable_swing(mpcq_session* s, const mpcq_swing_params* sp);
 
 /* ---- diagnostics -----------------------------------------------------------
  * Device buffer [B][16] (uint64) that a diagnostic build of the library

@@ -670,6 +670,97 @@ int mpcq_plan_batch(mpcq_ctx* c, const mpcq_planner_params* pp, int64_t B, uint3
   return MPCQ_OK;
 }
 
+// Swing-foot constants (TSID_Debug_controller_four_legs_fb_vel.py:96-97, 107; Interface.py:91;
+// main.py:21).
+void mpcq_default_swing_params(mpcq_swing_params* sp) {
+  if (!sp) return;
+  memset(sp, 0, sizeof(*sp));
+  sp->dt = 0.001;
+  sp->max_height = 0.05;
+  sp->t_lock = 0.05;
+  sp->feet_z = 0.0;
+  sp->k_mpc = 20;
+}
+
+static int swing_params(const mpcq_swing_params* sp, mpcq_swing_params* out) {
+  if (sp) *out = *sp;
+  else mpcq_default_swing_params(out);
+  if (!(out->dt > 0) || out->k_mpc < 1 || !(out->t_lock >= 0))
+    return fail(MPCQ_E_INVALID, "swing needs dt > 0, k_mpc >= 1, t_lock >= 0");
+  return MPCQ_OK;
+}
+
+int mpcq_swing_step_batch(mpcq_ctx* c, const mpcq_swing_params* sp, int64_t B, const double* in, double* state,
+                          double* out, uint32_t flags) {
+  int rc = check_ctx(c, B);
+  if (rc) return rc;
+  if (!in || !state || !out) return fail(MPCQ_E_INVALID, "in, state and out are required");
+  mpcq_swing_params P;
+  rc = swing_params(sp, &P);
+  if (rc) return rc;
+  if (B == 0) return MPCQ_OK;
+  DeviceGuard g(c->device);
+  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
+  enum { IN, ST, OUT, NX };
+  Xfer xs[NX] = {{in, nullptr, (size_t)B * 40 * 8, nullptr},
+                 {state, state, (size_t)B * 4 * MPCQ_SWING_STATE * 8, nullptr},
+                 {nullptr, out, (size_t)B * 44 * 8, nullptr}};
+  if (!dev) {
+    rc = stage(c, xs, NX);
+    if (rc) return rc;
+    HIP_TRY(mpcq::launch_swing_step(P, B, (const double*)xs[IN].dev, (double*)xs[ST].dev, (double*)xs[OUT].dev,
+                                    c->stream));
+    return unstage(c, xs, NX);
+  }
+  HIP_TRY(mpcq::launch_swing_step(P, B, in, state, out, c->stream));
+  if (!(flags & MPCQ_FLAG_ASYNC)) HIP_TRY(hipStreamSynchronize(c->stream));
+  return MPCQ_OK;
+}
+
+int mpcq_swing_batch(mpcq_ctx* c, const mpcq_swing_params* sp, int64_t B, int k_sub0, int n_sub,
+                     const double* gait, const double* fsteps, const double* frame, const double* feet0,
+                     double* state, double* ref, double* t0_out, int32_t* status, uint32_t flags) {
+  int rc = check_ctx(c, B);
+  if (rc) return rc;
+  if (!gait || !fsteps || !frame || !state || !ref)
+    return fail(MPCQ_E_INVALID, "gait, fsteps, frame, state and ref are required");
+  mpcq_swing_params P;
+  rc = swing_params(sp, &P);
+  if (rc) return rc;
+  if (k_sub0 < 0 || n_sub < 1 || (int64_t)k_sub0 + n_sub > P.k_mpc)
+    return fail(MPCQ_E_INVALID, "need 0 <= k_sub0, 1 <= n_sub, k_sub0 + n_sub <= k_mpc (%d)", P.k_mpc);
+  if (B == 0) return MPCQ_OK;
+  DeviceGuard g(c->device);
+  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
+  mpcq::SwingArgs a{};
+  a.batch = B;
+  a.k_sub0 = k_sub0;
+  a.n_sub = n_sub;
+  enum { GA, FS, FR, F0, ST, RF, T0, SS, NX };
+  Xfer xs[NX] = {{gait, nullptr, (size_t)B * 800, nullptr},
+                 {fsteps, nullptr, (size_t)B * 260 * 8, nullptr},
+                 {frame, nullptr, (size_t)B * 24, nullptr},
+                 {feet0, nullptr, (size_t)B * 24 * 8, nullptr},
+                 {state, state, (size_t)B * 4 * MPCQ_SWING_STATE * 8, nullptr},
+                 {nullptr, ref, (size_t)B * n_sub * 36 * 8, nullptr},
+                 {nullptr, t0_out, (size_t)B * n_sub * 4 * 8, nullptr},
+                 {nullptr, status, (size_t)B * 4, nullptr}};
+  if (!dev) {
+    rc = stage(c, xs, NX);
+    if (rc) return rc;
+    a.gait = (const double*)xs[GA].dev; a.fsteps = (const double*)xs[FS].dev; a.frame = (const double*)xs[FR].dev;
+    a.feet0 = (const double*)xs[F0].dev; a.state = (double*)xs[ST].dev; a.ref = (double*)xs[RF].dev;
+    a.t0_out = (double*)xs[T0].dev; a.status = (int32_t*)xs[SS].dev;
+  } else {
+    a.gait = gait; a.fsteps = fsteps; a.frame = frame; a.feet0 = feet0; a.state = state; a.ref = ref;
+    a.t0_out = t0_out; a.status = status;
+  }
+  HIP_TRY(mpcq::launch_swing(P, a, c->stream));
+  if (!dev) return unstage(c, xs, NX);
+  if (!(flags & MPCQ_FLAG_ASYNC)) HIP_TRY(hipStreamSynchronize(c->stream));
+  return MPCQ_OK;
+}
+
 // ---------------------------------------------------------------------------
 // Closed-loop session: per-robot state resident in HBM (include/mpcq.h).
 
@@ -692,6 +783,10 @@ struct mpcq_session {
   int32_t* order = nullptr;  // dispatch order of the next solve (longest previous first)
   bool have_order = false;
   bool use_order = true;  // MPCQ_DISPATCH_ORDER=0 turns it off (A/B timing only; results are identical)
+  // mpcq_session_enable_swing: the swing arrays (an allocation of their own) and parameters
+  bool swing = false;
+  mpcq_swing_params sp{};
+  void* swing_mem = nullptr;
 };
 
 namespace {
@@ -756,7 +851,8 @@ int mpcq_session_create(mpcq_ctx* c, int64_t B, const mpcq_planner_params* pp, c
     return fail(MPCQ_E_DEVICE, "hipMemset of the session failed");
   }
   char* base = (char*)s->mem;
-  for (int w = 0; w < MPCQ_SV_COUNT; ++w) s->arr[w] = base + off[w];
+  // (the swing arrays exist from mpcq_session_enable_swing on)
+  for (int w = 0; w < MPCQ_SV_COUNT; ++w) s->arr[w] = s->bytes[w] ? base + off[w] : nullptr;
   s->warm_x = (double*)(base + o_wx);
   s->plan_status = (int32_t*)(base + o_ps);
   s->info = (int32_t*)(base + o_in);
@@ -845,8 +941,39 @@ int mpcq_session_destroy(mpcq_session* s) {
     DeviceGuard g(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);
     (void)hipFree(s->mem);
+    if (s->swing_mem) (void)hipFree(s->swing_mem);
   }
   delete s;
+  return MPCQ_OK;
+}
+
+int mpcq_session_enable_swing(mpcq_session* s, const mpcq_swing_params* sp) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  mpcq_swing_params P;
+  int rc = swing_params(sp, &P);
+  if (rc) return rc;
+  if (s->swing) {
+    if (P.k_mpc != s->sp.k_mpc) return fail(MPCQ_E_INVALID, "swing is enabled with k_mpc = %d", s->sp.k_mpc);
+    s->sp = P;
+    return MPCQ_OK;
+  }
+  const size_t B = (size_t)s->B;
+  const size_t nb[3] = {B * P.k_mpc * 36 * 8, B * 4 * MPCQ_SWING_STATE * 8, B * 24};
+  size_t off[3], tot = 0;
+  for (int i = 0; i < 3; ++i) { off[i] = tot; tot += (nb[i] + 255) & ~size_t(255); }
+  DeviceGuard g(s->ctx->device);
+  if (hipMalloc(&s->swing_mem, tot) != hipSuccess) {
+    s->swing_mem = nullptr;
+    return fail(MPCQ_E_NOMEM, "hipMalloc(%zu) for the swing arrays failed", tot);
+  }
+  HIP_TRY(hipMemsetAsync(s->swing_mem, 0, tot, s->ctx->stream));  // all-zero state = new generators
+  HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+  for (int i = 0; i < 3; ++i) {
+    s->arr[MPCQ_SV_SWING_REF + i] = (char*)s->swing_mem + off[i];
+    s->bytes[MPCQ_SV_SWING_REF + i] = nb[i];
+  }
+  s->sp = P;
+  s->swing = true;
   return MPCQ_OK;
 }
 
@@ -956,9 +1083,27 @@ int mpcq_session_tick(mpcq_session* s, int k, const double* state, const double*
   for (int i = 0; i < 12; ++i) ra.state_weights[i] = c->p.state_weights[i];
   ra.force_weight = c->p.force_weight;
   for (int i = 0; i < 8; ++i) ra.shoulders[i] = s->pp.shoulders[i];
+  if (s->swing) {  // the frame of this tick's fsteps: q_w's x, y, yaw before the retrieve moves it
+    double* fr = (double*)s->arr[MPCQ_SV_FRAME];
+    const double* qw = (const double*)s->arr[MPCQ_SV_Q_W];
+    HIP_TRY(hipMemcpy2DAsync(fr, 24, qw, 48, 16, (size_t)B, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemcpy2DAsync(fr + 2, 24, qw + 5, 48, 8, (size_t)B, hipMemcpyDeviceToDevice, c->stream));
+  }
   HIP_TRY(mpcq::launch_retrieve(N, ra, c->stream));
   HIP_TRY(mpcq::launch_order((const int32_t*)s->arr[MPCQ_SV_ITERS], B, s->order, c->stream));
   s->have_order = true;
+  if (s->swing) {  // the tick's swing-foot references, substeps 0..k_mpc-1 (virtual-robot lift-off)
+    mpcq::SwingArgs sa{};
+    sa.batch = B;
+    sa.k_sub0 = 0;
+    sa.n_sub = s->sp.k_mpc;
+    sa.gait = (const double*)s->arr[MPCQ_SV_GAIT];
+    sa.fsteps = (const double*)s->arr[MPCQ_SV_FSTEPS];
+    sa.frame = (const double*)s->arr[MPCQ_SV_FRAME];
+    sa.state = (double*)s->arr[MPCQ_SV_SWING_STATE];
+    sa.ref = (double*)s->arr[MPCQ_SV_SWING_REF];
+    HIP_TRY(mpcq::launch_swing(s->sp, sa, c->stream));
+  }
   // host inputs are staged in buffers the next tick reuses: host calls block
   if (!(flags & MPCQ_FLAG_ASYNC) || !dev) HIP_TRY(hipStreamSynchronize(c->stream));
   return MPCQ_OK;
@@ -967,6 +1112,7 @@ int mpcq_session_tick(mpcq_session* s, int k, const double* state, const double*
 int mpcq_session_read(mpcq_session* s, int what, void* dst, uint32_t flags) {
   if (!s || !dst) return fail(MPCQ_E_INVALID, "NULL argument");
   if (what < 0 || what >= MPCQ_SV_COUNT) return fail(MPCQ_E_INVALID, "unknown session array %d", what);
+  if (!s->arr[what]) return fail(MPCQ_E_INVALID, "session array %d needs mpcq_session_enable_swing", what);
   DeviceGuard g(s->ctx->device);
   const hipMemcpyKind kind = (flags & MPCQ_FLAG_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
   HIP_TRY(hipMemcpyAsync(dst, s->arr[what], s->bytes[what], kind, s->ctx->stream));
@@ -977,8 +1123,11 @@ int mpcq_session_read(mpcq_session* s, int what, void* dst, uint32_t flags) {
 int mpcq_session_write(mpcq_session* s, int what, const void* src, uint32_t flags) {
   if (!s || !src) return fail(MPCQ_E_INVALID, "NULL argument");
   if (what < 0 || what >= MPCQ_SV_COUNT) return fail(MPCQ_E_INVALID, "unknown session array %d", what);
+  if (!s->arr[what]) return fail(MPCQ_E_INVALID, "session array %d needs mpcq_session_enable_swing", what);
   // the engine indexes robots through the order: only order_kernel writes it
   if (what == MPCQ_SV_ORDER) return fail(MPCQ_E_INVALID, "MPCQ_SV_ORDER is read-only");
+  if (what == MPCQ_SV_SWING_REF || what == MPCQ_SV_FRAME)
+    return fail(MPCQ_E_INVALID, "MPCQ_SV_SWING_REF and MPCQ_SV_FRAME are read-only");
   DeviceGuard g(s->ctx->device);
   const hipMemcpyKind kind = (flags & MPCQ_FLAG_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   HIP_TRY(hipMemcpyAsync(s->arr[what], src, s->bytes[what], kind, s->ctx->stream));
@@ -989,6 +1138,7 @@ int mpcq_session_write(mpcq_session* s, int what, const void* src, uint32_t flag
 int mpcq_session_device_ptr(mpcq_session* s, int what, void** out) {
   if (!s || !out) return fail(MPCQ_E_INVALID, "NULL argument");
   if (what < 0 || what >= MPCQ_SV_COUNT) return fail(MPCQ_E_INVALID, "unknown session array %d", what);
+  if (!s->arr[what]) return fail(MPCQ_E_INVALID, "session array %d needs mpcq_session_enable_swing", what);
   *out = s->arr[what];
   return MPCQ_OK;
 }

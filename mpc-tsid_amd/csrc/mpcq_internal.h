@@ -158,6 +158,24 @@ hipError_t launch_class_learn(const int32_t* cls, const int32_t* iters, int64_t 
 hipError_t launch_suspended(const int32_t* prev, int64_t n, const int32_t* status, const double* key,
                             int32_t* list, int32_t* count, int32_t* res_i, hipStream_t s);
 
+// Swing-foot trajectories (mpcq_swing.hip); layouts in include/mpcq.h (mpcq_swing_batch).
+struct SwingArgs {
+  int64_t batch;
+  int k_sub0, n_sub;
+  const double* gait;   // [B][20][5]
+  const double* fsteps; // [B][20][13]
+  const double* frame;  // [B][3]
+  const double* feet0;  // [B][4][6] or null
+  double* state;        // [B][4][40] in/out
+  double* ref;          // [B][n_sub][4][9]
+  double* t0_out;       // [B][n_sub][4] or null
+  int32_t* status;      // [B] or null
+};
+hipError_t launch_swing(const mpcq_swing_params& sp, const SwingArgs& a, hipStream_t s);
+// one get_next_foot per (robot, foot): in [B][4][10], state [B][4][40], out [B][4][11]
+hipError_t launch_swing_step(const mpcq_swing_params& sp, int64_t batch, const double* in, double* state,
+                             double* out, hipStream_t s);
+
 // Launchers (mpcq_engine.hip).  Return hipError_t.
 hipError_t launch_formulate(int N, const mpcq_params& p, const LaunchArgs& a, hipStream_t s);
 hipError_t launch_solve(int N, bool fused, const mpcq_params& p, const LaunchArgs& a, hipStream_t s);

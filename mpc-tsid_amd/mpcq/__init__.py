@@ -7,6 +7,7 @@ Public surface:
   pattern, dims     CSC pattern / sizes of MPC.create_ML
   Engine.plan       batched FootstepPlanner (roll / compute_footsteps / getRefStates)
   Session           B robots in closed loop, all per-tick state resident in HBM
+  Swing             batched swing-foot trajectories between two ticks (Session.enable_swing)
   synth             seeded synthetic inputs shaped like FootstepPlanner's
 """
 from . import synth  # noqa: F401
@@ -18,8 +19,10 @@ from ._lib import (FLAG_ASYNC, FLAG_DEVICE_PTRS, FLAG_ORDER_BY_CLASS, MODE_SETUP
                    STATUS_NONFINITE, STATUS_SOLVED, STATUS_SOLVED_INACCURATE, STATUS_PRIMAL_INFEASIBLE,
                    STATUS_DUAL_INFEASIBLE, STATUS_PRIMAL_INFEASIBLE_INACCURATE,
                    STATUS_DUAL_INFEASIBLE_INACCURATE, STATUS_BAD_BOUNDS, MpcqError,
-                   Params, build, build_info, default_params, lib, source_sha, supported_horizons)
+                   Params, build, build_info, default_params, lib, source_sha, supported_horizons,
+                   SV_FRAME, SV_SWING_REF, SV_SWING_STATE, SWING_STATE, SwingParams, default_swing_params)
 from .engine import Engine, dims, pattern  # noqa: F401
 from .session import Session  # noqa: F401
+from .swing import Swing  # noqa: F401
 
 __version__ = "0.1.0"

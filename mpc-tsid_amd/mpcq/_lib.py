@@ -60,6 +60,10 @@ PLAN_TICK = PLAN_ROLL | PLAN_FOOTSTEPS | PLAN_REFSTATES
 SV_F0, SV_X, SV_X_ROBOT, SV_Q_W, SV_COST, SV_XREF, SV_FSTEPS, SV_GAIT = range(8)
 SV_STATUS, SV_ITERS, SV_RHO, SV_Y, SV_STATE, SV_L_FEET, SV_ROT_FLAG, SV_H_ROT = range(8, 16)
 SV_ORDER = 16  # read-only: the next tick's dispatch order
+# only on a session with enable_swing: the tick's swing-foot references (read-only), the
+# generators' state, the frame of the tick's fsteps (read-only)
+SV_SWING_REF, SV_SWING_STATE, SV_FRAME = 17, 18, 19
+SWING_STATE = 40  # MPCQ_SWING_STATE: doubles per foot
 
 EXPORTS = ("mpcq_abi_version", "mpcq_default_params", "mpcq_dims", "mpcq_pattern",
            "mpcq_supported_horizons", "mpcq_last_error", "mpcq_create", "mpcq_destroy",
@@ -70,7 +74,9 @@ EXPORTS = ("mpcq_abi_version", "mpcq_default_params", "mpcq_dims", "mpcq_pattern
            "mpcq_build_info",
            "mpcq_debug_class_table_slots", "mpcq_debug_class_table_read", "mpcq_debug_class_table_write",
            "mpcq_debug_class_order", "mpcq_debug_class_learn", "mpcq_debug_suspended_status",
-           "mpcq_debug_suspended", "mpcq_debug_session_order", "mpcq_debug_last_dispatch")
+           "mpcq_debug_suspended", "mpcq_debug_session_order", "mpcq_debug_last_dispatch",
+           "mpcq_default_swing_params", "mpcq_swing_step_batch", "mpcq_swing_batch",
+           "mpcq_session_enable_swing")
 
 
 class MpcqError(RuntimeError):
@@ -136,6 +142,19 @@ class PlannerParams(C.Structure):
         ("shoulders", C.c_double * 8),
         ("reduced_offset", C.c_double * 8),
         ("reserved", C.c_int32 * 8),
+    ]
+
+
+class SwingParams(C.Structure):
+    """struct mpcq_swing_params (include/mpcq.h)."""
+
+    _fields_ = [
+        ("dt", C.c_double),
+        ("max_height", C.c_double),
+        ("t_lock", C.c_double),
+        ("feet_z", C.c_double),
+        ("k_mpc", C.c_int32),
+        ("reserved", C.c_int32 * 7),
     ]
 
 
@@ -223,6 +242,14 @@ def lib():
     L.mpcq_debug_suspended.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp]
     L.mpcq_debug_session_order.argtypes = [vp, C.c_int64, vp, vp]
     L.mpcq_debug_last_dispatch.argtypes = [vp, C.POINTER(C.c_int64), ip, ip, vp, vp, vp, ip, vp]
+    SP = C.POINTER(SwingParams)
+    L.mpcq_default_swing_params.argtypes = [SP]
+    L.mpcq_default_swing_params.restype = None
+    L.mpcq_swing_step_batch.argtypes = [vp, SP, C.c_int64, vp, vp, vp, C.c_uint32]
+    L.mpcq_swing_batch.argtypes = [vp, SP, C.c_int64, C.c_int, C.c_int] + [vp] * 8 + [C.c_uint32]
+    L.mpcq_session_enable_swing.argtypes = [vp, SP]
+    for name in ("mpcq_swing_step_batch", "mpcq_swing_batch", "mpcq_session_enable_swing"):
+        getattr(L, name).restype = C.c_int
     for name in ("mpcq_debug_class_table_read", "mpcq_debug_class_table_write", "mpcq_debug_class_order",
                  "mpcq_debug_class_learn", "mpcq_debug_suspended", "mpcq_debug_session_order",
                  "mpcq_debug_last_dispatch"):
@@ -263,6 +290,16 @@ def default_planner_params(**overrides) -> PlannerParams:
     for k, v in overrides.items():
         if not hasattr(p, k):
             raise AttributeError(f"unknown planner parameter {k}")
+        setattr(p, k, v)
+    return p
+
+
+def default_swing_params(**overrides) -> SwingParams:
+    p = SwingParams()
+    lib().mpcq_default_swing_params(C.byref(p))
+    for k, v in overrides.items():
+        if not hasattr(p, k):
+            raise AttributeError(f"unknown swing parameter {k}")
         setattr(p, k, v)
     return p
 

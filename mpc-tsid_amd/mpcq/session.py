@@ -51,6 +51,20 @@ class Session:
                                             None if g is None else C.c_void_p(g.ctypes.data), C.byref(h))
         self._h = h
         self.k = 0
+        self.swing_params = None
+
+    def enable_swing(self, params: L.SwingParams | None = None):
+        """Opt in to the swing-foot references: every later tick appends one swing launch over
+        substeps 0..k_mpc-1 of its gait / fsteps (SV_SWING_REF, SV_SWING_STATE, SV_FRAME)."""
+        sp = params or L.default_swing_params()
+        self.engine._call("mpcq_session_enable_swing", self._h, C.byref(sp))
+        self.swing_params = sp
+        B = self.batch
+        self._shapes.update({
+            L.SV_SWING_REF: ((B, int(sp.k_mpc), 4, 9), np.float64),
+            L.SV_SWING_STATE: ((B, 4, L.SWING_STATE), np.float64),
+            L.SV_FRAME: ((B, 3), np.float64),
+        })
 
     def close(self):
         if getattr(self, "_h", None):
@@ -98,14 +112,19 @@ class Session:
                                           flags)
         self.k = k + 1
 
+    def _shape(self, what: int):
+        if what not in self._shapes and what in (L.SV_SWING_REF, L.SV_SWING_STATE, L.SV_FRAME):
+            raise L.MpcqError(L.E_INVALID, f"session array {what} needs enable_swing()")
+        return self._shapes[what]
+
     def read(self, what: int):
-        shape, dt = self._shapes[what]
+        shape, dt = self._shape(what)
         out = np.empty(shape, dt)
         self.engine._call("mpcq_session_read", self._h, what, C.c_void_p(out.ctypes.data), 0)
         return out
 
     def write(self, what: int, value):
-        shape, dt = self._shapes[what]
+        shape, dt = self._shape(what)
         a = np.ascontiguousarray(np.broadcast_to(np.asarray(value, dt), shape))
         self.engine._call("mpcq_session_write", self._h, what, C.c_void_p(a.ctypes.data), 0)
 
