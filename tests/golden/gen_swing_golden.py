@@ -35,6 +35,16 @@ Tables (``tab_*``): gait tables that exercise the timing walk (random phases, a 
 over the table's end, blank rows) at random substeps, with whether the reference raises
 (IndexError: a swing foot without a stance row; the empty table) and t0 / t_swing otherwise.
 
+``params`` sub-command (``python tests/golden/gen_swing_golden.py params``): writes
+tests/golden/swing_params_golden.npz, the same capture under every case of
+tests/swing_param_cases.py (non-default dt, k_mpc, max_height, t_lock, mean_feet_z), keys
+``<case>_...``.  Per case: trot (``sub`` and ``tick``) and bounding (``tick``) for 10 ticks of
+the case's k_mpc substeps (the planner stays FootstepPlanner(0.02, n_periods): it only produces
+the tables, the swing code scales them by dt * k_mpc), with the case's own ``free_err``; one
+whole swing, re-targeted every step, for each t1 these scenarios produce, with the case's own
+``step_err`` / ``step_coef_scale``; and ``<case>_params`` = dt, max_height, t_lock, feet_z,
+k_mpc.  A plain run writes swing_golden.npz as before.
+
 Only data leaves this script.
 """
 from __future__ import annotations
@@ -42,6 +52,7 @@ from __future__ import annotations
 import os
 import sys
 import types
+from types import SimpleNamespace as NS
 
 import numpy as np
 
@@ -58,6 +69,8 @@ MASKS = {
     "side": ((1, 1, 1, 1), (1, 0, 1, 0), (1, 1, 1, 1), (0, 1, 0, 1)),
 }
 LD = np.longdouble
+# the reference's constants (TSID:96-97, 107; Interface.py:91; main.py:21): the plain run
+DEF = NS(k_mpc=K_MPC, dt=DT, max_height=MAX_H, t_lock=T_LOCK, feet_z=0.0, ticks=T_TICKS)
 
 
 def import_reference():
@@ -107,8 +120,10 @@ def gen_state(g):
 
 
 # ----------------------------------------------------------------------------- step cases
-def step_cases(ftg):
-    rng = np.random.default_rng(4100)
+def step_cases(ftg, P=DEF, t1s=(0.14, 0.16), swings=2, seed=4100,
+               fresh=((0.14, 0.10), (0.16, 0.159), (0.14, 0.09 + 1e-3))):
+    """``swings`` whole swings per t1 of ``t1s``, then the (t1, t0) of ``fresh`` on new generators."""
+    rng = np.random.default_rng(seed)
     rec = {k: [] for k in ("in", "pre", "out", "post", "out_ld", "post_ld")}
 
     def one(g64, gld, args):
@@ -124,28 +139,28 @@ def step_cases(ftg):
         rec["post_ld"].append(np.array(list(gld.lastCoeffs) + [gld.x1, gld.y1], LD))
         return o
 
-    for t1 in (0.14, 0.16):
-        for _ in range(2):
-            g64 = ftg.Foot_trajectory_generator(MAX_H, T_LOCK)
-            gld = ftg.Foot_trajectory_generator(MAX_H, T_LOCK)
+    for t1 in t1s:
+        for _ in range(swings):
+            g64 = ftg.Foot_trajectory_generator(P.max_height, P.t_lock)
+            gld = ftg.Foot_trajectory_generator(P.max_height, P.t_lock)
             p = [rng.uniform(-0.3, 0.3), rng.normal(0, 0.05), rng.normal(0, 0.5),
                  rng.uniform(-0.3, 0.3), rng.normal(0, 0.05), rng.normal(0, 0.5)]
             tgt = np.array([p[0], p[3]]) + rng.uniform(-0.08, 0.08, 2)
-            n = int(round(t1 / DT))
+            n = int(round(t1 / P.dt))
             for k in range(n):
-                t0 = float(np.round(k * DT, 3))
+                t0 = float(np.round(k * P.dt, 3))
                 tgt = tgt + rng.normal(0, 0.001, 2)  # the planner re-targets every step
-                o = one(g64, gld, (p[0], p[1], p[2], p[3], p[4], p[5], tgt[0], tgt[1], t0, t1, DT))
+                o = one(g64, gld, (p[0], p[1], p[2], p[3], p[4], p[5], tgt[0], tgt[1], t0, t1, P.dt))
                 p = [float(v) for v in o[:6]]
-    for t1, t0 in ((0.14, 0.10), (0.16, 0.159), (0.14, 0.09 + 1e-3)):  # locked on a new generator
-        g64 = ftg.Foot_trajectory_generator(MAX_H, T_LOCK)
-        gld = ftg.Foot_trajectory_generator(MAX_H, T_LOCK)
-        one(g64, gld, (0.1, 0.2, 0.3, -0.1, 0.0, 0.1, 0.15, -0.12, t0, t1, DT))
+    for t1, t0 in fresh:  # locked on a new generator
+        g64 = ftg.Foot_trajectory_generator(P.max_height, P.t_lock)
+        gld = ftg.Foot_trajectory_generator(P.max_height, P.t_lock)
+        one(g64, gld, (0.1, 0.2, 0.3, -0.1, 0.0, 0.1, 0.15, -0.12, t0, t1, P.dt))
     out = {}
     f64 = {k: np.array(rec[k], np.float64) for k in ("in", "pre", "out", "post")}
     old, pld = np.array(rec["out_ld"], LD), np.array(rec["post_ld"], LD)
-    mode = (f64["in"][:, 9] - f64["in"][:, 8]) > T_LOCK
-    mode_ld = (f64["in"][:, 9].astype(LD) - f64["in"][:, 8].astype(LD)) > LD(T_LOCK)
+    mode = (f64["in"][:, 9] - f64["in"][:, 8]) > P.t_lock
+    mode_ld = (f64["in"][:, 9].astype(LD) - f64["in"][:, 8].astype(LD)) > LD(P.t_lock)
     assert np.array_equal(mode, mode_ld)
     e = np.abs(f64["out"].astype(LD) - old)
     scale = np.abs(pld[:, :24]).max(axis=0)
@@ -176,15 +191,15 @@ class NoOp:
         return lambda *a, **k: None
 
 
-def make_stub(Rec, extended):
+def make_stub(Rec, extended, P=DEF):
     dt_ = LD if extended else np.float64
     st = types.SimpleNamespace()
-    st.k_mpc, st.dt = K_MPC, DT
+    st.k_mpc, st.dt = P.k_mpc, P.dt
     st.t_swing = np.zeros((4,))
     st.mgoals = np.zeros((6, 4), dt_)
     st.goals, st.vgoals, st.agoals = (np.full((3, 4), np.nan, dt_) for _ in range(3))
     st.footsteps = SHOULDERS.copy()
-    st.ftgs = [Rec(MAX_H, T_LOCK) for _ in range(4)]
+    st.ftgs = [Rec(P.max_height, P.t_lock) for _ in range(4)]
     for g in st.ftgs:
         g.extended = extended
     st.sampleFeet = [NoOp() for _ in range(4)]
@@ -206,13 +221,13 @@ def table(kind, n_periods, dt=0.02):
     return g
 
 
-def draw_script(seed, held):
+def draw_script(seed, held, P=DEF):
     """Everything random of a scenario, drawn once so the float64 and the extended run (and
     the planner) see the same numbers."""
     rng = np.random.default_rng(seed)
     s = {"v_ref": [], "state": [], "l_feet": [], "frame": [], "o": [], "ov": [], "oa": []}
     pose = np.array([rng.uniform(-1, 1), rng.uniform(-1, 1), rng.uniform(-3, 3)])
-    for _ in range(T_TICKS):
+    for _ in range(P.ticks):
         v_ref = np.zeros((6, 1))
         v_ref[0, 0], v_ref[1, 0], v_ref[5, 0] = rng.uniform(-0.5, 1.0), rng.uniform(-0.3, 0.3), rng.uniform(-0.5, 0.5)
         s["v_ref"].append(v_ref)
@@ -221,45 +236,45 @@ def draw_script(seed, held):
         s["state"].append((lC, abg, rng.normal(0, 0.2, (3, 1)), rng.normal(0, 0.2, (3, 1))))
         s["l_feet"].append(np.vstack([SHOULDERS + rng.uniform(-0.03, 0.03, (2, 4)), np.zeros((1, 4))]))
         fr = []
-        for ks in range(K_MPC):
+        for ks in range(P.k_mpc):
             c, sn = np.cos(pose[2]), np.sin(pose[2])
-            pose = pose + DT * np.array([c * v_ref[0, 0] - sn * v_ref[1, 0], sn * v_ref[0, 0] + c * v_ref[1, 0],
+            pose = pose + P.dt * np.array([c * v_ref[0, 0] - sn * v_ref[1, 0], sn * v_ref[0, 0] + c * v_ref[1, 0],
                                          v_ref[5, 0]]) + rng.normal(0, 1e-4, 3)
             fr.append(pose.copy() if not (held and ks) else fr[0].copy())
         s["frame"].append(fr)
         # measured feet (world): near the shoulders of the frame, moving
-        o = np.empty((K_MPC, 3, 4))
-        for ks in range(K_MPC):
+        o = np.empty((P.k_mpc, 3, 4))
+        for ks in range(P.k_mpc):
             F = Frame(*fr[ks])
             o[ks] = F * np.vstack([SHOULDERS, np.zeros((1, 4))]) + np.vstack([rng.normal(0, 0.01, (2, 4)), np.zeros((1, 4))])
         s["o"].append(o)
-        s["ov"].append(rng.normal(0, 0.05, (K_MPC, 3, 4)))
-        s["oa"].append(rng.normal(0, 0.5, (K_MPC, 3, 4)))
+        s["ov"].append(rng.normal(0, 0.05, (P.k_mpc, 3, 4)))
+        s["oa"].append(rng.normal(0, 0.5, (P.k_mpc, 3, 4)))
     return s
 
 
-def run_scenario(FP, ctl, Rec, kind, n_periods, script, extended):
+def run_scenario(FP, ctl, Rec, kind, n_periods, script, extended, P=DEF):
     pl = FP.FootstepPlanner(0.02, n_periods)
     pl.gait = table(kind, n_periods)
-    st = make_stub(Rec, extended)
+    st = make_stub(Rec, extended, P)
     cast = (lambda a: a.astype(LD)) if extended else (lambda a: a)
     rec = {k: [] for k in ("gait", "fsteps", "gen", "frame", "feet0", "t0", "t_swing", "mode", "ref")}
-    for j in range(T_TICKS):
+    for j in range(P.ticks):
         lC, abg, lV, lW = script["state"][j]
         v_ref, l_feet = script["v_ref"][j], script["l_feet"][j]
-        pl.update_fsteps(0 if j == 0 else j * K_MPC + 1, l_feet, np.vstack((lV, lW)), v_ref, lC[2, 0], None, None, False)
+        pl.update_fsteps(0 if j == 0 else j * P.k_mpc + 1, l_feet, np.vstack((lV, lW)), v_ref, lC[2, 0], None, None, False)
         gait, fsteps = pl.gait.copy(), pl.fsteps.copy()
         rec["gait"].append(gait)
         rec["fsteps"].append(fsteps)
-        for ks in range(K_MPC):
+        for ks in range(P.k_mpc):
             fr = script["frame"][j][ks]
             itf = types.SimpleNamespace(oMl=Frame(*fr), o_feet=cast(script["o"][j][ks]), ov_feet=cast(script["ov"][j][ks]),
-                                        oa_feet=cast(script["oa"][j][ks]), mean_feet_z=0.0)
+                                        oa_feet=cast(script["oa"][j][ks]), mean_feet_z=P.feet_z)
             for g in st.ftgs:
                 g.last = None
             st.goals[:], st.vgoals[:], st.agoals[:] = np.nan, np.nan, np.nan
             ctl.controller.update_footsteps(st, itf, fsteps)
-            ctl.controller.update_feet_tasks(st, j * K_MPC + ks, gait, 0, itf, [0, 0, 0, 0])
+            ctl.controller.update_feet_tasks(st, j * P.k_mpc + ks, gait, 0, itf, [0, 0, 0, 0])
             t0 = np.full(4, np.nan)
             ts = np.full(4, np.nan)
             mode = np.full(4, np.nan)
@@ -271,8 +286,8 @@ def run_scenario(FP, ctl, Rec, kind, n_periods, script, extended):
                     assert gait[0, 1 + i] != 0
                     continue
                 t0[i], ts[i] = a[8], a[9]
-                assert ts[i] == st.t_swing[i] and a[10] == DT
-                mode[i] = float((LD(a[9]) - LD(a[8])) > LD(T_LOCK)) if extended else float((a[9] - a[8]) > T_LOCK)
+                assert ts[i] == st.t_swing[i] and a[10] == P.dt
+                mode[i] = float((LD(a[9]) - LD(a[8])) > LD(P.t_lock)) if extended else float((a[9] - a[8]) > P.t_lock)
                 if t0[i] == 0:
                     feet0[i] = (script["o"][j][ks][0, i], script["ov"][j][ks][0, i], script["oa"][j][ks][0, i],
                                 script["o"][j][ks][1, i], script["ov"][j][ks][1, i], script["oa"][j][ks][1, i])
@@ -284,7 +299,7 @@ def run_scenario(FP, ctl, Rec, kind, n_periods, script, extended):
             rec["mode"].append(mode)
             rec["ref"].append(ref)
         rec["gen"].append(np.array([[float(v) for v in gen_state(g)] for g in st.ftgs]))
-    sh = (T_TICKS, K_MPC)
+    sh = (P.ticks, P.k_mpc)
     out = {"gait": np.array(rec["gait"]), "fsteps": np.array(rec["fsteps"]), "gen": np.array(rec["gen"])}
     for k in ("frame", "feet0", "t0", "t_swing", "mode", "ref"):
         a = np.array(rec[k])
@@ -350,7 +365,21 @@ def timing_tables(ctl, Rec):
     return {f"tab_{k}": np.array(v) for k, v in rec.items()}
 
 
-def main():
+def run_pair(FP, ctl, Rec, kind, n_periods, seed, held, P, tag):
+    """A scenario in float64 and with np.longdouble state: the float64 arrays and
+    max |float64 - longdouble| of positions, velocities, accelerations."""
+    script = draw_script(seed, held, P)
+    a = run_scenario(FP, ctl, Rec, kind, n_periods, script, False, P)
+    b = run_scenario(FP, ctl, Rec, kind, n_periods, script, True, P)
+    # both runs take the same branches
+    for k in ("t0", "t_swing", "mode", "gait", "fsteps", "feet0"):
+        assert nan_equal(a[k], b[k]), (tag, k)
+    assert np.array_equal(np.isnan(a["ref"]), np.isnan(b["ref"]))
+    d = np.abs(np.nan_to_num(a["ref"].astype(LD) - b["ref"]))
+    return a, np.array([d[..., 0:3].max(), d[..., 3:6].max(), d[..., 6:9].max()], LD)
+
+
+def main(path=None):
     FP, ftg, ctl = import_reference()
     Rec = recording_class(ftg)
     arrs = step_cases(ftg)
@@ -361,26 +390,58 @@ def main():
                                         ("static", "static", 1, 4304), ("trot2", "trot", 2, 4305)):
         names.append(name)
         for var, held in (("sub", False), ("tick", True)):
-            script = draw_script(seed, held)
-            a = run_scenario(FP, ctl, Rec, kind, n_periods, script, False)
-            b = run_scenario(FP, ctl, Rec, kind, n_periods, script, True)
-            # both runs take the same branches
-            for k in ("t0", "t_swing", "mode", "gait", "fsteps", "feet0"):
-                assert nan_equal(a[k], b[k]), (name, var, k)
-            assert np.array_equal(np.isnan(a["ref"]), np.isnan(b["ref"]))
-            d = np.abs(np.nan_to_num(a["ref"].astype(LD) - b["ref"]))
-            free_err = np.maximum(free_err, [d[..., 0:3].max(), d[..., 3:6].max(), d[..., 6:9].max()])
+            a, err = run_pair(FP, ctl, Rec, kind, n_periods, seed, held, DEF, (name, var))
+            free_err = np.maximum(free_err, err)
             for k, v in a.items():
                 arrs[f"{name}_{var}_{k}"] = v
     arrs["scenarios"] = np.array(names)
     arrs["free_err"] = free_err.astype(np.float64)
     arrs["params"] = np.array([DT, MAX_H, T_LOCK, 0.0, K_MPC])
-    path = os.path.join(HERE, "swing_golden.npz")
+    path = path or os.path.join(HERE, "swing_golden.npz")
     np.savez_compressed(path, **arrs)
     print("wrote", path, os.path.getsize(path), "bytes")
     print("step cases", arrs["step_in"].shape[0], "adaptive", int(arrs["step_mode"].sum()), "step_err", arrs["step_err"])
     print("free_err", arrs["free_err"], "tables raising", sorted(set(arrs["tab_raises"].tolist())))
 
 
+def main_params(path=None):
+    """swing_params_golden.npz: every case of tests/swing_param_cases.py."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import swing_param_cases as SC
+    FP, ftg, ctl = import_reference()
+    Rec = recording_class(ftg)
+    seeds = {"trot": 4301, "bound": 4302}
+    arrs = {}
+    for ci, case in enumerate(SC.NAMES):
+        v = SC.full(case)
+        P = NS(k_mpc=v["k_mpc"], dt=v["dt"], max_height=v["max_height"], t_lock=v["t_lock"], feet_z=v["feet_z"],
+               ticks=SC.TICKS)
+        free_err = np.zeros(3, LD)
+        t1s = set()
+        for name, var in SC.FREE:
+            a, err = run_pair(FP, ctl, Rec, name, 1, seeds[name], var == "tick", P, (case, name, var))
+            free_err = np.maximum(free_err, err)
+            t1s.update(np.unique(a["t_swing"][~np.isnan(a["t_swing"])]).tolist())
+            lift = a["t0"] == 0
+            assert lift.any() and (a["mode"] == 1).any() and (a["mode"] == 0).any(), (case, name, var)
+            for k in ("gait", "fsteps", "frame", "feet0", "t0", "t_swing", "mode", "ref"):
+                arrs[f"{case}_{name}_{var}_{k}"] = a[k]
+        # one whole swing for each t1 the case's scenarios produce
+        st = step_cases(ftg, P, sorted(t1s), swings=1, seed=4110 + ci, fresh=())
+        assert st["step_mode"].any() and (~st["step_mode"]).any() and (st["step_in"][:, 8] == 0).any(), case
+        for k, a in st.items():
+            arrs[f"{case}_{k}"] = a
+        arrs[f"{case}_free_err"] = free_err.astype(np.float64)
+        arrs[f"{case}_params"] = np.array([v[f] for f in SC.FIELDS], np.float64)
+        print(case, "t1", sorted(t1s), "step cases", st["step_in"].shape[0], "adaptive", int(st["step_mode"].sum()),
+              "step_err", st["step_err"], "free_err", arrs[f"{case}_free_err"])
+    arrs["cases"] = np.array(SC.NAMES)
+    path = path or os.path.join(HERE, "swing_params_golden.npz")
+    np.savez_compressed(path, **arrs)
+    print("wrote", path, os.path.getsize(path), "bytes")
+
+
 if __name__ == "__main__":
-    main()
+    argv = sys.argv[1:]
+    out = argv[argv.index("--out") + 1] if "--out" in argv else None  # default: next to this script
+    (main_params if "params" in argv[:1] else main)(out)

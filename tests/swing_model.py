@@ -154,7 +154,7 @@ def to_world(frame, px, py):
 
 def advance_one(p, gait, fsteps, frame, feet0, state, k_sub0, n_sub):
     """One robot: returns (ref [n_sub][4][9], t0 [n_sub][4], status); ``state`` [4][40] in place."""
-    ref = np.full((n_sub, 4, 9), np.nan)
+    ref = np.full((n_sub, 4, 9), np.nan, state.dtype)
     t0s = np.full((n_sub, 4), np.nan)
     swing = [gait[0, 1 + f] == 0 for f in range(4)]
     tim = [timing(gait, f, p["dt"], p["k_mpc"]) if swing[f] else None for f in range(4)]
@@ -186,11 +186,15 @@ def advance_one(p, gait, fsteps, frame, feet0, state, k_sub0, n_sub):
 
 def advance(gait, fsteps, frame, state, k_sub0=0, n_sub=None, feet0=None, params=None):
     """A batch: gait [B][20][5], fsteps [B][20][13], frame [B][3], state [B][4][40] (in place),
-    feet0 [B][4][6] or None.  Returns ref [B][n_sub][4][9], t0 [B][n_sub][4], status [B]."""
+    feet0 [B][4][6] or None.  Returns ref [B][n_sub][4][9], t0 [B][n_sub][4], status [B].
+    With fsteps, frame and state (and feet0) in np.longdouble the polynomials are evaluated in
+    that precision on the float64 run's branches (gait, the timing chain and t0 stay float64):
+    max |float64 - longdouble| is the model's own rounding error, the yardstick where no
+    fixture of the reference exists."""
     p = dict(DEFAULTS, **(params or {}))
     n = p["k_mpc"] - k_sub0 if n_sub is None else n_sub
     B = gait.shape[0]
-    ref = np.empty((B, n, 4, 9))
+    ref = np.empty((B, n, 4, 9), state.dtype)
     t0 = np.empty((B, n, 4))
     status = np.zeros(B, np.int32)
     for b in range(B):

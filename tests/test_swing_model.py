@@ -68,8 +68,9 @@ def test_model_step_cases(g):
     state[:, 0, :26] = g["step_pre"]
     args = g["step_in"][:, None, :]
     out = np.empty((n, 11))
+    dt, max_height, t_lock = (float(x) for x in g["params"][:3])
     for i in range(n):
-        out[i] = M.next_foot(state[i, 0], *args[i, 0], 0.001, 0.05, 0.05)
+        out[i] = M.next_foot(state[i, 0], *args[i, 0], dt, max_height, t_lock)
     assert np.array_equal(out[:, 9:11], g["step_out"][:, 9:11])  # gx, gy
     assert np.array_equal(state[:, 0, 24:26], g["step_post"][:, 24:26])
     assert np.array_equal(state[:, 0, 34] == 1.0, g["step_mode"])
