@@ -43,7 +43,9 @@ extern "C" {
  *      MPCQ_SLICE16 in the environment no longer slices a library compiled without it
  *   3 (additions, no bump): mpcq_default_swing_params, mpcq_swing_step_batch, mpcq_swing_batch,
  *      mpcq_session_enable_swing; MPCQ_SV_SWING_REF / _SWING_STATE / _FRAME (MPCQ_SV_COUNT
- *      17 -> 20; MPCQ_E_INVALID on a session that has not enabled swing) */
+ *      17 -> 20; MPCQ_E_INVALID on a session that has not enabled swing)
+ *   3 (additions, no bump): mpcq_robot, mpcq_default_robot, mpcq_set_robots,
+ *      mpcq_session_set_robots, mpcq_session_get_robots (per-instance mass, gI, mu, fz_max) */
 #define MPCQ_ABI_VERSION 3
 
 /* error codes (return values) */
@@ -172,6 +174,43 @@ int mpcq_last_kernel_ms(mpcq_ctx* ctx, double* formulate_ms, double* solve_ms);
  * launch reads its workgroup count on the device (MPCQ_FLAG_ASYNC holds).  0 (the default), a
  * slice of max_iter or more, and horizons up to 16: one launch. */
 int mpcq_set_slice(mpcq_ctx* ctx, int32_t slice_iters);
+
+/* ---- per-robot constants ----------------------------------------------------
+ * No reference counterpart (the reference is one robot): the four physical constants of
+ * mpcq_params that may differ between the instances of one batch.  Every other field (dt,
+ * gravity, weights, footholds, OSQP settings) shapes P, the scaling or the loop counters and
+ * stays per context. */
+typedef struct mpcq_robot {      /* 16 doubles = 128 bytes */
+  double mass;      /* > 0 */
+  double gI[9];     /* row-major 3x3, as mpcq_params.gI */
+  double mu;        /* > 0 */
+  double fz_max;    /* > 0 */
+  double reserved[4];            /* zero */
+} mpcq_robot;
+#ifdef __cplusplus
+static_assert(sizeof(mpcq_robot) == 128, "mpcq_robot is 16 doubles");
+#else
+_Static_assert(sizeof(mpcq_robot) == 128, "mpcq_robot is 16 doubles");
+#endif
+/* mass, gI, mu, fz_max of p (NULL = mpcq_default_params), reserved zero. */
+void mpcq_default_robot(const mpcq_params* p, mpcq_robot* r);
+/* Copies robots [count] into memory the context owns: from a host pointer the call blocks;
+ * with MPCQ_FLAG_DEVICE_PTRS the copy is device to device on ctx's stream.  In every later
+ * mpcq_formulate_batch and mpcq_solve_batch of ctx (both formulation modes, sliced and
+ * class-ordered solves included) instance b takes those four quantities from robots[b] --
+ * b is the instance index, whatever order the workgroups are dispatched in -- and everything
+ * else from ctx's mpcq_params.  count == 0 or robots == NULL clears the table (the context's
+ * mpcq_params again).  While a table is set, a launch with batch > count returns
+ * MPCQ_E_INVALID and launches nothing.
+ * A host table is validated: mass, mu, fz_max finite and > 0, every gI entry finite, reserved
+ * zero; otherwise MPCQ_E_INVALID (the message names the first offending index and field) and
+ * the table in force stays, as it does when the memory for a larger table cannot be
+ * allocated (MPCQ_E_NOMEM).  A device table is not validated: its values are the caller's
+ * responsibility; a NaN among them reaches the constraint values and ends as
+ * MPCQ_STATUS_NONFINITE through the solver's non-finite check.
+ * mpcq_qp_solve_batch is untouched by the table: its caller has formulated already, and P
+ * comes from the context. */
+int mpcq_set_robots(mpcq_ctx* ctx, int64_t count, const mpcq_robot* robots, uint32_t flags);
 
 /* ---- formulation -----------------------------------------------------------
  * Replaces MPC.construct_gait + update_matrices (MPC.py:635-652, 290-378) in
@@ -344,6 +383,15 @@ int mpcq_session_write(mpcq_session* s, int what, const void* src, uint32_t flag
  * MPCQ_SV_ORDER as its workgroup -> robot map: writing through its device address is not
  * allowed (a non-permutation would solve some robots twice and others not at all). */
 int mpcq_session_device_ptr(mpcq_session* s, int what, void** out);
+/* The session's own table of per-robot constants, robots [B] (mpcq_set_robots: the same
+ * copy, validation and flags); independent of the context's table, so a batch solve on the
+ * same context does not disturb the session, nor the session a batch solve.  May be called
+ * between any two ticks: the ticks after it use the new table.  NULL clears it.  A session
+ * that never sets one launches exactly what it did before. */
+int mpcq_session_set_robots(mpcq_session* s, const mpcq_robot* robots, uint32_t flags);
+/* The table in force, robots [B] (host, or device with MPCQ_FLAG_DEVICE_PTRS); blocking.
+ * Without a table: mpcq_default_robot(the context's params) for every robot. */
+int mpcq_session_get_robots(mpcq_session* s, mpcq_robot* robots, uint32_t flags);
 
 /* ---- swing-foot trajectories ----------------------------------------------
  * The consumer of (gait, fsteps) between two MPC ticks: the position, velocity and

@@ -14,6 +14,14 @@
 
 #include "mpcq_internal.h"
 
+// A table of per-robot constants on the device (mpcq_set_robots, mpcq_session_set_robots):
+// count > 0 = in force.
+struct RobotTable {
+  mpcq_robot* dev = nullptr;
+  int64_t cap = 0;
+  int64_t count = 0;
+};
+
 struct mpcq_ctx {
   int device = 0;
   int N = 0;
@@ -49,6 +57,7 @@ struct mpcq_ctx {
   int32_t* sl_buf = nullptr;
   int64_t sl_cap = 0;
   int32_t* sl_count = nullptr;
+  RobotTable robots;  // mpcq_set_robots
 };
 
 namespace {
@@ -260,6 +269,70 @@ int ensure_slice(mpcq_ctx* c, int64_t B) {
   return MPCQ_OK;
 }
 
+// The first entry of a host table that mpcq_set_robots rejects, named in the message.
+int check_robots(const mpcq_robot* r, int64_t count) {
+  for (int64_t i = 0; i < count; ++i) {
+    const char* what = nullptr;
+    if (!(isfinite(r[i].mass) && r[i].mass > 0)) what = "mass must be finite and > 0";
+    for (int j = 0; j < 9 && !what; ++j)
+      if (!isfinite(r[i].gI[j])) what = "gI must be finite";
+    if (!what && !(isfinite(r[i].mu) && r[i].mu > 0)) what = "mu must be finite and > 0";
+    if (!what && !(isfinite(r[i].fz_max) && r[i].fz_max > 0)) what = "fz_max must be finite and > 0";
+    for (int j = 0; j < 4 && !what; ++j)
+      if (!(r[i].reserved[j] == 0.0)) what = "reserved must be zero";
+    if (what) return fail(MPCQ_E_INVALID, "robots[%lld]: %s", (long long)i, what);
+  }
+  return MPCQ_OK;
+}
+
+// Replace (count > 0) or clear a table.  The copy runs on the context's stream, behind any
+// queued launch that still reads the old values; from a host pointer the call then blocks.
+int set_table(mpcq_ctx* c, RobotTable& t, int64_t count, const mpcq_robot* robots, uint32_t flags) {
+  if (count < 0 || count > (int64_t)0x7fffffff) return fail(MPCQ_E_INVALID, "bad robot count %lld", (long long)count);
+  if (count == 0 || !robots) {
+    t.count = 0;
+    return MPCQ_OK;
+  }
+  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
+  if (!dev) {
+    const int rc = check_robots(robots, count);
+    if (rc) return rc;
+  }
+  DeviceGuard g(c->device);
+  if (count > t.cap) {  // the new buffer first: a failed allocation leaves the table in force as it was
+    const size_t nb = (size_t)count * sizeof(mpcq_robot);
+    mpcq_robot* grown = nullptr;
+    if (hipMalloc(&grown, nb) != hipSuccess)
+      return fail(MPCQ_E_NOMEM, "hipMalloc(%zu) for the robot table failed", nb);
+    if (t.dev) {
+      hipError_t e = hipStreamSynchronize(c->stream);  // a queued launch may still read it
+      if (e == hipSuccess) e = hipFree(t.dev);
+      if (e != hipSuccess) {
+        (void)hipFree(grown);
+        return fail(MPCQ_E_DEVICE, "releasing the previous robot table failed: %s", hipGetErrorString(e));
+      }
+    }
+    t.dev = grown;
+    t.cap = count;
+    t.count = 0;  // (nothing copied yet)
+  }
+  HIP_TRY(hipMemcpyAsync(t.dev, robots, (size_t)count * sizeof(mpcq_robot),
+                         dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+  t.count = count;
+  if (!dev) HIP_TRY(hipStreamSynchronize(c->stream));
+  return MPCQ_OK;
+}
+
+// The table a launch of `batch` instances reads: null without one, an error if it is too short.
+int launch_table(const RobotTable& t, int64_t batch, const mpcq_robot** out) {
+  *out = nullptr;
+  if (t.count == 0) return MPCQ_OK;
+  if (batch > t.count)
+    return fail(MPCQ_E_INVALID, "batch %lld > the robot table's count %lld", (long long)batch, (long long)t.count);
+  *out = t.dev;
+  return MPCQ_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -347,6 +420,20 @@ int mpcq_pattern(int N, int32_t* indptr, int32_t* indices) {
   return MPCQ_OK;
 }
 
+void mpcq_default_robot(const mpcq_params* p, mpcq_robot* r) {
+  if (!r) return;
+  mpcq_params d;
+  if (!p) {
+    mpcq_default_params(&d);
+    p = &d;
+  }
+  memset(r, 0, sizeof(*r));
+  r->mass = p->mass;
+  memcpy(r->gI, p->gI, sizeof(r->gI));
+  r->mu = p->mu;
+  r->fz_max = p->fz_max;
+}
+
 int mpcq_supported_horizons(int32_t* out, int cap) { return mpcq::supported_horizons(out, cap); }
 
 const char* mpcq_last_error(void) { return g_err.c_str(); }
@@ -395,6 +482,7 @@ int mpcq_destroy(mpcq_ctx* c) {
   if (c->res) (void)hipFree(c->res);
   if (c->sl_buf) (void)hipFree(c->sl_buf);
   if (c->sl_count) (void)hipFree(c->sl_count);
+  if (c->robots.dev) (void)hipFree(c->robots.dev);
   for (auto& e : c->ev)
     if (e) (void)hipEventDestroy(e);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -413,6 +501,11 @@ int mpcq_set_slice(mpcq_ctx* c, int32_t slice_iters) {
   if (slice_iters < 0) return fail(MPCQ_E_INVALID, "slice_iters must be >= 0");
   c->slice_iters = slice_iters;
   return MPCQ_OK;
+}
+
+int mpcq_set_robots(mpcq_ctx* c, int64_t count, const mpcq_robot* robots, uint32_t flags) {
+  if (!c) return fail(MPCQ_E_INVALID, "ctx is NULL");
+  return set_table(c, c->robots, count, robots, flags);
 }
 
 int mpcq_last_kernel_ms(mpcq_ctx* c, double* fms, double* sms) {
@@ -451,6 +544,8 @@ int mpcq_formulate_batch(mpcq_ctx* c, int64_t B, const double* xref, const doubl
   mpcq::LaunchArgs a{};
   a.batch = B;
   a.mode = mode;
+  rc = launch_table(c->robots, B, &a.robots);
+  if (rc) return rc;
   const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
   Xfer xs[6] = {{xref, nullptr, B * n12 * 8, nullptr}, {fsteps, nullptr, (size_t)B * 260 * 8, nullptr},
                 {nullptr, Ax, B * nnz * 8, nullptr},   {nullptr, l, B * m * 8, nullptr},
@@ -487,6 +582,10 @@ static int solve_common(mpcq_ctx* c, int64_t B, bool fused, const double* xref, 
   mpcq::LaunchArgs a{};
   a.batch = B;
   a.mode = mode;
+  if (fused) {  // (the qp path has formulated already)
+    rc = launch_table(c->robots, B, &a.robots);
+    if (rc) return rc;
+  }
   const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
   enum { XR, FS, AX, L, U, WX, WY, RI, F0, X, Y, ST, IT, RO, IN, NX };
   Xfer xs[NX] = {
@@ -787,6 +886,7 @@ struct mpcq_session {
   bool swing = false;
   mpcq_swing_params sp{};
   void* swing_mem = nullptr;
+  RobotTable robots;  // mpcq_session_set_robots (the session's own, not the context's)
 };
 
 namespace {
@@ -942,8 +1042,42 @@ int mpcq_session_destroy(mpcq_session* s) {
     (void)hipStreamSynchronize(s->ctx->stream);
     (void)hipFree(s->mem);
     if (s->swing_mem) (void)hipFree(s->swing_mem);
+    if (s->robots.dev) (void)hipFree(s->robots.dev);
   }
   delete s;
+  return MPCQ_OK;
+}
+
+int mpcq_session_set_robots(mpcq_session* s, const mpcq_robot* robots, uint32_t flags) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  return set_table(s->ctx, s->robots, robots ? s->B : 0, robots, flags);
+}
+
+int mpcq_session_get_robots(mpcq_session* s, mpcq_robot* robots, uint32_t flags) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  if (!robots) return fail(MPCQ_E_INVALID, "robots is NULL");
+  mpcq_ctx* c = s->ctx;
+  DeviceGuard g(c->device);
+  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
+  const size_t nb = (size_t)s->B * sizeof(mpcq_robot);
+  if (s->robots.count) {
+    HIP_TRY(hipMemcpyAsync(robots, s->robots.dev, nb, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
+                           c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MPCQ_OK;
+  }
+  mpcq_robot d;
+  mpcq_default_robot(&c->p, &d);
+  if (!dev) {
+    for (int64_t b = 0; b < s->B; ++b) robots[b] = d;
+    return MPCQ_OK;
+  }
+  mpcq_robot* h = (mpcq_robot*)malloc(nb);
+  if (!h) return fail(MPCQ_E_NOMEM, "host malloc failed");
+  for (int64_t b = 0; b < s->B; ++b) h[b] = d;
+  const hipError_t e = hipMemcpy(robots, h, nb, hipMemcpyHostToDevice);
+  free(h);
+  HIP_TRY(e);
   return MPCQ_OK;
 }
 
@@ -1054,6 +1188,7 @@ int mpcq_session_tick(mpcq_session* s, int k, const double* state, const double*
   // longest-first by the previous tick's iteration counts (a tick k == 0 restarts cold)
   if (k == 0) s->have_order = false;
   la.order = s->have_order && s->use_order ? s->order : nullptr;
+  la.robots = s->robots.count ? s->robots.dev : nullptr;
   {
     const int wrc = ensure_work(c, B, &la.work);
     if (wrc) return wrc;

@@ -554,11 +554,27 @@ __device__ __forceinline__ void inv3(const double* M, double* R) {
   R[6] = C * id; R[7] = -(a * h - b * g) * id; R[8] = (a * e - b * d) * id;
 }
 
+// The per-robot constants of the workgroup's instance (ROB kernels: LaunchArgs::robots[b],
+// mpcq_set_robots; the others take the launch's mpcq_params, the code they always had).  b is
+// the instance (after the order[] mapping), the same for every lane, so each value is fetched
+// once and comes back uniform in SGPRs (uni): fz_max at kernel entry (the bounds need it to the
+// end), mass / gI / mu where the formulation starts (their 22 SGPRs are dead again before the
+// solve).
+struct RobotK {
+  double mass, gI[9], mu;
+};
+__device__ __forceinline__ void load_robot(const mpcq_robot* r, RobotK& rb) {
+  rb.mass = uni(r->mass);
+#pragma unroll
+  for (int j = 0; j < 9; ++j) rb.gI[j] = uni(r->gI[j]);
+  rb.mu = uni(r->mu);
+}
+
 // The 24 CSC values of one foot's three force columns in one stage: dt/m row,
 // B rows 9..11 = dt inv(Rz(yaw) gI) [lever]x (MPC.py:339-345), swing flag S
 // (MPC.py:628), friction-cone coefficients (MPC.py:136-148).
-__device__ __forceinline__ void form_foot(const mpcq_params& p, double yaw, double l0, double l1, double l2,
-                                          double swing, double* out) {
+__device__ __forceinline__ void form_foot(const mpcq_params& p, double mass, const double (&gI)[9], double mu,
+                                          double yaw, double l0, double l1, double l2, double swing, double* out) {
   const double cy = cos(yaw), sy = sin(yaw);
   const double R[9] = {cy, -sy, 0.0, sy, cy, 0.0, 0.0, 0.0, 1.0};
   double M[9], Mi[9];
@@ -566,11 +582,11 @@ __device__ __forceinline__ void form_foot(const mpcq_params& p, double yaw, doub
   for (int r = 0; r < 3; ++r)
 #pragma unroll
     for (int t = 0; t < 3; ++t)
-      M[3 * r + t] = R[3 * r + 0] * p.gI[0 * 3 + t] + R[3 * r + 1] * p.gI[1 * 3 + t] +
-                     R[3 * r + 2] * p.gI[2 * 3 + t];
+      M[3 * r + t] = R[3 * r + 0] * gI[0 * 3 + t] + R[3 * r + 1] * gI[1 * 3 + t] +
+                     R[3 * r + 2] * gI[2 * 3 + t];
   inv3(M, Mi);
   const double S[9] = {0.0, -l2, l1, l2, 0.0, -l0, -l1, l0, 0.0};
-  const double dtm = p.dt / p.mass;
+  const double dtm = p.dt / mass;
   int pos = 0;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
@@ -585,7 +601,7 @@ __device__ __forceinline__ void form_foot(const mpcq_params& p, double yaw, doub
       out[pos++] = -1.0;
     } else {
 #pragma unroll
-      for (int t = 0; t < 4; ++t) out[pos++] = -p.mu;
+      for (int t = 0; t < 4; ++t) out[pos++] = -mu;
       out[pos++] = -1.0;
     }
   }
@@ -907,7 +923,11 @@ struct Prologue {
 // The engine kernel.  FUSED: formulate from (xref, fsteps) then solve.
 // !FUSED: solve the given (Ax, l, u).  SOLVE=false: formulation only.
 
-template <int N, bool FUSED, bool SOLVE, bool POLISH>
+// ROB: the per-robot table (LaunchArgs::robots, not null) in place of p.mass / gI / mu / fz_max.
+// An instantiation of its own, so that the kernels of a launch without a table are instruction
+// for instruction what they were before the table existed (the formulation's kernels only: the
+// qp path takes Ax, l, u as given).
+template <int N, bool FUSED, bool SOLVE, bool POLISH, bool ROB = false>
 __global__ __launch_bounds__((16 * kRows<N> * (kKI<N, SOLVE, POLISH> ? 2 : 1)), (kKI<N, SOLVE, POLISH> ? 1 : kOcc<N>))
 void engine_kernel(mpcq_params p, LaunchArgs a) {
   // KI: the explicit inverse (kKI): twice the threads, waves NW.. are the helpers
@@ -936,6 +956,12 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
     if (a.batch_dev && (int64_t)blockIdx.x >= (int64_t)*a.batch_dev) return;
   }
   const int64_t b = a.order ? (int64_t)a.order[blockIdx.x] : (int64_t)blockIdx.x;  // the instance
+  [[maybe_unused]] double fz_rob = 0.0;
+  if constexpr (ROB) fz_rob = uni(a.robots[b].fz_max);
+  auto fz_max = [&]() __attribute__((always_inline)) -> double {
+    if constexpr (ROB) return fz_rob;
+    else return p.fz_max;
+  };
   STAMP_DECL
   constexpr bool BIG = kBig<N>, ABG = kAbG<N>;
   // the scaled constraint values: LDS, or (N > 49) this instance's workspace (the
@@ -1099,6 +1125,8 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
           else AbW[xo + 1] = 1.0;
         }
       }
+      [[maybe_unused]] RobotK rb;
+      if constexpr (ROB) load_robot(a.robots + b, rb);
       for (int e = t; e < 4 * N; e += T) {  // foot q of stage kk
         const int kk = e >> 2, q = e & 3;
         const int j = pos_[kk];
@@ -1115,8 +1143,12 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
           }
           lv[r] = ft - xr[r * (N + 1) + kk];
         }
-        form_foot(p, xr[5 * (N + 1) + kk], lv[0], lv[1], lv[2], 1.0 - (double)con_[4 * j + q],
-                  AbW + FO<N>(kk, q, 0));
+        if constexpr (ROB)
+          form_foot(p, rb.mass, rb.gI, rb.mu, xr[5 * (N + 1) + kk], lv[0], lv[1], lv[2],
+                    1.0 - (double)con_[4 * j + q], AbW + FO<N>(kk, q, 0));
+        else
+          form_foot(p, p.mass, p.gI, p.mu, xr[5 * (N + 1) + kk], lv[0], lv[1], lv[2],
+                    1.0 - (double)con_[4 * j + q], AbW + FO<N>(kk, q, 0));
       }
       bnd = dyn_bound<N>(p, xr, k, ph);
     }
@@ -1138,7 +1170,7 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
           else { l = -INFINITY; u = 0.0; }
         } else {
           u = 0.0;
-          l = slot == 1 ? -p.fz_max : -INFINITY;  // l[24N+4::5] = -25 (MPC.py:228)
+          l = slot == 1 ? -fz_max() : -INFINITY;  // l[24N+4::5] = -25 (MPC.py:228)
         }
         a.l_out[b * m + r] = l;
         a.u_out[b * m + r] = u;
@@ -1220,7 +1252,7 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
     auto lo_of = [&](int j) __attribute__((always_inline)) -> double {
       if constexpr (FUSED) {
         if (j == 0) return cl ? bnd : -kInf * E[0];
-        if (j == 1) return cl ? 0.0 : -p.fz_max * E[1];
+        if (j == 1) return cl ? 0.0 : -fz_max() * E[1];
         return cl ? -kInf * E[2] : -kInf;
       } else {
         return lo_g[j];
@@ -2173,7 +2205,7 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
         __attribute__((always_inline)) {
       if constexpr (FUSED) {
         const double e0 = cv[CK_E0], e1 = cv[CK_E1], e2 = cv[CK_E2], bd = cv[CK_BND];
-        double fz = p.fz_max;
+        double fz = fz_max();
         asm volatile("" : "+v"(fz));
         lo[0] = cl ? bd : -kInf * e0;
         lo[1] = cl ? 0.0 : -fz * e1;
@@ -3901,7 +3933,11 @@ hipError_t launch_t(bool fused, bool solve, const mpcq_params& p, const LaunchAr
   // polish lives in its own instantiation: the production kernel's code (and its
   // register allocation in the ADMM loop) does not carry it
   const bool pol = p.polish != 0;
-  if (!solve) hipLaunchKernelGGL((engine_kernel<N, true, false, false>), grid, block, 0, s, p, a);
+  const bool rob = a.robots != nullptr && (fused || !solve);
+  if (rob && !solve) hipLaunchKernelGGL((engine_kernel<N, true, false, false, true>), grid, block, 0, s, p, a);
+  else if (rob && pol) hipLaunchKernelGGL((engine_kernel<N, true, true, true, true>), grid, block, 0, s, p, a);
+  else if (rob) hipLaunchKernelGGL((engine_kernel<N, true, true, false, true>), grid, block2, 0, s, p, a);
+  else if (!solve) hipLaunchKernelGGL((engine_kernel<N, true, false, false>), grid, block, 0, s, p, a);
   else if (fused && pol) hipLaunchKernelGGL((engine_kernel<N, true, true, true>), grid, block, 0, s, p, a);
   else if (fused) hipLaunchKernelGGL((engine_kernel<N, true, true, false>), grid, block2, 0, s, p, a);
   else if (pol) hipLaunchKernelGGL((engine_kernel<N, false, true, true>), grid, block, 0, s, p, a);

@@ -50,6 +50,11 @@ struct LaunchArgs {
                         // their decay since -- the resumed launch's order
   int32_t* res_i;       // [B][8]: next iteration, to the next check, to the next adaptation, rho
                         // updates, the half-way sample's iteration, 3 spare
+  // [B] per-instance mass, gI, mu, fz_max (mpcq_set_robots), or null: the launch's mpcq_params.
+  // Indexed by the instance (after the order[] mapping), never by the workgroup; read by the
+  // formulation only: not null selects the engine's ROB instantiations.
+  // (Last, so that the other arguments keep their offsets.)
+  const mpcq_robot* robots;
 };
 constexpr int32_t kStatusSuspended = 100;  // (internal: the host loop resumes these)
 constexpr int64_t res_lanes(int N) { return 16 * (int64_t)((N + 3) & ~3); }

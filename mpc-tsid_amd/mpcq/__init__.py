@@ -7,6 +7,8 @@ Public surface:
   pattern, dims     CSC pattern / sizes of MPC.create_ML
   Engine.plan       batched FootstepPlanner (roll / compute_footsteps / getRefStates)
   Session           B robots in closed loop, all per-tick state resident in HBM
+  robots            per-robot mass / inertia / friction / force limit tables
+                    (Engine.set_robots, Session.set_robots)
   Swing             batched swing-foot trajectories between two ticks (Session.enable_swing)
   synth             seeded synthetic inputs shaped like FootstepPlanner's
 """
@@ -20,8 +22,9 @@ from ._lib import (FLAG_ASYNC, FLAG_DEVICE_PTRS, FLAG_ORDER_BY_CLASS, MODE_SETUP
                    STATUS_DUAL_INFEASIBLE, STATUS_PRIMAL_INFEASIBLE_INACCURATE,
                    STATUS_DUAL_INFEASIBLE_INACCURATE, STATUS_BAD_BOUNDS, MpcqError,
                    Params, build, build_info, default_params, lib, source_sha, supported_horizons,
-                   SV_FRAME, SV_SWING_REF, SV_SWING_STATE, SWING_STATE, SwingParams, default_swing_params)
-from .engine import Engine, dims, pattern  # noqa: F401
+                   SV_FRAME, SV_SWING_REF, SV_SWING_STATE, SWING_STATE, SwingParams, default_swing_params,
+                   Robot, default_robot)
+from .engine import ROBOT_DTYPE, Engine, dims, pattern, robots  # noqa: F401
 from .session import Session  # noqa: F401
 from .swing import Swing  # noqa: F401
 

@@ -76,7 +76,8 @@ EXPORTS = ("mpcq_abi_version", "mpcq_default_params", "mpcq_dims", "mpcq_pattern
            "mpcq_debug_class_order", "mpcq_debug_class_learn", "mpcq_debug_suspended_status",
            "mpcq_debug_suspended", "mpcq_debug_session_order", "mpcq_debug_last_dispatch",
            "mpcq_default_swing_params", "mpcq_swing_step_batch", "mpcq_swing_batch",
-           "mpcq_session_enable_swing")
+           "mpcq_session_enable_swing",
+           "mpcq_default_robot", "mpcq_set_robots", "mpcq_session_set_robots", "mpcq_session_get_robots")
 
 
 class MpcqError(RuntimeError):
@@ -155,6 +156,18 @@ class SwingParams(C.Structure):
         ("feet_z", C.c_double),
         ("k_mpc", C.c_int32),
         ("reserved", C.c_int32 * 7),
+    ]
+
+
+class Robot(C.Structure):
+    """struct mpcq_robot (include/mpcq.h): the per-instance constants of a batch."""
+
+    _fields_ = [
+        ("mass", C.c_double),
+        ("gI", C.c_double * 9),
+        ("mu", C.c_double),
+        ("fz_max", C.c_double),
+        ("reserved", C.c_double * 4),
     ]
 
 
@@ -250,6 +263,13 @@ def lib():
     L.mpcq_session_enable_swing.argtypes = [vp, SP]
     for name in ("mpcq_swing_step_batch", "mpcq_swing_batch", "mpcq_session_enable_swing"):
         getattr(L, name).restype = C.c_int
+    L.mpcq_default_robot.argtypes = [PP, C.POINTER(Robot)]
+    L.mpcq_default_robot.restype = None
+    L.mpcq_set_robots.argtypes = [vp, C.c_int64, vp, C.c_uint32]
+    L.mpcq_session_set_robots.argtypes = [vp, vp, C.c_uint32]
+    L.mpcq_session_get_robots.argtypes = [vp, vp, C.c_uint32]
+    for name in ("mpcq_set_robots", "mpcq_session_set_robots", "mpcq_session_get_robots"):
+        getattr(L, name).restype = C.c_int
     for name in ("mpcq_debug_class_table_read", "mpcq_debug_class_table_write", "mpcq_debug_class_order",
                  "mpcq_debug_class_learn", "mpcq_debug_suspended", "mpcq_debug_session_order",
                  "mpcq_debug_last_dispatch"):
@@ -302,6 +322,13 @@ def default_swing_params(**overrides) -> SwingParams:
             raise AttributeError(f"unknown swing parameter {k}")
         setattr(p, k, v)
     return p
+
+
+def default_robot(params: Params | None = None) -> Robot:
+    """mpcq_default_robot: mass, gI, mu, fz_max of ``params`` (None: the defaults)."""
+    r = Robot()
+    lib().mpcq_default_robot(C.byref(params) if params is not None else None, C.byref(r))
+    return r
 
 
 def build_info() -> dict:

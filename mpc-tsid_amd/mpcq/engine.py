@@ -50,6 +50,36 @@ def _f64(a, shape=None):
     return a
 
 
+# numpy mirror of struct mpcq_robot (L.Robot), gI as the 3x3 it is
+ROBOT_DTYPE = np.dtype([("mass", np.float64), ("gI", np.float64, (3, 3)), ("mu", np.float64),
+                        ("fz_max", np.float64), ("reserved", np.float64, (4,))])
+
+
+def robots(B: int, mass=None, gI=None, mu=None, fz_max=None, params: L.Params | None = None):
+    """A table of per-robot constants for ``Engine.set_robots`` / ``Session.set_robots``: a
+    contiguous (B,) array of ROBOT_DTYPE.  mass, mu, fz_max: a scalar or (B,); gI: (3,3) or
+    (B,3,3).  A field left None comes from ``params`` (None: the default parameters)."""
+    B = int(B)
+    d = L.default_robot(params)
+    out = np.zeros(B, ROBOT_DTYPE)
+    for name, v in (("mass", mass), ("mu", mu), ("fz_max", fz_max)):
+        out[name] = np.broadcast_to(np.asarray(getattr(d, name) if v is None else v, np.float64), (B,))
+    g = np.array(d.gI[:]).reshape(3, 3) if gI is None else np.asarray(gI, np.float64)
+    out["gI"] = np.broadcast_to(g, (B, 3, 3))
+    return out
+
+
+def _robot_table(table, count=None):
+    """(B,) ROBOT_DTYPE, contiguous, from a ROBOT_DTYPE array or a ctypes array of L.Robot."""
+    if not isinstance(table, np.ndarray):
+        table = np.frombuffer(bytes(table), ROBOT_DTYPE)
+    if table.dtype != ROBOT_DTYPE or table.ndim != 1:
+        raise ValueError("a robot table is a (B,) array of mpcq.ROBOT_DTYPE (mpcq.robots())")
+    if count is not None and table.shape[0] != count:
+        raise ValueError(f"expected {count} robots, got {table.shape[0]}")
+    return np.ascontiguousarray(table)
+
+
 class Engine:
     """One HIP context (device, horizon N, parameters)."""
 
@@ -61,6 +91,7 @@ class Engine:
             setattr(self.params, k, v)
         self.n, self.m, self.nnz = dims(self.n_steps)
         self.lock = threading.RLock()
+        self.has_robots = False  # whether a per-robot table is in force (set_robots / set_robots_device)
         h = C.c_void_p()
         L.check(L.lib().mpcq_create(self.device, self.n_steps, C.byref(self.params), C.byref(h)))
         self._h = h
@@ -209,6 +240,24 @@ class Engine:
         second launch, the farthest from convergence first, to their end -- bit-identical
         outputs, a shorter dispatch tail.  0: off."""
         self._call("mpcq_set_slice", self._h, int(slice_iters))
+
+    def set_robots(self, table):
+        """Per-instance mass, gI, mu, fz_max (mpcq_set_robots): instance b of every later
+        formulate / solve takes them from ``table[b]`` (``mpcq.robots()``), everything else from
+        the engine's parameters; a batch larger than the table is an error.  None clears it."""
+        if table is None:
+            self._call("mpcq_set_robots", self._h, 0, None, 0)
+            self.has_robots = False
+            return
+        t = _robot_table(table)
+        self._call("mpcq_set_robots", self._h, t.shape[0], _p(t), 0)
+        self.has_robots = t.shape[0] > 0
+
+    def set_robots_device(self, ptr: int, count: int):
+        """The same from ``count`` mpcq_robot records in device memory (copied on the engine's
+        stream, not validated)."""
+        self._call("mpcq_set_robots", self._h, int(count), C.c_void_p(ptr) if ptr else None, L.FLAG_DEVICE_PTRS)
+        self.has_robots = bool(ptr) and int(count) > 0
 
     def solve_device(self, batch: int, xref_ptr: int, fsteps_ptr: int, f0_ptr: int, status_ptr: int,
                      iters_ptr: int = 0, x_ptr: int = 0, y_ptr: int = 0, mode: int = L.MODE_UPDATE,

@@ -18,7 +18,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from .engine import Engine
+from .engine import ROBOT_DTYPE, Engine, _robot_table
 
 
 def _shapes(B, N):
@@ -65,6 +65,18 @@ class Session:
             L.SV_SWING_STATE: ((B, 4, L.SWING_STATE), np.float64),
             L.SV_FRAME: ((B, 3), np.float64),
         })
+
+    def set_robots(self, table):
+        """The session's own per-robot mass, gI, mu, fz_max (``mpcq.robots(B, ...)``), used from
+        the next tick on; independent of the engine's table.  None clears it."""
+        t = None if table is None else _robot_table(table, self.batch)
+        self.engine._call("mpcq_session_set_robots", self._h, None if t is None else C.c_void_p(t.ctypes.data), 0)
+
+    def get_robots(self):
+        """The table in force, (B,) ROBOT_DTYPE (without one: the engine's parameters)."""
+        out = np.zeros(self.batch, ROBOT_DTYPE)
+        self.engine._call("mpcq_session_get_robots", self._h, C.c_void_p(out.ctypes.data), 0)
+        return out
 
     def close(self):
         if getattr(self, "_h", None):

@@ -269,10 +269,27 @@ class MPC_Wrapper:
         self.not_first_iter = True
         return np.array([0.0, 0.0, 8.0] * 4)
 
-    def solve_batch(self, xref, fsteps, mode: int = L.MODE_UPDATE, want_x: bool = False):
+    def solve_batch(self, xref, fsteps, mode: int = L.MODE_UPDATE, want_x: bool = False, robots=None):
         """Batched hot path: B independent ticks (cold-started OSQP solves) -> f0 (B, 12).
-        Returns (f0, info) with info = dict(status, iters, x)."""
-        r = self.mpc.engine.solve(xref, fsteps, mode, want_x=want_x)  # after any pending tick
+        Returns (f0, info) with info = dict(status, iters, x).  ``robots`` (``mpcq.robots(B,
+        ...)``): per-instance mass, gI, mu, fz_max for this call only -- the engine's table is set for
+        the call and cleared after it, so the single-tick ``run`` keeps the engine's parameters.
+        An engine that already has a table (``Engine.set_robots``) uses it when ``robots`` is
+        None; passing ``robots`` as well is a ValueError, since the call could not put the
+        engine's own table back."""
+        eng = self.mpc.engine  # after any pending tick
+        if robots is not None:
+            with eng.lock:
+                if eng.has_robots:
+                    raise ValueError("the engine already has a robot table (Engine.set_robots): clear it, or "
+                                     "leave robots= out to use it")
+                eng.set_robots(robots)
+                try:
+                    r = eng.solve(xref, fsteps, mode, want_x=want_x)
+                finally:
+                    eng.set_robots(None)
+            return r["f0"], dict(status=r["status"], iters=r["iters"], x=r["x"])
+        r = eng.solve(xref, fsteps, mode, want_x=want_x)
         return r["f0"], dict(status=r["status"], iters=r["iters"], x=r["x"])
 
 

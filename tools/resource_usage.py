@@ -17,8 +17,12 @@ import subprocess
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(REPO, "mpc-tsid_amd", "csrc")
-KIND = {"ELb1ELb1ELb0EE": "fused solve (production)", "ELb1ELb1ELb1EE": "fused solve + polish",
-        "ELb0ELb1ELb0EE": "qp_solve", "ELb0ELb1ELb1EE": "qp_solve + polish", "ELb1ELb0ELb0EE": "formulation only"}
+KIND = {"ELb1ELb1ELb0ELb0EE": "fused solve (production)", "ELb1ELb1ELb1ELb0EE": "fused solve + polish",
+        "ELb0ELb1ELb0ELb0EE": "qp_solve", "ELb0ELb1ELb1ELb0EE": "qp_solve + polish",
+        "ELb1ELb0ELb0ELb0EE": "formulation only",
+        # the instantiations that read a per-robot table (mpcq_set_robots)
+        "ELb1ELb1ELb0ELb1EE": "fused solve, robot table", "ELb1ELb1ELb1ELb1EE": "fused solve + polish, robot table",
+        "ELb1ELb0ELb0ELb1EE": "formulation only, robot table"}
 
 
 def usage(N, extra=()):
