@@ -147,6 +147,10 @@ __device__ __forceinline__ double rbc(double v) { return dppd<0x150 + J>(v); }
 // broadcast lane J of each quad (quad_perm J,J,J,J)
 template <int J>
 __device__ __forceinline__ double qbc(double v) { return dppd<85 * J>(v); }
+// lane i of each quad takes the quad's lane Ji (quad_perm [J0, J1, J2, J3]): a select between
+// quad broadcasts on the lane's place in its quad, as one move
+template <int J0, int J1, int J2, int J3>
+__device__ __forceinline__ double qperm(double v) { return dppd<J0 + 4 * J1 + 16 * J2 + 64 * J3>(v); }
 
 // i0 + sum_{j<12} g_j * v_j, v_j broadcast from lane j of the row (v_fmac_f64_dpp).
 // One dependent chain: the fmac issue interval exceeds its latency.  s_nop 1: a VALU
@@ -221,6 +225,14 @@ __device__ __forceinline__ double bdot_ln6v(const double (&g)[6], double v, doub
       : "+v"(a0)
       : "v"(v), "v"(g[0]), "v"(g[1]), "v"(g[2]), "v"(g[3]), "v"(g[4]), "v"(g[5]));
   return a0;
+}
+// (a + b) * m, rounded as the two C operations, issued where the statement stands relative
+// to the other volatile asm blocks (the sweeps' chains)
+__device__ __forceinline__ double add_mul_here(double a, double b, double m) {
+  double r;
+  asm volatile("v_add_f64 %0, %1, %2\n\t"
+               "v_mul_f64 %0, %0, %3" : "=&v"(r) : "v"(a), "v"(b), "v"(m));
+  return r;
 }
 // lower half: keep a; upper half: b of lane l - 32 (one permlane32_swap per dword)
 __device__ __forceinline__ double keep_lo_take_lo(double a, double b) {
@@ -1474,6 +1486,10 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
             lds_d* const sink = (lds_d*)&sh.red[0] + (t & 31);
             lds_d* const Yb = (half == 1 && s < 12) ? (lds_d*)YVB + (12 * (cr == 0 ? -2 : MID - 1) + rr_)
                                                     : sink;
+            // step MID+1's store: every lane has one target, so it is one store and no branch
+            lds_d* const Ym = ((NS & 1) || cr == 0) ? Yb + 12 * (MID + 1) : sink;
+            lds_d* const Pm = (half == 0 && cr == 0 && s < 12)
+                                  ? (lds_d*)XSB + (12 * SIGX<NS>(MID + 1) + rr_) : Ym;
             // right-hand sides run two steps ahead: step j sums the one of step j+1
             // (loaded during step j-1) and loads the one of step j+2; half 1 (the w
             // products) starts its chain from 0.  The first two (y_kk(0) and step 1's)
@@ -1482,9 +1498,8 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
             const double m0 = half == 0 ? 1.0 : 0.0;
             double s0 = rhs(0)[0], s1 = rhs(0)[RO];
             double c0 = rhs(1)[0], c1 = rhs(1)[RO];
-            asm volatile("" : "+v"(s0), "+v"(s1), "+v"(c0), "+v"(c1));
             double src = half == 0 ? s0 + s1 : 0.0;  // y_kk(0) (half 0)
-            double bcn = (c0 + c1) * m0;
+            double bcn = add_mul_here(c0, c1, m0);
             double b0 = rhs(2)[0], b1 = rhs(2)[RO];
 #pragma unroll
             for (int j = 1; j <= MID + 1; ++j) {
@@ -1510,29 +1525,30 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
               // the next right-hand side is summed after the chain: its loads were
               // issued at the end of the previous step, and summing them ahead of the
               // chain would put their LDS latency on the critical path
-              asm volatile("" : "+v"(b0), "+v"(b1));
-              if (j < MID) bcn = (b0 + b1) * m0;
+              // (the sum and its mask as a volatile asm, which keeps its place behind the chain's
+              // block: an empty-asm launder of b0 / b1 did too, but it redefines them, and the
+              // compiler then copied the first pair and put a wait state in front of every sum)
+              if (j < MID) bcn = add_mul_here(b0, b1, m0);
               if (j + 2 <= MID) {
                 b0 = rhs(j + 2)[0]; b1 = rhs(j + 2)[RO];
               }
               if (j >= 2 && j <= MID) {  // half 1: w of stage kk(j-2)
                 Yb[12 * j] = acc;
-              } else if (j == MID + 1) {  // even N: the bottom's kk(MID-1) is the meeting stage (no w)
-                if constexpr (NS & 1) Yb[12 * j] = acc;
-                else *(cr == 0 ? Yb + 12 * j : sink) = acc;
+              } else if (j == MID + 1) {
+                // the last step's one store: x_m from row 0's state lanes, half 1's last w
+                // (even N: the bottom's kk(MID-1) is the meeting stage, no w), else the sink
+                *Pm = acc;
               }
               if (j <= MID) {
                 // half 0 continues with y_kk(j) (the bottom chain stops after step BOT), half 1
                 // receives y_kk(j-1) from half 0
                 const bool adv = j <= BOT || cr == 0;
                 src = keep_lo_take_lo(adv ? acc : src, src);
+                // (the hand-off stays ahead of the next step's row reads: with the reads
+                // between it and the chain, the chain's opening s_nop is dropped, nop_elide.py)
+                asm volatile("" : "+v"(src));
               } else {
                 xp = acc;
-                // (lane ids from a laundered thread index: held across the loop, the
-                // condition's operand was spilled and its reload waited for here)
-                int tl_ = t;
-                asm volatile("" : "+v"(tl_));
-                if (((tl_ >> 4) & 3) == 0 && (tl_ & 15) < 12) XSB[12 * SIGX<NS>(MID + 1) + (tl_ & 15)] = xp;
               }
             }
             STAMP(6);
@@ -2727,11 +2743,14 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
                   "v"(o.cf[2]));
             static_assert(LN(6) == 8 && LN(7) == 9 && LN(8) == 10 && LN(9) == 12 && LN(10) == 13 && LN(11) == 14,
                           "the broadcast lanes above");
-            const double wf0 = qbc<0>(w[2]), wf1 = qbc<1>(w[2]), wf2 = qbc<2>(w[2]);
+            const double wf1 = qbc<1>(w[2]), wf2 = qbc<2>(w[2]);
             const double wf3 = qbc<3>(w[0]), wf4 = qbc<3>(w[1]);
+            // cc == 1 ? wf2 : wf0 as one quad permute (cc is the lane's place in its quad,
+            // lane 3 shadowing lane 2): two DPP moves instead of four and two selects
+            const double wf02 = qperm<0, 2, 0, 0>(w[2]);
             const double* const A = o.cf;
             sA += A[4] * w[1];
-            sB += A[5] * (cc == 1 ? wf2 : wf0);
+            sB += A[5] * wf02;
             sA += A[6] * (cc == 1 ? wf3 : wf1);
             const double sC = (A[7] * wf2 + A[8] * wf3) + A[9] * wf4;
             colf = (sA + sB) + m2 * sC;
@@ -3169,8 +3188,15 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
               const double bfv = beta * ri0 - bdot_ln6v(qll, gv, 0.0);
               const double dyn = (gv + eH6 * xb) + bfv;
               // friction rows: lane c < 3 owns row c, lane 3 rows 3 and 4 (all loads unconditional)
-              const double q0 = qbc<0>(sf), q1 = qbc<1>(sf), q2 = qbc<2>(sf);
-              const double frA = cFb * q2 + cFa * (ta0 ? q0 : q1);
+              const double q2 = qbc<2>(sf);
+              double q01;
+              if constexpr (kColfFold) {  // ta0 ? q0 : q1 (ta0: quad lanes 0, 1) as one quad permute
+                q01 = qperm<0, 0, 1, 1>(sf);
+              } else {
+                const double q0 = qbc<0>(sf), q1 = qbc<1>(sf);
+                q01 = ta0 ? q0 : q1;
+              }
+              const double frA = cFb * q2 + cFa * q01;
               const double frB = cF4 * q2;
               const double swg = cSw * sf;
               ax[0] = cl ? dyn : frA;
