@@ -152,6 +152,31 @@ __device__ __forceinline__ double qbc(double v) { return dppd<85 * J>(v); }
 template <int J0, int J1, int J2, int J3>
 __device__ __forceinline__ double qperm(double v) { return dppd<J0 + 4 * J1 + 16 * J2 + 64 * J3>(v); }
 
+// Every element of a[] in a register at one point: one empty asm reads and redefines them
+// all, so the loads that produce them are all issued ahead of it and waited for once.  Left
+// to itself the compiler put some of the check's LDS reads one behind the other through the
+// same registers, each with its own s_waitcnt lgkmcnt(0) in front of its use (N = 16: twelve
+// round trips in a row in the residuals' primal side).  Values and
+// arithmetic are untouched.
+#define MPCQ_HV(i) "+v"(a[i])
+#define MPCQ_HV4(i) MPCQ_HV(i), MPCQ_HV(i + 1), MPCQ_HV(i + 2), MPCQ_HV(i + 3)
+template <int n>
+__device__ __forceinline__ void hold_all(double (&a)[n]) {
+  static_assert((n >= 1 && n <= 8) || n == 15 || n == 21, "hold_all: spell this count out");
+  if constexpr (n == 1) asm volatile("" : MPCQ_HV(0));
+  if constexpr (n == 2) asm volatile("" : MPCQ_HV(0), MPCQ_HV(1));
+  if constexpr (n == 3) asm volatile("" : MPCQ_HV(0), MPCQ_HV(1), MPCQ_HV(2));
+  if constexpr (n == 4) asm volatile("" : MPCQ_HV4(0));
+  if constexpr (n == 5) asm volatile("" : MPCQ_HV4(0), MPCQ_HV(4));
+  if constexpr (n == 6) asm volatile("" : MPCQ_HV4(0), MPCQ_HV(4), MPCQ_HV(5));
+  if constexpr (n == 7) asm volatile("" : MPCQ_HV4(0), MPCQ_HV(4), MPCQ_HV(5), MPCQ_HV(6));
+  if constexpr (n == 8) asm volatile("" : MPCQ_HV4(0), MPCQ_HV4(4));
+  if constexpr (n == 15) asm volatile("" : MPCQ_HV4(0), MPCQ_HV4(4), MPCQ_HV4(8), MPCQ_HV(12), MPCQ_HV(13), MPCQ_HV(14));
+  if constexpr (n == 21) asm volatile("" : MPCQ_HV4(0), MPCQ_HV4(4), MPCQ_HV4(8), MPCQ_HV4(12), MPCQ_HV4(16), MPCQ_HV(20));
+}
+#undef MPCQ_HV4
+#undef MPCQ_HV
+
 // i0 + sum_{j<12} g_j * v_j, v_j broadcast from lane j of the row (v_fmac_f64_dpp).
 // One dependent chain: the fmac issue interval exceeds its latency.  s_nop 1: a VALU
 // write of v then a DPP read of it needs two wait states.
@@ -2026,7 +2051,7 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
       }
       return o;
     };
-    const LaneOffs O0 = offs();
+    LaneOffs O0 = offs();  // (re-derived at the top of every stretch of iterations up to 32 stages, below)
 #define MPCQ_LANE_OFFS(RECOMP)                                                                              \
   if constexpr (RECOMP) launder();                                                                         \
   const LaneOffs O_ = (RECOMP) ? offs() : O0;                                                              \
@@ -2058,12 +2083,6 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
       sA += A[6] * (cc == 1 ? wf3 : wf1);
       const double sC = (A[7] * wf2 + A[8] * wf3) + A[9] * wf4;  // friction rows 2..4 (cc == 2)
       return (sA + sB) + m2 * sC;
-    };
-    auto colF_off = [&](const double (&v)[3]) __attribute__((always_inline)) -> double {
-      double A[10];
-#pragma unroll
-      for (int i = 0; i < 10; ++i) A[i] = Ab[fo + i];
-      return colF_c(A, v);
     };
     // Row maxima of several quantities at once, by a transposing butterfly over the
     // 16-lane row: each step pairs lane s with a partner that differs in one bit
@@ -2106,24 +2125,32 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
     // A v on the own rows for own-column values (vf, vX), the previous stage's states in P
     auto rowA = [&](double vf, double vX, lds_cd* P, double (&ax)[3]) __attribute__((always_inline)) {
       MPCQ_LANE_OFFS(true);
+      const int zP = (int)((lds_cd*)sh.zero - P);  // stage 0 has no X_0 term: read zeros, not slot -1
+      // every operand of the rows in one batch of loads (up to 32 stages, hold_all): the
+      // twelve B coefficients, then the state terms' and the friction / swing rows'
+      double L[21];
+#pragma unroll
+      for (int psi = 0; psi < 12; ++psi) L[psi] = Ab[oB0 + 24 * (psi / 3) + 7 * (psi % 3)];
+      L[12] = Ab[oXd]; L[13] = Ab[oHd]; L[14] = P[hp ? oXSp - 12 : zP];
+      L[15] = Ab[oH6]; L[16] = P[hp ? oXSp6 - 12 : zP];
+      L[17] = Ab[oFb]; L[18] = Ab[oFa]; L[19] = Ab[oF4]; L[20] = Ab[oF + 4];
+      if constexpr (!BIG) hold_all(L);
       double bco[12];
 #pragma unroll
       for (int psi = 0; psi < 12; ++psi) {
-        const int fp = psi / 3, cp = psi % 3;
-        const double v = Ab[oB0 + 24 * fp + 7 * cp];
-        bco[psi] = (ph >= 9 || (isv && cp == ph - 6)) ? v : 0.0;
+        const int cp = psi % 3;
+        bco[psi] = (ph >= 9 || (isv && cp == ph - 6)) ? L[psi] : 0.0;
       }
       const double bfx = bdot_ln12(bco, vf, 0.0);
-      double dyn = Ab[oXd] * vX;
-      const int zP = (int)((lds_cd*)sh.zero - P);  // stage 0 has no X_0 term: read zeros, not slot -1
-      const double d1 = dyn + Ab[oHd] * P[hp ? oXSp - 12 : zP];
-      const double d2 = d1 + Ab[oH6] * P[hp ? oXSp6 - 12 : zP];
+      double dyn = L[12] * vX;
+      const double d1 = dyn + L[13] * L[14];
+      const double d2 = d1 + L[15] * L[16];
       dyn = hp ? (isv ? d1 : d2) : dyn;
       dyn = isv ? dyn + bfx : dyn;
       const double q0 = qbc<0>(vf), q1 = qbc<1>(vf), q2 = qbc<2>(vf);
-      const double frA = Ab[oFb] * q2 + Ab[oFa] * (ta0 ? q0 : q1);
-      const double frB = Ab[oF4] * q2;
-      const double swg = Ab[oF + 4] * vf;
+      const double frA = L[17] * q2 + L[18] * (ta0 ? q0 : q1);
+      const double frB = L[19] * q2;
+      const double swg = L[20] * vf;
       ax[0] = cl ? dyn : frA;
       ax[1] = cl ? swg : frB;
       ax[2] = cl ? frA : 0.0;
@@ -2132,11 +2159,20 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
     auto colAt = [&](const double (&w)[3], const double* W, double& atf, double& atX)
         __attribute__((always_inline)) {
       MPCQ_LANE_OFFS(true);
-      atf = colF_off(w);
       const double* wn = W + 12 * (k < N - 1 ? k + 1 : k);
-      const double sXv = Ab[oXd] * w[0];
-      const double x1 = sXv + Ab[oXd + 1] * wn[isv ? ph - 6 : ph];
-      const double x2 = x1 + Ab[oXd + 2] * wn[ph];
+      // the force column's ten coefficients, then the state column's and the next stage's
+      // duals: one batch of loads (up to 32 stages, hold_all)
+      double L[15];
+#pragma unroll
+      for (int i = 0; i < 10; ++i) L[i] = Ab[fo + i];
+      L[10] = Ab[oXd]; L[11] = Ab[oXd + 1]; L[12] = Ab[oXd + 2];
+      L[13] = wn[isv ? ph - 6 : ph]; L[14] = wn[ph];
+      if constexpr (!BIG) hold_all(L);
+      const double A[10] = {L[0], L[1], L[2], L[3], L[4], L[5], L[6], L[7], L[8], L[9]};
+      atf = colF_c(A, w);
+      const double sXv = L[10] * w[0];
+      const double x1 = sXv + L[11] * L[13];
+      const double x2 = x1 + L[12] * L[14];
       atX = k < N - 1 ? (isv ? x2 : x1) : sXv;
     };
     // OSQP 0.6's infeasibility tests (auxil.c is_primal_infeasible / is_dual_infeasible)
@@ -2437,12 +2473,15 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
       if constexpr (INF) {
         // the cheap conditions of infeas_cheap: slots 0 ||E dy||, 2 ||D dx||, 3 ||D^-1 P dx||, 6 u'dy+ + l'dy-
         const int e = s == 2 || s == 3 || s == 6 ? s : 0;
-        double v = D[16 + e];
+        // (every wave's partial read first, up to 32 stages in one batch: the select between the
+        // sum and the maximum is a branch, and each read sat inside it behind its own wait)
+        double tv[NW];
 #pragma unroll
-        for (int w = 1; w < NW; ++w) {
-          const double t2 = D[DS * w + 16 + e];
-          v = s == 6 ? v + t2 : fmax_hw(v, t2);
-        }
+        for (int w = 0; w < NW; ++w) tv[w] = D[DS * w + 16 + e];
+        if constexpr (!BIG) hold_all(tv);
+        double v = tv[0];
+#pragma unroll
+        for (int w = 1; w < NW; ++w) v = s == 6 ? v + tv[w] : fmax_hw(v, tv[w]);
         // kept in VGPRs (every lane holds the same values) and folded into one uniform
         // int at the end: SGPRs here would push loop-carried scalars into VGPR lanes
         // (v_readlane on the hot path, measured)
@@ -3620,7 +3659,15 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
           // held in registers through the iterations up to the next check: no LDS traffic
           // for them in the loop
           RhsOps ops;
-          if constexpr (!kBig<N>) load_rhs_ops(ops);
+          // The offsets the loop's phases take from O0 are derived again here from laundered
+          // coordinates: held across the check, five of them were spilled, and each came back
+          // here as a scratch reload waited for on its own, one round trip after another in
+          // front of the first iteration.
+          if constexpr (!kBig<N>) {
+            launder();
+            O0 = offs();
+            load_rhs_ops(ops);
+          }
           double cvp[CK_COUNT];
 #pragma nounroll
           for (int r_ = 1; r_ < until; ++r_, ++iter)

@@ -1,8 +1,8 @@
 """Cost of one termination check / rho-adaptation step, measured on the production kernel.
 
-    python tools/checkcost.py [--N 16]
+    python tools/checkcost.py [--N 16] [--copies 256]
 
-Runs 256 copies of one C2 instance (one per CU) with adaptive rho off and
+Runs 256 copies of one C2 instance (one per CU; --copies 512: two per CU) with adaptive rho off and
 max_iter fixed, so every configuration runs exactly max_iter iterations, and
 varies check_termination: the time difference per check is the check's cost on
 the critical path.  (A timing experiment only: the solver settings here are not
@@ -22,12 +22,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--N", type=int, default=16)
     ap.add_argument("--iters", type=int, default=2000)
+    ap.add_argument("--copies", type=int, default=256, help="instances in flight (256: one per CU, 512: two)")
     a = ap.parse_args()
     import torch
     import mpcq
     dev = torch.device("cuda", 0)
     src = mpcq.synth.make_batch(1024, a.N, gaits=("trot",), seed=2)
-    B, iters = 256, a.iters
+    B, iters = a.copies, a.iters
     xr = torch.from_numpy(np.ascontiguousarray(np.repeat(src["xref"][:1], B, axis=0))).to(dev)
     fs = torch.from_numpy(np.ascontiguousarray(np.repeat(src["fsteps"][:1], B, axis=0))).to(dev)
     f0 = torch.empty((B, 12), dtype=torch.float64, device=dev)
