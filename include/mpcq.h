@@ -45,7 +45,9 @@ extern "C" {
  *      mpcq_session_enable_swing; MPCQ_SV_SWING_REF / _SWING_STATE / _FRAME (MPCQ_SV_COUNT
  *      17 -> 20; MPCQ_E_INVALID on a session that has not enabled swing)
  *   3 (additions, no bump): mpcq_robot, mpcq_default_robot, mpcq_set_robots,
- *      mpcq_session_set_robots, mpcq_session_get_robots (per-instance mass, gI, mu, fz_max) */
+ *      mpcq_session_set_robots, mpcq_session_get_robots (per-instance mass, gI, mu, fz_max)
+ *   3 (additions, no bump): mpcq_session_reset (any subset of a session's robots back to their
+ *      state after create, between two ticks); MPCQ_SV_FIRST (MPCQ_SV_COUNT 20 -> 21, read-only) */
 #define MPCQ_ABI_VERSION 3
 
 /* error codes (return values) */
@@ -373,11 +375,14 @@ int mpcq_session_tick(mpcq_session* s, int k, const double* state, const double*
 #define MPCQ_SV_SWING_STATE 18 /* [B][4][MPCQ_SWING_STATE] the foot trajectory generators */
 #define MPCQ_SV_FRAME 19    /* [B][3] x, y, yaw of MPCQ_SV_Q_W as they stood before this tick's
                                update: the frame of the tick's fsteps (read-only) */
-#define MPCQ_SV_COUNT 20
+#define MPCQ_SV_FIRST 20    /* [B] int32: 1 = a reset is pending, the robot's next tick runs as a first
+                               tick whatever k says (read-only: mpcq_session_reset sets it, the tick's
+                               retrieve clears it; 0 after create) */
+#define MPCQ_SV_COUNT 21
 /* Copy array `what` to dst (host, or device with MPCQ_FLAG_DEVICE_PTRS); blocking. */
 int mpcq_session_read(mpcq_session* s, int what, void* dst, uint32_t flags);
 /* Overwrite array `what` from src (host, or device with MPCQ_FLAG_DEVICE_PTRS); blocking.
- * MPCQ_SV_ORDER is read-only (MPCQ_E_INVALID). */
+ * MPCQ_SV_ORDER and MPCQ_SV_FIRST are read-only (MPCQ_E_INVALID). */
 int mpcq_session_write(mpcq_session* s, int what, const void* src, uint32_t flags);
 /* Device address of array `what` (valid until mpcq_session_destroy).  The engine reads
  * MPCQ_SV_ORDER as its workgroup -> robot map: writing through its device address is not
@@ -392,6 +397,29 @@ int mpcq_session_set_robots(mpcq_session* s, const mpcq_robot* robots, uint32_t 
 /* The table in force, robots [B] (host, or device with MPCQ_FLAG_DEVICE_PTRS); blocking.
  * Without a table: mpcq_default_robot(the context's params) for every robot. */
 int mpcq_session_get_robots(mpcq_session* s, mpcq_robot* robots, uint32_t flags);
+/* Restart a subset of the robots between two ticks; the others are not written at all.
+ *   mask  [B] int32, nonzero = reset this robot; NULL = every robot
+ *   gait0 [B][20][5] or NULL (the table the session was created with, of which it keeps a
+ *         device copy); q_w0 [B][6] or NULL ((0, 0, 0.2027682, 0, 0, 0), MPC.py:53-56).
+ *         Only the rows of masked robots are read.
+ * Host pointers (blocking, as mpcq_session_tick), or device pointers with
+ * MPCQ_FLAG_DEVICE_PTRS; with MPCQ_FLAG_DEVICE_PTRS | MPCQ_FLAG_ASYNC the call enqueues on
+ * the context's stream and returns: a mask computed on the device never visits the host.
+ * Every per-robot array of a masked robot goes back to what mpcq_session_create leaves
+ * (GAIT: the gait0 row or the creation table; ROT_FLAG 0, H_ROT 0.20, XREF 0, FSTEPS NaN,
+ * Q_W: q_w0 or the default; STATE / L_FEET: the virtual robot standing at h_ref, feet under
+ * the shoulders; RHO params.rho; Y, the warm start, X, F0, X_ROBOT, COST, STATUS, ITERS 0;
+ * with swing enabled SWING_STATE, SWING_REF, FRAME 0), and its MPCQ_SV_FIRST is set: its next
+ * tick is a first tick whatever k the call passes (the extra compute_footsteps, h_ref in
+ * getRefStates, create_matrices, a cold solve at params.rho that reads no warm x or y), while
+ * every other robot runs as k says (k == 0 still makes every robot first).  The tick's
+ * retrieve clears the flag.  Robots with a pending reset go to the front of MPCQ_SV_ORDER (a
+ * cold solve is a robot's longest).  The session's robots table is kept.  Nothing but s is
+ * validated: a malformed gait0 row shows as MPCQ_STATUS_BAD_GAIT on the robot's next tick,
+ * as at create.  A session on which this was never called launches exactly what it did
+ * before. */
+int mpcq_session_reset(mpcq_session* s, const int32_t* mask, const double* gait0,
+                       const double* q_w0, uint32_t flags);
 
 /* ---- swing-foot trajectories ----------------------------------------------
  * The consumer of (gait, fsteps) between two MPC ticks: the position, velocity and

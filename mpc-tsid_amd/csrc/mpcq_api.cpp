@@ -887,6 +887,11 @@ struct mpcq_session {
   mpcq_swing_params sp{};
   void* swing_mem = nullptr;
   RobotTable robots;  // mpcq_session_set_robots (the session's own, not the context's)
+  // mpcq_session_reset: the gait table every robot was created with, and whether a reset was
+  // ever called (from then on the ticks consult MPCQ_SV_FIRST)
+  double* gait_init = nullptr;
+  double* in_gait = nullptr;  // staging of a host gait0
+  bool resets = false;
 };
 
 namespace {
@@ -911,6 +916,7 @@ size_t sv_bytes(int what, int64_t B, int N) {
     case MPCQ_SV_ROT_FLAG: return b * 4;
     case MPCQ_SV_H_ROT: return b * 8;
     case MPCQ_SV_ORDER: return b * 4;
+    case MPCQ_SV_FIRST: return b * 4;
   }
   return 0;
 }
@@ -939,7 +945,7 @@ int mpcq_session_create(mpcq_ctx* c, int64_t B, const mpcq_planner_params* pp, c
   for (int w = 0; w < MPCQ_SV_COUNT; ++w) { s->bytes[w] = sv_bytes(w, B, N); off[w] = take(s->bytes[w]); }
   const size_t o_wx = take((size_t)B * 24 * N * 8), o_ps = take((size_t)B * 4), o_in = take((size_t)B * 16),
                o_st = take((size_t)B * 96), o_lf = take((size_t)B * 96), o_vr = take((size_t)B * 48),
-               o_rd = take((size_t)B * 4);
+               o_rd = take((size_t)B * 4), o_gi = take((size_t)B * 100 * 8), o_gs = take((size_t)B * 100 * 8);
   DeviceGuard g(c->device);
   if (hipMalloc(&s->mem, tot) != hipSuccess) {
     delete s;
@@ -960,6 +966,8 @@ int mpcq_session_create(mpcq_ctx* c, int64_t B, const mpcq_planner_params* pp, c
   s->in_lfeet = (double*)(base + o_lf);
   s->in_vref = (double*)(base + o_vr);
   s->in_reduced = (int32_t*)(base + o_rd);
+  s->gait_init = (double*)(base + o_gi);
+  s->in_gait = (double*)(base + o_gs);
   s->order = (int32_t*)s->arr[MPCQ_SV_ORDER];
   {
     const char* e = getenv("MPCQ_DISPATCH_ORDER");
@@ -975,8 +983,12 @@ int mpcq_session_create(mpcq_ctx* c, int64_t B, const mpcq_planner_params* pp, c
   auto put = [&](int w, const void* src) {
     if (!err && hipMemcpy(s->arr[w], src, s->bytes[w], hipMemcpyHostToDevice) != hipSuccess) err = 1;
   };
+  auto keep_gait = [&](const void* src) {  // the table a reset without gait0 goes back to
+    if (!err && hipMemcpy(s->gait_init, src, s->bytes[MPCQ_SV_GAIT], hipMemcpyHostToDevice) != hipSuccess) err = 1;
+  };
   if (gait0) {
     put(MPCQ_SV_GAIT, gait0);
+    keep_gait(gait0);
   } else {  // create_walking_trot (FootstepPlanner.py:193-214): [1, 7, 1, 7] per 16-step period
     const int half = (int)(0.5 * s->pp.T_gait / s->pp.dt);
     const int per = 2 * half, nper = per > 0 ? N / per : 0;
@@ -997,6 +1009,7 @@ int mpcq_session_create(mpcq_ctx* c, int64_t B, const mpcq_planner_params* pp, c
       }
     }
     put(MPCQ_SV_GAIT, h);
+    keep_gait(h);
   }
   for (size_t e = 0; e < (size_t)B * 12 * (N + 1); ++e) h[e] = 0.0;
   put(MPCQ_SV_XREF, h);  // FootstepPlanner.py:58
@@ -1157,8 +1170,14 @@ int mpcq_session_tick(mpcq_session* s, int k, const double* state, const double*
   pa.xref = (double*)s->arr[MPCQ_SV_XREF];
   pa.fsteps = (double*)s->arr[MPCQ_SV_FSTEPS];
   pa.status = s->plan_status;
+  // after a mpcq_session_reset: a robot whose MPCQ_SV_FIRST is set runs this tick as a first
+  // tick whatever k says (the planner's extra pass then touches those robots only)
+  // (k == 0 makes every robot first by itself: only the retrieve takes the flags then, to clear them)
+  int32_t* const first = s->resets ? (int32_t*)s->arr[MPCQ_SV_FIRST] : nullptr;
+  const int32_t* const first_k = k == 0 ? nullptr : first;
+  pa.first = first_k;
   HIP_TRY(hipEventRecord(c->ev[0], c->stream));
-  if (k == 0) {  // update_fsteps(0, ...): no roll
+  if (k == 0 || first_k) {  // update_fsteps(0, ...): no roll
     pa.ops = MPCQ_PLAN_FOOTSTEPS;
     HIP_TRY(mpcq::launch_plan(s->pp, pa, c->stream));
   }
@@ -1189,6 +1208,7 @@ int mpcq_session_tick(mpcq_session* s, int k, const double* state, const double*
   if (k == 0) s->have_order = false;
   la.order = s->have_order && s->use_order ? s->order : nullptr;
   la.robots = s->robots.count ? s->robots.dev : nullptr;
+  la.first = first_k;
   {
     const int wrc = ensure_work(c, B, &la.work);
     if (wrc) return wrc;
@@ -1218,6 +1238,7 @@ int mpcq_session_tick(mpcq_session* s, int k, const double* state, const double*
   for (int i = 0; i < 12; ++i) ra.state_weights[i] = c->p.state_weights[i];
   ra.force_weight = c->p.force_weight;
   for (int i = 0; i < 8; ++i) ra.shoulders[i] = s->pp.shoulders[i];
+  ra.first = first;
   if (s->swing) {  // the frame of this tick's fsteps: q_w's x, y, yaw before the retrieve moves it
     double* fr = (double*)s->arr[MPCQ_SV_FRAME];
     const double* qw = (const double*)s->arr[MPCQ_SV_Q_W];
@@ -1225,7 +1246,8 @@ int mpcq_session_tick(mpcq_session* s, int k, const double* state, const double*
     HIP_TRY(hipMemcpy2DAsync(fr + 2, 24, qw + 5, 48, 8, (size_t)B, hipMemcpyDeviceToDevice, c->stream));
   }
   HIP_TRY(mpcq::launch_retrieve(N, ra, c->stream));
-  HIP_TRY(mpcq::launch_order((const int32_t*)s->arr[MPCQ_SV_ITERS], B, s->order, c->stream));
+  // (the retrieve has cleared every pending reset: the order is by iteration counts alone)
+  HIP_TRY(mpcq::launch_order((const int32_t*)s->arr[MPCQ_SV_ITERS], nullptr, B, s->order, c->stream));
   s->have_order = true;
   if (s->swing) {  // the tick's swing-foot references, substeps 0..k_mpc-1 (virtual-robot lift-off)
     mpcq::SwingArgs sa{};
@@ -1241,6 +1263,82 @@ int mpcq_session_tick(mpcq_session* s, int k, const double* state, const double*
   }
   // host inputs are staged in buffers the next tick reuses: host calls block
   if (!(flags & MPCQ_FLAG_ASYNC) || !dev) HIP_TRY(hipStreamSynchronize(c->stream));
+  return MPCQ_OK;
+}
+
+int mpcq_session_reset(mpcq_session* s, const int32_t* mask, const double* gait0, const double* q_w0,
+                       uint32_t flags) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  mpcq_ctx* c = s->ctx;
+  DeviceGuard g(c->device);
+  const int N = c->N;
+  const int64_t B = s->B;
+  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
+  // host arrays go through the session's staging buffers (the tick's, and one for the gait
+  // tables): stream-ordered with the ticks, and the call blocks before they can be reused
+  if (!dev) {
+    hipError_t e = hipSuccess;
+    if (mask) {
+      e = hipMemcpyAsync(s->in_reduced, mask, (size_t)B * 4, hipMemcpyHostToDevice, c->stream);
+      mask = s->in_reduced;
+    }
+    if (gait0 && e == hipSuccess) {
+      e = hipMemcpyAsync(s->in_gait, gait0, (size_t)B * 800, hipMemcpyHostToDevice, c->stream);
+      gait0 = s->in_gait;
+    }
+    if (q_w0 && e == hipSuccess) {
+      e = hipMemcpyAsync(s->in_vref, q_w0, (size_t)B * 48, hipMemcpyHostToDevice, c->stream);
+      q_w0 = s->in_vref;
+    }
+    if (e != hipSuccess) {
+      (void)hipStreamSynchronize(c->stream);
+      return fail(MPCQ_E_DEVICE, "staging the reset's inputs failed");
+    }
+  }
+  mpcq::ResetArgs ra{};
+  ra.batch = B;
+  ra.N = N;
+  ra.mask = mask;
+  ra.gait_src = gait0 ? gait0 : s->gait_init;
+  ra.q_w0 = q_w0;
+  ra.h_ref = s->pp.h_ref;
+  ra.rho0 = c->p.rho;
+  for (int i = 0; i < 8; ++i) ra.shoulders[i] = s->pp.shoulders[i];
+  ra.gait = (double*)s->arr[MPCQ_SV_GAIT];
+  ra.rot_flag = (int32_t*)s->arr[MPCQ_SV_ROT_FLAG];
+  ra.h_rot = (double*)s->arr[MPCQ_SV_H_ROT];
+  ra.xref = (double*)s->arr[MPCQ_SV_XREF];
+  ra.fsteps = (double*)s->arr[MPCQ_SV_FSTEPS];
+  ra.q_w = (double*)s->arr[MPCQ_SV_Q_W];
+  ra.state = (double*)s->arr[MPCQ_SV_STATE];
+  ra.l_feet = (double*)s->arr[MPCQ_SV_L_FEET];
+  ra.rho = (double*)s->arr[MPCQ_SV_RHO];
+  ra.y = (double*)s->arr[MPCQ_SV_Y];
+  ra.warm_x = s->warm_x;
+  ra.x = (double*)s->arr[MPCQ_SV_X];
+  ra.f0 = (double*)s->arr[MPCQ_SV_F0];
+  ra.x_robot = (double*)s->arr[MPCQ_SV_X_ROBOT];
+  ra.cost = (double*)s->arr[MPCQ_SV_COST];
+  ra.status = (int32_t*)s->arr[MPCQ_SV_STATUS];
+  ra.iters = (int32_t*)s->arr[MPCQ_SV_ITERS];
+  ra.first = (int32_t*)s->arr[MPCQ_SV_FIRST];
+  if (s->swing) {
+    ra.swing_ref = (double*)s->arr[MPCQ_SV_SWING_REF];
+    ra.swing_ref_doubles = (int64_t)s->sp.k_mpc * 36;
+    ra.swing_state = (double*)s->arr[MPCQ_SV_SWING_STATE];
+    ra.frame = (double*)s->arr[MPCQ_SV_FRAME];
+  }
+  hipError_t e = mpcq::launch_reset(ra, c->stream);
+  // the robots with a pending reset to the front of the next solve's dispatch (a session that
+  // has not ticked yet has no order in use: it keeps the identity)
+  if (e == hipSuccess && s->have_order)
+    e = mpcq::launch_order((const int32_t*)s->arr[MPCQ_SV_ITERS], ra.first, B, s->order, c->stream);
+  s->resets = true;
+  if (!(flags & MPCQ_FLAG_ASYNC) || !dev) {
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = es;
+  }
+  HIP_TRY(e);
   return MPCQ_OK;
 }
 
@@ -1261,6 +1359,8 @@ int mpcq_session_write(mpcq_session* s, int what, const void* src, uint32_t flag
   if (!s->arr[what]) return fail(MPCQ_E_INVALID, "session array %d needs mpcq_session_enable_swing", what);
   // the engine indexes robots through the order: only order_kernel writes it
   if (what == MPCQ_SV_ORDER) return fail(MPCQ_E_INVALID, "MPCQ_SV_ORDER is read-only");
+  // only mpcq_session_reset sets it (with the state a first tick needs), only the retrieve clears it
+  if (what == MPCQ_SV_FIRST) return fail(MPCQ_E_INVALID, "MPCQ_SV_FIRST is read-only");
   if (what == MPCQ_SV_SWING_REF || what == MPCQ_SV_FRAME)
     return fail(MPCQ_E_INVALID, "MPCQ_SV_SWING_REF and MPCQ_SV_FRAME are read-only");
   DeviceGuard g(s->ctx->device);
@@ -1381,7 +1481,7 @@ int mpcq_debug_session_order(mpcq_ctx* c, int64_t B, const int32_t* iters, int32
   Xfer xs[2] = {{iters, nullptr, (size_t)B * 4, nullptr}, {nullptr, order, (size_t)B * 4, nullptr}};
   rc = stage(c, xs, 2);
   if (rc) return rc;
-  HIP_TRY(mpcq::launch_order((const int32_t*)xs[0].dev, B, (int32_t*)xs[1].dev, c->stream));
+  HIP_TRY(mpcq::launch_order((const int32_t*)xs[0].dev, nullptr, B, (int32_t*)xs[1].dev, c->stream));
   return unstage(c, xs, 2);
 }
 

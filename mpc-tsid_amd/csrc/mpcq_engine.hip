@@ -993,6 +993,10 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
     if (a.batch_dev && (int64_t)blockIdx.x >= (int64_t)*a.batch_dev) return;
   }
   const int64_t b = a.order ? (int64_t)a.order[blockIdx.x] : (int64_t)blockIdx.x;  // the instance
+  // a session's robot with a pending reset (uniform per workgroup): the first tick's
+  // formulation and a cold start, whatever a.mode and the warm pointers say.  The warm loads
+  // are skipped, not fed zeros: row_A of a zero vector may leave -0 where the cold point holds +0.
+  const bool first = a.first && a.first[b] != 0;
   [[maybe_unused]] double fz_rob = 0.0;
   if constexpr (ROB) fz_rob = uni(a.robots[b].fz_max);
   auto fz_max = [&]() __attribute__((always_inline)) -> double {
@@ -1171,7 +1175,7 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
           double ft;
-          if (a.mode == MPCQ_MODE_SETUP)
+          if (first || a.mode == MPCQ_MODE_SETUP)
             ft = q == 0 ? p.footholds[4 * r] : (q == 1 ? p.footholds[4 * r + 1]
                                               : (q == 2 ? p.footholds[4 * r + 2] : p.footholds[4 * r + 3]));
           else {
@@ -1263,7 +1267,7 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
     uint64_t fac_cycles = 0;
 #endif
     // (a resumed slice: the rho and the update count it was suspended with)
-    double rho_s = kSlice<N> && a.resume ? a.res_rho[b] : (a.rho_in ? a.rho_in[b] : p.rho);
+    double rho_s = kSlice<N> && a.resume ? a.res_rho[b] : (a.rho_in && !first ? a.rho_in[b] : p.rho);
     rho_s = fmin(fmax(rho_s, kRhoMin), kRhoMax);
     if (kSlice<N> && a.resume) n_upd = a.res_i[8 * b + 3];
 
@@ -2646,7 +2650,7 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
         q[CK_E0] = E[0]; q[CK_E1] = E[1]; q[CK_E2] = E[2]; q[CK_BND] = bnd;
       }
       // warm start (osqp_warm_start: x = D^-1 x0, z = A x; y = c E^-1 y0)
-      if (a.warm_x) {
+      if (a.warm_x && !first) {
         xf = a.warm_x[b * n + colF] / Df;
         xX = a.warm_x[b * n + colX] / DX;
         if (cl) sh.u.it.xs[k + 1][ph] = xX;
@@ -2655,7 +2659,7 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
         if (!cl) z[2] = 0.0;
         sync_all();
       }
-      if (a.warm_y) {
+      if (a.warm_y && !first) {
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
           const int r = nat_row(j);

@@ -55,6 +55,10 @@ struct LaunchArgs {
   // formulation only: not null selects the engine's ROB instantiations.
   // (Last, so that the other arguments keep their offsets.)
   const mpcq_robot* robots;
+  // [B] or null (a session after mpcq_session_reset): nonzero = this instance (after the
+  // order[] mapping) runs a first tick -- MPCQ_MODE_SETUP and a cold start that reads none of
+  // warm_x, warm_y, rho_in -- whatever mode and the warm pointers say.  Batch solves: null.
+  const int32_t* first;
 };
 constexpr int32_t kStatusSuspended = 100;  // (internal: the host loop resumes these)
 constexpr int64_t res_lanes(int N) { return 16 * (int64_t)((N + 3) & ~3); }
@@ -113,6 +117,10 @@ struct PlanArgs {
   double* xref;        // [B][12][N+1] in/out
   double* fsteps;      // [B][20][13] out
   int32_t* status;     // [B] or null
+  // [B] or null (a session after mpcq_session_reset): instance b plans with k = 0 where
+  // first[b] != 0, else with k; a launch of MPCQ_PLAN_FOOTSTEPS alone (the first tick's
+  // extra pass) then touches only the instances with first[b] != 0
+  const int32_t* first;
 };
 
 hipError_t launch_plan(const mpcq_planner_params& pp, const PlanArgs& a, hipStream_t s);
@@ -138,12 +146,50 @@ struct SessionArgs {
   double state_weights[12];
   double force_weight;
   double shoulders[8];
+  int32_t* first;        // [B] or null: cleared (the robot's pending reset is served)
 };
 
 hipError_t launch_retrieve(int N, const SessionArgs& a, hipStream_t s);
 // Dispatch order of the next tick's solve (mpcq_session.hip): the robots sorted by
-// this tick's iteration counts, longest first (buckets of 16 iterations).
-hipError_t launch_order(const int32_t* iters, int64_t batch, int32_t* order, hipStream_t s);
+// this tick's iteration counts, longest first (buckets of 16 iterations); first [B] or
+// null: a robot with a pending reset (a cold solve next) goes into the top bucket.
+hipError_t launch_order(const int32_t* iters, const int32_t* first, int64_t batch, int32_t* order, hipStream_t s);
+
+// mpcq_session_reset (mpcq_session.hip): the per-robot arrays of the robots with
+// mask[b] != 0 (null: all) back to what mpcq_session_create leaves; one wave64 per robot.
+struct ResetArgs {
+  int64_t batch;
+  int N;
+  const int32_t* mask;   // [B] or null
+  const double* gait_src;// [B][20][5]: the caller's gait0 or the session's creation table
+  const double* q_w0;    // [B][6] or null: the default pose
+  double h_ref, rho0;
+  double shoulders[8];
+  double* gait;          // [B][20][5]
+  int32_t* rot_flag;     // [B]
+  double* h_rot;         // [B]
+  double* xref;          // [B][12][N+1]
+  double* fsteps;        // [B][20][13]
+  double* q_w;           // [B][6]
+  double* state;         // [B][12]
+  double* l_feet;        // [B][3][4]
+  double* rho;           // [B]
+  double* y;             // [B][44N]
+  double* warm_x;        // [B][24N]
+  double* x;             // [B][24N]
+  double* f0;            // [B][12]
+  double* x_robot;       // [B][12][N]
+  double* cost;          // [B][13]
+  int32_t* status;       // [B]
+  int32_t* iters;        // [B]
+  int32_t* first;        // [B] set to 1
+  // the swing arrays, or null on a session without them
+  double* swing_ref;     // [B][swing_ref_doubles]
+  int64_t swing_ref_doubles;
+  double* swing_state;   // [B][4][MPCQ_SWING_STATE]
+  double* frame;         // [B][3]
+};
+hipError_t launch_reset(const ResetArgs& a, hipStream_t s);
 
 // Dispatch order of a batch solve by gait class (mpcq_order.hip, MPCQ_FLAG_ORDER_BY_CLASS):
 // cls[B] = each instance's class slot, order[B] = the instances by the expected cost their

@@ -87,6 +87,11 @@ __global__ __launch_bounds__(64) void planner_kernel(mpcq_planner_params pp, Pla
   PlanShared<WIDE, L>& sh = shv[sub];
   const int64_t b = (int64_t)blockIdx.x * RPW + sub;
   if (b >= a.batch) return;  // (the other half, if any, runs on alone: no barrier below)
+  // a session after mpcq_session_reset: the tick index is the instance's own (per half of the
+  // wave at L = 32), and the first tick's extra pass is for the first instances alone
+  const bool first = a.first && a.first[b] != 0;
+  if (a.first && a.ops == MPCQ_PLAN_FOOTSTEPS && !first) return;
+  const int tick_k = first ? 0 : a.k;
   const int N = a.N, NP = a.N + 1;
   double* gg = a.gait + b * 100;
   double* gx = a.xref + b * 12 * NP;
@@ -291,7 +296,7 @@ __global__ __launch_bounds__(64) void planner_kernel(mpcq_planner_params pp, Pla
       }
       x[0] = dt * a0 + st[0];
       x[1] = dt * a1 + st[1];
-      if (a.k == 0) x[2] = pp.h_ref;
+      if (tick_k == 0) x[2] = pp.h_ref;
       x[5] = vr[5] * linspace_at(dt, Tg, N, j - 1);
       x[11] = vr[5];
     }
@@ -387,7 +392,7 @@ __global__ __launch_bounds__(64) void planner_kernel(mpcq_planner_params pp, Pla
         }
         xx[0] = dt * a0 + st[0];
         xx[1] = dt * a1 + st[1];
-        if (a.k == 0) xx[2] = pp.h_ref;
+        if (tick_k == 0) xx[2] = pp.h_ref;
         xx[5] = vr[5] * linspace_at(dt, Tg, N, j - 1);
         xx[11] = vr[5];
       }

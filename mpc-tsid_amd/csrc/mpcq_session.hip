@@ -91,6 +91,7 @@ __global__ __launch_bounds__(64) void retrieve_kernel(SessionArgs a) {
   if (lane < 12) a.cost[b * 13 + lane] = pairwise<N>(cost + lane, 12);
   if (lane == 12) a.cost[b * 13 + 12] = pairwise<12 * N>(cost + 12 * N, 1);
   if (lane == 0 && a.plan_status[b] != 0) a.status[b] = a.plan_status[b];
+  if (lane == 0 && a.first) a.first[b] = 0;  // a pending reset is served: the next tick runs as k says
   if (lane == 0 && !failed) {  // a failed robot keeps its pose and virtual state
     // q_next = x_robot[0:6, 0], v_next = x_robot[6:12, 0]
     double qn[12];
@@ -150,33 +151,95 @@ __global__ __launch_bounds__(64) void retrieve_kernel(SessionArgs a) {
 // one (tools/tick_iters.py), and index-order dispatch puts long solves that land
 // late in the launch on its critical path.
 constexpr int kOrderBuckets = 256;
-__global__ __launch_bounds__(1024) void order_kernel(const int32_t* __restrict__ iters, int64_t B,
+// first (or null): a robot with a pending reset solves cold next, the longest a robot ever
+// runs: a bucket of its own above every iteration count.
+__global__ __launch_bounds__(1024) void order_kernel(const int32_t* __restrict__ iters,
+                                                     const int32_t* __restrict__ first, int64_t B,
                                                      int32_t* __restrict__ order) {
-  __shared__ int hist[kOrderBuckets];
+  __shared__ int hist[kOrderBuckets + 1];
   const int t = threadIdx.x;
-  auto bucket = [](int32_t it) { const int q = (it > 0 ? it : 0) >> 4; return q < kOrderBuckets - 1 ? q : kOrderBuckets - 1; };
-  if (t < kOrderBuckets) hist[t] = 0;
+  auto bucket = [&](int64_t i) {
+    if (first && first[i] != 0) return kOrderBuckets;
+    const int32_t it = iters[i];
+    const int q = (it > 0 ? it : 0) >> 4;
+    return q < kOrderBuckets - 1 ? q : kOrderBuckets - 1;
+  };
+  if (t <= kOrderBuckets) hist[t] = 0;
   __syncthreads();
-  for (int64_t i = t; i < B; i += blockDim.x) atomicAdd(&hist[bucket(iters[i])], 1);
+  for (int64_t i = t; i < B; i += blockDim.x) atomicAdd(&hist[bucket(i)], 1);
   __syncthreads();
   if (t == 0) {  // exclusive offsets, the longest bucket first
     int acc = 0;
-    for (int q = kOrderBuckets - 1; q >= 0; --q) {
+    for (int q = kOrderBuckets; q >= 0; --q) {
       const int h = hist[q];
       hist[q] = acc;
       acc += h;
     }
   }
   __syncthreads();
-  for (int64_t i = t; i < B; i += blockDim.x) order[atomicAdd(&hist[bucket(iters[i])], 1)] = (int32_t)i;
+  for (int64_t i = t; i < B; i += blockDim.x) order[atomicAdd(&hist[bucket(i)], 1)] = (int32_t)i;
+}
+
+// mpcq_session_reset: one wave64 per robot; a robot whose mask entry is 0 is not touched.
+__global__ __launch_bounds__(64) void reset_kernel(ResetArgs a) {
+  const int lane = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  if (b >= a.batch) return;
+  if (a.mask && a.mask[b] == 0) return;
+  const int N = a.N;
+  auto fill = [&](double* p, int64_t per, double v) __attribute__((always_inline)) {
+    double* q = p + b * per;
+    for (int64_t e = lane; e < per; e += 64) q[e] = v;
+  };
+  {
+    const double* gs = a.gait_src + b * 100;
+    double* gd = a.gait + b * 100;
+    for (int e = lane; e < 100; e += 64) gd[e] = gs[e];
+  }
+  fill(a.xref, 12 * (N + 1), 0.0);
+  fill(a.fsteps, 260, NAN);
+  fill(a.y, 44 * N, 0.0);
+  fill(a.warm_x, 24 * N, 0.0);
+  fill(a.x, 24 * N, 0.0);
+  fill(a.x_robot, 12 * N, 0.0);
+  fill(a.f0, 12, 0.0);
+  fill(a.cost, 13, 0.0);
+  if (lane < 6) {  // MPC.py:53-56
+    const double d = lane == 2 ? 0.2027682 : 0.0;
+    a.q_w[b * 6 + lane] = a.q_w0 ? a.q_w0[b * 6 + lane] : d;
+  }
+  if (lane < 12) {  // the virtual robot standing at h_ref, its feet under the shoulders
+    a.state[b * 12 + lane] = lane == 2 ? a.h_ref : 0.0;
+    a.l_feet[b * 12 + lane] = lane < 8 ? a.shoulders[lane] : 0.0;
+  }
+  if (lane == 0) {
+    a.rot_flag[b] = 0;
+    a.h_rot[b] = 0.20;  // FootstepPlanner.py:68
+    a.rho[b] = a.rho0;
+    a.status[b] = 0;
+    a.iters[b] = 0;
+    a.first[b] = 1;
+  }
+  if (a.swing_state) {  // all-zero state = new generators
+    fill(a.swing_ref, a.swing_ref_doubles, 0.0);
+    fill(a.swing_state, 4 * MPCQ_SWING_STATE, 0.0);
+    fill(a.frame, 3, 0.0);
+  }
 }
 
 }  // namespace
 
-hipError_t launch_order(const int32_t* iters, int64_t batch, int32_t* order, hipStream_t s) {
+hipError_t launch_order(const int32_t* iters, const int32_t* first, int64_t batch, int32_t* order, hipStream_t s) {
   if (batch <= 0) return hipSuccess;
   if (batch > INT32_MAX) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(order_kernel, dim3(1), dim3(1024), 0, s, iters, batch, order);
+  hipLaunchKernelGGL(order_kernel, dim3(1), dim3(1024), 0, s, iters, first, batch, order);
+  return hipGetLastError();
+}
+
+hipError_t launch_reset(const ResetArgs& a, hipStream_t s) {
+  if (a.batch <= 0) return hipSuccess;
+  if (a.batch > INT32_MAX) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(reset_kernel, dim3((unsigned)a.batch), dim3(64), 0, s, a);
   return hipGetLastError();
 }
 

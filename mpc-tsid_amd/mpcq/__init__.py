@@ -7,6 +7,7 @@ Public surface:
   pattern, dims     CSC pattern / sizes of MPC.create_ML
   Engine.plan       batched FootstepPlanner (roll / compute_footsteps / getRefStates)
   Session           B robots in closed loop, all per-tick state resident in HBM
+                    (Session.reset: any subset of them back to their initial state)
   robots            per-robot mass / inertia / friction / force limit tables
                     (Engine.set_robots, Session.set_robots)
   Swing             batched swing-foot trajectories between two ticks (Session.enable_swing)
@@ -16,7 +17,7 @@ from . import synth  # noqa: F401
 from ._lib import (FLAG_ASYNC, FLAG_DEVICE_PTRS, FLAG_ORDER_BY_CLASS, MODE_SETUP, MODE_UPDATE,  # noqa: F401
                    PLAN_FOOTSTEPS, PLAN_REFSTATES, PLAN_ROLL, PLAN_TICK, PlannerParams,
                    default_planner_params, STATUS_BAD_GAIT, SV_COST, SV_F0, SV_FSTEPS, SV_GAIT,
-                   SV_H_ROT, SV_ITERS, SV_ORDER, SV_L_FEET, SV_Q_W, SV_RHO, SV_ROT_FLAG, SV_STATE, SV_STATUS, SV_X,
+                   SV_H_ROT, SV_ITERS, SV_ORDER, SV_FIRST, SV_L_FEET, SV_Q_W, SV_RHO, SV_ROT_FLAG, SV_STATE, SV_STATUS, SV_X,
                    SV_X_ROBOT, SV_XREF, SV_Y, STATUS_FACTOR_FAILED, STATUS_MAX_ITER_REACHED,
                    STATUS_NONFINITE, STATUS_SOLVED, STATUS_SOLVED_INACCURATE, STATUS_PRIMAL_INFEASIBLE,
                    STATUS_DUAL_INFEASIBLE, STATUS_PRIMAL_INFEASIBLE_INACCURATE,

@@ -63,6 +63,7 @@ SV_ORDER = 16  # read-only: the next tick's dispatch order
 # only on a session with enable_swing: the tick's swing-foot references (read-only), the
 # generators' state, the frame of the tick's fsteps (read-only)
 SV_SWING_REF, SV_SWING_STATE, SV_FRAME = 17, 18, 19
+SV_FIRST = 20  # read-only: 1 = a reset is pending, the robot's next tick runs as a first tick
 SWING_STATE = 40  # MPCQ_SWING_STATE: doubles per foot
 
 EXPORTS = ("mpcq_abi_version", "mpcq_default_params", "mpcq_dims", "mpcq_pattern",
@@ -77,7 +78,8 @@ EXPORTS = ("mpcq_abi_version", "mpcq_default_params", "mpcq_dims", "mpcq_pattern
            "mpcq_debug_suspended", "mpcq_debug_session_order", "mpcq_debug_last_dispatch",
            "mpcq_default_swing_params", "mpcq_swing_step_batch", "mpcq_swing_batch",
            "mpcq_session_enable_swing",
-           "mpcq_default_robot", "mpcq_set_robots", "mpcq_session_set_robots", "mpcq_session_get_robots")
+           "mpcq_default_robot", "mpcq_set_robots", "mpcq_session_set_robots", "mpcq_session_get_robots",
+           "mpcq_session_reset")
 
 
 class MpcqError(RuntimeError):
@@ -270,6 +272,8 @@ def lib():
     L.mpcq_session_get_robots.argtypes = [vp, vp, C.c_uint32]
     for name in ("mpcq_set_robots", "mpcq_session_set_robots", "mpcq_session_get_robots"):
         getattr(L, name).restype = C.c_int
+    L.mpcq_session_reset.argtypes = [vp, vp, vp, vp, C.c_uint32]
+    L.mpcq_session_reset.restype = C.c_int
     for name in ("mpcq_debug_class_table_read", "mpcq_debug_class_table_write", "mpcq_debug_class_order",
                  "mpcq_debug_class_learn", "mpcq_debug_suspended", "mpcq_debug_session_order",
                  "mpcq_debug_last_dispatch"):

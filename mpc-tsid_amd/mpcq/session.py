@@ -30,7 +30,7 @@ def _shapes(B, N):
         L.SV_STATUS: ((B,), np.int32), L.SV_ITERS: ((B,), np.int32), L.SV_RHO: ((B,), np.float64),
         L.SV_Y: ((B, 44 * N), np.float64), L.SV_STATE: ((B, 12), np.float64),
         L.SV_L_FEET: ((B, 3, 4), np.float64), L.SV_ROT_FLAG: ((B,), np.int32), L.SV_H_ROT: ((B,), np.float64),
-        L.SV_ORDER: ((B,), np.int32),
+        L.SV_ORDER: ((B,), np.int32), L.SV_FIRST: ((B,), np.int32),
     }
 
 
@@ -123,6 +123,27 @@ class Session:
         self.engine._call("mpcq_session_tick", self._h, k, v(state_ptr), v(l_feet_ptr), v(v_ref_ptr), v(reduced_ptr),
                                           flags)
         self.k = k + 1
+
+    def reset(self, mask=None, gait0=None, q_w0=None):
+        """Restart the robots with a nonzero ``mask`` entry (None: all) between two ticks (host
+        arrays): their state goes back to what the constructor leaves, with the gait table
+        ``gait0`` (None: the table the session was created with) and the world pose ``q_w0``
+        (None: the default), and their next tick runs as a first tick whatever ``k`` is; the
+        other robots are not touched.  ``mask`` broadcasts to (B,), ``gait0`` to (B, 20, 5),
+        ``q_w0`` to (B, 6).  ``Session.k`` keeps counting."""
+        B = self.batch
+        m = None if mask is None else np.ascontiguousarray(np.broadcast_to(np.asarray(mask) != 0, (B,)), np.int32)
+        g = self._in(gait0, (B, 20, 5))
+        q = self._in(q_w0, (B, 6))
+        p = lambda a: None if a is None else C.c_void_p(a.ctypes.data)  # noqa: E731
+        self.engine._call("mpcq_session_reset", self._h, p(m), p(g), p(q), 0)
+
+    def reset_device(self, mask_ptr: int = 0, gait0_ptr: int = 0, q_w0_ptr: int = 0, asynchronous: bool = True):
+        """``reset`` on device-resident arrays (int32 mask [B], gait0 [B, 20, 5], q_w0 [B, 6]; 0 =
+        absent), enqueued on the engine's stream: a mask computed on the device stays there."""
+        v = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        flags = L.FLAG_DEVICE_PTRS | (L.FLAG_ASYNC if asynchronous else 0)
+        self.engine._call("mpcq_session_reset", self._h, v(mask_ptr), v(gait0_ptr), v(q_w0_ptr), flags)
 
     def _shape(self, what: int):
         if what not in self._shapes and what in (L.SV_SWING_REF, L.SV_SWING_STATE, L.SV_FRAME):
