@@ -47,7 +47,11 @@ extern "C" {
  *   3 (additions, no bump): mpcq_robot, mpcq_default_robot, mpcq_set_robots,
  *      mpcq_session_set_robots, mpcq_session_get_robots (per-instance mass, gI, mu, fz_max)
  *   3 (additions, no bump): mpcq_session_reset (any subset of a session's robots back to their
- *      state after create, between two ticks); MPCQ_SV_FIRST (MPCQ_SV_COUNT 20 -> 21, read-only) */
+ *      state after create, between two ticks); MPCQ_SV_FIRST (MPCQ_SV_COUNT 20 -> 21, read-only)
+ *   3 (additions, no bump): mpcq_plant_params, mpcq_default_plant_params, mpcq_plant_step_batch,
+ *      mpcq_session_enable_plant / _disable_plant / _set_plant_robots / _set_wrench /
+ *      _plant_read / _plant_device_ptr (a rigid-body plant between two ticks); its arrays have
+ *      ids of their own, MPCQ_PV_*: MPCQ_SV_COUNT stays 21 */
 #define MPCQ_ABI_VERSION 3
 
 /* error codes (return values) */
@@ -485,6 +489,103 @@ int mpcq_swing_batch(mpcq_ctx* ctx, const mpcq_swing_params* sp, int64_t batch, 
  * fsteps with feet0 = NULL and the frame MPCQ_SV_FRAME.  A session that never calls it
  * launches exactly what it did before. */
 int mpcq_session_enable_swing(mpcq_session* s, const mpcq_swing_params* sp);
+
+/* ---- rigid-body plant ------------------------------------------------------
+ * No reference counterpart (the reference closes its loop with PyBullet and TSID): the object
+ * the MPC is a discretisation of, a single rigid body under the forces of its stance feet,
+ * integrated on the device over one MPC tick, with constants of its own and an external
+ * wrench -- so that the robot a session moves can disagree with the controller's model
+ * (an unknown payload, another friction, a push).  FP64, one thread per robot.
+ *
+ * Everything of one robot is expressed in one inertial frame (in a session: the tick's local
+ * frame).  Effective forces, once per tick: a swing foot (any NaN coordinate) applies none;
+ * with clamp != 0 a stance foot's fz is limited to [0, fz_max] and its tangential part, if
+ * t = sqrt(fx^2 + fy^2) > mu fz, scaled by mu fz / t onto the Coulomb cone (the model's
+ * friction pyramid admits sqrt(2) mu, so the clamp bites even with the model's own mu).
+ * F = sum f_i + wrench[0:3], tau = sum (p_i - c0) x f_i + wrench[3:6]: the lever arms are
+ * taken at the tick's start and held, as the MPC holds them.
+ *   MPCQ_PLANT_MODEL  the MPC's own discrete step (MPC.py:110-119, 171-178, 201) with the
+ *                     plant's constants: c += dt v0, rpy += dt w0, v += dt F / m - dt g e_z,
+ *                     w += dt inv(Rz(yaw0) gI) tau (the reference's Rz gI, not Rz gI Rz');
+ *                     n_sub is ignored
+ *   MPCQ_PLANT_RIGID  n_sub semi-implicit Euler substeps of h = dt / n_sub: R = Rz(yaw)
+ *                     Ry(pitch) Rx(roll), Iw = R gI R', a = F / m - g e_z, alpha = inv(Iw)
+ *                     (tau - w x Iw w), v += h a, w += h alpha, c += h v, rpy += h E w (new v
+ *                     and w, the substep's old angles; E maps the world-frame angular
+ *                     velocity to ZYX angle rates)
+ * 3x3 inverses by the adjugate; sums left to right in foot order; no contraction, so a host
+ * restatement in the same order (tests/plant_model.py) differs by the sin / cos only.  A NaN
+ * among a robot's inputs spreads through that robot's arithmetic and to no other robot. */
+#define MPCQ_PLANT_MODEL 0
+#define MPCQ_PLANT_RIGID 1
+typedef struct mpcq_plant_params {   /* 48 bytes */
+  double dt;          /* 0.02: one MPC tick */
+  double gravity;     /* 9.81 */
+  int32_t n_sub;      /* 20 (k_mpc, main.py:21); >= 1 */
+  int32_t integrator; /* MPCQ_PLANT_RIGID */
+  int32_t clamp;      /* 1 */
+  int32_t reserved[5];
+} mpcq_plant_params;
+#ifdef __cplusplus
+static_assert(sizeof(mpcq_plant_params) == 48, "mpcq_plant_params is 48 bytes");
+#else
+_Static_assert(sizeof(mpcq_plant_params) == 48, "mpcq_plant_params is 48 bytes");
+#endif
+void mpcq_default_plant_params(mpcq_plant_params* pl);
+/* One tick of the plant for a batch.
+ *   state     [B][12] c, rpy, v, w
+ *   feet      [B][3][4] foot positions, laid out as l_feet; NaN = swing
+ *   f         [B][12] foot-major fx, fy, fz per foot, as f_applied
+ *   wrench    [B][6] force, then torque about the centre of mass; NULL = none
+ *   robots    [B] mass, gI, mu, fz_max per robot; NULL = ctx's mpcq_params (a host table is
+ *             validated as in mpcq_set_robots, a device table is not)
+ *   state_out [B][12]; may be state itself
+ *   f_eff     [B][12] the effective forces; NULL = not wanted
+ * pl NULL = mpcq_default_plant_params.  Host pointers, or device pointers with
+ * MPCQ_FLAG_DEVICE_PTRS (then MPCQ_FLAG_ASYNC does not wait for the stream).  dt <= 0, n_sub < 1,
+ * an unknown integrator or a NULL required pointer: MPCQ_E_INVALID, nothing is launched. */
+int mpcq_plant_step_batch(mpcq_ctx* ctx, const mpcq_plant_params* pl, int64_t batch,
+                          const double* state, const double* feet, const double* f,
+                          const double* wrench, const mpcq_robot* robots, double* state_out,
+                          double* f_eff, uint32_t flags);
+
+/* Opt-in (pl NULL = mpcq_default_plant_params with ctx's dt; a dt other than ctx's is
+ * MPCQ_E_INVALID): while enabled, every mpcq_session_tick runs one plant launch directly after
+ * its retrieve, on the context's stream, no host synchronisation.  Per robot it integrates the
+ * state the tick's planner read, under MPCQ_SV_F0 at the stance feet of row 0 of the tick's
+ * fsteps, the session's wrench, and the plant's table of robots (without one the session's
+ * model table, without that ctx's params), and rewrites MPCQ_SV_Q_W, MPCQ_SV_STATE and
+ * MPCQ_SV_L_FEET by the retrieve's own formulas with the plant's end state in place of the
+ * prediction x_robot[:, 0], from MPCQ_SV_Q_W as it stood before the tick.  MPCQ_SV_X_ROBOT,
+ * the warm start and every other array stay the MPC's: x_robot[:, 0] - MPCQ_PV_STATE_END is
+ * the tracking error.  A robot the retrieve treats as failed (status not SOLVED,
+ * SOLVED_INACCURATE or MAX_ITER_REACHED) keeps what the retrieve left; its MPCQ_PV_STATE_END
+ * and MPCQ_PV_F_EFF rows are NaN.  The swing launch and the dispatch order are unaffected.
+ * Calling it again replaces the parameters.  A session that never enables it launches exactly
+ * what it did before. */
+int mpcq_session_enable_plant(mpcq_session* s, const mpcq_plant_params* pl);
+/* The ticks after it run without the plant launch; the wrench and the plant's table stay. */
+int mpcq_session_disable_plant(mpcq_session* s);
+/* The true robots, robots [B] (mpcq_session_set_robots: the same copy, validation and flags),
+ * distinct from the model's table; NULL clears it.  Kept across mpcq_session_reset. */
+int mpcq_session_set_plant_robots(mpcq_session* s, const mpcq_robot* robots, uint32_t flags);
+/* The external wrench, wrench [B][6]: force, then torque about the centre of mass, in the
+ * WORLD frame; each tick rotates force and torque separately by Rz(-yaw) into its local frame,
+ * yaw = MPCQ_SV_Q_W[5] as it stood before the tick.  NULL = zero.  Host pointer (the call
+ * blocks), or device pointer with MPCQ_FLAG_DEVICE_PTRS (copied on the context's stream;
+ * MPCQ_FLAG_ASYNC does not wait).  It persists until changed, across mpcq_session_reset too,
+ * and may be set before the plant is enabled. */
+int mpcq_session_set_wrench(mpcq_session* s, const double* wrench, uint32_t flags);
+/* The plant's arrays; they exist from the first mpcq_session_enable_plant or
+ * mpcq_session_set_wrench on (before: MPCQ_E_INVALID), zero until written. */
+#define MPCQ_PV_STATE_END 0  /* [B][12] plant state at the tick's end, in the tick's frame */
+#define MPCQ_PV_F_EFF 1      /* [B][12] the effective forces of the tick */
+#define MPCQ_PV_WRENCH 2     /* [B][6]  the wrench as set (world frame) */
+#define MPCQ_PV_COUNT 3
+/* Copy array `what` to dst (host, or device with MPCQ_FLAG_DEVICE_PTRS); blocking. */
+int mpcq_session_plant_read(mpcq_session* s, int what, void* dst, uint32_t flags);
+/* Device address of array `what` (valid until mpcq_session_destroy). */
+int mpcq_session_plant_device_ptr(mpcq_session* s, int what, void** out);
 
 /* ---- diagnostics -----------------------------------------------------------
  * Device buffer [B][16] (uint64) that a diagnostic build of the library

@@ -860,6 +860,72 @@ int mpcq_swing_batch(mpcq_ctx* c, const mpcq_swing_params* sp, int64_t B, int k_
   return MPCQ_OK;
 }
 
+// Rigid-body plant: one MPC tick of dt, k_mpc substeps (main.py:21), the Coulomb clamp on.
+void mpcq_default_plant_params(mpcq_plant_params* pl) {
+  if (!pl) return;
+  memset(pl, 0, sizeof(*pl));
+  pl->dt = 0.02;
+  pl->gravity = 9.81;
+  pl->n_sub = 20;
+  pl->integrator = MPCQ_PLANT_RIGID;
+  pl->clamp = 1;
+}
+
+static int plant_params(const mpcq_plant_params* pl, double dt_default, mpcq_plant_params* out) {
+  if (pl) *out = *pl;
+  else {
+    mpcq_default_plant_params(out);
+    if (dt_default > 0) out->dt = dt_default;
+  }
+  if (!(out->dt > 0) || out->n_sub < 1 ||
+      (out->integrator != MPCQ_PLANT_MODEL && out->integrator != MPCQ_PLANT_RIGID))
+    return fail(MPCQ_E_INVALID, "the plant needs dt > 0, n_sub >= 1, integrator MPCQ_PLANT_MODEL or MPCQ_PLANT_RIGID");
+  return MPCQ_OK;
+}
+
+int mpcq_plant_step_batch(mpcq_ctx* c, const mpcq_plant_params* pl, int64_t B, const double* state,
+                          const double* feet, const double* f, const double* wrench, const mpcq_robot* robots,
+                          double* state_out, double* f_eff, uint32_t flags) {
+  int rc = check_ctx(c, B);
+  if (rc) return rc;
+  if (!state || !feet || !f || !state_out) return fail(MPCQ_E_INVALID, "state, feet, f and state_out are required");
+  mpcq_plant_params P;
+  rc = plant_params(pl, 0.0, &P);
+  if (rc) return rc;
+  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
+  if (robots && !dev) {
+    rc = check_robots(robots, B);
+    if (rc) return rc;
+  }
+  if (B == 0) return MPCQ_OK;
+  DeviceGuard g(c->device);
+  mpcq::PlantArgs a{};
+  a.batch = B;
+  mpcq_default_robot(&c->p, &a.dflt);
+  enum { ST, FT, FF, WR, RB, SO, FE, NX };
+  Xfer xs[NX] = {{state, nullptr, (size_t)B * 96, nullptr},
+                 {feet, nullptr, (size_t)B * 96, nullptr},
+                 {f, nullptr, (size_t)B * 96, nullptr},
+                 {wrench, nullptr, (size_t)B * 48, nullptr},
+                 {robots, nullptr, (size_t)B * sizeof(mpcq_robot), nullptr},
+                 {nullptr, state_out, (size_t)B * 96, nullptr},
+                 {nullptr, f_eff, (size_t)B * 96, nullptr}};
+  if (!dev) {
+    rc = stage(c, xs, NX);
+    if (rc) return rc;
+    a.state = (const double*)xs[ST].dev; a.feet = (const double*)xs[FT].dev; a.f = (const double*)xs[FF].dev;
+    a.wrench = (const double*)xs[WR].dev; a.robots = (const mpcq_robot*)xs[RB].dev;
+    a.state_out = (double*)xs[SO].dev; a.f_eff = (double*)xs[FE].dev;
+  } else {
+    a.state = state; a.feet = feet; a.f = f; a.wrench = wrench; a.robots = robots;
+    a.state_out = state_out; a.f_eff = f_eff;
+  }
+  HIP_TRY(mpcq::launch_plant(P, a, c->stream));
+  if (!dev) return unstage(c, xs, NX);
+  if (!(flags & MPCQ_FLAG_ASYNC)) HIP_TRY(hipStreamSynchronize(c->stream));
+  return MPCQ_OK;
+}
+
 // ---------------------------------------------------------------------------
 // Closed-loop session: per-robot state resident in HBM (include/mpcq.h).
 
@@ -892,6 +958,15 @@ struct mpcq_session {
   double* gait_init = nullptr;
   double* in_gait = nullptr;  // staging of a host gait0
   bool resets = false;
+  // mpcq_session_enable_plant: the plant's arrays (MPCQ_PV_*, an allocation of their own, made
+  // by the first enable or set_wrench) and the copy of q_w a tick takes before its retrieve
+  bool plant = false;
+  mpcq_plant_params pl{};
+  void* plant_mem = nullptr;
+  void* parr[MPCQ_PV_COUNT] = {};
+  size_t pbytes[MPCQ_PV_COUNT] = {};
+  double* qw_prev = nullptr;
+  RobotTable plant_robots;  // mpcq_session_set_plant_robots
 };
 
 namespace {
@@ -1056,6 +1131,8 @@ int mpcq_session_destroy(mpcq_session* s) {
     (void)hipFree(s->mem);
     if (s->swing_mem) (void)hipFree(s->swing_mem);
     if (s->robots.dev) (void)hipFree(s->robots.dev);
+    if (s->plant_mem) (void)hipFree(s->plant_mem);
+    if (s->plant_robots.dev) (void)hipFree(s->plant_robots.dev);
   }
   delete s;
   return MPCQ_OK;
@@ -1121,6 +1198,91 @@ int mpcq_session_enable_swing(mpcq_session* s, const mpcq_swing_params* sp) {
   }
   s->sp = P;
   s->swing = true;
+  return MPCQ_OK;
+}
+
+// The plant's arrays, all zero: made by the first mpcq_session_enable_plant / _set_wrench.
+static int ensure_plant_mem(mpcq_session* s) {
+  if (s->plant_mem) return MPCQ_OK;
+  const size_t B = (size_t)s->B;
+  const size_t nb[MPCQ_PV_COUNT + 1] = {B * 96, B * 96, B * 48, B * 48};  // STATE_END, F_EFF, WRENCH, qw_prev
+  size_t off[MPCQ_PV_COUNT + 1], tot = 0;
+  for (int i = 0; i <= MPCQ_PV_COUNT; ++i) { off[i] = tot; tot += (nb[i] + 255) & ~size_t(255); }
+  void* mem = nullptr;
+  if (hipMalloc(&mem, tot) != hipSuccess) return fail(MPCQ_E_NOMEM, "hipMalloc(%zu) for the plant arrays failed", tot);
+  hipError_t e = hipMemsetAsync(mem, 0, tot, s->ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(s->ctx->stream);
+  if (e != hipSuccess) {
+    (void)hipFree(mem);
+    return fail(MPCQ_E_DEVICE, "zeroing the plant arrays failed: %s", hipGetErrorString(e));
+  }
+  s->plant_mem = mem;
+  for (int i = 0; i < MPCQ_PV_COUNT; ++i) {
+    s->parr[i] = (char*)mem + off[i];
+    s->pbytes[i] = nb[i];
+  }
+  s->qw_prev = (double*)((char*)mem + off[MPCQ_PV_COUNT]);
+  return MPCQ_OK;
+}
+
+int mpcq_session_enable_plant(mpcq_session* s, const mpcq_plant_params* pl) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  mpcq_plant_params P;
+  int rc = plant_params(pl, s->ctx->p.dt, &P);
+  if (rc) return rc;
+  if (P.dt != s->ctx->p.dt)
+    return fail(MPCQ_E_INVALID, "the plant's dt %g is not the context's %g", P.dt, s->ctx->p.dt);
+  DeviceGuard g(s->ctx->device);
+  rc = ensure_plant_mem(s);
+  if (rc) return rc;
+  s->pl = P;
+  s->plant = true;
+  return MPCQ_OK;
+}
+
+int mpcq_session_disable_plant(mpcq_session* s) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  s->plant = false;
+  return MPCQ_OK;
+}
+
+int mpcq_session_set_plant_robots(mpcq_session* s, const mpcq_robot* robots, uint32_t flags) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  return set_table(s->ctx, s->plant_robots, robots ? s->B : 0, robots, flags);
+}
+
+int mpcq_session_set_wrench(mpcq_session* s, const double* wrench, uint32_t flags) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  mpcq_ctx* c = s->ctx;
+  DeviceGuard g(c->device);
+  const int rc = ensure_plant_mem(s);
+  if (rc) return rc;
+  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
+  void* dst = s->parr[MPCQ_PV_WRENCH];
+  const size_t nb = s->pbytes[MPCQ_PV_WRENCH];
+  // on the context's stream: behind every queued tick that still reads the old wrench
+  if (!wrench) HIP_TRY(hipMemsetAsync(dst, 0, nb, c->stream));
+  else HIP_TRY(hipMemcpyAsync(dst, wrench, nb, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+  if (!(flags & MPCQ_FLAG_ASYNC) || !dev) HIP_TRY(hipStreamSynchronize(c->stream));
+  return MPCQ_OK;
+}
+
+int mpcq_session_plant_read(mpcq_session* s, int what, void* dst, uint32_t flags) {
+  if (!s || !dst) return fail(MPCQ_E_INVALID, "NULL argument");
+  if (what < 0 || what >= MPCQ_PV_COUNT) return fail(MPCQ_E_INVALID, "unknown plant array %d", what);
+  if (!s->plant_mem) return fail(MPCQ_E_INVALID, "plant array %d needs mpcq_session_enable_plant", what);
+  DeviceGuard g(s->ctx->device);
+  const hipMemcpyKind kind = (flags & MPCQ_FLAG_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  HIP_TRY(hipMemcpyAsync(dst, s->parr[what], s->pbytes[what], kind, s->ctx->stream));
+  HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+  return MPCQ_OK;
+}
+
+int mpcq_session_plant_device_ptr(mpcq_session* s, int what, void** out) {
+  if (!s || !out) return fail(MPCQ_E_INVALID, "NULL argument");
+  if (what < 0 || what >= MPCQ_PV_COUNT) return fail(MPCQ_E_INVALID, "unknown plant array %d", what);
+  if (!s->plant_mem) return fail(MPCQ_E_INVALID, "plant array %d needs mpcq_session_enable_plant", what);
+  *out = s->parr[what];
   return MPCQ_OK;
 }
 
@@ -1245,7 +1407,31 @@ int mpcq_session_tick(mpcq_session* s, int k, const double* state, const double*
     HIP_TRY(hipMemcpy2DAsync(fr, 24, qw, 48, 16, (size_t)B, hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(hipMemcpy2DAsync(fr + 2, 24, qw + 5, 48, 8, (size_t)B, hipMemcpyDeviceToDevice, c->stream));
   }
+  if (s->plant)  // the plant starts from the world pose as it stands before the retrieve moves it
+    HIP_TRY(hipMemcpyAsync(s->qw_prev, s->arr[MPCQ_SV_Q_W], (size_t)B * 48, hipMemcpyDeviceToDevice, c->stream));
   HIP_TRY(mpcq::launch_retrieve(N, ra, c->stream));
+  if (s->plant) {  // the rigid body under this tick's forces takes the place of the prediction
+    mpcq::PlantArgs pa2{};
+    pa2.batch = B;
+    pa2.state = st;
+    pa2.fsteps = (const double*)s->arr[MPCQ_SV_FSTEPS];
+    pa2.f = (const double*)s->arr[MPCQ_SV_F0];
+    pa2.wrench = (const double*)s->parr[MPCQ_PV_WRENCH];
+    pa2.robots = s->plant_robots.count ? s->plant_robots.dev : s->robots.count ? s->robots.dev : nullptr;
+    mpcq_default_robot(&c->p, &pa2.dflt);
+    pa2.state_out = (double*)s->parr[MPCQ_PV_STATE_END];
+    pa2.f_eff = (double*)s->parr[MPCQ_PV_F_EFF];
+    pa2.tail = 1;
+    pa2.status = (const int32_t*)s->arr[MPCQ_SV_STATUS];
+    pa2.plan_status = s->plan_status;
+    pa2.gait = (const double*)s->arr[MPCQ_SV_GAIT];
+    pa2.q_w_prev = s->qw_prev;
+    pa2.q_w = (double*)s->arr[MPCQ_SV_Q_W];
+    pa2.next_state = (double*)s->arr[MPCQ_SV_STATE];
+    pa2.next_l_feet = (double*)s->arr[MPCQ_SV_L_FEET];
+    for (int i = 0; i < 8; ++i) pa2.shoulders[i] = s->pp.shoulders[i];
+    HIP_TRY(mpcq::launch_plant(s->pl, pa2, c->stream));
+  }
   // (the retrieve has cleared every pending reset: the order is by iteration counts alone)
   HIP_TRY(mpcq::launch_order((const int32_t*)s->arr[MPCQ_SV_ITERS], nullptr, B, s->order, c->stream));
   s->have_order = true;

@@ -227,6 +227,34 @@ hipError_t launch_swing(const mpcq_swing_params& sp, const SwingArgs& a, hipStre
 hipError_t launch_swing_step(const mpcq_swing_params& sp, int64_t batch, const double* in, double* state,
                              double* out, hipStream_t s);
 
+// Rigid-body plant (mpcq_plant.hip); layouts and equations in include/mpcq.h
+// (mpcq_plant_step_batch, mpcq_session_enable_plant).  One thread per robot.
+struct PlantArgs {
+  int64_t batch;
+  const double* state;     // [B][12]
+  const double* feet;      // [B][3][4], or null with fsteps
+  const double* fsteps;    // [B][20][13] (a session's tick): the feet are row 0's
+  const double* f;         // [B][12]
+  const double* wrench;    // [B][6] or null
+  const mpcq_robot* robots;// [B] or null: dflt
+  mpcq_robot dflt;
+  double* state_out;       // [B][12]
+  double* f_eff;           // [B][12] or null
+  // a session's tick only (tail != 0): the wrench is a world-frame one, rotated by
+  // Rz(-q_w_prev[5]); a failed robot gets NaN rows and nothing else; the others' world pose
+  // and virtual robot are rewritten from the plant's end state (mpcq_virtual.h)
+  int tail;
+  const int32_t* status;      // [B] after the retrieve
+  const int32_t* plan_status; // [B]
+  const double* gait;         // [B][20][5]
+  const double* q_w_prev;     // [B][6] the world pose before the tick
+  double* q_w;                // [B][6]
+  double* next_state;         // [B][12]
+  double* next_l_feet;        // [B][3][4]
+  double shoulders[8];
+};
+hipError_t launch_plant(const mpcq_plant_params& pl, const PlantArgs& a, hipStream_t s);
+
 // Launchers (mpcq_engine.hip).  Return hipError_t.
 hipError_t launch_formulate(int N, const mpcq_params& p, const LaunchArgs& a, hipStream_t s);
 hipError_t launch_solve(int N, bool fused, const mpcq_params& p, const LaunchArgs& a, hipStream_t s);

@@ -19,6 +19,8 @@
 
 #pragma clang fp contract(off)
 
+#include "mpcq_virtual.h"
+
 namespace mpcq {
 namespace {
 
@@ -98,49 +100,8 @@ __global__ __launch_bounds__(64) void retrieve_kernel(SessionArgs a) {
 #pragma unroll
     for (int r = 0; r < 12; ++r) qn[r] = xs[r] + xr[r * NP + 1];
     double* qw = a.q_w + b * 6;
-    const double c = cos(qw[5]), s = sin(qw[5]);
-    const double d0 = fma(c, qn[0], (-s) * qn[1]);
-    const double d1 = fma(s, qn[0], c * qn[1]);
-    qw[0] = qw[0] + d0;
-    qw[1] = qw[1] + d1;
-    qw[2] = qn[2];
-    qw[3] = qn[3];
-    qw[4] = qn[4];
-    qw[5] = qw[5] + qn[5];
-    // virtual robot: new local frame under the predicted base, yaw removed
-    const double cy = cos(qn[5]), sy = sin(qn[5]);
-    double* ns = a.next_state + b * 12;
-    ns[0] = 0.0;
-    ns[1] = 0.0;
-    ns[2] = qn[2];
-    ns[3] = qn[3];
-    ns[4] = qn[4];
-    ns[5] = 0.0;
-    ns[6] = cy * qn[6] + sy * qn[7];
-    ns[7] = -sy * qn[6] + cy * qn[7];
-    ns[8] = qn[8];
-    ns[9] = cy * qn[9] + sy * qn[10];
-    ns[10] = -sy * qn[9] + cy * qn[10];
-    ns[11] = qn[11];
-    // feet: the phase that will be current after the next roll holds the
-    // positions of the feet then in stance (row 0 if the phase goes on, row 1
-    // if it ends); swing feet sit under their shoulders
-    const double* fs = a.fsteps + b * 260;
-    const double* gt = a.gait + b * 100;
-    const int row = gt[0] > 1.0 ? 0 : 1;
-    double* lf = a.next_l_feet + b * 12;
-    for (int q = 0; q < 4; ++q) {
-      double px = fs[13 * row + 1 + 3 * q], py = fs[13 * row + 2 + 3 * q], pz = fs[13 * row + 3 + 3 * q];
-      if (isnan(px) || isnan(py) || isnan(pz)) {
-        px = a.shoulders[q] + qn[0];
-        py = a.shoulders[4 + q] + qn[1];
-        pz = 0.0;
-      }
-      const double dx = px - qn[0], dy = py - qn[1];
-      lf[q] = cy * dx + sy * dy;
-      lf[4 + q] = -sy * dx + cy * dy;
-      lf[8 + q] = pz;
-    }
+    advance_virtual(qn, qw, qw, a.next_state + b * 12, a.next_l_feet + b * 12, a.fsteps + b * 260,
+                    a.gait + b * 100, a.shoulders);
   }
 }
 

@@ -11,6 +11,8 @@ Public surface:
   robots            per-robot mass / inertia / friction / force limit tables
                     (Engine.set_robots, Session.set_robots)
   Swing             batched swing-foot trajectories between two ticks (Session.enable_swing)
+  Plant             batched rigid-body plant under the stance feet's forces: true robots that
+                    differ from the model, external pushes (Session.enable_plant)
   synth             seeded synthetic inputs shaped like FootstepPlanner's
 """
 from . import synth  # noqa: F401
@@ -24,8 +26,10 @@ from ._lib import (FLAG_ASYNC, FLAG_DEVICE_PTRS, FLAG_ORDER_BY_CLASS, MODE_SETUP
                    STATUS_DUAL_INFEASIBLE_INACCURATE, STATUS_BAD_BOUNDS, MpcqError,
                    Params, build, build_info, default_params, lib, source_sha, supported_horizons,
                    SV_FRAME, SV_SWING_REF, SV_SWING_STATE, SWING_STATE, SwingParams, default_swing_params,
-                   Robot, default_robot)
+                   Robot, default_robot,
+                   PLANT_MODEL, PLANT_RIGID, PV_F_EFF, PV_STATE_END, PV_WRENCH, PlantParams, default_plant_params)
 from .engine import ROBOT_DTYPE, Engine, dims, pattern, robots  # noqa: F401
+from .plant import Plant  # noqa: F401
 from .session import Session  # noqa: F401
 from .swing import Swing  # noqa: F401
 

@@ -65,6 +65,9 @@ SV_ORDER = 16  # read-only: the next tick's dispatch order
 SV_SWING_REF, SV_SWING_STATE, SV_FRAME = 17, 18, 19
 SV_FIRST = 20  # read-only: 1 = a reset is pending, the robot's next tick runs as a first tick
 SWING_STATE = 40  # MPCQ_SWING_STATE: doubles per foot
+# the rigid-body plant: integrators (MPCQ_PLANT_*) and a session's plant arrays (MPCQ_PV_*)
+PLANT_MODEL, PLANT_RIGID = 0, 1
+PV_STATE_END, PV_F_EFF, PV_WRENCH = 0, 1, 2
 
 EXPORTS = ("mpcq_abi_version", "mpcq_default_params", "mpcq_dims", "mpcq_pattern",
            "mpcq_supported_horizons", "mpcq_last_error", "mpcq_create", "mpcq_destroy",
@@ -79,7 +82,10 @@ EXPORTS = ("mpcq_abi_version", "mpcq_default_params", "mpcq_dims", "mpcq_pattern
            "mpcq_default_swing_params", "mpcq_swing_step_batch", "mpcq_swing_batch",
            "mpcq_session_enable_swing",
            "mpcq_default_robot", "mpcq_set_robots", "mpcq_session_set_robots", "mpcq_session_get_robots",
-           "mpcq_session_reset")
+           "mpcq_session_reset",
+           "mpcq_default_plant_params", "mpcq_plant_step_batch", "mpcq_session_enable_plant",
+           "mpcq_session_disable_plant", "mpcq_session_set_plant_robots", "mpcq_session_set_wrench",
+           "mpcq_session_plant_read", "mpcq_session_plant_device_ptr")
 
 
 class MpcqError(RuntimeError):
@@ -158,6 +164,19 @@ class SwingParams(C.Structure):
         ("feet_z", C.c_double),
         ("k_mpc", C.c_int32),
         ("reserved", C.c_int32 * 7),
+    ]
+
+
+class PlantParams(C.Structure):
+    """struct mpcq_plant_params (include/mpcq.h)."""
+
+    _fields_ = [
+        ("dt", C.c_double),
+        ("gravity", C.c_double),
+        ("n_sub", C.c_int32),
+        ("integrator", C.c_int32),
+        ("clamp", C.c_int32),
+        ("reserved", C.c_int32 * 5),
     ]
 
 
@@ -274,6 +293,20 @@ def lib():
         getattr(L, name).restype = C.c_int
     L.mpcq_session_reset.argtypes = [vp, vp, vp, vp, C.c_uint32]
     L.mpcq_session_reset.restype = C.c_int
+    PL = C.POINTER(PlantParams)
+    L.mpcq_default_plant_params.argtypes = [PL]
+    L.mpcq_default_plant_params.restype = None
+    L.mpcq_plant_step_batch.argtypes = [vp, PL, C.c_int64] + [vp] * 7 + [C.c_uint32]
+    L.mpcq_session_enable_plant.argtypes = [vp, PL]
+    L.mpcq_session_disable_plant.argtypes = [vp]
+    L.mpcq_session_set_plant_robots.argtypes = [vp, vp, C.c_uint32]
+    L.mpcq_session_set_wrench.argtypes = [vp, vp, C.c_uint32]
+    L.mpcq_session_plant_read.argtypes = [vp, C.c_int, vp, C.c_uint32]
+    L.mpcq_session_plant_device_ptr.argtypes = [vp, C.c_int, C.POINTER(vp)]
+    for name in ("mpcq_plant_step_batch", "mpcq_session_enable_plant", "mpcq_session_disable_plant",
+                 "mpcq_session_set_plant_robots", "mpcq_session_set_wrench", "mpcq_session_plant_read",
+                 "mpcq_session_plant_device_ptr"):
+        getattr(L, name).restype = C.c_int
     for name in ("mpcq_debug_class_table_read", "mpcq_debug_class_table_write", "mpcq_debug_class_order",
                  "mpcq_debug_class_learn", "mpcq_debug_suspended", "mpcq_debug_session_order",
                  "mpcq_debug_last_dispatch"):
@@ -324,6 +357,16 @@ def default_swing_params(**overrides) -> SwingParams:
     for k, v in overrides.items():
         if not hasattr(p, k):
             raise AttributeError(f"unknown swing parameter {k}")
+        setattr(p, k, v)
+    return p
+
+
+def default_plant_params(**overrides) -> PlantParams:
+    p = PlantParams()
+    lib().mpcq_default_plant_params(C.byref(p))
+    for k, v in overrides.items():
+        if not hasattr(p, k):
+            raise AttributeError(f"unknown plant parameter {k}")
         setattr(p, k, v)
     return p
 

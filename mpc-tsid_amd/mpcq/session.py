@@ -9,7 +9,10 @@ components (Logger.py:406-418) — as three launches on the engine's stream.
 
 Passing ``state=None`` / ``l_feet=None`` runs the virtual robot: the next
 state is the previous tick's prediction x_robot[:, 0] re-expressed in the new
-local frame (processing.py:33-38 is the reference's precedent).
+local frame (processing.py:33-38 is the reference's precedent).  With
+``enable_plant`` the next state is instead where a rigid body with constants of
+its own (``set_plant_robots``) and an external wrench (``set_wrench``) ends the
+tick under the forces the MPC applied: a robot that can disagree with the model.
 """
 from __future__ import annotations
 
@@ -52,6 +55,7 @@ class Session:
         self._h = h
         self.k = 0
         self.swing_params = None
+        self.plant_params = None
 
     def enable_swing(self, params: L.SwingParams | None = None):
         """Opt in to the swing-foot references: every later tick appends one swing launch over
@@ -77,6 +81,59 @@ class Session:
         out = np.zeros(self.batch, ROBOT_DTYPE)
         self.engine._call("mpcq_session_get_robots", self._h, C.c_void_p(out.ctypes.data), 0)
         return out
+
+    # ------------------------------------------------------------------ rigid-body plant
+    def enable_plant(self, params: L.PlantParams | None = None):
+        """Opt in to the rigid-body plant: every later tick integrates, directly after its
+        retrieve, the state its planner read under SV_F0, the wrench and the plant's robots,
+        and SV_Q_W / SV_STATE / SV_L_FEET follow the plant's end state instead of the MPC's
+        prediction (``plant_read``: PV_STATE_END, PV_F_EFF, PV_WRENCH).  ``params`` None: the
+        defaults with the engine's dt.  Calling it again replaces the parameters."""
+        pl = params or L.default_plant_params(dt=self.engine.params.dt)
+        self.engine._call("mpcq_session_enable_plant", self._h, C.byref(pl))
+        self.plant_params = pl
+
+    def disable_plant(self):
+        """The ticks after it run without the plant; the wrench and the plant's table stay."""
+        self.engine._call("mpcq_session_disable_plant", self._h)
+        self.plant_params = None
+
+    def set_plant_robots(self, table):
+        """The true robots the plant moves (``mpcq.robots(B, ...)``, or one entry for every
+        robot), distinct from the model's table of ``set_robots``.  None clears it: the plant
+        then uses the model's table, or without one the engine's parameters."""
+        t = None
+        if table is not None:
+            t = _robot_table(table)
+            if t.shape[0] == 1:
+                t = np.ascontiguousarray(np.broadcast_to(t, (self.batch,)))
+            t = _robot_table(t, self.batch)
+        self.engine._call("mpcq_session_set_plant_robots", self._h, None if t is None else C.c_void_p(t.ctypes.data), 0)
+
+    def set_wrench(self, w):
+        """The external wrench on every robot: ``w`` broadcasts to (B, 6) = force, then torque
+        about the centre of mass, in the WORLD frame.  None: zero.  It persists until changed,
+        across ``reset`` too."""
+        a = self._in(w, (self.batch, 6))
+        self.engine._call("mpcq_session_set_wrench", self._h, None if a is None else C.c_void_p(a.ctypes.data), 0)
+
+    def set_wrench_device(self, ptr: int, asynchronous: bool = True):
+        """``set_wrench`` from a device array (B, 6) (0: zero), copied on the engine's stream."""
+        flags = L.FLAG_DEVICE_PTRS | (L.FLAG_ASYNC if asynchronous else 0)
+        self.engine._call("mpcq_session_set_wrench", self._h, C.c_void_p(ptr) if ptr else None, flags)
+
+    def plant_read(self, what: int):
+        """PV_STATE_END (B, 12), PV_F_EFF (B, 12) or PV_WRENCH (B, 6)."""
+        if what not in (L.PV_STATE_END, L.PV_F_EFF, L.PV_WRENCH):
+            raise L.MpcqError(L.E_INVALID, f"unknown plant array {what}")
+        out = np.empty((self.batch, 6 if what == L.PV_WRENCH else 12))
+        self.engine._call("mpcq_session_plant_read", self._h, what, C.c_void_p(out.ctypes.data), 0)
+        return out
+
+    def plant_device_ptr(self, what: int) -> int:
+        out = C.c_void_p()
+        self.engine._call("mpcq_session_plant_device_ptr", self._h, what, C.byref(out))
+        return int(out.value or 0)
 
     def close(self):
         if getattr(self, "_h", None):
