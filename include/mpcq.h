@@ -51,7 +51,12 @@ extern "C" {
  *   3 (additions, no bump): mpcq_plant_params, mpcq_default_plant_params, mpcq_plant_step_batch,
  *      mpcq_session_enable_plant / _disable_plant / _set_plant_robots / _set_wrench /
  *      _plant_read / _plant_device_ptr (a rigid-body plant between two ticks); its arrays have
- *      ids of their own, MPCQ_PV_*: MPCQ_SV_COUNT stays 21 */
+ *      ids of their own, MPCQ_PV_*: MPCQ_SV_COUNT stays 21
+ *   3 (additions, no bump): mpcq_monitor_params, mpcq_default_monitor_params,
+ *      mpcq_monitor_step_batch, mpcq_session_enable_monitor / _disable_monitor / _monitor_read /
+ *      _monitor_device_ptr, mpcq_session_run (episodes: on-device termination, statistics,
+ *      auto-reset, multi-tick rollouts); the monitor's arrays have ids of their own, MPCQ_MV_*:
+ *      MPCQ_SV_COUNT stays 21 */
 #define MPCQ_ABI_VERSION 3
 
 /* error codes (return values) */
@@ -586,6 +591,116 @@ int mpcq_session_set_wrench(mpcq_session* s, const double* wrench, uint32_t flag
 int mpcq_session_plant_read(mpcq_session* s, int what, void* dst, uint32_t flags);
 /* Device address of array `what` (valid until mpcq_session_destroy). */
 int mpcq_session_plant_device_ptr(mpcq_session* s, int what, void** out);
+
+/* ---- episode monitor -------------------------------------------------------
+ * No reference counterpart (the reference runs one robot until its script ends): what turns a
+ * session into a batch of episodes.  After a tick, one thread per robot decides whether the
+ * robot's episode ended, keeps the episode's statistics, and leaves the done bits as an int32
+ * mask on the device -- the mask mpcq_session_reset takes.  FP64, no contraction, every sum
+ * left to right in index order: tests/monitor_model.py restates it in numpy, bit for bit.
+ *
+ * Done bits of a tick (0 = the episode goes on): */
+#define MPCQ_DONE_NONFINITE 1 /* some q_w[0..5] is NaN or infinite */
+#define MPCQ_DONE_TILT 2      /* fabs(q_w[3]) > max_tilt or fabs(q_w[4]) > max_tilt */
+#define MPCQ_DONE_HEIGHT 4    /* q_w[2] < min_height */
+#define MPCQ_DONE_SOLVER 8    /* status none of SOLVED, SOLVED_INACCURATE, MAX_ITER_REACHED: the
+                                 retrieve's own test, so MPCQ_STATUS_BAD_GAIT sets it */
+#define MPCQ_DONE_TIMEOUT 16  /* max_ticks > 0 and the episode has run max_ticks ticks, this one
+                                 included */
+/* TILT and HEIGHT are comparisons, false on NaN: a NaN pose sets NONFINITE only.  A value equal
+ * to its threshold is not a violation.
+ *
+ * Episode accumulators ep [B][8], updated every tick:
+ *   0  sum of the tick's cost: the 13 entries of MPCQ_SV_COST summed left to right, then added
+ *   1  sum of f0 . f0 (the 12 squares summed left to right)
+ *   2  sum of iters
+ *   3  max over the ticks of max(fabs(roll), fabs(pitch))
+ *   4  min over the ticks of z (+inf before the first tick)
+ *   5  sum of (state[6] - v_ref[0])^2 + (state[7] - v_ref[1])^2 + (state[11] - v_ref[5])^2.
+ *      Frame caveat: state is the virtual robot's NEXT state, its velocity expressed in the next
+ *      tick's local frame, while v_ref is this tick's command in this tick's frame; the two
+ *      differ by the yaw the robot turned during the tick (a rotation of the x, y components).
+ *   6, 7  zero
+ * A tick with the SOLVER bit adds nothing to 0, 1 and 5 (a failed solve's f0 and cost are not
+ * the controller's); a tick with the NONFINITE bit leaves 3 and 4 alone.  ep_ticks [B] int32
+ * counts the episode's ticks.
+ * On a tick with done != 0: last [B][16] = ep[0..7] with this tick in, the tick count, the done
+ * bits, q_w[0..5]; episodes [B] int32 is incremented; ep and ep_ticks restart (ep[3] = 0,
+ * ep[4] = +inf).
+ * totals [8] uint64, cumulative, never cleared by a tick: 0 robot-ticks monitored, 1 episodes
+ * ended, 2..6 how often each done bit was set (NONFINITE .. TIMEOUT), 7 zero.
+ * trace [B][MPCQ_TRACE] (optional), all doubles: 0..5 q_w, 6 done bits, 7 status, 8 iters,
+ * 9 the episode's ticks with this one in and before any restart, 10 the tick's cost sum,
+ * 11 f0 . f0, 12..15 zero. */
+#define MPCQ_TRACE 16
+typedef struct mpcq_monitor_params {  /* 64 bytes */
+  double max_tilt;     /* 0.5 rad; > 0, +inf switches the test off */
+  double min_height;   /* 0.10 (half of h_ref); finite, or -inf to switch the test off */
+  int32_t max_ticks;   /* 0 = no limit; >= 0 */
+  int32_t auto_reset;  /* 0; 1: a session's tick restarts the robots whose episode ended */
+  int32_t reserved[10];
+} mpcq_monitor_params;
+#ifdef __cplusplus
+static_assert(sizeof(mpcq_monitor_params) == 64, "mpcq_monitor_params is 64 bytes");
+#else
+_Static_assert(sizeof(mpcq_monitor_params) == 64, "mpcq_monitor_params is 64 bytes");
+#endif
+void mpcq_default_monitor_params(mpcq_monitor_params* mp);
+/* The monitor on its own, one tick for a batch.
+ *   q_w [B][6], status [B], iters [B], f0 [B][12], cost [B][13], state [B][12], v_ref [B][6]: in
+ *   ep [B][8], ep_ticks [B], done [B]: in/out (done: out)
+ *   episodes [B], last [B][16], totals [8], trace [B][MPCQ_TRACE]: in/out, each optional (NULL)
+ * mp NULL = mpcq_default_monitor_params (auto_reset is ignored here).  Host pointers, or device
+ * pointers with MPCQ_FLAG_DEVICE_PTRS (then MPCQ_FLAG_ASYNC does not wait for the stream).  A
+ * NaN or out-of-range field of mp or a NULL required pointer: MPCQ_E_INVALID, nothing is
+ * launched. */
+int mpcq_monitor_step_batch(mpcq_ctx* ctx, const mpcq_monitor_params* mp, int64_t batch,
+                            const double* q_w, const int32_t* status, const int32_t* iters,
+                            const double* f0, const double* cost, const double* state,
+                            const double* v_ref, double* ep, int32_t* ep_ticks, int32_t* episodes,
+                            double* last, int32_t* done, uint64_t* totals, double* trace,
+                            uint32_t flags);
+
+/* Opt-in (mp NULL = mpcq_default_monitor_params): while enabled, every mpcq_session_tick runs one
+ * monitor launch directly after its plant launch (without a plant: after its retrieve), on the
+ * context's stream, over MPCQ_SV_Q_W, _STATUS, _ITERS, _F0, _COST, _STATE as the tick leaves
+ * them and the tick's v_ref.  The monitor's arrays are made by the first enable, zero then
+ * (ep[4] = +inf); calling it again replaces the parameters and keeps the arrays.
+ * With auto_reset = 1 the tick ends, after its last launch (the swing launch included, which
+ * still sees the tick's gait and fsteps), by enqueueing exactly what mpcq_session_reset(s,
+ * MPCQ_MV_DONE's device address, NULL, NULL, MPCQ_FLAG_DEVICE_PTRS | MPCQ_FLAG_ASYNC) enqueues:
+ * the robots whose episode ended start their next tick as a first tick from the creation table
+ * and the default pose; their terminal pose survives in MPCQ_MV_LAST and in the trace.
+ * An explicit mpcq_session_reset of a robot discards its running episode (ep and ep_ticks
+ * restart, no episode is counted, last is kept).  A session that never enables the monitor
+ * launches exactly what it did before. */
+int mpcq_session_enable_monitor(mpcq_session* s, const mpcq_monitor_params* mp);
+/* The ticks after it run without the monitor launch and the auto-reset; the arrays stay. */
+int mpcq_session_disable_monitor(mpcq_session* s);
+/* The monitor's arrays; they exist from the first mpcq_session_enable_monitor on (before:
+ * MPCQ_E_INVALID). */
+#define MPCQ_MV_DONE 0      /* [B] int32   the last tick's done bits */
+#define MPCQ_MV_EP 1        /* [B][8]      the running episode's accumulators */
+#define MPCQ_MV_EP_TICKS 2  /* [B] int32   the running episode's ticks */
+#define MPCQ_MV_EPISODES 3  /* [B] int32   episodes ended */
+#define MPCQ_MV_LAST 4      /* [B][16]     the last ended episode */
+#define MPCQ_MV_TOTALS 5    /* [8] uint64  batch totals */
+#define MPCQ_MV_COUNT 6
+/* Copy array `what` to dst (host, or device with MPCQ_FLAG_DEVICE_PTRS); blocking. */
+int mpcq_session_monitor_read(mpcq_session* s, int what, void* dst, uint32_t flags);
+/* Device address of array `what` (valid until mpcq_session_destroy). */
+int mpcq_session_monitor_device_ptr(mpcq_session* s, int what, void** out);
+
+/* n_ticks ticks of the virtual robot (or the plant) enqueued in one call: tick t runs as
+ * mpcq_session_tick(s, k0 + t, NULL, NULL, v_ref row min(t, v_ref_ticks - 1), NULL, ...) and
+ * leaves every array as that sequence of calls does.
+ *   v_ref [v_ref_ticks][B][6] device; trace [n_ticks][B][MPCQ_TRACE] device or NULL: tick t's
+ *   monitor writes row t (a trace on a session whose monitor is not enabled: MPCQ_E_INVALID)
+ * flags must include MPCQ_FLAG_DEVICE_PTRS; the call blocks unless MPCQ_FLAG_ASYNC.  k0 < 0,
+ * n_ticks < 1, v_ref_ticks < 1, a NULL v_ref or host pointers: MPCQ_E_INVALID, nothing is
+ * launched. */
+int mpcq_session_run(mpcq_session* s, int k0, int n_ticks, const double* v_ref, int v_ref_ticks,
+                     double* trace, uint32_t flags);
 
 /* ---- diagnostics -----------------------------------------------------------
  * Device buffer [B][16] (uint64) that a diagnostic build of the library

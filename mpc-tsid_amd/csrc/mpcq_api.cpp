@@ -926,6 +926,72 @@ int mpcq_plant_step_batch(mpcq_ctx* c, const mpcq_plant_params* pl, int64_t B, c
   return MPCQ_OK;
 }
 
+// Episode monitor: tilt beyond 0.5 rad or the base below half of h_ref ends an episode.
+void mpcq_default_monitor_params(mpcq_monitor_params* mp) {
+  if (!mp) return;
+  memset(mp, 0, sizeof(*mp));
+  mp->max_tilt = 0.5;
+  mp->min_height = 0.10;
+  mp->max_ticks = 0;
+  mp->auto_reset = 0;
+}
+
+static int monitor_params(const mpcq_monitor_params* mp, mpcq_monitor_params* out) {
+  if (mp) *out = *mp;
+  else mpcq_default_monitor_params(out);
+  if (!(out->max_tilt > 0)) return fail(MPCQ_E_INVALID, "the monitor needs max_tilt > 0 (+inf: no tilt test)");
+  if (isnan(out->min_height) || out->min_height == INFINITY)
+    return fail(MPCQ_E_INVALID, "the monitor needs a finite min_height (or -inf: no height test)");
+  if (out->max_ticks < 0) return fail(MPCQ_E_INVALID, "the monitor needs max_ticks >= 0");
+  if (out->auto_reset != 0 && out->auto_reset != 1) return fail(MPCQ_E_INVALID, "auto_reset must be 0 or 1");
+  return MPCQ_OK;
+}
+
+int mpcq_monitor_step_batch(mpcq_ctx* c, const mpcq_monitor_params* mp, int64_t B, const double* q_w,
+                            const int32_t* status, const int32_t* iters, const double* f0, const double* cost,
+                            const double* state, const double* v_ref, double* ep, int32_t* ep_ticks,
+                            int32_t* episodes, double* last, int32_t* done, uint64_t* totals, double* trace,
+                            uint32_t flags) {
+  int rc = check_ctx(c, B);
+  if (rc) return rc;
+  if (!q_w || !status || !iters || !f0 || !cost || !state || !v_ref || !ep || !ep_ticks || !done)
+    return fail(MPCQ_E_INVALID, "q_w, status, iters, f0, cost, state, v_ref, ep, ep_ticks and done are required");
+  mpcq_monitor_params P;
+  rc = monitor_params(mp, &P);
+  if (rc) return rc;
+  if (B == 0) return MPCQ_OK;
+  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
+  DeviceGuard g(c->device);
+  mpcq::MonitorArgs a{};
+  a.batch = B;
+  const size_t b = (size_t)B;
+  enum { QW, ST, IT, F0, CO, SA, VR, EP, ET, ES, LA, DO, TO, TR, NX };
+  Xfer xs[NX] = {{q_w, nullptr, b * 48, nullptr},      {status, nullptr, b * 4, nullptr},
+                 {iters, nullptr, b * 4, nullptr},     {f0, nullptr, b * 96, nullptr},
+                 {cost, nullptr, b * 104, nullptr},    {state, nullptr, b * 96, nullptr},
+                 {v_ref, nullptr, b * 48, nullptr},    {ep, ep, b * 64, nullptr},
+                 {ep_ticks, ep_ticks, b * 4, nullptr}, {episodes, episodes, b * 4, nullptr},
+                 {last, last, b * 128, nullptr},       {nullptr, done, b * 4, nullptr},
+                 {totals, totals, 64, nullptr},        {trace, trace, b * MPCQ_TRACE * 8, nullptr}};
+  if (!dev) {
+    rc = stage(c, xs, NX);
+    if (rc) return rc;
+    a.q_w = (const double*)xs[QW].dev; a.status = (const int32_t*)xs[ST].dev; a.iters = (const int32_t*)xs[IT].dev;
+    a.f0 = (const double*)xs[F0].dev; a.cost = (const double*)xs[CO].dev; a.state = (const double*)xs[SA].dev;
+    a.v_ref = (const double*)xs[VR].dev; a.ep = (double*)xs[EP].dev; a.ep_ticks = (int32_t*)xs[ET].dev;
+    a.episodes = (int32_t*)xs[ES].dev; a.last = (double*)xs[LA].dev; a.done = (int32_t*)xs[DO].dev;
+    a.totals = (unsigned long long*)xs[TO].dev; a.trace = (double*)xs[TR].dev;
+  } else {
+    a.q_w = q_w; a.status = status; a.iters = iters; a.f0 = f0; a.cost = cost; a.state = state; a.v_ref = v_ref;
+    a.ep = ep; a.ep_ticks = ep_ticks; a.episodes = episodes; a.last = last; a.done = done;
+    a.totals = (unsigned long long*)totals; a.trace = trace;
+  }
+  HIP_TRY(mpcq::launch_monitor(P, a, c->stream));
+  if (!dev) return unstage(c, xs, NX);
+  if (!(flags & MPCQ_FLAG_ASYNC)) HIP_TRY(hipStreamSynchronize(c->stream));
+  return MPCQ_OK;
+}
+
 // ---------------------------------------------------------------------------
 // Closed-loop session: per-robot state resident in HBM (include/mpcq.h).
 
@@ -967,6 +1033,13 @@ struct mpcq_session {
   size_t pbytes[MPCQ_PV_COUNT] = {};
   double* qw_prev = nullptr;
   RobotTable plant_robots;  // mpcq_session_set_plant_robots
+  // mpcq_session_enable_monitor: the monitor's arrays (MPCQ_MV_*, an allocation of their own,
+  // made by the first enable)
+  bool monitor = false;
+  mpcq_monitor_params mp{};
+  void* mon_mem = nullptr;
+  void* marr[MPCQ_MV_COUNT] = {};
+  size_t mbytes[MPCQ_MV_COUNT] = {};
 };
 
 namespace {
@@ -1133,6 +1206,7 @@ int mpcq_session_destroy(mpcq_session* s) {
     if (s->robots.dev) (void)hipFree(s->robots.dev);
     if (s->plant_mem) (void)hipFree(s->plant_mem);
     if (s->plant_robots.dev) (void)hipFree(s->plant_robots.dev);
+    if (s->mon_mem) (void)hipFree(s->mon_mem);
   }
   delete s;
   return MPCQ_OK;
@@ -1286,8 +1360,128 @@ int mpcq_session_plant_device_ptr(mpcq_session* s, int what, void** out) {
   return MPCQ_OK;
 }
 
-int mpcq_session_tick(mpcq_session* s, int k, const double* state, const double* l_feet, const double* v_ref,
-                      const int32_t* reduced, uint32_t flags) {
+int mpcq_session_enable_monitor(mpcq_session* s, const mpcq_monitor_params* mp) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  mpcq_monitor_params P;
+  const int rc = monitor_params(mp, &P);
+  if (rc) return rc;
+  if (!s->mon_mem) {  // the arrays, zero but for ep[4] = +inf
+    DeviceGuard g(s->ctx->device);
+    const size_t B = (size_t)s->B;
+    const size_t nb[MPCQ_MV_COUNT] = {B * 4, B * 64, B * 4, B * 4, B * 128, 64};
+    size_t off[MPCQ_MV_COUNT], tot = 0;
+    for (int i = 0; i < MPCQ_MV_COUNT; ++i) { off[i] = tot; tot += (nb[i] + 255) & ~size_t(255); }
+    double* h = (double*)malloc(nb[MPCQ_MV_EP]);
+    if (!h) return fail(MPCQ_E_NOMEM, "host malloc failed");
+    for (size_t e = 0; e < B * 8; ++e) h[e] = e % 8 == 4 ? INFINITY : 0.0;
+    void* mem = nullptr;
+    if (hipMalloc(&mem, tot) != hipSuccess) {
+      free(h);
+      return fail(MPCQ_E_NOMEM, "hipMalloc(%zu) for the monitor arrays failed", tot);
+    }
+    hipError_t e = hipMemsetAsync(mem, 0, tot, s->ctx->stream);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync((char*)mem + off[MPCQ_MV_EP], h, nb[MPCQ_MV_EP], hipMemcpyHostToDevice, s->ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->ctx->stream);
+    free(h);
+    if (e != hipSuccess) {
+      (void)hipFree(mem);
+      return fail(MPCQ_E_DEVICE, "initialising the monitor arrays failed: %s", hipGetErrorString(e));
+    }
+    s->mon_mem = mem;
+    for (int i = 0; i < MPCQ_MV_COUNT; ++i) {
+      s->marr[i] = (char*)mem + off[i];
+      s->mbytes[i] = nb[i];
+    }
+  }
+  s->mp = P;
+  s->monitor = true;
+  return MPCQ_OK;
+}
+
+int mpcq_session_disable_monitor(mpcq_session* s) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  s->monitor = false;
+  return MPCQ_OK;
+}
+
+int mpcq_session_monitor_read(mpcq_session* s, int what, void* dst, uint32_t flags) {
+  if (!s || !dst) return fail(MPCQ_E_INVALID, "NULL argument");
+  if (what < 0 || what >= MPCQ_MV_COUNT) return fail(MPCQ_E_INVALID, "unknown monitor array %d", what);
+  if (!s->mon_mem) return fail(MPCQ_E_INVALID, "monitor array %d needs mpcq_session_enable_monitor", what);
+  DeviceGuard g(s->ctx->device);
+  const hipMemcpyKind kind = (flags & MPCQ_FLAG_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  HIP_TRY(hipMemcpyAsync(dst, s->marr[what], s->mbytes[what], kind, s->ctx->stream));
+  HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+  return MPCQ_OK;
+}
+
+int mpcq_session_monitor_device_ptr(mpcq_session* s, int what, void** out) {
+  if (!s || !out) return fail(MPCQ_E_INVALID, "NULL argument");
+  if (what < 0 || what >= MPCQ_MV_COUNT) return fail(MPCQ_E_INVALID, "unknown monitor array %d", what);
+  if (!s->mon_mem) return fail(MPCQ_E_INVALID, "monitor array %d needs mpcq_session_enable_monitor", what);
+  *out = s->marr[what];
+  return MPCQ_OK;
+}
+
+}  // extern "C"
+
+// What mpcq_session_reset enqueues on the context's stream, from device pointers: the reset
+// launch and, on a session that has ticked, the next solve's order.  Shared with a tick's
+// auto-reset (mpcq_session_enable_monitor).
+static hipError_t enqueue_reset(mpcq_session* s, const int32_t* mask, const double* gait0, const double* q_w0) {
+  mpcq_ctx* c = s->ctx;
+  const int N = c->N;
+  const int64_t B = s->B;
+  mpcq::ResetArgs ra{};
+  ra.batch = B;
+  ra.N = N;
+  ra.mask = mask;
+  ra.gait_src = gait0 ? gait0 : s->gait_init;
+  ra.q_w0 = q_w0;
+  ra.h_ref = s->pp.h_ref;
+  ra.rho0 = c->p.rho;
+  for (int i = 0; i < 8; ++i) ra.shoulders[i] = s->pp.shoulders[i];
+  ra.gait = (double*)s->arr[MPCQ_SV_GAIT];
+  ra.rot_flag = (int32_t*)s->arr[MPCQ_SV_ROT_FLAG];
+  ra.h_rot = (double*)s->arr[MPCQ_SV_H_ROT];
+  ra.xref = (double*)s->arr[MPCQ_SV_XREF];
+  ra.fsteps = (double*)s->arr[MPCQ_SV_FSTEPS];
+  ra.q_w = (double*)s->arr[MPCQ_SV_Q_W];
+  ra.state = (double*)s->arr[MPCQ_SV_STATE];
+  ra.l_feet = (double*)s->arr[MPCQ_SV_L_FEET];
+  ra.rho = (double*)s->arr[MPCQ_SV_RHO];
+  ra.y = (double*)s->arr[MPCQ_SV_Y];
+  ra.warm_x = s->warm_x;
+  ra.x = (double*)s->arr[MPCQ_SV_X];
+  ra.f0 = (double*)s->arr[MPCQ_SV_F0];
+  ra.x_robot = (double*)s->arr[MPCQ_SV_X_ROBOT];
+  ra.cost = (double*)s->arr[MPCQ_SV_COST];
+  ra.status = (int32_t*)s->arr[MPCQ_SV_STATUS];
+  ra.iters = (int32_t*)s->arr[MPCQ_SV_ITERS];
+  ra.first = (int32_t*)s->arr[MPCQ_SV_FIRST];
+  if (s->swing) {
+    ra.swing_ref = (double*)s->arr[MPCQ_SV_SWING_REF];
+    ra.swing_ref_doubles = (int64_t)s->sp.k_mpc * 36;
+    ra.swing_state = (double*)s->arr[MPCQ_SV_SWING_STATE];
+    ra.frame = (double*)s->arr[MPCQ_SV_FRAME];
+  }
+  if (s->mon_mem) {  // a reset robot's running episode is discarded
+    ra.ep = (double*)s->marr[MPCQ_MV_EP];
+    ra.ep_ticks = (int32_t*)s->marr[MPCQ_MV_EP_TICKS];
+  }
+  hipError_t e = mpcq::launch_reset(ra, c->stream);
+  // the robots with a pending reset to the front of the next solve's dispatch (a session that
+  // has not ticked yet has no order in use: it keeps the identity)
+  if (e == hipSuccess && s->have_order)
+    e = mpcq::launch_order((const int32_t*)s->arr[MPCQ_SV_ITERS], ra.first, B, s->order, c->stream);
+  s->resets = true;
+  return e;
+}
+
+// One tick; trace [B][MPCQ_TRACE] (device) or null: the monitor's row of this tick.
+static int session_tick(mpcq_session* s, int k, const double* state, const double* l_feet, const double* v_ref,
+                        const int32_t* reduced, uint32_t flags, double* trace) {
   if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
   if (!v_ref) return fail(MPCQ_E_INVALID, "v_ref is required");
   if (k < 0) return fail(MPCQ_E_INVALID, "k must be >= 0");
@@ -1432,6 +1626,25 @@ int mpcq_session_tick(mpcq_session* s, int k, const double* state, const double*
     for (int i = 0; i < 8; ++i) pa2.shoulders[i] = s->pp.shoulders[i];
     HIP_TRY(mpcq::launch_plant(s->pl, pa2, c->stream));
   }
+  if (s->monitor) {  // whose episode ended with this tick, and the episodes' statistics
+    mpcq::MonitorArgs ma{};
+    ma.batch = B;
+    ma.q_w = (const double*)s->arr[MPCQ_SV_Q_W];
+    ma.status = (const int32_t*)s->arr[MPCQ_SV_STATUS];
+    ma.iters = (const int32_t*)s->arr[MPCQ_SV_ITERS];
+    ma.f0 = (const double*)s->arr[MPCQ_SV_F0];
+    ma.cost = (const double*)s->arr[MPCQ_SV_COST];
+    ma.state = (const double*)s->arr[MPCQ_SV_STATE];
+    ma.v_ref = vr;
+    ma.ep = (double*)s->marr[MPCQ_MV_EP];
+    ma.ep_ticks = (int32_t*)s->marr[MPCQ_MV_EP_TICKS];
+    ma.episodes = (int32_t*)s->marr[MPCQ_MV_EPISODES];
+    ma.last = (double*)s->marr[MPCQ_MV_LAST];
+    ma.done = (int32_t*)s->marr[MPCQ_MV_DONE];
+    ma.totals = (unsigned long long*)s->marr[MPCQ_MV_TOTALS];
+    ma.trace = trace;
+    HIP_TRY(mpcq::launch_monitor(s->mp, ma, c->stream));
+  }
   // (the retrieve has cleared every pending reset: the order is by iteration counts alone)
   HIP_TRY(mpcq::launch_order((const int32_t*)s->arr[MPCQ_SV_ITERS], nullptr, B, s->order, c->stream));
   s->have_order = true;
@@ -1447,8 +1660,44 @@ int mpcq_session_tick(mpcq_session* s, int k, const double* state, const double*
     sa.ref = (double*)s->arr[MPCQ_SV_SWING_REF];
     HIP_TRY(mpcq::launch_swing(s->sp, sa, c->stream));
   }
+  // auto-reset, last: the swing launch above has read the tick's gait and fsteps
+  if (s->monitor && s->mp.auto_reset)
+    HIP_TRY(enqueue_reset(s, (const int32_t*)s->marr[MPCQ_MV_DONE], nullptr, nullptr));
   // host inputs are staged in buffers the next tick reuses: host calls block
   if (!(flags & MPCQ_FLAG_ASYNC) || !dev) HIP_TRY(hipStreamSynchronize(c->stream));
+  return MPCQ_OK;
+}
+
+extern "C" {
+
+int mpcq_session_tick(mpcq_session* s, int k, const double* state, const double* l_feet, const double* v_ref,
+                      const int32_t* reduced, uint32_t flags) {
+  return session_tick(s, k, state, l_feet, v_ref, reduced, flags, nullptr);
+}
+
+int mpcq_session_run(mpcq_session* s, int k0, int n_ticks, const double* v_ref, int v_ref_ticks, double* trace,
+                     uint32_t flags) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  if (!(flags & MPCQ_FLAG_DEVICE_PTRS)) return fail(MPCQ_E_INVALID, "mpcq_session_run needs MPCQ_FLAG_DEVICE_PTRS");
+  if (!v_ref || v_ref_ticks < 1) return fail(MPCQ_E_INVALID, "v_ref [v_ref_ticks][B][6] with v_ref_ticks >= 1 is required");
+  if (k0 < 0 || n_ticks < 1) return fail(MPCQ_E_INVALID, "need k0 >= 0 and n_ticks >= 1");
+  if (k0 > INT32_MAX - n_ticks) return fail(MPCQ_E_INVALID, "k0 + n_ticks overflows");
+  if (trace && !s->monitor) return fail(MPCQ_E_INVALID, "a trace needs mpcq_session_enable_monitor");
+  const size_t B = (size_t)s->B;
+  for (int t = 0; t < n_ticks; ++t) {
+    const int row = t < v_ref_ticks ? t : v_ref_ticks - 1;
+    const int rc = session_tick(s, k0 + t, nullptr, nullptr, v_ref + (size_t)row * B * 6, nullptr,
+                                MPCQ_FLAG_DEVICE_PTRS | MPCQ_FLAG_ASYNC,
+                                trace ? trace + (size_t)t * B * MPCQ_TRACE : nullptr);
+    if (rc) {
+      (void)hipStreamSynchronize(s->ctx->stream);
+      return rc;
+    }
+  }
+  if (!(flags & MPCQ_FLAG_ASYNC)) {
+    DeviceGuard g(s->ctx->device);
+    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+  }
   return MPCQ_OK;
 }
 
@@ -1457,7 +1706,6 @@ int mpcq_session_reset(mpcq_session* s, const int32_t* mask, const double* gait0
   if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
   mpcq_ctx* c = s->ctx;
   DeviceGuard g(c->device);
-  const int N = c->N;
   const int64_t B = s->B;
   const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
   // host arrays go through the session's staging buffers (the tick's, and one for the gait
@@ -1481,45 +1729,7 @@ int mpcq_session_reset(mpcq_session* s, const int32_t* mask, const double* gait0
       return fail(MPCQ_E_DEVICE, "staging the reset's inputs failed");
     }
   }
-  mpcq::ResetArgs ra{};
-  ra.batch = B;
-  ra.N = N;
-  ra.mask = mask;
-  ra.gait_src = gait0 ? gait0 : s->gait_init;
-  ra.q_w0 = q_w0;
-  ra.h_ref = s->pp.h_ref;
-  ra.rho0 = c->p.rho;
-  for (int i = 0; i < 8; ++i) ra.shoulders[i] = s->pp.shoulders[i];
-  ra.gait = (double*)s->arr[MPCQ_SV_GAIT];
-  ra.rot_flag = (int32_t*)s->arr[MPCQ_SV_ROT_FLAG];
-  ra.h_rot = (double*)s->arr[MPCQ_SV_H_ROT];
-  ra.xref = (double*)s->arr[MPCQ_SV_XREF];
-  ra.fsteps = (double*)s->arr[MPCQ_SV_FSTEPS];
-  ra.q_w = (double*)s->arr[MPCQ_SV_Q_W];
-  ra.state = (double*)s->arr[MPCQ_SV_STATE];
-  ra.l_feet = (double*)s->arr[MPCQ_SV_L_FEET];
-  ra.rho = (double*)s->arr[MPCQ_SV_RHO];
-  ra.y = (double*)s->arr[MPCQ_SV_Y];
-  ra.warm_x = s->warm_x;
-  ra.x = (double*)s->arr[MPCQ_SV_X];
-  ra.f0 = (double*)s->arr[MPCQ_SV_F0];
-  ra.x_robot = (double*)s->arr[MPCQ_SV_X_ROBOT];
-  ra.cost = (double*)s->arr[MPCQ_SV_COST];
-  ra.status = (int32_t*)s->arr[MPCQ_SV_STATUS];
-  ra.iters = (int32_t*)s->arr[MPCQ_SV_ITERS];
-  ra.first = (int32_t*)s->arr[MPCQ_SV_FIRST];
-  if (s->swing) {
-    ra.swing_ref = (double*)s->arr[MPCQ_SV_SWING_REF];
-    ra.swing_ref_doubles = (int64_t)s->sp.k_mpc * 36;
-    ra.swing_state = (double*)s->arr[MPCQ_SV_SWING_STATE];
-    ra.frame = (double*)s->arr[MPCQ_SV_FRAME];
-  }
-  hipError_t e = mpcq::launch_reset(ra, c->stream);
-  // the robots with a pending reset to the front of the next solve's dispatch (a session that
-  // has not ticked yet has no order in use: it keeps the identity)
-  if (e == hipSuccess && s->have_order)
-    e = mpcq::launch_order((const int32_t*)s->arr[MPCQ_SV_ITERS], ra.first, B, s->order, c->stream);
-  s->resets = true;
+  hipError_t e = enqueue_reset(s, mask, gait0, q_w0);
   if (!(flags & MPCQ_FLAG_ASYNC) || !dev) {
     const hipError_t es = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = es;

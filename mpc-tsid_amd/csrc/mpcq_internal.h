@@ -188,6 +188,9 @@ struct ResetArgs {
   int64_t swing_ref_doubles;
   double* swing_state;   // [B][4][MPCQ_SWING_STATE]
   double* frame;         // [B][3]
+  // the monitor's running episode, or null on a session without a monitor: discarded
+  double* ep;            // [B][8]
+  int32_t* ep_ticks;     // [B]
 };
 hipError_t launch_reset(const ResetArgs& a, hipStream_t s);
 
@@ -254,6 +257,27 @@ struct PlantArgs {
   double shoulders[8];
 };
 hipError_t launch_plant(const mpcq_plant_params& pl, const PlantArgs& a, hipStream_t s);
+
+// Episode monitor (mpcq_monitor.hip); semantics and layouts in include/mpcq.h
+// (mpcq_monitor_step_batch, mpcq_session_enable_monitor).  One thread per robot.
+struct MonitorArgs {
+  int64_t batch;
+  const double* q_w;       // [B][6]
+  const int32_t* status;   // [B]
+  const int32_t* iters;    // [B]
+  const double* f0;        // [B][12]
+  const double* cost;      // [B][13]
+  const double* state;     // [B][12]
+  const double* v_ref;     // [B][6]
+  double* ep;              // [B][8] in/out
+  int32_t* ep_ticks;       // [B] in/out
+  int32_t* episodes;       // [B] in/out, or null
+  double* last;            // [B][16] or null
+  int32_t* done;           // [B] out
+  unsigned long long* totals;  // [8] or null
+  double* trace;           // [B][MPCQ_TRACE] or null
+};
+hipError_t launch_monitor(const mpcq_monitor_params& mp, const MonitorArgs& a, hipStream_t s);
 
 // Launchers (mpcq_engine.hip).  Return hipError_t.
 hipError_t launch_formulate(int N, const mpcq_params& p, const LaunchArgs& a, hipStream_t s);

@@ -186,6 +186,10 @@ __global__ __launch_bounds__(64) void reset_kernel(ResetArgs a) {
     fill(a.swing_state, 4 * MPCQ_SWING_STATE, 0.0);
     fill(a.frame, 3, 0.0);
   }
+  if (a.ep) {  // the running episode is discarded: no episode is counted (mpcq_monitor.hip)
+    if (lane < 8) a.ep[b * 8 + lane] = lane == 4 ? INFINITY : 0.0;
+    if (lane == 0) a.ep_ticks[b] = 0;
+  }
 }
 
 }  // namespace

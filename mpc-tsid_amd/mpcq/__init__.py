@@ -13,6 +13,9 @@ Public surface:
   Swing             batched swing-foot trajectories between two ticks (Session.enable_swing)
   Plant             batched rigid-body plant under the stance feet's forces: true robots that
                     differ from the model, external pushes (Session.enable_plant)
+  Monitor           episodes on the device: per-robot termination, episode statistics, batch
+                    totals (Session.enable_monitor: auto-reset; Session.run: whole rollouts
+                    with a per-tick trace)
   synth             seeded synthetic inputs shaped like FootstepPlanner's
 """
 from . import synth  # noqa: F401
@@ -27,8 +30,11 @@ from ._lib import (FLAG_ASYNC, FLAG_DEVICE_PTRS, FLAG_ORDER_BY_CLASS, MODE_SETUP
                    Params, build, build_info, default_params, lib, source_sha, supported_horizons,
                    SV_FRAME, SV_SWING_REF, SV_SWING_STATE, SWING_STATE, SwingParams, default_swing_params,
                    Robot, default_robot,
-                   PLANT_MODEL, PLANT_RIGID, PV_F_EFF, PV_STATE_END, PV_WRENCH, PlantParams, default_plant_params)
+                   PLANT_MODEL, PLANT_RIGID, PV_F_EFF, PV_STATE_END, PV_WRENCH, PlantParams, default_plant_params,
+                   DONE_HEIGHT, DONE_NONFINITE, DONE_SOLVER, DONE_TILT, DONE_TIMEOUT, MV_DONE, MV_EP, MV_EP_TICKS,
+                   MV_EPISODES, MV_LAST, MV_TOTALS, TRACE, MonitorParams, default_monitor_params)
 from .engine import ROBOT_DTYPE, Engine, dims, pattern, robots  # noqa: F401
+from .monitor import Monitor  # noqa: F401
 from .plant import Plant  # noqa: F401
 from .session import Session  # noqa: F401
 from .swing import Swing  # noqa: F401

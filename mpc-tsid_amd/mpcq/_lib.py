@@ -68,6 +68,11 @@ SWING_STATE = 40  # MPCQ_SWING_STATE: doubles per foot
 # the rigid-body plant: integrators (MPCQ_PLANT_*) and a session's plant arrays (MPCQ_PV_*)
 PLANT_MODEL, PLANT_RIGID = 0, 1
 PV_STATE_END, PV_F_EFF, PV_WRENCH = 0, 1, 2
+# the episode monitor: done bits (MPCQ_DONE_*), a session's monitor arrays (MPCQ_MV_*), the
+# doubles of a trace row (MPCQ_TRACE)
+DONE_NONFINITE, DONE_TILT, DONE_HEIGHT, DONE_SOLVER, DONE_TIMEOUT = 1, 2, 4, 8, 16
+MV_DONE, MV_EP, MV_EP_TICKS, MV_EPISODES, MV_LAST, MV_TOTALS = range(6)
+TRACE = 16
 
 EXPORTS = ("mpcq_abi_version", "mpcq_default_params", "mpcq_dims", "mpcq_pattern",
            "mpcq_supported_horizons", "mpcq_last_error", "mpcq_create", "mpcq_destroy",
@@ -85,7 +90,10 @@ EXPORTS = ("mpcq_abi_version", "mpcq_default_params", "mpcq_dims", "mpcq_pattern
            "mpcq_session_reset",
            "mpcq_default_plant_params", "mpcq_plant_step_batch", "mpcq_session_enable_plant",
            "mpcq_session_disable_plant", "mpcq_session_set_plant_robots", "mpcq_session_set_wrench",
-           "mpcq_session_plant_read", "mpcq_session_plant_device_ptr")
+           "mpcq_session_plant_read", "mpcq_session_plant_device_ptr",
+           "mpcq_default_monitor_params", "mpcq_monitor_step_batch", "mpcq_session_enable_monitor",
+           "mpcq_session_disable_monitor", "mpcq_session_monitor_read", "mpcq_session_monitor_device_ptr",
+           "mpcq_session_run")
 
 
 class MpcqError(RuntimeError):
@@ -177,6 +185,18 @@ class PlantParams(C.Structure):
         ("integrator", C.c_int32),
         ("clamp", C.c_int32),
         ("reserved", C.c_int32 * 5),
+    ]
+
+
+class MonitorParams(C.Structure):
+    """struct mpcq_monitor_params (include/mpcq.h)."""
+
+    _fields_ = [
+        ("max_tilt", C.c_double),
+        ("min_height", C.c_double),
+        ("max_ticks", C.c_int32),
+        ("auto_reset", C.c_int32),
+        ("reserved", C.c_int32 * 10),
     ]
 
 
@@ -307,6 +327,18 @@ def lib():
                  "mpcq_session_set_plant_robots", "mpcq_session_set_wrench", "mpcq_session_plant_read",
                  "mpcq_session_plant_device_ptr"):
         getattr(L, name).restype = C.c_int
+    MP = C.POINTER(MonitorParams)
+    L.mpcq_default_monitor_params.argtypes = [MP]
+    L.mpcq_default_monitor_params.restype = None
+    L.mpcq_monitor_step_batch.argtypes = [vp, MP, C.c_int64] + [vp] * 14 + [C.c_uint32]
+    L.mpcq_session_enable_monitor.argtypes = [vp, MP]
+    L.mpcq_session_disable_monitor.argtypes = [vp]
+    L.mpcq_session_monitor_read.argtypes = [vp, C.c_int, vp, C.c_uint32]
+    L.mpcq_session_monitor_device_ptr.argtypes = [vp, C.c_int, C.POINTER(vp)]
+    L.mpcq_session_run.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_uint32]
+    for name in ("mpcq_monitor_step_batch", "mpcq_session_enable_monitor", "mpcq_session_disable_monitor",
+                 "mpcq_session_monitor_read", "mpcq_session_monitor_device_ptr", "mpcq_session_run"):
+        getattr(L, name).restype = C.c_int
     for name in ("mpcq_debug_class_table_read", "mpcq_debug_class_table_write", "mpcq_debug_class_order",
                  "mpcq_debug_class_learn", "mpcq_debug_suspended", "mpcq_debug_session_order",
                  "mpcq_debug_last_dispatch"):
@@ -367,6 +399,16 @@ def default_plant_params(**overrides) -> PlantParams:
     for k, v in overrides.items():
         if not hasattr(p, k):
             raise AttributeError(f"unknown plant parameter {k}")
+        setattr(p, k, v)
+    return p
+
+
+def default_monitor_params(**overrides) -> MonitorParams:
+    p = MonitorParams()
+    lib().mpcq_default_monitor_params(C.byref(p))
+    for k, v in overrides.items():
+        if not hasattr(p, k):
+            raise AttributeError(f"unknown monitor parameter {k}")
         setattr(p, k, v)
     return p
 

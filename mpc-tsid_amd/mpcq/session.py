@@ -56,6 +56,7 @@ class Session:
         self.k = 0
         self.swing_params = None
         self.plant_params = None
+        self.monitor_params = None
 
     def enable_swing(self, params: L.SwingParams | None = None):
         """Opt in to the swing-foot references: every later tick appends one swing launch over
@@ -134,6 +135,90 @@ class Session:
         out = C.c_void_p()
         self.engine._call("mpcq_session_plant_device_ptr", self._h, what, C.byref(out))
         return int(out.value or 0)
+
+    # ------------------------------------------------------------------ episode monitor
+    def enable_monitor(self, params: L.MonitorParams | None = None, **overrides):
+        """Opt in to episodes: every later tick runs the monitor directly after its plant launch
+        (without a plant: after its retrieve): MV_DONE holds the tick's done bits (``DONE_*``), a
+        device mask ``reset_device`` takes; MV_EP / MV_EP_TICKS the running episode, MV_LAST the
+        last ended one, MV_EPISODES and MV_TOTALS the counts.  With ``auto_reset=1`` the tick
+        itself restarts the robots whose episode ended.  ``params`` None: the defaults, with
+        ``overrides`` (``max_tilt``, ``min_height``, ``max_ticks``, ``auto_reset``).  Calling it
+        again replaces the parameters and keeps the arrays."""
+        if params is not None and overrides:
+            raise ValueError("pass params or overrides, not both")
+        mp = params or L.default_monitor_params(**overrides)
+        self.engine._call("mpcq_session_enable_monitor", self._h, C.byref(mp))
+        self.monitor_params = mp
+
+    def disable_monitor(self):
+        """The ticks after it run without the monitor and its auto-reset; the arrays stay."""
+        self.engine._call("mpcq_session_disable_monitor", self._h)
+        self.monitor_params = None
+
+    def _monitor_shape(self, what: int):
+        B = self.batch
+        shapes = {L.MV_DONE: ((B,), np.int32), L.MV_EP: ((B, 8), np.float64), L.MV_EP_TICKS: ((B,), np.int32),
+                  L.MV_EPISODES: ((B,), np.int32), L.MV_LAST: ((B, 16), np.float64), L.MV_TOTALS: ((8,), np.uint64)}
+        if what not in shapes:
+            raise L.MpcqError(L.E_INVALID, f"unknown monitor array {what}")
+        return shapes[what]
+
+    def monitor_read(self, what: int):
+        """MV_DONE (B,) int32, MV_EP (B, 8), MV_EP_TICKS (B,) int32, MV_EPISODES (B,) int32,
+        MV_LAST (B, 16) or MV_TOTALS (8,) uint64."""
+        shape, dt = self._monitor_shape(what)
+        out = np.empty(shape, dt)
+        self.engine._call("mpcq_session_monitor_read", self._h, what, C.c_void_p(out.ctypes.data), 0)
+        return out
+
+    def monitor_device_ptr(self, what: int) -> int:
+        out = C.c_void_p()
+        self.engine._call("mpcq_session_monitor_device_ptr", self._h, what, C.byref(out))
+        return int(out.value or 0)
+
+    # ------------------------------------------------------------------ rollouts
+    def _to_device(self, a):
+        """A host array on the engine's device through torch: (the tensor, which owns the memory,
+        its address).  The copy has completed when this returns."""
+        import torch
+        t = torch.from_numpy(a).to(f"cuda:{self.engine.device}")
+        return t, t.data_ptr()
+
+    def _new_device(self, shape):
+        """An uninitialised float64 device array through torch: (tensor, address, to_numpy)."""
+        import torch
+        t = torch.empty(shape, dtype=torch.float64, device=f"cuda:{self.engine.device}")
+        return t, t.data_ptr(), lambda: t.cpu().numpy()
+
+    def run(self, v_ref, n_ticks: int, trace: bool = False, k: int | None = None):
+        """``n_ticks`` ticks of the virtual robot (or the plant) enqueued in one call.  ``v_ref``
+        (host) is (6,) or (B, 6) for every tick, or a schedule (T, B, 6) whose last row is held
+        once the ticks outrun it.  ``trace=True`` (needs ``enable_monitor``) returns the
+        monitor's per-tick rows (n_ticks, B, TRACE), otherwise None."""
+        B = self.batch
+        n_ticks = int(n_ticks)
+        v = np.asarray(v_ref, np.float64)
+        if v.ndim < 3:
+            v = np.broadcast_to(v, (1, B, 6))
+        elif v.ndim != 3 or v.shape[0] < 1:
+            raise ValueError(f"v_ref must be (6,), ({B}, 6) or (T, {B}, 6); got {v.shape}")
+        v = np.ascontiguousarray(np.broadcast_to(v, (v.shape[0], B, 6)))
+        keep, v_ptr = self._to_device(v)
+        tr, tr_ptr, fetch = self._new_device((max(n_ticks, 0), B, L.TRACE)) if trace else (None, 0, None)
+        self.run_device(v_ptr, n_ticks, v_ref_ticks=v.shape[0], trace_ptr=tr_ptr, k=k, asynchronous=False)
+        del keep
+        return fetch() if trace else None
+
+    def run_device(self, v_ref_ptr: int, n_ticks: int, v_ref_ticks: int = 1, trace_ptr: int = 0,
+                   k: int | None = None, asynchronous: bool = True):
+        """``run`` on device arrays: v_ref (v_ref_ticks, B, 6), trace (n_ticks, B, TRACE) or 0."""
+        k = self.k if k is None else int(k)
+        v = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        flags = L.FLAG_DEVICE_PTRS | (L.FLAG_ASYNC if asynchronous else 0)
+        self.engine._call("mpcq_session_run", self._h, k, int(n_ticks), v(v_ref_ptr), int(v_ref_ticks), v(trace_ptr),
+                          flags)
+        self.k = k + int(n_ticks)
 
     def close(self):
         if getattr(self, "_h", None):
