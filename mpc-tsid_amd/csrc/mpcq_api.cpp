@@ -1,71 +1,25 @@
-// mpcq_api.cpp — host side of the C ABI declared in include/mpcq.h.
+// mpcq_api.cpp — host side of the C ABI declared in include/mpcq.h: contexts, the batch
+// entry points and the mpcq_debug_* diagnostics (sessions: mpcq_session_api.cpp).
 //
 // Owns HIP contexts, device staging buffers for host-pointer calls, stream
-// and event handling.  All numerics run in the HIP kernels
-// (mpcq_kernels.hip); there is no CPU fallback: a missing device is an error.
+// and event handling.  All numerics run in the HIP kernels (mpcq_engine.hip,
+// mpcq_planner.hip, mpcq_session.hip, mpcq_order.hip, mpcq_swing.hip, mpcq_plant.hip,
+// mpcq_monitor.hip); there is no CPU fallback: a missing device is an error.
 #include <math.h>
 #include <stdarg.h>
 #include <stdlib.h>
 #include <stdio.h>
 #include <string.h>
 
-#include <mutex>
 #include <string>
 
-#include "mpcq_internal.h"
+#include "mpcq_host.h"
 
-// A table of per-robot constants on the device (mpcq_set_robots, mpcq_session_set_robots):
-// count > 0 = in force.
-struct RobotTable {
-  mpcq_robot* dev = nullptr;
-  int64_t cap = 0;
-  int64_t count = 0;
-};
+using namespace mpcq;
 
-struct mpcq_ctx {
-  int device = 0;
-  int N = 0;
-  mpcq_params p{};
-  hipStream_t own_stream = nullptr;
-  hipStream_t stream = nullptr;
-  void* arena = nullptr;
-  size_t arena_bytes = 0;
-  void* work = nullptr;  // engine workspace (horizons beyond 32 stages)
-  size_t work_bytes = 0;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  bool have_form = false, have_solve = false;
-  uint64_t* stamps = nullptr;
-  // MPCQ_FLAG_ORDER_BY_CLASS: the class table (sum of iterations, count per slot) and the
-  // per-instance scratch (class slot, dispatch order, iteration counts when the caller
-  // passes none)
-  uint64_t* cls_sum = nullptr;
-  uint64_t* cls_cnt = nullptr;
-  int32_t* ord_buf = nullptr;
-  int64_t ord_cap = 0;
-  // what the last batch solve dispatched by (mpcq_debug_last_dispatch): host bookkeeping only
-  int64_t last_B = 0;
-  bool last_by_class = false, last_sliced = false;
-  // sliced solves (mpcq_set_slice): the slice length (0: off), the suspended instances'
-  // iterates (mpcq::res_lanes(N) x 8 doubles, rho, key, 4 counters each), the resumed launch's
-  // dispatch list (B int32, of 3 B: two once held alternating lists) and a status scratch, the
-  // resumed launch's workgroup count (device)
-  int32_t slice_iters = 0;
-  double* res = nullptr;
-  double* res_rho = nullptr;
-  double* res_key = nullptr;
-  int32_t* res_i = nullptr;
-  int32_t* sl_buf = nullptr;
-  int64_t sl_cap = 0;
-  int32_t* sl_count = nullptr;
-  RobotTable robots;  // mpcq_set_robots
-};
+static thread_local std::string g_err;  // mpcq_last_error
 
-namespace {
-
-thread_local std::string g_err;
-
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int code, const char* fmt, ...) {
+int mpcq::fail(int code, const char* fmt, ...) {
   char buf[512];
   va_list ap;
   va_start(ap, fmt);
@@ -75,23 +29,7 @@ int fail(int code, const char* fmt, ...) {
   return code;
 }
 
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t e_ = (expr);                                                             \
-    if (e_ != hipSuccess)                                                               \
-      return fail(MPCQ_E_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_));        \
-  } while (0)
-
-struct DeviceGuard {
-  int prev = -1;
-  explicit DeviceGuard(int d) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != d) (void)hipSetDevice(d);
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
+namespace {
 
 int check_params(const mpcq_params* p) {
   if (!p) return fail(MPCQ_E_INVALID, "params is NULL");
@@ -134,32 +72,6 @@ int ensure_arena(mpcq_ctx* c, size_t bytes) {
     return fail(MPCQ_E_NOMEM, "hipMalloc(%zu) failed", want);
   }
   c->arena_bytes = want;
-  return MPCQ_OK;
-}
-
-// The engine's per-instance workspace (mpcq::work_doubles(N), zero up to 32 stages).
-int ensure_work(mpcq_ctx* c, int64_t B, double** out) {
-  *out = nullptr;
-  const size_t bytes = (size_t)mpcq::work_doubles(c->N) * 8 * (size_t)B;
-  if (bytes == 0) return MPCQ_OK;
-  if (bytes > c->work_bytes) {
-    if (c->work) {
-      HIP_TRY(hipStreamSynchronize(c->stream));  // a queued launch may still use it
-      HIP_TRY(hipFree(c->work));
-    }
-    c->work = nullptr;
-    c->work_bytes = 0;
-    if (hipMalloc(&c->work, bytes) != hipSuccess) {
-      c->work = nullptr;
-      return fail(MPCQ_E_NOMEM, "hipMalloc(%zu) for the engine workspace failed", bytes);
-    }
-    // zeroed once, as a guard only: no kernel reads a workspace slot it has not
-    // written earlier in the same launch (DESIGN.md §4.1 "LDS hygiene"; the suite
-    // passes on a build without the LDS zeroing either)
-    HIP_TRY(hipMemsetAsync(c->work, 0, bytes, c->stream));
-    c->work_bytes = bytes;
-  }
-  *out = (double*)c->work;
   return MPCQ_OK;
 }
 
@@ -223,12 +135,6 @@ int unstage(mpcq_ctx* c, Xfer* xs, int nx) {
   return MPCQ_OK;
 }
 
-int check_ctx(mpcq_ctx* c, int64_t batch) {
-  if (!c) return fail(MPCQ_E_INVALID, "ctx is NULL");
-  if (batch < 0 || batch > (int64_t)0x7fffffff) return fail(MPCQ_E_INVALID, "bad batch %lld", (long long)batch);
-  return MPCQ_OK;
-}
-
 // Sliced-solve scratch (mpcq_set_slice): the suspended iterates, the dispatch lists, the count
 int ensure_slice(mpcq_ctx* c, int64_t B) {
   if (!c->sl_count) {
@@ -285,9 +191,83 @@ int check_robots(const mpcq_robot* r, int64_t count) {
   return MPCQ_OK;
 }
 
-// Replace (count > 0) or clear a table.  The copy runs on the context's stream, behind any
-// queued launch that still reads the old values; from a host pointer the call then blocks.
-int set_table(mpcq_ctx* c, RobotTable& t, int64_t count, const mpcq_robot* robots, uint32_t flags) {
+// The table a launch of `batch` instances reads: null without one, an error if it is too short.
+int launch_table(const RobotTable& t, int64_t batch, const mpcq_robot** out) {
+  *out = nullptr;
+  if (t.count == 0) return MPCQ_OK;
+  if (batch > t.count)
+    return fail(MPCQ_E_INVALID, "batch %lld > the robot table's count %lld", (long long)batch, (long long)t.count);
+  *out = t.dev;
+  return MPCQ_OK;
+}
+
+}  // namespace
+
+// What mpcq_session_api.cpp shares (mpcq_host.h).
+
+int mpcq::swing_params(const mpcq_swing_params* sp, mpcq_swing_params* out) {
+  if (sp) *out = *sp;
+  else mpcq_default_swing_params(out);
+  if (!(out->dt > 0) || out->k_mpc < 1 || !(out->t_lock >= 0))
+    return fail(MPCQ_E_INVALID, "swing needs dt > 0, k_mpc >= 1, t_lock >= 0");
+  return MPCQ_OK;
+}
+
+int mpcq::plant_params(const mpcq_plant_params* pl, double dt_default, mpcq_plant_params* out) {
+  if (pl) *out = *pl;
+  else {
+    mpcq_default_plant_params(out);
+    if (dt_default > 0) out->dt = dt_default;
+  }
+  if (!(out->dt > 0) || out->n_sub < 1 ||
+      (out->integrator != MPCQ_PLANT_MODEL && out->integrator != MPCQ_PLANT_RIGID))
+    return fail(MPCQ_E_INVALID, "the plant needs dt > 0, n_sub >= 1, integrator MPCQ_PLANT_MODEL or MPCQ_PLANT_RIGID");
+  return MPCQ_OK;
+}
+
+int mpcq::monitor_params(const mpcq_monitor_params* mp, mpcq_monitor_params* out) {
+  if (mp) *out = *mp;
+  else mpcq_default_monitor_params(out);
+  if (!(out->max_tilt > 0)) return fail(MPCQ_E_INVALID, "the monitor needs max_tilt > 0 (+inf: no tilt test)");
+  if (isnan(out->min_height) || out->min_height == INFINITY)
+    return fail(MPCQ_E_INVALID, "the monitor needs a finite min_height (or -inf: no height test)");
+  if (out->max_ticks < 0) return fail(MPCQ_E_INVALID, "the monitor needs max_ticks >= 0");
+  if (out->auto_reset != 0 && out->auto_reset != 1) return fail(MPCQ_E_INVALID, "auto_reset must be 0 or 1");
+  return MPCQ_OK;
+}
+
+int mpcq::check_ctx(mpcq_ctx* c, int64_t batch) {
+  if (!c) return fail(MPCQ_E_INVALID, "ctx is NULL");
+  if (batch < 0 || batch > (int64_t)0x7fffffff) return fail(MPCQ_E_INVALID, "bad batch %lld", (long long)batch);
+  return MPCQ_OK;
+}
+
+int mpcq::ensure_work(mpcq_ctx* c, int64_t B, double** out) {
+  *out = nullptr;
+  const size_t bytes = (size_t)mpcq::work_doubles(c->N) * 8 * (size_t)B;
+  if (bytes == 0) return MPCQ_OK;
+  if (bytes > c->work_bytes) {
+    if (c->work) {
+      HIP_TRY(hipStreamSynchronize(c->stream));  // a queued launch may still use it
+      HIP_TRY(hipFree(c->work));
+    }
+    c->work = nullptr;
+    c->work_bytes = 0;
+    if (hipMalloc(&c->work, bytes) != hipSuccess) {
+      c->work = nullptr;
+      return fail(MPCQ_E_NOMEM, "hipMalloc(%zu) for the engine workspace failed", bytes);
+    }
+    // zeroed once, as a guard only: no kernel reads a workspace slot it has not
+    // written earlier in the same launch (DESIGN.md §4.1 "LDS hygiene"; the suite
+    // passes on a build without the LDS zeroing either)
+    HIP_TRY(hipMemsetAsync(c->work, 0, bytes, c->stream));
+    c->work_bytes = bytes;
+  }
+  *out = (double*)c->work;
+  return MPCQ_OK;
+}
+
+int mpcq::set_table(mpcq_ctx* c, RobotTable& t, int64_t count, const mpcq_robot* robots, uint32_t flags) {
   if (count < 0 || count > (int64_t)0x7fffffff) return fail(MPCQ_E_INVALID, "bad robot count %lld", (long long)count);
   if (count == 0 || !robots) {
     t.count = 0;
@@ -322,18 +302,6 @@ int set_table(mpcq_ctx* c, RobotTable& t, int64_t count, const mpcq_robot* robot
   if (!dev) HIP_TRY(hipStreamSynchronize(c->stream));
   return MPCQ_OK;
 }
-
-// The table a launch of `batch` instances reads: null without one, an error if it is too short.
-int launch_table(const RobotTable& t, int64_t batch, const mpcq_robot** out) {
-  *out = nullptr;
-  if (t.count == 0) return MPCQ_OK;
-  if (batch > t.count)
-    return fail(MPCQ_E_INVALID, "batch %lld > the robot table's count %lld", (long long)batch, (long long)t.count);
-  *out = t.dev;
-  return MPCQ_OK;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -781,14 +749,6 @@ void mpcq_default_swing_params(mpcq_swing_params* sp) {
   sp->k_mpc = 20;
 }
 
-static int swing_params(const mpcq_swing_params* sp, mpcq_swing_params* out) {
-  if (sp) *out = *sp;
-  else mpcq_default_swing_params(out);
-  if (!(out->dt > 0) || out->k_mpc < 1 || !(out->t_lock >= 0))
-    return fail(MPCQ_E_INVALID, "swing needs dt > 0, k_mpc >= 1, t_lock >= 0");
-  return MPCQ_OK;
-}
-
 int mpcq_swing_step_batch(mpcq_ctx* c, const mpcq_swing_params* sp, int64_t B, const double* in, double* state,
                           double* out, uint32_t flags) {
   int rc = check_ctx(c, B);
@@ -871,18 +831,6 @@ void mpcq_default_plant_params(mpcq_plant_params* pl) {
   pl->clamp = 1;
 }
 
-static int plant_params(const mpcq_plant_params* pl, double dt_default, mpcq_plant_params* out) {
-  if (pl) *out = *pl;
-  else {
-    mpcq_default_plant_params(out);
-    if (dt_default > 0) out->dt = dt_default;
-  }
-  if (!(out->dt > 0) || out->n_sub < 1 ||
-      (out->integrator != MPCQ_PLANT_MODEL && out->integrator != MPCQ_PLANT_RIGID))
-    return fail(MPCQ_E_INVALID, "the plant needs dt > 0, n_sub >= 1, integrator MPCQ_PLANT_MODEL or MPCQ_PLANT_RIGID");
-  return MPCQ_OK;
-}
-
 int mpcq_plant_step_batch(mpcq_ctx* c, const mpcq_plant_params* pl, int64_t B, const double* state,
                           const double* feet, const double* f, const double* wrench, const mpcq_robot* robots,
                           double* state_out, double* f_eff, uint32_t flags) {
@@ -936,17 +884,6 @@ void mpcq_default_monitor_params(mpcq_monitor_params* mp) {
   mp->auto_reset = 0;
 }
 
-static int monitor_params(const mpcq_monitor_params* mp, mpcq_monitor_params* out) {
-  if (mp) *out = *mp;
-  else mpcq_default_monitor_params(out);
-  if (!(out->max_tilt > 0)) return fail(MPCQ_E_INVALID, "the monitor needs max_tilt > 0 (+inf: no tilt test)");
-  if (isnan(out->min_height) || out->min_height == INFINITY)
-    return fail(MPCQ_E_INVALID, "the monitor needs a finite min_height (or -inf: no height test)");
-  if (out->max_ticks < 0) return fail(MPCQ_E_INVALID, "the monitor needs max_ticks >= 0");
-  if (out->auto_reset != 0 && out->auto_reset != 1) return fail(MPCQ_E_INVALID, "auto_reset must be 0 or 1");
-  return MPCQ_OK;
-}
-
 int mpcq_monitor_step_batch(mpcq_ctx* c, const mpcq_monitor_params* mp, int64_t B, const double* q_w,
                             const int32_t* status, const int32_t* iters, const double* f0, const double* cost,
                             const double* state, const double* v_ref, double* ep, int32_t* ep_ticks,
@@ -989,788 +926,6 @@ int mpcq_monitor_step_batch(mpcq_ctx* c, const mpcq_monitor_params* mp, int64_t 
   HIP_TRY(mpcq::launch_monitor(P, a, c->stream));
   if (!dev) return unstage(c, xs, NX);
   if (!(flags & MPCQ_FLAG_ASYNC)) HIP_TRY(hipStreamSynchronize(c->stream));
-  return MPCQ_OK;
-}
-
-// ---------------------------------------------------------------------------
-// Closed-loop session: per-robot state resident in HBM (include/mpcq.h).
-
-}  // extern "C"
-
-struct mpcq_session {
-  mpcq_ctx* ctx = nullptr;
-  int64_t B = 0;
-  mpcq_planner_params pp{};
-  void* mem = nullptr;
-  void* arr[MPCQ_SV_COUNT] = {};
-  size_t bytes[MPCQ_SV_COUNT] = {};
-  double* warm_x = nullptr;
-  int32_t* plan_status = nullptr;
-  int32_t* info = nullptr;
-  double* in_state = nullptr;   // staging of host inputs
-  double* in_lfeet = nullptr;
-  double* in_vref = nullptr;
-  int32_t* in_reduced = nullptr;
-  int32_t* order = nullptr;  // dispatch order of the next solve (longest previous first)
-  bool have_order = false;
-  bool use_order = true;  // MPCQ_DISPATCH_ORDER=0 turns it off (A/B timing only; results are identical)
-  // mpcq_session_enable_swing: the swing arrays (an allocation of their own) and parameters
-  bool swing = false;
-  mpcq_swing_params sp{};
-  void* swing_mem = nullptr;
-  RobotTable robots;  // mpcq_session_set_robots (the session's own, not the context's)
-  // mpcq_session_reset: the gait table every robot was created with, and whether a reset was
-  // ever called (from then on the ticks consult MPCQ_SV_FIRST)
-  double* gait_init = nullptr;
-  double* in_gait = nullptr;  // staging of a host gait0
-  bool resets = false;
-  // mpcq_session_enable_plant: the plant's arrays (MPCQ_PV_*, an allocation of their own, made
-  // by the first enable or set_wrench) and the copy of q_w a tick takes before its retrieve
-  bool plant = false;
-  mpcq_plant_params pl{};
-  void* plant_mem = nullptr;
-  void* parr[MPCQ_PV_COUNT] = {};
-  size_t pbytes[MPCQ_PV_COUNT] = {};
-  double* qw_prev = nullptr;
-  RobotTable plant_robots;  // mpcq_session_set_plant_robots
-  // mpcq_session_enable_monitor: the monitor's arrays (MPCQ_MV_*, an allocation of their own,
-  // made by the first enable)
-  bool monitor = false;
-  mpcq_monitor_params mp{};
-  void* mon_mem = nullptr;
-  void* marr[MPCQ_MV_COUNT] = {};
-  size_t mbytes[MPCQ_MV_COUNT] = {};
-};
-
-namespace {
-
-size_t sv_bytes(int what, int64_t B, int N) {
-  const size_t b = (size_t)B;
-  switch (what) {
-    case MPCQ_SV_F0: return b * 12 * 8;
-    case MPCQ_SV_X: return b * 24 * N * 8;
-    case MPCQ_SV_X_ROBOT: return b * 12 * N * 8;
-    case MPCQ_SV_Q_W: return b * 6 * 8;
-    case MPCQ_SV_COST: return b * 13 * 8;
-    case MPCQ_SV_XREF: return b * 12 * (N + 1) * 8;
-    case MPCQ_SV_FSTEPS: return b * 260 * 8;
-    case MPCQ_SV_GAIT: return b * 100 * 8;
-    case MPCQ_SV_STATUS: return b * 4;
-    case MPCQ_SV_ITERS: return b * 4;
-    case MPCQ_SV_RHO: return b * 8;
-    case MPCQ_SV_Y: return b * 44 * N * 8;
-    case MPCQ_SV_STATE: return b * 12 * 8;
-    case MPCQ_SV_L_FEET: return b * 12 * 8;
-    case MPCQ_SV_ROT_FLAG: return b * 4;
-    case MPCQ_SV_H_ROT: return b * 8;
-    case MPCQ_SV_ORDER: return b * 4;
-    case MPCQ_SV_FIRST: return b * 4;
-  }
-  return 0;
-}
-
-}  // namespace
-
-extern "C" {
-
-int mpcq_session_create(mpcq_ctx* c, int64_t B, const mpcq_planner_params* pp, const double* gait0,
-                        mpcq_session** out) {
-  if (!out) return fail(MPCQ_E_INVALID, "out is NULL");
-  *out = nullptr;
-  int rc = check_ctx(c, B);
-  if (rc) return rc;
-  if (B < 1) return fail(MPCQ_E_INVALID, "a session needs batch >= 1");
-  const int N = c->N;
-  mpcq_session* s = new mpcq_session();
-  s->ctx = c;
-  s->B = B;
-  if (pp) s->pp = *pp;
-  else mpcq_default_planner_params(&s->pp);
-  // one allocation: the named arrays, then the private ones
-  size_t off[MPCQ_SV_COUNT + 8];
-  size_t tot = 0;
-  auto take = [&](size_t nb) { size_t o = tot; tot += (nb + 255) & ~size_t(255); return o; };
-  for (int w = 0; w < MPCQ_SV_COUNT; ++w) { s->bytes[w] = sv_bytes(w, B, N); off[w] = take(s->bytes[w]); }
-  const size_t o_wx = take((size_t)B * 24 * N * 8), o_ps = take((size_t)B * 4), o_in = take((size_t)B * 16),
-               o_st = take((size_t)B * 96), o_lf = take((size_t)B * 96), o_vr = take((size_t)B * 48),
-               o_rd = take((size_t)B * 4), o_gi = take((size_t)B * 100 * 8), o_gs = take((size_t)B * 100 * 8);
-  DeviceGuard g(c->device);
-  if (hipMalloc(&s->mem, tot) != hipSuccess) {
-    delete s;
-    return fail(MPCQ_E_NOMEM, "hipMalloc(%zu) for the session failed", tot);
-  }
-  if (hipMemset(s->mem, 0, tot) != hipSuccess) {  // every array defined before the first tick
-    (void)hipFree(s->mem);
-    delete s;
-    return fail(MPCQ_E_DEVICE, "hipMemset of the session failed");
-  }
-  char* base = (char*)s->mem;
-  // (the swing arrays exist from mpcq_session_enable_swing on)
-  for (int w = 0; w < MPCQ_SV_COUNT; ++w) s->arr[w] = s->bytes[w] ? base + off[w] : nullptr;
-  s->warm_x = (double*)(base + o_wx);
-  s->plan_status = (int32_t*)(base + o_ps);
-  s->info = (int32_t*)(base + o_in);
-  s->in_state = (double*)(base + o_st);
-  s->in_lfeet = (double*)(base + o_lf);
-  s->in_vref = (double*)(base + o_vr);
-  s->in_reduced = (int32_t*)(base + o_rd);
-  s->gait_init = (double*)(base + o_gi);
-  s->in_gait = (double*)(base + o_gs);
-  s->order = (int32_t*)s->arr[MPCQ_SV_ORDER];
-  {
-    const char* e = getenv("MPCQ_DISPATCH_ORDER");
-    s->use_order = !(e && e[0] == '0');
-  }
-  // initial values: the reference objects' constructors
-  const size_t hb = sv_bytes(MPCQ_SV_XREF, B, N) > sv_bytes(MPCQ_SV_FSTEPS, B, N) ? sv_bytes(MPCQ_SV_XREF, B, N)
-                                                                                  : sv_bytes(MPCQ_SV_FSTEPS, B, N);
-  double* h = (double*)malloc(hb > (size_t)B * 100 * 8 ? hb : (size_t)B * 100 * 8);
-  int32_t* hi = (int32_t*)malloc((size_t)B * 4);
-  if (!h || !hi) { free(h); free(hi); mpcq_session_destroy(s); return fail(MPCQ_E_NOMEM, "host malloc failed"); }
-  int err = 0;
-  auto put = [&](int w, const void* src) {
-    if (!err && hipMemcpy(s->arr[w], src, s->bytes[w], hipMemcpyHostToDevice) != hipSuccess) err = 1;
-  };
-  auto keep_gait = [&](const void* src) {  // the table a reset without gait0 goes back to
-    if (!err && hipMemcpy(s->gait_init, src, s->bytes[MPCQ_SV_GAIT], hipMemcpyHostToDevice) != hipSuccess) err = 1;
-  };
-  if (gait0) {
-    put(MPCQ_SV_GAIT, gait0);
-    keep_gait(gait0);
-  } else {  // create_walking_trot (FootstepPlanner.py:193-214): [1, 7, 1, 7] per 16-step period
-    const int half = (int)(0.5 * s->pp.T_gait / s->pp.dt);
-    const int per = 2 * half, nper = per > 0 ? N / per : 0;
-    if (nper < 1 || nper * per != N || 4 * nper > 19) {
-      free(h); free(hi); mpcq_session_destroy(s);
-      return fail(MPCQ_E_INVALID, "no walking-trot table for N=%d with T_gait/dt = %d; pass gait0", N, per);
-    }
-    for (int64_t b = 0; b < B; ++b) {
-      double* gt = h + b * 100;
-      for (int e = 0; e < 100; ++e) gt[e] = 0.0;
-      for (int i = 0; i < nper; ++i) {
-        const double d[4] = {1.0, half - 1.0, 1.0, half - 1.0};
-        const int m[4][4] = {{1, 1, 1, 1}, {1, 0, 0, 1}, {1, 1, 1, 1}, {0, 1, 1, 0}};
-        for (int r = 0; r < 4; ++r) {
-          gt[5 * (4 * i + r)] = d[r];
-          for (int q = 0; q < 4; ++q) gt[5 * (4 * i + r) + 1 + q] = m[r][q];
-        }
-      }
-    }
-    put(MPCQ_SV_GAIT, h);
-    keep_gait(h);
-  }
-  for (size_t e = 0; e < (size_t)B * 12 * (N + 1); ++e) h[e] = 0.0;
-  put(MPCQ_SV_XREF, h);  // FootstepPlanner.py:58
-  for (int64_t b = 0; b < B; ++b) {
-    double* q = h + b * 6;  // MPC.py:53-56
-    q[0] = 0.0; q[1] = 0.0; q[2] = 0.2027682; q[3] = 0.0; q[4] = 0.0; q[5] = 0.0;
-  }
-  put(MPCQ_SV_Q_W, h);
-  for (int64_t b = 0; b < B; ++b) {  // virtual robot standing at h_ref, feet under the shoulders
-    double* st = h + b * 12;
-    for (int e = 0; e < 12; ++e) st[e] = 0.0;
-    st[2] = s->pp.h_ref;
-  }
-  put(MPCQ_SV_STATE, h);
-  for (int64_t b = 0; b < B; ++b) {
-    double* lf = h + b * 12;
-    for (int q = 0; q < 4; ++q) { lf[q] = s->pp.shoulders[q]; lf[4 + q] = s->pp.shoulders[4 + q]; lf[8 + q] = 0.0; }
-  }
-  put(MPCQ_SV_L_FEET, h);
-  for (int64_t b = 0; b < B; ++b) h[b] = 0.20;  // FootstepPlanner.py:68
-  put(MPCQ_SV_H_ROT, h);
-  for (int64_t b = 0; b < B; ++b) h[b] = c->p.rho;
-  put(MPCQ_SV_RHO, h);
-  for (int64_t b = 0; b < B; ++b) hi[b] = 0;
-  put(MPCQ_SV_ROT_FLAG, hi);
-  put(MPCQ_SV_STATUS, hi);
-  put(MPCQ_SV_ITERS, hi);
-  for (int64_t b = 0; b < B; ++b) hi[b] = (int32_t)b;  // a permutation from the start: the identity
-  put(MPCQ_SV_ORDER, hi);
-  for (size_t e = 0; e < (size_t)B * 260; ++e) h[e] = NAN;
-  put(MPCQ_SV_FSTEPS, h);
-  free(h);
-  free(hi);
-  if (err) { mpcq_session_destroy(s); return fail(MPCQ_E_DEVICE, "initialising the session failed"); }
-  *out = s;
-  return MPCQ_OK;
-}
-
-int mpcq_session_destroy(mpcq_session* s) {
-  if (!s) return MPCQ_OK;
-  if (s->mem) {
-    DeviceGuard g(s->ctx->device);
-    (void)hipStreamSynchronize(s->ctx->stream);
-    (void)hipFree(s->mem);
-    if (s->swing_mem) (void)hipFree(s->swing_mem);
-    if (s->robots.dev) (void)hipFree(s->robots.dev);
-    if (s->plant_mem) (void)hipFree(s->plant_mem);
-    if (s->plant_robots.dev) (void)hipFree(s->plant_robots.dev);
-    if (s->mon_mem) (void)hipFree(s->mon_mem);
-  }
-  delete s;
-  return MPCQ_OK;
-}
-
-int mpcq_session_set_robots(mpcq_session* s, const mpcq_robot* robots, uint32_t flags) {
-  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
-  return set_table(s->ctx, s->robots, robots ? s->B : 0, robots, flags);
-}
-
-int mpcq_session_get_robots(mpcq_session* s, mpcq_robot* robots, uint32_t flags) {
-  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
-  if (!robots) return fail(MPCQ_E_INVALID, "robots is NULL");
-  mpcq_ctx* c = s->ctx;
-  DeviceGuard g(c->device);
-  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
-  const size_t nb = (size_t)s->B * sizeof(mpcq_robot);
-  if (s->robots.count) {
-    HIP_TRY(hipMemcpyAsync(robots, s->robots.dev, nb, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
-                           c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return MPCQ_OK;
-  }
-  mpcq_robot d;
-  mpcq_default_robot(&c->p, &d);
-  if (!dev) {
-    for (int64_t b = 0; b < s->B; ++b) robots[b] = d;
-    return MPCQ_OK;
-  }
-  mpcq_robot* h = (mpcq_robot*)malloc(nb);
-  if (!h) return fail(MPCQ_E_NOMEM, "host malloc failed");
-  for (int64_t b = 0; b < s->B; ++b) h[b] = d;
-  const hipError_t e = hipMemcpy(robots, h, nb, hipMemcpyHostToDevice);
-  free(h);
-  HIP_TRY(e);
-  return MPCQ_OK;
-}
-
-int mpcq_session_enable_swing(mpcq_session* s, const mpcq_swing_params* sp) {
-  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
-  mpcq_swing_params P;
-  int rc = swing_params(sp, &P);
-  if (rc) return rc;
-  if (s->swing) {
-    if (P.k_mpc != s->sp.k_mpc) return fail(MPCQ_E_INVALID, "swing is enabled with k_mpc = %d", s->sp.k_mpc);
-    s->sp = P;
-    return MPCQ_OK;
-  }
-  const size_t B = (size_t)s->B;
-  const size_t nb[3] = {B * P.k_mpc * 36 * 8, B * 4 * MPCQ_SWING_STATE * 8, B * 24};
-  size_t off[3], tot = 0;
-  for (int i = 0; i < 3; ++i) { off[i] = tot; tot += (nb[i] + 255) & ~size_t(255); }
-  DeviceGuard g(s->ctx->device);
-  if (hipMalloc(&s->swing_mem, tot) != hipSuccess) {
-    s->swing_mem = nullptr;
-    return fail(MPCQ_E_NOMEM, "hipMalloc(%zu) for the swing arrays failed", tot);
-  }
-  HIP_TRY(hipMemsetAsync(s->swing_mem, 0, tot, s->ctx->stream));  // all-zero state = new generators
-  HIP_TRY(hipStreamSynchronize(s->ctx->stream));
-  for (int i = 0; i < 3; ++i) {
-    s->arr[MPCQ_SV_SWING_REF + i] = (char*)s->swing_mem + off[i];
-    s->bytes[MPCQ_SV_SWING_REF + i] = nb[i];
-  }
-  s->sp = P;
-  s->swing = true;
-  return MPCQ_OK;
-}
-
-// The plant's arrays, all zero: made by the first mpcq_session_enable_plant / _set_wrench.
-static int ensure_plant_mem(mpcq_session* s) {
-  if (s->plant_mem) return MPCQ_OK;
-  const size_t B = (size_t)s->B;
-  const size_t nb[MPCQ_PV_COUNT + 1] = {B * 96, B * 96, B * 48, B * 48};  // STATE_END, F_EFF, WRENCH, qw_prev
-  size_t off[MPCQ_PV_COUNT + 1], tot = 0;
-  for (int i = 0; i <= MPCQ_PV_COUNT; ++i) { off[i] = tot; tot += (nb[i] + 255) & ~size_t(255); }
-  void* mem = nullptr;
-  if (hipMalloc(&mem, tot) != hipSuccess) return fail(MPCQ_E_NOMEM, "hipMalloc(%zu) for the plant arrays failed", tot);
-  hipError_t e = hipMemsetAsync(mem, 0, tot, s->ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(s->ctx->stream);
-  if (e != hipSuccess) {
-    (void)hipFree(mem);
-    return fail(MPCQ_E_DEVICE, "zeroing the plant arrays failed: %s", hipGetErrorString(e));
-  }
-  s->plant_mem = mem;
-  for (int i = 0; i < MPCQ_PV_COUNT; ++i) {
-    s->parr[i] = (char*)mem + off[i];
-    s->pbytes[i] = nb[i];
-  }
-  s->qw_prev = (double*)((char*)mem + off[MPCQ_PV_COUNT]);
-  return MPCQ_OK;
-}
-
-int mpcq_session_enable_plant(mpcq_session* s, const mpcq_plant_params* pl) {
-  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
-  mpcq_plant_params P;
-  int rc = plant_params(pl, s->ctx->p.dt, &P);
-  if (rc) return rc;
-  if (P.dt != s->ctx->p.dt)
-    return fail(MPCQ_E_INVALID, "the plant's dt %g is not the context's %g", P.dt, s->ctx->p.dt);
-  DeviceGuard g(s->ctx->device);
-  rc = ensure_plant_mem(s);
-  if (rc) return rc;
-  s->pl = P;
-  s->plant = true;
-  return MPCQ_OK;
-}
-
-int mpcq_session_disable_plant(mpcq_session* s) {
-  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
-  s->plant = false;
-  return MPCQ_OK;
-}
-
-int mpcq_session_set_plant_robots(mpcq_session* s, const mpcq_robot* robots, uint32_t flags) {
-  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
-  return set_table(s->ctx, s->plant_robots, robots ? s->B : 0, robots, flags);
-}
-
-int mpcq_session_set_wrench(mpcq_session* s, const double* wrench, uint32_t flags) {
-  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
-  mpcq_ctx* c = s->ctx;
-  DeviceGuard g(c->device);
-  const int rc = ensure_plant_mem(s);
-  if (rc) return rc;
-  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
-  void* dst = s->parr[MPCQ_PV_WRENCH];
-  const size_t nb = s->pbytes[MPCQ_PV_WRENCH];
-  // on the context's stream: behind every queued tick that still reads the old wrench
-  if (!wrench) HIP_TRY(hipMemsetAsync(dst, 0, nb, c->stream));
-  else HIP_TRY(hipMemcpyAsync(dst, wrench, nb, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
-  if (!(flags & MPCQ_FLAG_ASYNC) || !dev) HIP_TRY(hipStreamSynchronize(c->stream));
-  return MPCQ_OK;
-}
-
-int mpcq_session_plant_read(mpcq_session* s, int what, void* dst, uint32_t flags) {
-  if (!s || !dst) return fail(MPCQ_E_INVALID, "NULL argument");
-  if (what < 0 || what >= MPCQ_PV_COUNT) return fail(MPCQ_E_INVALID, "unknown plant array %d", what);
-  if (!s->plant_mem) return fail(MPCQ_E_INVALID, "plant array %d needs mpcq_session_enable_plant", what);
-  DeviceGuard g(s->ctx->device);
-  const hipMemcpyKind kind = (flags & MPCQ_FLAG_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  HIP_TRY(hipMemcpyAsync(dst, s->parr[what], s->pbytes[what], kind, s->ctx->stream));
-  HIP_TRY(hipStreamSynchronize(s->ctx->stream));
-  return MPCQ_OK;
-}
-
-int mpcq_session_plant_device_ptr(mpcq_session* s, int what, void** out) {
-  if (!s || !out) return fail(MPCQ_E_INVALID, "NULL argument");
-  if (what < 0 || what >= MPCQ_PV_COUNT) return fail(MPCQ_E_INVALID, "unknown plant array %d", what);
-  if (!s->plant_mem) return fail(MPCQ_E_INVALID, "plant array %d needs mpcq_session_enable_plant", what);
-  *out = s->parr[what];
-  return MPCQ_OK;
-}
-
-int mpcq_session_enable_monitor(mpcq_session* s, const mpcq_monitor_params* mp) {
-  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
-  mpcq_monitor_params P;
-  const int rc = monitor_params(mp, &P);
-  if (rc) return rc;
-  if (!s->mon_mem) {  // the arrays, zero but for ep[4] = +inf
-    DeviceGuard g(s->ctx->device);
-    const size_t B = (size_t)s->B;
-    const size_t nb[MPCQ_MV_COUNT] = {B * 4, B * 64, B * 4, B * 4, B * 128, 64};
-    size_t off[MPCQ_MV_COUNT], tot = 0;
-    for (int i = 0; i < MPCQ_MV_COUNT; ++i) { off[i] = tot; tot += (nb[i] + 255) & ~size_t(255); }
-    double* h = (double*)malloc(nb[MPCQ_MV_EP]);
-    if (!h) return fail(MPCQ_E_NOMEM, "host malloc failed");
-    for (size_t e = 0; e < B * 8; ++e) h[e] = e % 8 == 4 ? INFINITY : 0.0;
-    void* mem = nullptr;
-    if (hipMalloc(&mem, tot) != hipSuccess) {
-      free(h);
-      return fail(MPCQ_E_NOMEM, "hipMalloc(%zu) for the monitor arrays failed", tot);
-    }
-    hipError_t e = hipMemsetAsync(mem, 0, tot, s->ctx->stream);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync((char*)mem + off[MPCQ_MV_EP], h, nb[MPCQ_MV_EP], hipMemcpyHostToDevice, s->ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(s->ctx->stream);
-    free(h);
-    if (e != hipSuccess) {
-      (void)hipFree(mem);
-      return fail(MPCQ_E_DEVICE, "initialising the monitor arrays failed: %s", hipGetErrorString(e));
-    }
-    s->mon_mem = mem;
-    for (int i = 0; i < MPCQ_MV_COUNT; ++i) {
-      s->marr[i] = (char*)mem + off[i];
-      s->mbytes[i] = nb[i];
-    }
-  }
-  s->mp = P;
-  s->monitor = true;
-  return MPCQ_OK;
-}
-
-int mpcq_session_disable_monitor(mpcq_session* s) {
-  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
-  s->monitor = false;
-  return MPCQ_OK;
-}
-
-int mpcq_session_monitor_read(mpcq_session* s, int what, void* dst, uint32_t flags) {
-  if (!s || !dst) return fail(MPCQ_E_INVALID, "NULL argument");
-  if (what < 0 || what >= MPCQ_MV_COUNT) return fail(MPCQ_E_INVALID, "unknown monitor array %d", what);
-  if (!s->mon_mem) return fail(MPCQ_E_INVALID, "monitor array %d needs mpcq_session_enable_monitor", what);
-  DeviceGuard g(s->ctx->device);
-  const hipMemcpyKind kind = (flags & MPCQ_FLAG_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  HIP_TRY(hipMemcpyAsync(dst, s->marr[what], s->mbytes[what], kind, s->ctx->stream));
-  HIP_TRY(hipStreamSynchronize(s->ctx->stream));
-  return MPCQ_OK;
-}
-
-int mpcq_session_monitor_device_ptr(mpcq_session* s, int what, void** out) {
-  if (!s || !out) return fail(MPCQ_E_INVALID, "NULL argument");
-  if (what < 0 || what >= MPCQ_MV_COUNT) return fail(MPCQ_E_INVALID, "unknown monitor array %d", what);
-  if (!s->mon_mem) return fail(MPCQ_E_INVALID, "monitor array %d needs mpcq_session_enable_monitor", what);
-  *out = s->marr[what];
-  return MPCQ_OK;
-}
-
-}  // extern "C"
-
-// What mpcq_session_reset enqueues on the context's stream, from device pointers: the reset
-// launch and, on a session that has ticked, the next solve's order.  Shared with a tick's
-// auto-reset (mpcq_session_enable_monitor).
-static hipError_t enqueue_reset(mpcq_session* s, const int32_t* mask, const double* gait0, const double* q_w0) {
-  mpcq_ctx* c = s->ctx;
-  const int N = c->N;
-  const int64_t B = s->B;
-  mpcq::ResetArgs ra{};
-  ra.batch = B;
-  ra.N = N;
-  ra.mask = mask;
-  ra.gait_src = gait0 ? gait0 : s->gait_init;
-  ra.q_w0 = q_w0;
-  ra.h_ref = s->pp.h_ref;
-  ra.rho0 = c->p.rho;
-  for (int i = 0; i < 8; ++i) ra.shoulders[i] = s->pp.shoulders[i];
-  ra.gait = (double*)s->arr[MPCQ_SV_GAIT];
-  ra.rot_flag = (int32_t*)s->arr[MPCQ_SV_ROT_FLAG];
-  ra.h_rot = (double*)s->arr[MPCQ_SV_H_ROT];
-  ra.xref = (double*)s->arr[MPCQ_SV_XREF];
-  ra.fsteps = (double*)s->arr[MPCQ_SV_FSTEPS];
-  ra.q_w = (double*)s->arr[MPCQ_SV_Q_W];
-  ra.state = (double*)s->arr[MPCQ_SV_STATE];
-  ra.l_feet = (double*)s->arr[MPCQ_SV_L_FEET];
-  ra.rho = (double*)s->arr[MPCQ_SV_RHO];
-  ra.y = (double*)s->arr[MPCQ_SV_Y];
-  ra.warm_x = s->warm_x;
-  ra.x = (double*)s->arr[MPCQ_SV_X];
-  ra.f0 = (double*)s->arr[MPCQ_SV_F0];
-  ra.x_robot = (double*)s->arr[MPCQ_SV_X_ROBOT];
-  ra.cost = (double*)s->arr[MPCQ_SV_COST];
-  ra.status = (int32_t*)s->arr[MPCQ_SV_STATUS];
-  ra.iters = (int32_t*)s->arr[MPCQ_SV_ITERS];
-  ra.first = (int32_t*)s->arr[MPCQ_SV_FIRST];
-  if (s->swing) {
-    ra.swing_ref = (double*)s->arr[MPCQ_SV_SWING_REF];
-    ra.swing_ref_doubles = (int64_t)s->sp.k_mpc * 36;
-    ra.swing_state = (double*)s->arr[MPCQ_SV_SWING_STATE];
-    ra.frame = (double*)s->arr[MPCQ_SV_FRAME];
-  }
-  if (s->mon_mem) {  // a reset robot's running episode is discarded
-    ra.ep = (double*)s->marr[MPCQ_MV_EP];
-    ra.ep_ticks = (int32_t*)s->marr[MPCQ_MV_EP_TICKS];
-  }
-  hipError_t e = mpcq::launch_reset(ra, c->stream);
-  // the robots with a pending reset to the front of the next solve's dispatch (a session that
-  // has not ticked yet has no order in use: it keeps the identity)
-  if (e == hipSuccess && s->have_order)
-    e = mpcq::launch_order((const int32_t*)s->arr[MPCQ_SV_ITERS], ra.first, B, s->order, c->stream);
-  s->resets = true;
-  return e;
-}
-
-// One tick; trace [B][MPCQ_TRACE] (device) or null: the monitor's row of this tick.
-static int session_tick(mpcq_session* s, int k, const double* state, const double* l_feet, const double* v_ref,
-                        const int32_t* reduced, uint32_t flags, double* trace) {
-  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
-  if (!v_ref) return fail(MPCQ_E_INVALID, "v_ref is required");
-  if (k < 0) return fail(MPCQ_E_INVALID, "k must be >= 0");
-  mpcq_ctx* c = s->ctx;
-  DeviceGuard g(c->device);
-  const int N = c->N;
-  const int64_t B = s->B;
-  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
-  auto in = [&](const void* src, void* stage_buf, size_t nb) -> const void* {
-    if (!src) return nullptr;
-    if (dev) return src;
-    if (hipMemcpyAsync(stage_buf, src, nb, hipMemcpyHostToDevice, c->stream) != hipSuccess) return nullptr;
-    return stage_buf;
-  };
-  const double* st = state ? (const double*)in(state, s->in_state, (size_t)B * 96) : (const double*)s->arr[MPCQ_SV_STATE];
-  const double* lf = l_feet ? (const double*)in(l_feet, s->in_lfeet, (size_t)B * 96) : (const double*)s->arr[MPCQ_SV_L_FEET];
-  const double* vr = (const double*)in(v_ref, s->in_vref, (size_t)B * 48);
-  const int32_t* rd = reduced ? (const int32_t*)in(reduced, s->in_reduced, (size_t)B * 4) : nullptr;
-  if (!st || !lf || !vr || (reduced && !rd)) return fail(MPCQ_E_DEVICE, "staging the tick inputs failed");
-  // the virtual robot's state lives in buffers the retrieve kernel rewrites:
-  // this tick reads a copy
-  if (!state) {
-    HIP_TRY(hipMemcpyAsync(s->in_state, st, (size_t)B * 96, hipMemcpyDeviceToDevice, c->stream));
-    st = s->in_state;
-  }
-  if (!l_feet) {
-    HIP_TRY(hipMemcpyAsync(s->in_lfeet, lf, (size_t)B * 96, hipMemcpyDeviceToDevice, c->stream));
-    lf = s->in_lfeet;
-  }
-  // 1. planner (processing.py:80-89, 131)
-  mpcq::PlanArgs pa{};
-  pa.batch = B;
-  pa.N = N;
-  pa.k = k;
-  pa.state = st;
-  pa.l_feet = lf;
-  pa.v_ref = vr;
-  pa.reduced = rd;
-  pa.gait = (double*)s->arr[MPCQ_SV_GAIT];
-  pa.rot_flag = (int32_t*)s->arr[MPCQ_SV_ROT_FLAG];
-  pa.h_rot = (double*)s->arr[MPCQ_SV_H_ROT];
-  pa.xref = (double*)s->arr[MPCQ_SV_XREF];
-  pa.fsteps = (double*)s->arr[MPCQ_SV_FSTEPS];
-  pa.status = s->plan_status;
-  // after a mpcq_session_reset: a robot whose MPCQ_SV_FIRST is set runs this tick as a first
-  // tick whatever k says (the planner's extra pass then touches those robots only)
-  // (k == 0 makes every robot first by itself: only the retrieve takes the flags then, to clear them)
-  int32_t* const first = s->resets ? (int32_t*)s->arr[MPCQ_SV_FIRST] : nullptr;
-  const int32_t* const first_k = k == 0 ? nullptr : first;
-  pa.first = first_k;
-  HIP_TRY(hipEventRecord(c->ev[0], c->stream));
-  if (k == 0 || first_k) {  // update_fsteps(0, ...): no roll
-    pa.ops = MPCQ_PLAN_FOOTSTEPS;
-    HIP_TRY(mpcq::launch_plan(s->pp, pa, c->stream));
-  }
-  pa.ops = MPCQ_PLAN_TICK;
-  HIP_TRY(mpcq::launch_plan(s->pp, pa, c->stream));
-  HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-  c->have_form = true;
-  // 2. MPC.run: formulation + OSQP solve (warm from the previous tick when k > 0)
-  mpcq::LaunchArgs la{};
-  la.batch = B;
-  la.mode = k == 0 ? MPCQ_MODE_SETUP : MPCQ_MODE_UPDATE;
-  la.xref = (const double*)s->arr[MPCQ_SV_XREF];
-  la.fsteps = (const double*)s->arr[MPCQ_SV_FSTEPS];
-  if (k > 0) {
-    la.warm_x = s->warm_x;
-    la.warm_y = (const double*)s->arr[MPCQ_SV_Y];
-    la.rho_in = (const double*)s->arr[MPCQ_SV_RHO];
-  }
-  la.f0 = (double*)s->arr[MPCQ_SV_F0];
-  la.x = (double*)s->arr[MPCQ_SV_X];
-  la.y = (double*)s->arr[MPCQ_SV_Y];
-  la.status = (int32_t*)s->arr[MPCQ_SV_STATUS];
-  la.iters = (int32_t*)s->arr[MPCQ_SV_ITERS];
-  la.rho_out = (double*)s->arr[MPCQ_SV_RHO];
-  la.info = s->info;
-  la.stamps = c->stamps;
-  // longest-first by the previous tick's iteration counts (a tick k == 0 restarts cold)
-  if (k == 0) s->have_order = false;
-  la.order = s->have_order && s->use_order ? s->order : nullptr;
-  la.robots = s->robots.count ? s->robots.dev : nullptr;
-  la.first = first_k;
-  {
-    const int wrc = ensure_work(c, B, &la.work);
-    if (wrc) return wrc;
-  }
-  HIP_TRY(hipEventRecord(c->ev[2], c->stream));
-  HIP_TRY(mpcq::launch_solve(N, true, c->p, la, c->stream));
-  HIP_TRY(hipEventRecord(c->ev[3], c->stream));
-  c->have_solve = true;
-  // 3. retrieve_result, q_w, Logger cost, next warm start, virtual robot
-  mpcq::SessionArgs ra{};
-  ra.batch = B;
-  ra.x = (const double*)s->arr[MPCQ_SV_X];
-  ra.xref = (const double*)s->arr[MPCQ_SV_XREF];
-  ra.fsteps = (const double*)s->arr[MPCQ_SV_FSTEPS];
-  ra.gait = (const double*)s->arr[MPCQ_SV_GAIT];
-  ra.status = (int32_t*)s->arr[MPCQ_SV_STATUS];
-  ra.plan_status = s->plan_status;
-  ra.x_robot = (double*)s->arr[MPCQ_SV_X_ROBOT];
-  ra.warm_x = s->warm_x;
-  ra.y = (double*)s->arr[MPCQ_SV_Y];
-  ra.rho = (double*)s->arr[MPCQ_SV_RHO];
-  ra.rho0 = c->p.rho;
-  ra.cost = (double*)s->arr[MPCQ_SV_COST];
-  ra.q_w = (double*)s->arr[MPCQ_SV_Q_W];
-  ra.next_state = (double*)s->arr[MPCQ_SV_STATE];
-  ra.next_l_feet = (double*)s->arr[MPCQ_SV_L_FEET];
-  for (int i = 0; i < 12; ++i) ra.state_weights[i] = c->p.state_weights[i];
-  ra.force_weight = c->p.force_weight;
-  for (int i = 0; i < 8; ++i) ra.shoulders[i] = s->pp.shoulders[i];
-  ra.first = first;
-  if (s->swing) {  // the frame of this tick's fsteps: q_w's x, y, yaw before the retrieve moves it
-    double* fr = (double*)s->arr[MPCQ_SV_FRAME];
-    const double* qw = (const double*)s->arr[MPCQ_SV_Q_W];
-    HIP_TRY(hipMemcpy2DAsync(fr, 24, qw, 48, 16, (size_t)B, hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(hipMemcpy2DAsync(fr + 2, 24, qw + 5, 48, 8, (size_t)B, hipMemcpyDeviceToDevice, c->stream));
-  }
-  if (s->plant)  // the plant starts from the world pose as it stands before the retrieve moves it
-    HIP_TRY(hipMemcpyAsync(s->qw_prev, s->arr[MPCQ_SV_Q_W], (size_t)B * 48, hipMemcpyDeviceToDevice, c->stream));
-  HIP_TRY(mpcq::launch_retrieve(N, ra, c->stream));
-  if (s->plant) {  // the rigid body under this tick's forces takes the place of the prediction
-    mpcq::PlantArgs pa2{};
-    pa2.batch = B;
-    pa2.state = st;
-    pa2.fsteps = (const double*)s->arr[MPCQ_SV_FSTEPS];
-    pa2.f = (const double*)s->arr[MPCQ_SV_F0];
-    pa2.wrench = (const double*)s->parr[MPCQ_PV_WRENCH];
-    pa2.robots = s->plant_robots.count ? s->plant_robots.dev : s->robots.count ? s->robots.dev : nullptr;
-    mpcq_default_robot(&c->p, &pa2.dflt);
-    pa2.state_out = (double*)s->parr[MPCQ_PV_STATE_END];
-    pa2.f_eff = (double*)s->parr[MPCQ_PV_F_EFF];
-    pa2.tail = 1;
-    pa2.status = (const int32_t*)s->arr[MPCQ_SV_STATUS];
-    pa2.plan_status = s->plan_status;
-    pa2.gait = (const double*)s->arr[MPCQ_SV_GAIT];
-    pa2.q_w_prev = s->qw_prev;
-    pa2.q_w = (double*)s->arr[MPCQ_SV_Q_W];
-    pa2.next_state = (double*)s->arr[MPCQ_SV_STATE];
-    pa2.next_l_feet = (double*)s->arr[MPCQ_SV_L_FEET];
-    for (int i = 0; i < 8; ++i) pa2.shoulders[i] = s->pp.shoulders[i];
-    HIP_TRY(mpcq::launch_plant(s->pl, pa2, c->stream));
-  }
-  if (s->monitor) {  // whose episode ended with this tick, and the episodes' statistics
-    mpcq::MonitorArgs ma{};
-    ma.batch = B;
-    ma.q_w = (const double*)s->arr[MPCQ_SV_Q_W];
-    ma.status = (const int32_t*)s->arr[MPCQ_SV_STATUS];
-    ma.iters = (const int32_t*)s->arr[MPCQ_SV_ITERS];
-    ma.f0 = (const double*)s->arr[MPCQ_SV_F0];
-    ma.cost = (const double*)s->arr[MPCQ_SV_COST];
-    ma.state = (const double*)s->arr[MPCQ_SV_STATE];
-    ma.v_ref = vr;
-    ma.ep = (double*)s->marr[MPCQ_MV_EP];
-    ma.ep_ticks = (int32_t*)s->marr[MPCQ_MV_EP_TICKS];
-    ma.episodes = (int32_t*)s->marr[MPCQ_MV_EPISODES];
-    ma.last = (double*)s->marr[MPCQ_MV_LAST];
-    ma.done = (int32_t*)s->marr[MPCQ_MV_DONE];
-    ma.totals = (unsigned long long*)s->marr[MPCQ_MV_TOTALS];
-    ma.trace = trace;
-    HIP_TRY(mpcq::launch_monitor(s->mp, ma, c->stream));
-  }
-  // (the retrieve has cleared every pending reset: the order is by iteration counts alone)
-  HIP_TRY(mpcq::launch_order((const int32_t*)s->arr[MPCQ_SV_ITERS], nullptr, B, s->order, c->stream));
-  s->have_order = true;
-  if (s->swing) {  // the tick's swing-foot references, substeps 0..k_mpc-1 (virtual-robot lift-off)
-    mpcq::SwingArgs sa{};
-    sa.batch = B;
-    sa.k_sub0 = 0;
-    sa.n_sub = s->sp.k_mpc;
-    sa.gait = (const double*)s->arr[MPCQ_SV_GAIT];
-    sa.fsteps = (const double*)s->arr[MPCQ_SV_FSTEPS];
-    sa.frame = (const double*)s->arr[MPCQ_SV_FRAME];
-    sa.state = (double*)s->arr[MPCQ_SV_SWING_STATE];
-    sa.ref = (double*)s->arr[MPCQ_SV_SWING_REF];
-    HIP_TRY(mpcq::launch_swing(s->sp, sa, c->stream));
-  }
-  // auto-reset, last: the swing launch above has read the tick's gait and fsteps
-  if (s->monitor && s->mp.auto_reset)
-    HIP_TRY(enqueue_reset(s, (const int32_t*)s->marr[MPCQ_MV_DONE], nullptr, nullptr));
-  // host inputs are staged in buffers the next tick reuses: host calls block
-  if (!(flags & MPCQ_FLAG_ASYNC) || !dev) HIP_TRY(hipStreamSynchronize(c->stream));
-  return MPCQ_OK;
-}
-
-extern "C" {
-
-int mpcq_session_tick(mpcq_session* s, int k, const double* state, const double* l_feet, const double* v_ref,
-                      const int32_t* reduced, uint32_t flags) {
-  return session_tick(s, k, state, l_feet, v_ref, reduced, flags, nullptr);
-}
-
-int mpcq_session_run(mpcq_session* s, int k0, int n_ticks, const double* v_ref, int v_ref_ticks, double* trace,
-                     uint32_t flags) {
-  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
-  if (!(flags & MPCQ_FLAG_DEVICE_PTRS)) return fail(MPCQ_E_INVALID, "mpcq_session_run needs MPCQ_FLAG_DEVICE_PTRS");
-  if (!v_ref || v_ref_ticks < 1) return fail(MPCQ_E_INVALID, "v_ref [v_ref_ticks][B][6] with v_ref_ticks >= 1 is required");
-  if (k0 < 0 || n_ticks < 1) return fail(MPCQ_E_INVALID, "need k0 >= 0 and n_ticks >= 1");
-  if (k0 > INT32_MAX - n_ticks) return fail(MPCQ_E_INVALID, "k0 + n_ticks overflows");
-  if (trace && !s->monitor) return fail(MPCQ_E_INVALID, "a trace needs mpcq_session_enable_monitor");
-  const size_t B = (size_t)s->B;
-  for (int t = 0; t < n_ticks; ++t) {
-    const int row = t < v_ref_ticks ? t : v_ref_ticks - 1;
-    const int rc = session_tick(s, k0 + t, nullptr, nullptr, v_ref + (size_t)row * B * 6, nullptr,
-                                MPCQ_FLAG_DEVICE_PTRS | MPCQ_FLAG_ASYNC,
-                                trace ? trace + (size_t)t * B * MPCQ_TRACE : nullptr);
-    if (rc) {
-      (void)hipStreamSynchronize(s->ctx->stream);
-      return rc;
-    }
-  }
-  if (!(flags & MPCQ_FLAG_ASYNC)) {
-    DeviceGuard g(s->ctx->device);
-    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
-  }
-  return MPCQ_OK;
-}
-
-int mpcq_session_reset(mpcq_session* s, const int32_t* mask, const double* gait0, const double* q_w0,
-                       uint32_t flags) {
-  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
-  mpcq_ctx* c = s->ctx;
-  DeviceGuard g(c->device);
-  const int64_t B = s->B;
-  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
-  // host arrays go through the session's staging buffers (the tick's, and one for the gait
-  // tables): stream-ordered with the ticks, and the call blocks before they can be reused
-  if (!dev) {
-    hipError_t e = hipSuccess;
-    if (mask) {
-      e = hipMemcpyAsync(s->in_reduced, mask, (size_t)B * 4, hipMemcpyHostToDevice, c->stream);
-      mask = s->in_reduced;
-    }
-    if (gait0 && e == hipSuccess) {
-      e = hipMemcpyAsync(s->in_gait, gait0, (size_t)B * 800, hipMemcpyHostToDevice, c->stream);
-      gait0 = s->in_gait;
-    }
-    if (q_w0 && e == hipSuccess) {
-      e = hipMemcpyAsync(s->in_vref, q_w0, (size_t)B * 48, hipMemcpyHostToDevice, c->stream);
-      q_w0 = s->in_vref;
-    }
-    if (e != hipSuccess) {
-      (void)hipStreamSynchronize(c->stream);
-      return fail(MPCQ_E_DEVICE, "staging the reset's inputs failed");
-    }
-  }
-  hipError_t e = enqueue_reset(s, mask, gait0, q_w0);
-  if (!(flags & MPCQ_FLAG_ASYNC) || !dev) {
-    const hipError_t es = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = es;
-  }
-  HIP_TRY(e);
-  return MPCQ_OK;
-}
-
-int mpcq_session_read(mpcq_session* s, int what, void* dst, uint32_t flags) {
-  if (!s || !dst) return fail(MPCQ_E_INVALID, "NULL argument");
-  if (what < 0 || what >= MPCQ_SV_COUNT) return fail(MPCQ_E_INVALID, "unknown session array %d", what);
-  if (!s->arr[what]) return fail(MPCQ_E_INVALID, "session array %d needs mpcq_session_enable_swing", what);
-  DeviceGuard g(s->ctx->device);
-  const hipMemcpyKind kind = (flags & MPCQ_FLAG_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  HIP_TRY(hipMemcpyAsync(dst, s->arr[what], s->bytes[what], kind, s->ctx->stream));
-  HIP_TRY(hipStreamSynchronize(s->ctx->stream));
-  return MPCQ_OK;
-}
-
-int mpcq_session_write(mpcq_session* s, int what, const void* src, uint32_t flags) {
-  if (!s || !src) return fail(MPCQ_E_INVALID, "NULL argument");
-  if (what < 0 || what >= MPCQ_SV_COUNT) return fail(MPCQ_E_INVALID, "unknown session array %d", what);
-  if (!s->arr[what]) return fail(MPCQ_E_INVALID, "session array %d needs mpcq_session_enable_swing", what);
-  // the engine indexes robots through the order: only order_kernel writes it
-  if (what == MPCQ_SV_ORDER) return fail(MPCQ_E_INVALID, "MPCQ_SV_ORDER is read-only");
-  // only mpcq_session_reset sets it (with the state a first tick needs), only the retrieve clears it
-  if (what == MPCQ_SV_FIRST) return fail(MPCQ_E_INVALID, "MPCQ_SV_FIRST is read-only");
-  if (what == MPCQ_SV_SWING_REF || what == MPCQ_SV_FRAME)
-    return fail(MPCQ_E_INVALID, "MPCQ_SV_SWING_REF and MPCQ_SV_FRAME are read-only");
-  DeviceGuard g(s->ctx->device);
-  const hipMemcpyKind kind = (flags & MPCQ_FLAG_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  HIP_TRY(hipMemcpyAsync(s->arr[what], src, s->bytes[what], kind, s->ctx->stream));
-  HIP_TRY(hipStreamSynchronize(s->ctx->stream));
-  return MPCQ_OK;
-}
-
-int mpcq_session_device_ptr(mpcq_session* s, int what, void** out) {
-  if (!s || !out) return fail(MPCQ_E_INVALID, "NULL argument");
-  if (what < 0 || what >= MPCQ_SV_COUNT) return fail(MPCQ_E_INVALID, "unknown session array %d", what);
-  if (!s->arr[what]) return fail(MPCQ_E_INVALID, "session array %d needs mpcq_session_enable_swing", what);
-  *out = s->arr[what];
   return MPCQ_OK;
 }
 

@@ -1,0 +1,87 @@
+// mpcq_host.h — what the two host units of the C ABI share: mpcq_api.cpp (contexts, batch
+// entry points, diagnostics; it defines everything declared here) and mpcq_session_api.cpp
+// (closed-loop sessions).
+#pragma once
+#include "mpcq_internal.h"
+
+// A table of per-robot constants on the device (mpcq_set_robots, mpcq_session_set_robots):
+// count > 0 = in force.
+struct RobotTable {
+  mpcq_robot* dev = nullptr;
+  int64_t cap = 0;
+  int64_t count = 0;
+};
+
+struct mpcq_ctx {
+  int device = 0;
+  int N = 0;
+  mpcq_params p{};
+  hipStream_t own_stream = nullptr;
+  hipStream_t stream = nullptr;
+  void* arena = nullptr;
+  size_t arena_bytes = 0;
+  void* work = nullptr;  // engine workspace (horizons beyond 32 stages)
+  size_t work_bytes = 0;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  bool have_form = false, have_solve = false;
+  uint64_t* stamps = nullptr;
+  // MPCQ_FLAG_ORDER_BY_CLASS: the class table (sum of iterations, count per slot) and the
+  // per-instance scratch (class slot, dispatch order, iteration counts when the caller
+  // passes none)
+  uint64_t* cls_sum = nullptr;
+  uint64_t* cls_cnt = nullptr;
+  int32_t* ord_buf = nullptr;
+  int64_t ord_cap = 0;
+  // what the last batch solve dispatched by (mpcq_debug_last_dispatch): host bookkeeping only
+  int64_t last_B = 0;
+  bool last_by_class = false, last_sliced = false;
+  // sliced solves (mpcq_set_slice): the slice length (0: off), the suspended instances'
+  // iterates (mpcq::res_lanes(N) x 8 doubles, rho, key, 4 counters each), the resumed launch's
+  // dispatch list (B int32, of 3 B: two once held alternating lists) and a status scratch, the
+  // resumed launch's workgroup count (device)
+  int32_t slice_iters = 0;
+  double* res = nullptr;
+  double* res_rho = nullptr;
+  double* res_key = nullptr;
+  int32_t* res_i = nullptr;
+  int32_t* sl_buf = nullptr;
+  int64_t sl_cap = 0;
+  int32_t* sl_count = nullptr;
+  RobotTable robots;  // mpcq_set_robots
+};
+
+namespace mpcq {
+
+// Sets the calling thread's mpcq_last_error text; returns code.
+int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+
+#define HIP_TRY(expr)                                                                   \
+  do {                                                                                  \
+    hipError_t e_ = (expr);                                                             \
+    if (e_ != hipSuccess)                                                               \
+      return mpcq::fail(MPCQ_E_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_));  \
+  } while (0)
+
+struct DeviceGuard {
+  int prev = -1;
+  explicit DeviceGuard(int d) {
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    if (prev != d) (void)hipSetDevice(d);
+  }
+  ~DeviceGuard() {
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+};
+
+int check_ctx(mpcq_ctx* c, int64_t batch);
+// The engine's per-instance workspace (mpcq::work_doubles(N), zero up to 32 stages).
+int ensure_work(mpcq_ctx* c, int64_t B, double** out);
+// Replace (count > 0) or clear a table.  The copy runs on the context's stream, behind any
+// queued launch that still reads the old values; from a host pointer the call then blocks.
+int set_table(mpcq_ctx* c, RobotTable& t, int64_t count, const mpcq_robot* robots, uint32_t flags);
+// The caller's parameters (null: the defaults) into *out, or MPCQ_E_INVALID.
+int swing_params(const mpcq_swing_params* sp, mpcq_swing_params* out);
+int plant_params(const mpcq_plant_params* pl, double dt_default, mpcq_plant_params* out);
+int monitor_params(const mpcq_monitor_params* mp, mpcq_monitor_params* out);
+
+}  // namespace mpcq

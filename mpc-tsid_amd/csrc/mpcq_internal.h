@@ -156,7 +156,9 @@ hipError_t launch_retrieve(int N, const SessionArgs& a, hipStream_t s);
 hipError_t launch_order(const int32_t* iters, const int32_t* first, int64_t batch, int32_t* order, hipStream_t s);
 
 // mpcq_session_reset (mpcq_session.hip): the per-robot arrays of the robots with
-// mask[b] != 0 (null: all) back to what mpcq_session_create leaves; one wave64 per robot.
+// mask[b] != 0 (null: all) to the state of a new robot; one wave64 per robot.
+// mpcq_session_create launches it too (over its zeroed allocation, first null): the only
+// statement of that state.
 struct ResetArgs {
   int64_t batch;
   int N;
@@ -182,7 +184,7 @@ struct ResetArgs {
   double* cost;          // [B][13]
   int32_t* status;       // [B]
   int32_t* iters;        // [B]
-  int32_t* first;        // [B] set to 1
+  int32_t* first;        // [B] set to 1 (a reset is pending), or null: not marked
   // the swing arrays, or null on a session without them
   double* swing_ref;     // [B][swing_ref_doubles]
   int64_t swing_ref_doubles;

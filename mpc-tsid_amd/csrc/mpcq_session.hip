@@ -141,7 +141,8 @@ __global__ __launch_bounds__(1024) void order_kernel(const int32_t* __restrict__
   for (int64_t i = t; i < B; i += blockDim.x) order[atomicAdd(&hist[bucket(i)], 1)] = (int32_t)i;
 }
 
-// mpcq_session_reset: one wave64 per robot; a robot whose mask entry is 0 is not touched.
+// mpcq_session_reset, and the state mpcq_session_create leaves (no mask, first null): one
+// wave64 per robot; a robot whose mask entry is 0 is not touched.
 __global__ __launch_bounds__(64) void reset_kernel(ResetArgs a) {
   const int lane = threadIdx.x;
   const int64_t b = blockIdx.x;
@@ -179,7 +180,7 @@ __global__ __launch_bounds__(64) void reset_kernel(ResetArgs a) {
     a.rho[b] = a.rho0;
     a.status[b] = 0;
     a.iters[b] = 0;
-    a.first[b] = 1;
+    if (a.first) a.first[b] = 1;
   }
   if (a.swing_state) {  // all-zero state = new generators
     fill(a.swing_ref, a.swing_ref_doubles, 0.0);

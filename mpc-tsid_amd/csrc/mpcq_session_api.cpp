@@ -1,0 +1,715 @@
+// mpcq_session_api.cpp — the mpcq_session_* entry points of include/mpcq.h: closed-loop
+// sessions, per-robot state resident in HBM.
+//
+// A session's device arrays come in groups (alloc_group): the main one made by
+// mpcq_session_create, and one each for swing, plant and monitor, made when they are first
+// enabled.  A tick (session_tick) is a list of stages, each filling the argument struct of
+// its launch from the groups' arrays.  All numerics run in the HIP kernels.
+#include <math.h>
+#include <stdlib.h>
+
+#include "mpcq_host.h"
+
+using namespace mpcq;
+
+namespace {
+
+// Private arrays, behind the named ones of their group: the warm start, the planner's
+// status, the engine's info, the staging of host inputs (tick: state, l_feet, v_ref,
+// reduced; reset: mask in IN_REDUCED, q_w0 in IN_VREF, gait0 in IN_GAIT), the gait table
+// every robot was created with; the copy of q_w a tick with the plant takes before its
+// retrieve.
+enum { SP_WARM_X = MPCQ_SV_COUNT, SP_PLAN_STATUS, SP_INFO, SP_IN_STATE, SP_IN_LFEET, SP_IN_VREF, SP_IN_REDUCED,
+       SP_GAIT_INIT, SP_IN_GAIT, SP_COUNT };
+enum { PP_QW_PREV = MPCQ_PV_COUNT, PP_COUNT };
+
+// The arrays of one kind of id: MPCQ_SV_* (the swing slots are null until
+// mpcq_session_enable_swing), MPCQ_PV_*, MPCQ_MV_*.
+struct Group {
+  const char *kind, *enable;  // "<kind> array %d needs mpcq_session_enable_<enable>"
+  int named;                  // the ids the _read / _write / _device_ptr entry points reach
+  void* mem = nullptr;
+  void* ptr[SP_COUNT] = {};
+  size_t bytes[SP_COUNT] = {};
+  double* d(int w) const { return (double*)ptr[w]; }
+  int32_t* i(int w) const { return (int32_t*)ptr[w]; }
+};
+
+}  // namespace
+
+struct mpcq_session {
+  mpcq_ctx* ctx = nullptr;
+  int64_t B = 0;
+  mpcq_planner_params pp{};
+  Group sv{"session", "swing", MPCQ_SV_COUNT};
+  Group pv{"plant", "plant", MPCQ_PV_COUNT};      // made by the first enable_plant / set_wrench
+  Group mv{"monitor", "monitor", MPCQ_MV_COUNT};  // made by the first enable_monitor
+  void* swing_mem = nullptr;                      // MPCQ_SV_SWING_REF, _SWING_STATE, _FRAME
+  bool have_order = false;  // MPCQ_SV_ORDER holds the next solve's order (longest previous first)
+  bool use_order = true;    // MPCQ_DISPATCH_ORDER=0 turns it off (A/B timing only; results are identical)
+  bool resets = false;      // mpcq_session_reset was called: from then on the ticks consult MPCQ_SV_FIRST
+  bool swing = false, plant = false, monitor = false;
+  mpcq_swing_params sp{};
+  mpcq_plant_params pl{};
+  mpcq_monitor_params mp{};
+  RobotTable robots;        // mpcq_session_set_robots (the session's own, not the context's)
+  RobotTable plant_robots;  // mpcq_session_set_plant_robots
+};
+
+namespace {
+
+// Bytes of an array of the main group (layouts: include/mpcq.h).
+size_t sv_bytes(int what, int64_t B, int N) {
+  const size_t b = (size_t)B;
+  switch (what) {
+    case MPCQ_SV_F0: case MPCQ_SV_STATE: case MPCQ_SV_L_FEET: case SP_IN_STATE: case SP_IN_LFEET: return b * 12 * 8;
+    case MPCQ_SV_X: case SP_WARM_X: return b * 24 * N * 8;
+    case MPCQ_SV_X_ROBOT: return b * 12 * N * 8;
+    case MPCQ_SV_Q_W: case SP_IN_VREF: return b * 6 * 8;
+    case MPCQ_SV_COST: return b * 13 * 8;
+    case MPCQ_SV_XREF: return b * 12 * (N + 1) * 8;
+    case MPCQ_SV_FSTEPS: return b * 260 * 8;
+    case MPCQ_SV_GAIT: case SP_GAIT_INIT: case SP_IN_GAIT: return b * 100 * 8;
+    case MPCQ_SV_Y: return b * 44 * N * 8;
+    case MPCQ_SV_RHO: case MPCQ_SV_H_ROT: return b * 8;
+    case MPCQ_SV_STATUS: case MPCQ_SV_ITERS: case MPCQ_SV_ROT_FLAG: case MPCQ_SV_ORDER: case MPCQ_SV_FIRST:
+    case SP_PLAN_STATUS: case SP_IN_REDUCED: return b * 4;
+    case SP_INFO: return b * 16;
+  }
+  return 0;  // (the swing arrays exist from mpcq_session_enable_swing on)
+}
+
+// n arrays of nb[i] bytes, each 256-B aligned, in one allocation zeroed on the context's
+// stream (the call blocks): *mem, ptr[i] (null where nb[i] is 0) and bytes[i].  On a failure
+// nothing stays allocated and nothing is written.
+int alloc_group(mpcq_ctx* c, const char* what, int n, const size_t* nb, void** mem, void** ptr, size_t* bytes) {
+  auto padded = [](size_t b) { return (b + 255) & ~size_t(255); };
+  size_t tot = 0;
+  for (int i = 0; i < n; ++i) tot += padded(nb[i]);
+  void* m = nullptr;
+  if (hipMalloc(&m, tot) != hipSuccess) return fail(MPCQ_E_NOMEM, "hipMalloc(%zu) for %s failed", tot, what);
+  hipError_t e = hipMemsetAsync(m, 0, tot, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) {
+    (void)hipFree(m);
+    return fail(MPCQ_E_DEVICE, "zeroing %s failed: %s", what, hipGetErrorString(e));
+  }
+  size_t off = 0;
+  for (int i = 0; i < n; ++i) {
+    ptr[i] = nb[i] ? (char*)m + off : nullptr;
+    bytes[i] = nb[i];
+    off += padded(nb[i]);
+  }
+  *mem = m;
+  return MPCQ_OK;
+}
+
+// The array behind an id of group g, for the _read / _write / _device_ptr entry points.
+int find(const Group& g, int what) {
+  if (what < 0 || what >= g.named) return fail(MPCQ_E_INVALID, "unknown %s array %d", g.kind, what);
+  if (!g.ptr[what]) return fail(MPCQ_E_INVALID, "%s array %d needs mpcq_session_enable_%s", g.kind, what, g.enable);
+  return MPCQ_OK;
+}
+
+int group_read(mpcq_session* s, Group mpcq_session::*group, int what, void* dst, uint32_t flags) {
+  if (!s || !dst) return fail(MPCQ_E_INVALID, "NULL argument");
+  const Group& g = s->*group;
+  const int rc = find(g, what);
+  if (rc) return rc;
+  DeviceGuard dg(s->ctx->device);
+  const hipMemcpyKind kind = (flags & MPCQ_FLAG_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  HIP_TRY(hipMemcpyAsync(dst, g.ptr[what], g.bytes[what], kind, s->ctx->stream));
+  HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+  return MPCQ_OK;
+}
+
+int group_device_ptr(mpcq_session* s, Group mpcq_session::*group, int what, void** out) {
+  if (!s || !out) return fail(MPCQ_E_INVALID, "NULL argument");
+  const int rc = find(s->*group, what);
+  if (rc) return rc;
+  *out = (s->*group).ptr[what];
+  return MPCQ_OK;
+}
+
+// An optional input array where the kernels read it: a device pointer as it is; a host array
+// through the session's staging buffer `buf`, copied on the context's stream (stream-ordered
+// with the ticks; the call has to block before the buffer can be reused).  *e keeps the
+// first error.
+template <class T>
+const T* staged(mpcq_session* s, bool dev, const T* src, int buf, hipError_t* e) {
+  if (!src || dev) return src;
+  if (*e == hipSuccess)
+    *e = hipMemcpyAsync(s->sv.ptr[buf], src, s->sv.bytes[buf], hipMemcpyHostToDevice, s->ctx->stream);
+  return (const T*)s->sv.ptr[buf];
+}
+
+// What mpcq_session_reset enqueues on the context's stream, from device pointers: the reset
+// launch and, on a session that has ticked, the next solve's order.  Shared with a tick's
+// auto-reset (mpcq_session_enable_monitor) and, with mark == false over all robots, with
+// mpcq_session_create: the creation state is what reset_kernel writes, and nothing else.
+hipError_t enqueue_reset(mpcq_session* s, const int32_t* mask, const double* gait0, const double* q_w0, bool mark) {
+  mpcq_ctx* c = s->ctx;
+  const Group& v = s->sv;
+  mpcq::ResetArgs ra{};
+  ra.batch = s->B; ra.N = c->N; ra.mask = mask; ra.q_w0 = q_w0;
+  ra.gait_src = gait0 ? gait0 : v.d(SP_GAIT_INIT);
+  ra.h_ref = s->pp.h_ref; ra.rho0 = c->p.rho;
+  for (int i = 0; i < 8; ++i) ra.shoulders[i] = s->pp.shoulders[i];
+  ra.gait = v.d(MPCQ_SV_GAIT); ra.rot_flag = v.i(MPCQ_SV_ROT_FLAG); ra.h_rot = v.d(MPCQ_SV_H_ROT);
+  ra.xref = v.d(MPCQ_SV_XREF); ra.fsteps = v.d(MPCQ_SV_FSTEPS); ra.q_w = v.d(MPCQ_SV_Q_W);
+  ra.state = v.d(MPCQ_SV_STATE); ra.l_feet = v.d(MPCQ_SV_L_FEET); ra.rho = v.d(MPCQ_SV_RHO);
+  ra.y = v.d(MPCQ_SV_Y); ra.warm_x = v.d(SP_WARM_X); ra.x = v.d(MPCQ_SV_X); ra.f0 = v.d(MPCQ_SV_F0);
+  ra.x_robot = v.d(MPCQ_SV_X_ROBOT); ra.cost = v.d(MPCQ_SV_COST);
+  ra.status = v.i(MPCQ_SV_STATUS); ra.iters = v.i(MPCQ_SV_ITERS);
+  ra.first = mark ? v.i(MPCQ_SV_FIRST) : nullptr;
+  if (s->swing) {
+    ra.swing_ref = v.d(MPCQ_SV_SWING_REF); ra.swing_ref_doubles = (int64_t)s->sp.k_mpc * 36;
+    ra.swing_state = v.d(MPCQ_SV_SWING_STATE); ra.frame = v.d(MPCQ_SV_FRAME);
+  }
+  if (s->mv.mem) {  // a reset robot's running episode is discarded
+    ra.ep = s->mv.d(MPCQ_MV_EP); ra.ep_ticks = s->mv.i(MPCQ_MV_EP_TICKS);
+  }
+  hipError_t e = mpcq::launch_reset(ra, c->stream);
+  // the robots with a pending reset to the front of the next solve's dispatch (a session that
+  // has not ticked yet has no order in use: it keeps the identity)
+  if (e == hipSuccess && s->have_order)
+    e = mpcq::launch_order(v.i(MPCQ_SV_ITERS), ra.first, s->B, v.i(MPCQ_SV_ORDER), c->stream);
+  if (mark) s->resets = true;
+  return e;
+}
+
+// The plant's arrays, all zero: made by the first mpcq_session_enable_plant / _set_wrench.
+int ensure_plant_mem(mpcq_session* s) {
+  if (s->pv.mem) return MPCQ_OK;
+  const size_t B = (size_t)s->B;
+  const size_t nb[PP_COUNT] = {B * 96, B * 96, B * 48, B * 48};  // STATE_END, F_EFF, WRENCH, qw_prev
+  return alloc_group(s->ctx, "the plant arrays", PP_COUNT, nb, &s->pv.mem, s->pv.ptr, s->pv.bytes);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mpcq_session_create(mpcq_ctx* c, int64_t B, const mpcq_planner_params* pp, const double* gait0,
+                        mpcq_session** out) {
+  if (!out) return fail(MPCQ_E_INVALID, "out is NULL");
+  *out = nullptr;
+  int rc = check_ctx(c, B);
+  if (rc) return rc;
+  if (B < 1) return fail(MPCQ_E_INVALID, "a session needs batch >= 1");
+  const int N = c->N;
+  mpcq_planner_params P;
+  if (pp) P = *pp;
+  else mpcq_default_planner_params(&P);
+  // host scratch: without gait0 the walking-trot table, then the identity order
+  const size_t gb = gait0 ? 0 : (size_t)B * 800;
+  char* h = (char*)malloc(gb + (size_t)B * 4);
+  if (!h) return fail(MPCQ_E_NOMEM, "host malloc failed");
+  if (!gait0) {  // create_walking_trot (FootstepPlanner.py:193-214): [1, 7, 1, 7] per 16-step period
+    const int half = (int)(0.5 * P.T_gait / P.dt);
+    const int per = 2 * half, nper = per > 0 ? N / per : 0;
+    if (nper < 1 || nper * per != N || 4 * nper > 19) {
+      free(h);
+      return fail(MPCQ_E_INVALID, "no walking-trot table for N=%d with T_gait/dt = %d; pass gait0", N, per);
+    }
+    for (int64_t b = 0; b < B; ++b) {
+      double* gt = (double*)h + b * 100;
+      for (int e = 0; e < 100; ++e) gt[e] = 0.0;
+      for (int i = 0; i < nper; ++i) {
+        const double d[4] = {1.0, half - 1.0, 1.0, half - 1.0};
+        const int m[4][4] = {{1, 1, 1, 1}, {1, 0, 0, 1}, {1, 1, 1, 1}, {0, 1, 1, 0}};
+        for (int r = 0; r < 4; ++r) {
+          gt[5 * (4 * i + r)] = d[r];
+          for (int q = 0; q < 4; ++q) gt[5 * (4 * i + r) + 1 + q] = m[r][q];
+        }
+      }
+    }
+    gait0 = (const double*)h;
+  }
+  int32_t* ident = (int32_t*)(h + gb);  // a permutation from the start
+  for (int64_t b = 0; b < B; ++b) ident[b] = (int32_t)b;
+  mpcq_session* s = new mpcq_session();
+  s->ctx = c;
+  s->B = B;
+  s->pp = P;
+  {
+    const char* e = getenv("MPCQ_DISPATCH_ORDER");
+    s->use_order = !(e && e[0] == '0');
+  }
+  size_t nb[SP_COUNT];
+  for (int w = 0; w < SP_COUNT; ++w) nb[w] = sv_bytes(w, B, N);
+  DeviceGuard g(c->device);
+  rc = alloc_group(c, "the session", SP_COUNT, nb, &s->sv.mem, s->sv.ptr, s->sv.bytes);
+  if (rc) {
+    free(h);
+    delete s;
+    return rc;
+  }
+  // every array defined before the first tick: the table a reset without gait0 goes back to,
+  // the order, and what a reset of every robot writes (the gait table from gait_init) -- but
+  // with no reset pending: MPCQ_SV_FIRST stays zero
+  const Group& v = s->sv;
+  hipError_t e = hipMemcpyAsync(v.ptr[SP_GAIT_INIT], gait0, v.bytes[SP_GAIT_INIT], hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(v.ptr[MPCQ_SV_ORDER], ident, v.bytes[MPCQ_SV_ORDER], hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = enqueue_reset(s, nullptr, nullptr, nullptr, false);
+  const hipError_t es = hipStreamSynchronize(c->stream);
+  free(h);
+  if (e != hipSuccess || es != hipSuccess) {
+    mpcq_session_destroy(s);
+    return fail(MPCQ_E_DEVICE, "initialising the session failed");
+  }
+  *out = s;
+  return MPCQ_OK;
+}
+
+int mpcq_session_destroy(mpcq_session* s) {
+  if (!s) return MPCQ_OK;
+  if (s->sv.mem) {
+    DeviceGuard g(s->ctx->device);
+    (void)hipStreamSynchronize(s->ctx->stream);
+    (void)hipFree(s->sv.mem);
+    if (s->swing_mem) (void)hipFree(s->swing_mem);
+    if (s->robots.dev) (void)hipFree(s->robots.dev);
+    if (s->pv.mem) (void)hipFree(s->pv.mem);
+    if (s->plant_robots.dev) (void)hipFree(s->plant_robots.dev);
+    if (s->mv.mem) (void)hipFree(s->mv.mem);
+  }
+  delete s;
+  return MPCQ_OK;
+}
+
+int mpcq_session_set_robots(mpcq_session* s, const mpcq_robot* robots, uint32_t flags) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  return set_table(s->ctx, s->robots, robots ? s->B : 0, robots, flags);
+}
+
+int mpcq_session_get_robots(mpcq_session* s, mpcq_robot* robots, uint32_t flags) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  if (!robots) return fail(MPCQ_E_INVALID, "robots is NULL");
+  mpcq_ctx* c = s->ctx;
+  DeviceGuard g(c->device);
+  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
+  const size_t nb = (size_t)s->B * sizeof(mpcq_robot);
+  if (s->robots.count) {
+    HIP_TRY(hipMemcpyAsync(robots, s->robots.dev, nb, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
+                           c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MPCQ_OK;
+  }
+  mpcq_robot d;
+  mpcq_default_robot(&c->p, &d);
+  if (!dev) {
+    for (int64_t b = 0; b < s->B; ++b) robots[b] = d;
+    return MPCQ_OK;
+  }
+  mpcq_robot* h = (mpcq_robot*)malloc(nb);
+  if (!h) return fail(MPCQ_E_NOMEM, "host malloc failed");
+  for (int64_t b = 0; b < s->B; ++b) h[b] = d;
+  const hipError_t e = hipMemcpy(robots, h, nb, hipMemcpyHostToDevice);
+  free(h);
+  HIP_TRY(e);
+  return MPCQ_OK;
+}
+
+int mpcq_session_enable_swing(mpcq_session* s, const mpcq_swing_params* sp) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  mpcq_swing_params P;
+  int rc = swing_params(sp, &P);
+  if (rc) return rc;
+  if (s->swing) {
+    if (P.k_mpc != s->sp.k_mpc) return fail(MPCQ_E_INVALID, "swing is enabled with k_mpc = %d", s->sp.k_mpc);
+    s->sp = P;
+    return MPCQ_OK;
+  }
+  const size_t B = (size_t)s->B;
+  const size_t nb[3] = {B * P.k_mpc * 36 * 8, B * 4 * MPCQ_SWING_STATE * 8, B * 24};  // all-zero state = new generators
+  DeviceGuard g(s->ctx->device);
+  rc = alloc_group(s->ctx, "the swing arrays", 3, nb, &s->swing_mem, s->sv.ptr + MPCQ_SV_SWING_REF,
+                   s->sv.bytes + MPCQ_SV_SWING_REF);
+  if (rc) return rc;
+  s->sp = P;
+  s->swing = true;
+  return MPCQ_OK;
+}
+
+int mpcq_session_enable_plant(mpcq_session* s, const mpcq_plant_params* pl) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  mpcq_plant_params P;
+  int rc = plant_params(pl, s->ctx->p.dt, &P);
+  if (rc) return rc;
+  if (P.dt != s->ctx->p.dt)
+    return fail(MPCQ_E_INVALID, "the plant's dt %g is not the context's %g", P.dt, s->ctx->p.dt);
+  DeviceGuard g(s->ctx->device);
+  rc = ensure_plant_mem(s);
+  if (rc) return rc;
+  s->pl = P;
+  s->plant = true;
+  return MPCQ_OK;
+}
+
+int mpcq_session_disable_plant(mpcq_session* s) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  s->plant = false;
+  return MPCQ_OK;
+}
+
+int mpcq_session_set_plant_robots(mpcq_session* s, const mpcq_robot* robots, uint32_t flags) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  return set_table(s->ctx, s->plant_robots, robots ? s->B : 0, robots, flags);
+}
+
+int mpcq_session_set_wrench(mpcq_session* s, const double* wrench, uint32_t flags) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  mpcq_ctx* c = s->ctx;
+  DeviceGuard g(c->device);
+  const int rc = ensure_plant_mem(s);
+  if (rc) return rc;
+  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
+  void* dst = s->pv.ptr[MPCQ_PV_WRENCH];
+  const size_t nb = s->pv.bytes[MPCQ_PV_WRENCH];
+  // on the context's stream: behind every queued tick that still reads the old wrench
+  if (!wrench) HIP_TRY(hipMemsetAsync(dst, 0, nb, c->stream));
+  else HIP_TRY(hipMemcpyAsync(dst, wrench, nb, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+  if (!(flags & MPCQ_FLAG_ASYNC) || !dev) HIP_TRY(hipStreamSynchronize(c->stream));
+  return MPCQ_OK;
+}
+
+int mpcq_session_enable_monitor(mpcq_session* s, const mpcq_monitor_params* mp) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  mpcq_monitor_params P;
+  int rc = monitor_params(mp, &P);
+  if (rc) return rc;
+  if (!s->mv.mem) {  // the arrays, zero but for ep[4] = +inf
+    mpcq_ctx* c = s->ctx;
+    DeviceGuard g(c->device);
+    const size_t B = (size_t)s->B;
+    const size_t nb[MPCQ_MV_COUNT] = {B * 4, B * 64, B * 4, B * 4, B * 128, 64};
+    double* h = (double*)malloc(nb[MPCQ_MV_EP]);
+    if (!h) return fail(MPCQ_E_NOMEM, "host malloc failed");
+    for (size_t e = 0; e < B * 8; ++e) h[e] = e % 8 == 4 ? INFINITY : 0.0;
+    Group mv = s->mv;
+    rc = alloc_group(c, "the monitor arrays", MPCQ_MV_COUNT, nb, &mv.mem, mv.ptr, mv.bytes);
+    hipError_t e = hipSuccess;
+    if (!rc) e = hipMemcpyAsync(mv.ptr[MPCQ_MV_EP], h, nb[MPCQ_MV_EP], hipMemcpyHostToDevice, c->stream);
+    if (!rc && e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    free(h);
+    if (rc) return rc;
+    if (e != hipSuccess) {
+      (void)hipFree(mv.mem);
+      return fail(MPCQ_E_DEVICE, "initialising the monitor arrays failed: %s", hipGetErrorString(e));
+    }
+    s->mv = mv;
+  }
+  s->mp = P;
+  s->monitor = true;
+  return MPCQ_OK;
+}
+
+int mpcq_session_disable_monitor(mpcq_session* s) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  s->monitor = false;
+  return MPCQ_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// One tick's inputs where its kernels read them, and what makes it a first tick.
+struct Tick {
+  int k;
+  const double *state, *l_feet, *v_ref;
+  const int32_t* reduced;  // or null
+  // after a mpcq_session_reset: a robot whose MPCQ_SV_FIRST is set runs this tick as a first
+  // tick whatever k says (the planner's extra pass then touches those robots only)
+  // (k == 0 makes every robot first by itself: only the retrieve takes the flags then, to clear them)
+  int32_t* first;          // MPCQ_SV_FIRST, or null before any reset
+  const int32_t* first_k;  // first, or null at k == 0
+  double* trace;           // [B][MPCQ_TRACE] (device) or null: the monitor's row of this tick
+};
+
+// Host arrays through the staging buffers; the virtual robot's state (state / l_feet null)
+// lives in arrays the retrieve kernel rewrites: this tick reads a copy.
+int tick_inputs(mpcq_session* s, const double* state, const double* l_feet, const double* v_ref,
+                const int32_t* reduced, bool dev, Tick& t) {
+  const Group& v = s->sv;
+  hipStream_t st = s->ctx->stream;
+  hipError_t e = hipSuccess;
+  t.state = staged(s, dev, state, SP_IN_STATE, &e);
+  t.l_feet = staged(s, dev, l_feet, SP_IN_LFEET, &e);
+  t.v_ref = staged(s, dev, v_ref, SP_IN_VREF, &e);
+  t.reduced = staged(s, dev, reduced, SP_IN_REDUCED, &e);
+  if (e != hipSuccess) return fail(MPCQ_E_DEVICE, "staging the tick inputs failed");
+  if (!state) {
+    HIP_TRY(hipMemcpyAsync(v.ptr[SP_IN_STATE], v.ptr[MPCQ_SV_STATE], v.bytes[SP_IN_STATE], hipMemcpyDeviceToDevice, st));
+    t.state = v.d(SP_IN_STATE);
+  }
+  if (!l_feet) {
+    HIP_TRY(hipMemcpyAsync(v.ptr[SP_IN_LFEET], v.ptr[MPCQ_SV_L_FEET], v.bytes[SP_IN_LFEET], hipMemcpyDeviceToDevice, st));
+    t.l_feet = v.d(SP_IN_LFEET);
+  }
+  t.first = s->resets ? v.i(MPCQ_SV_FIRST) : nullptr;
+  t.first_k = t.k == 0 ? nullptr : t.first;
+  return MPCQ_OK;
+}
+
+// The planner (processing.py:80-89, 131), between ev[0] and ev[1].
+int tick_plan(mpcq_session* s, const Tick& t) {
+  mpcq_ctx* c = s->ctx;
+  const Group& v = s->sv;
+  mpcq::PlanArgs a{};
+  a.batch = s->B; a.N = c->N; a.k = t.k; a.first = t.first_k;
+  a.state = t.state; a.l_feet = t.l_feet; a.v_ref = t.v_ref; a.reduced = t.reduced;
+  a.gait = v.d(MPCQ_SV_GAIT); a.rot_flag = v.i(MPCQ_SV_ROT_FLAG); a.h_rot = v.d(MPCQ_SV_H_ROT);
+  a.xref = v.d(MPCQ_SV_XREF); a.fsteps = v.d(MPCQ_SV_FSTEPS); a.status = v.i(SP_PLAN_STATUS);
+  HIP_TRY(hipEventRecord(c->ev[0], c->stream));
+  if (t.k == 0 || t.first_k) {  // update_fsteps(0, ...): no roll
+    a.ops = MPCQ_PLAN_FOOTSTEPS;
+    HIP_TRY(mpcq::launch_plan(s->pp, a, c->stream));
+  }
+  a.ops = MPCQ_PLAN_TICK;
+  HIP_TRY(mpcq::launch_plan(s->pp, a, c->stream));
+  HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+  c->have_form = true;
+  return MPCQ_OK;
+}
+
+// MPC.run: formulation + OSQP solve (warm from the previous tick when k > 0), between ev[2]
+// and ev[3].
+int tick_solve(mpcq_session* s, const Tick& t) {
+  mpcq_ctx* c = s->ctx;
+  const Group& v = s->sv;
+  mpcq::LaunchArgs a{};
+  a.batch = s->B;
+  a.mode = t.k == 0 ? MPCQ_MODE_SETUP : MPCQ_MODE_UPDATE;
+  a.xref = v.d(MPCQ_SV_XREF); a.fsteps = v.d(MPCQ_SV_FSTEPS);
+  if (t.k > 0) {
+    a.warm_x = v.d(SP_WARM_X); a.warm_y = v.d(MPCQ_SV_Y); a.rho_in = v.d(MPCQ_SV_RHO);
+  }
+  a.f0 = v.d(MPCQ_SV_F0); a.x = v.d(MPCQ_SV_X); a.y = v.d(MPCQ_SV_Y); a.rho_out = v.d(MPCQ_SV_RHO);
+  a.status = v.i(MPCQ_SV_STATUS); a.iters = v.i(MPCQ_SV_ITERS); a.info = v.i(SP_INFO);
+  a.stamps = c->stamps;
+  // longest-first by the previous tick's iteration counts (a tick k == 0 restarts cold)
+  if (t.k == 0) s->have_order = false;
+  a.order = s->have_order && s->use_order ? v.i(MPCQ_SV_ORDER) : nullptr;
+  a.robots = s->robots.count ? s->robots.dev : nullptr;
+  a.first = t.first_k;
+  const int rc = ensure_work(c, s->B, &a.work);
+  if (rc) return rc;
+  HIP_TRY(hipEventRecord(c->ev[2], c->stream));
+  HIP_TRY(mpcq::launch_solve(c->N, true, c->p, a, c->stream));
+  HIP_TRY(hipEventRecord(c->ev[3], c->stream));
+  c->have_solve = true;
+  return MPCQ_OK;
+}
+
+// retrieve_result, q_w, Logger cost, next warm start, virtual robot; before it, the copies of
+// q_w that swing and plant need as it stands before the retrieve moves it.
+int tick_retrieve(mpcq_session* s, const Tick& t) {
+  mpcq_ctx* c = s->ctx;
+  const Group& v = s->sv;
+  const size_t B = (size_t)s->B;
+  mpcq::SessionArgs a{};
+  a.batch = s->B;
+  a.x = v.d(MPCQ_SV_X); a.xref = v.d(MPCQ_SV_XREF); a.fsteps = v.d(MPCQ_SV_FSTEPS); a.gait = v.d(MPCQ_SV_GAIT);
+  a.status = v.i(MPCQ_SV_STATUS); a.plan_status = v.i(SP_PLAN_STATUS);
+  a.x_robot = v.d(MPCQ_SV_X_ROBOT); a.warm_x = v.d(SP_WARM_X); a.y = v.d(MPCQ_SV_Y);
+  a.rho = v.d(MPCQ_SV_RHO); a.rho0 = c->p.rho; a.cost = v.d(MPCQ_SV_COST); a.q_w = v.d(MPCQ_SV_Q_W);
+  a.next_state = v.d(MPCQ_SV_STATE); a.next_l_feet = v.d(MPCQ_SV_L_FEET);
+  for (int i = 0; i < 12; ++i) a.state_weights[i] = c->p.state_weights[i];
+  a.force_weight = c->p.force_weight;
+  for (int i = 0; i < 8; ++i) a.shoulders[i] = s->pp.shoulders[i];
+  a.first = t.first;
+  if (s->swing) {  // the frame of this tick's fsteps: q_w's x, y, yaw
+    double* fr = v.d(MPCQ_SV_FRAME);
+    HIP_TRY(hipMemcpy2DAsync(fr, 24, a.q_w, 48, 16, B, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemcpy2DAsync(fr + 2, 24, a.q_w + 5, 48, 8, B, hipMemcpyDeviceToDevice, c->stream));
+  }
+  if (s->plant)  // the world pose the plant starts from
+    HIP_TRY(hipMemcpyAsync(s->pv.ptr[PP_QW_PREV], a.q_w, B * 48, hipMemcpyDeviceToDevice, c->stream));
+  HIP_TRY(mpcq::launch_retrieve(c->N, a, c->stream));
+  return MPCQ_OK;
+}
+
+// The rigid body under this tick's forces takes the place of the prediction.
+int tick_plant(mpcq_session* s, const Tick& t) {
+  mpcq_ctx* c = s->ctx;
+  const Group& v = s->sv;
+  mpcq::PlantArgs a{};
+  a.batch = s->B;
+  a.state = t.state; a.fsteps = v.d(MPCQ_SV_FSTEPS); a.f = v.d(MPCQ_SV_F0); a.wrench = s->pv.d(MPCQ_PV_WRENCH);
+  a.robots = s->plant_robots.count ? s->plant_robots.dev : s->robots.count ? s->robots.dev : nullptr;
+  mpcq_default_robot(&c->p, &a.dflt);
+  a.state_out = s->pv.d(MPCQ_PV_STATE_END); a.f_eff = s->pv.d(MPCQ_PV_F_EFF);
+  a.tail = 1;
+  a.status = v.i(MPCQ_SV_STATUS); a.plan_status = v.i(SP_PLAN_STATUS); a.gait = v.d(MPCQ_SV_GAIT);
+  a.q_w_prev = s->pv.d(PP_QW_PREV); a.q_w = v.d(MPCQ_SV_Q_W);
+  a.next_state = v.d(MPCQ_SV_STATE); a.next_l_feet = v.d(MPCQ_SV_L_FEET);
+  for (int i = 0; i < 8; ++i) a.shoulders[i] = s->pp.shoulders[i];
+  HIP_TRY(mpcq::launch_plant(s->pl, a, c->stream));
+  return MPCQ_OK;
+}
+
+// Whose episode ended with this tick, and the episodes' statistics.
+int tick_monitor(mpcq_session* s, const Tick& t) {
+  const Group &v = s->sv, &m = s->mv;
+  mpcq::MonitorArgs a{};
+  a.batch = s->B;
+  a.q_w = v.d(MPCQ_SV_Q_W); a.status = v.i(MPCQ_SV_STATUS); a.iters = v.i(MPCQ_SV_ITERS); a.f0 = v.d(MPCQ_SV_F0);
+  a.cost = v.d(MPCQ_SV_COST); a.state = v.d(MPCQ_SV_STATE); a.v_ref = t.v_ref;
+  a.ep = m.d(MPCQ_MV_EP); a.ep_ticks = m.i(MPCQ_MV_EP_TICKS); a.episodes = m.i(MPCQ_MV_EPISODES);
+  a.last = m.d(MPCQ_MV_LAST); a.done = m.i(MPCQ_MV_DONE); a.totals = (unsigned long long*)m.ptr[MPCQ_MV_TOTALS];
+  a.trace = t.trace;
+  HIP_TRY(mpcq::launch_monitor(s->mp, a, s->ctx->stream));
+  return MPCQ_OK;
+}
+
+// The next solve's dispatch order (the retrieve has cleared every pending reset: by
+// iteration counts alone).
+int tick_order(mpcq_session* s) {
+  const Group& v = s->sv;
+  HIP_TRY(mpcq::launch_order(v.i(MPCQ_SV_ITERS), nullptr, s->B, v.i(MPCQ_SV_ORDER), s->ctx->stream));
+  s->have_order = true;
+  return MPCQ_OK;
+}
+
+// The tick's swing-foot references, substeps 0..k_mpc-1 (virtual-robot lift-off).
+int tick_swing(mpcq_session* s) {
+  const Group& v = s->sv;
+  mpcq::SwingArgs a{};
+  a.batch = s->B; a.k_sub0 = 0; a.n_sub = s->sp.k_mpc;
+  a.gait = v.d(MPCQ_SV_GAIT); a.fsteps = v.d(MPCQ_SV_FSTEPS); a.frame = v.d(MPCQ_SV_FRAME);
+  a.state = v.d(MPCQ_SV_SWING_STATE); a.ref = v.d(MPCQ_SV_SWING_REF);
+  HIP_TRY(mpcq::launch_swing(s->sp, a, s->ctx->stream));
+  return MPCQ_OK;
+}
+
+// One tick: its stages in stream order.
+int session_tick(mpcq_session* s, int k, const double* state, const double* l_feet, const double* v_ref,
+                 const int32_t* reduced, uint32_t flags, double* trace) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  if (!v_ref) return fail(MPCQ_E_INVALID, "v_ref is required");
+  if (k < 0) return fail(MPCQ_E_INVALID, "k must be >= 0");
+  mpcq_ctx* c = s->ctx;
+  DeviceGuard g(c->device);
+  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
+  Tick t{};
+  t.k = k;
+  t.trace = trace;
+  int rc = tick_inputs(s, state, l_feet, v_ref, reduced, dev, t);
+  if (!rc) rc = tick_plan(s, t);
+  if (!rc) rc = tick_solve(s, t);
+  if (!rc) rc = tick_retrieve(s, t);
+  if (!rc && s->plant) rc = tick_plant(s, t);
+  if (!rc && s->monitor) rc = tick_monitor(s, t);
+  if (!rc) rc = tick_order(s);
+  if (!rc && s->swing) rc = tick_swing(s);
+  if (rc) return rc;
+  // auto-reset, last: the swing launch above has read the tick's gait and fsteps
+  if (s->monitor && s->mp.auto_reset) HIP_TRY(enqueue_reset(s, s->mv.i(MPCQ_MV_DONE), nullptr, nullptr, true));
+  // host inputs are staged in buffers the next tick reuses: host calls block
+  if (!(flags & MPCQ_FLAG_ASYNC) || !dev) HIP_TRY(hipStreamSynchronize(c->stream));
+  return MPCQ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mpcq_session_tick(mpcq_session* s, int k, const double* state, const double* l_feet, const double* v_ref,
+                      const int32_t* reduced, uint32_t flags) {
+  return session_tick(s, k, state, l_feet, v_ref, reduced, flags, nullptr);
+}
+
+int mpcq_session_run(mpcq_session* s, int k0, int n_ticks, const double* v_ref, int v_ref_ticks, double* trace,
+                     uint32_t flags) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  if (!(flags & MPCQ_FLAG_DEVICE_PTRS)) return fail(MPCQ_E_INVALID, "mpcq_session_run needs MPCQ_FLAG_DEVICE_PTRS");
+  if (!v_ref || v_ref_ticks < 1) return fail(MPCQ_E_INVALID, "v_ref [v_ref_ticks][B][6] with v_ref_ticks >= 1 is required");
+  if (k0 < 0 || n_ticks < 1) return fail(MPCQ_E_INVALID, "need k0 >= 0 and n_ticks >= 1");
+  if (k0 > INT32_MAX - n_ticks) return fail(MPCQ_E_INVALID, "k0 + n_ticks overflows");
+  if (trace && !s->monitor) return fail(MPCQ_E_INVALID, "a trace needs mpcq_session_enable_monitor");
+  const size_t B = (size_t)s->B;
+  for (int t = 0; t < n_ticks; ++t) {
+    const int row = t < v_ref_ticks ? t : v_ref_ticks - 1;
+    const int rc = session_tick(s, k0 + t, nullptr, nullptr, v_ref + (size_t)row * B * 6, nullptr,
+                                MPCQ_FLAG_DEVICE_PTRS | MPCQ_FLAG_ASYNC,
+                                trace ? trace + (size_t)t * B * MPCQ_TRACE : nullptr);
+    if (rc) {
+      (void)hipStreamSynchronize(s->ctx->stream);
+      return rc;
+    }
+  }
+  if (!(flags & MPCQ_FLAG_ASYNC)) {
+    DeviceGuard g(s->ctx->device);
+    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+  }
+  return MPCQ_OK;
+}
+
+int mpcq_session_reset(mpcq_session* s, const int32_t* mask, const double* gait0, const double* q_w0,
+                       uint32_t flags) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  mpcq_ctx* c = s->ctx;
+  DeviceGuard g(c->device);
+  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
+  hipError_t e = hipSuccess;
+  mask = staged(s, dev, mask, SP_IN_REDUCED, &e);
+  gait0 = staged(s, dev, gait0, SP_IN_GAIT, &e);
+  q_w0 = staged(s, dev, q_w0, SP_IN_VREF, &e);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(c->stream);
+    return fail(MPCQ_E_DEVICE, "staging the reset's inputs failed");
+  }
+  e = enqueue_reset(s, mask, gait0, q_w0, true);
+  if (!(flags & MPCQ_FLAG_ASYNC) || !dev) {
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = es;
+  }
+  HIP_TRY(e);
+  return MPCQ_OK;
+}
+
+int mpcq_session_read(mpcq_session* s, int what, void* dst, uint32_t flags) {
+  return group_read(s, &mpcq_session::sv, what, dst, flags);
+}
+
+int mpcq_session_plant_read(mpcq_session* s, int what, void* dst, uint32_t flags) {
+  return group_read(s, &mpcq_session::pv, what, dst, flags);
+}
+
+int mpcq_session_monitor_read(mpcq_session* s, int what, void* dst, uint32_t flags) {
+  return group_read(s, &mpcq_session::mv, what, dst, flags);
+}
+
+int mpcq_session_device_ptr(mpcq_session* s, int what, void** out) {
+  return group_device_ptr(s, &mpcq_session::sv, what, out);
+}
+
+int mpcq_session_plant_device_ptr(mpcq_session* s, int what, void** out) {
+  return group_device_ptr(s, &mpcq_session::pv, what, out);
+}
+
+int mpcq_session_monitor_device_ptr(mpcq_session* s, int what, void** out) {
+  return group_device_ptr(s, &mpcq_session::mv, what, out);
+}
+
+int mpcq_session_write(mpcq_session* s, int what, const void* src, uint32_t flags) {
+  if (!s || !src) return fail(MPCQ_E_INVALID, "NULL argument");
+  const int rc = find(s->sv, what);
+  if (rc) return rc;
+  // the engine indexes robots through the order: only order_kernel writes it
+  if (what == MPCQ_SV_ORDER) return fail(MPCQ_E_INVALID, "MPCQ_SV_ORDER is read-only");
+  // only mpcq_session_reset sets it (with the state a first tick needs), only the retrieve clears it
+  if (what == MPCQ_SV_FIRST) return fail(MPCQ_E_INVALID, "MPCQ_SV_FIRST is read-only");
+  if (what == MPCQ_SV_SWING_REF || what == MPCQ_SV_FRAME)
+    return fail(MPCQ_E_INVALID, "MPCQ_SV_SWING_REF and MPCQ_SV_FRAME are read-only");
+  DeviceGuard g(s->ctx->device);
+  const hipMemcpyKind kind = (flags & MPCQ_FLAG_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  HIP_TRY(hipMemcpyAsync(s->sv.ptr[what], src, s->sv.bytes[what], kind, s->ctx->stream));
+  HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+  return MPCQ_OK;
+}
+
+}  // extern "C"

@@ -30,17 +30,20 @@ for n in $HS; do
   J=$((J + 1)); if [ $((J % 8)) -eq 0 ]; then wait; fi
 done
 wait
-# only the variant's horizons (a dispatch unit restricted to them: the library stays
-# small, every gpurun call ships it)
+# only the variant's horizons (a dispatch unit restricted to them: the library stays small)
 OBJS=""
 HX=""
 for n in $HS; do OBJS="$OBJS $OUT/$NAME/e$n.o"; HX="$HX X($n)"; done
 printf '#include "mpcq_internal.h"\n#undef MPCQ_HORIZONS\n#define MPCQ_HORIZONS(X) %s\n#include "mpcq_dispatch.cpp"\n' "$HX" > $OUT/$NAME/dispatch.cpp
 /opt/rocm/bin/hipcc $F "$@" -I$R/include -c -o $OUT/$NAME/dispatch.o $OUT/$NAME/dispatch.cpp
-# the C ABI with the variant's flags too (a layout switch changes work_doubles)
+# the C ABI (both units) with the variant's flags too (a layout switch changes work_doubles)
 /opt/rocm/bin/hipcc $F "$@" -I$R/include -c -o $OUT/$NAME/api.o $C/mpcq_api.cpp
+/opt/rocm/bin/hipcc $F "$@" -I$R/include -c -o $OUT/$NAME/session_api.o $C/mpcq_session_api.cpp
 # the variant's own build stamp
 /opt/rocm/bin/hipcc $F -DMPCQ_SRC_SHA="\"$VSHA\"" -DMPCQ_ARCH='"gfx950"' -c -o $OUT/$NAME/build.o $C/mpcq_build.cpp
-/opt/rocm/bin/hipcc $F -shared -o $OUT/libmpcq_$NAME.so $OBJS $C/build/mpcq_planner.o $C/build/mpcq_session.o $C/build/mpcq_order.o $C/build/mpcq_swing.o \
-  $OUT/$NAME/api.o $OUT/$NAME/build.o $OUT/$NAME/dispatch.o
+# the other kernels' objects as the production build made them: the Makefile's own list
+# (paths relative to csrc)
+KERNELS=$(make -s --no-print-directory -C $C print-variant-objs)
+(cd $C && /opt/rocm/bin/hipcc $F -shared -o $OUT/libmpcq_$NAME.so $OBJS $KERNELS \
+  $OUT/$NAME/api.o $OUT/$NAME/session_api.o $OUT/$NAME/build.o $OUT/$NAME/dispatch.o)
 echo "built $OUT/libmpcq_$NAME.so"
