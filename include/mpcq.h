@@ -56,7 +56,12 @@ extern "C" {
  *      mpcq_monitor_step_batch, mpcq_session_enable_monitor / _disable_monitor / _monitor_read /
  *      _monitor_device_ptr, mpcq_session_run (episodes: on-device termination, statistics,
  *      auto-reset, multi-tick rollouts); the monitor's arrays have ids of their own, MPCQ_MV_*:
- *      MPCQ_SV_COUNT stays 21 */
+ *      MPCQ_SV_COUNT stays 21
+ *   3 (additions, no bump): mpcq_scenario_params, mpcq_default_scenario_params,
+ *      mpcq_scenario_step_batch, mpcq_session_enable_scenario / _disable_scenario /
+ *      _scenario_read / _scenario_device_ptr (per-episode random commands, pushes and payloads
+ *      drawn on the device); its arrays have ids of their own, MPCQ_CV_*; with a scenario that
+ *      commands, mpcq_session_tick and mpcq_session_run accept v_ref == NULL */
 #define MPCQ_ABI_VERSION 3
 
 /* error codes (return values) */
@@ -701,6 +706,131 @@ int mpcq_session_monitor_device_ptr(mpcq_session* s, int what, void** out);
  * launched. */
 int mpcq_session_run(mpcq_session* s, int k0, int n_ticks, const double* v_ref, int v_ref_ticks,
                      double* trace, uint32_t flags);
+
+/* ---- scenarios -------------------------------------------------------------
+ * The producer of v_ref, and of what disturbs a robot, on the device: per robot and per episode
+ * a command profile relative to the episode's start (the reference's one command source in use,
+ * Joystick.update_v_ref_predefined, Joystick.py:70-83, is its default), push windows, and the
+ * true mass and friction of the plant's robot.  One thread per robot, stateless but for two
+ * integers per robot (the episode's number `epoch` and the episode's tick `tau`); every draw
+ * comes from a counter-based generator, so a host restatement (mpcq/scenario.py in the Python
+ * package) reproduces any episode from (seed, robot, epoch), bit for bit.
+ *
+ * Generator: Philox4x32-10, multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 /
+ * 0xBB67AE85, called as philox(counter = (b, epoch, index, stream), key = (seed & 0xffffffff,
+ * seed >> 32)) -> w0..w3; streams: 0 the episode's constants, 1 commands, 2 pushes.
+ *   u(wa, wb)        = ((wa >> 5) * 67108864.0 + (wb >> 6)) * 2^-53      a double in [0, 1)
+ *   range(lo, hi, u) = lo + (hi - lo) * u                                no contraction
+ *   int(a, n, w)     = a + (int)(((uint64)w * n) >> 32)                  in [a, a + n - 1]
+ *   prob(w, p)       = (double)w * 2^-32 < p
+ *
+ * A robot-tick.  On a tick where the robot is first, epoch += 1 and tau = 0; otherwise tau is
+ * the stored tick.  After the tick's computation the stored tick is tau + 1.
+ *   Constants (a first tick only): philox(b, epoch, 0, 0): mass_scale = range(mass_scale_lo,
+ *     mass_scale_hi, u(w0, w1)), mu = range(mu_lo, mu_hi, u(w2, w3)).  robots_out[b] = the base
+ *     row, with (robots & 1) mass and the nine gI entries times mass_scale, with (robots & 2) mu
+ *     replaced.  draw[b] = mass_scale, mu, (double)epoch, five zeros.
+ *   Commands (commands != 0): segment j = cmd_period > 0 ? tau / cmd_period : 0; its target:
+ *     philox(b, epoch, 2j, 1) -> vx = range(v_lo[0], v_hi[0], u(w0, w1)), vy = range(v_lo[1],
+ *     v_hi[1], u(w2, w3)); philox(b, epoch, 2j + 1, 1) -> wyaw = range(v_lo[2], v_hi[2],
+ *     u(w0, w1)).  prev = the target of segment j - 1, zero for j = 0 (a start from rest).
+ *     t = tau - j * cmd_period - (j == 0 ? cmd_start : 0); alpha = cmd_ramp > 0 ?
+ *     clamp((double)t / (double)cmd_ramp, 0, 1) : (t >= 0 ? 1 : 0).  v_ref[b][0, 1, 5] = target
+ *     when alpha == 1, prev when alpha == 0, else prev + (target - prev) * alpha; v_ref[b][2, 3,
+ *     4] = 0.  With commands == 0 v_ref[b] is written as zeros.
+ *   Pushes (pushes != 0): none while tau < push_first; else window j = push_period > 0 ?
+ *     (tau - push_first) / push_period : 0; philox(b, epoch, 4j, 2): jitter = int(0,
+ *     push_jitter + 1, w0), occurs = prob(w1, push_prob), w2 = the flip bits; the window starts
+ *     at s = push_first + j * push_period + jitter and is active iff occurs and s <= tau <
+ *     s + push_ticks.  Its wrench: philox(b, epoch, 4j + 1 + i / 2, 2) for i = 0..5 gives
+ *     range(wrench_lo[i], wrench_hi[i], u) with u = u(w0, w1) for even i, u(w2, w3) for odd i,
+ *     negated when bit i of push_flip and bit i of w2 are both set.  push[b] = that wrench while
+ *     active, else zeros; wrench_out[b] = wrench_in[b] (zeros if NULL) + push[b] component by
+ *     component while active, else a plain copy of wrench_in[b].  With pushes == 0 push[b] is
+ *     zeros and wrench_out[b] the copy. */
+typedef struct mpcq_scenario_params {   /* 256 bytes */
+  uint64_t seed;
+  double v_lo[3], v_hi[3];              /* vx, vy, wyaw */
+  double wrench_lo[6], wrench_hi[6];    /* force, then torque (a session: world frame) */
+  double push_prob;                     /* in [0, 1] */
+  double mass_scale_lo, mass_scale_hi, mu_lo, mu_hi;
+  int32_t commands, cmd_start, cmd_ramp, cmd_period;
+  int32_t pushes, push_first, push_period, push_jitter, push_ticks, push_flip;
+  int32_t robots;                       /* bit 1: mass and gI scale, bit 2: mu */
+  int32_t reserved[5];
+} mpcq_scenario_params;
+#ifdef __cplusplus
+static_assert(sizeof(mpcq_scenario_params) == 256, "mpcq_scenario_params is 256 bytes");
+#else
+_Static_assert(sizeof(mpcq_scenario_params) == 256, "mpcq_scenario_params is 256 bytes");
+#endif
+/* The reference's predefined joystick at MPC ticks (Joystick.py:82 evaluates (k_loop - 960) /
+ * 3500 at k_loop = 20 tau, the same rational as (tau - 48) / 175): seed 0, commands 1, v_lo =
+ * v_hi = (1, 0, 0), cmd_start 48, cmd_ramp 175, cmd_period 0; pushes 0, push_prob 1, push_ticks
+ * 10, the other push fields and both wrench bounds 0; mass_scale 1..1, mu 0.9..0.9, robots 0. */
+void mpcq_default_scenario_params(mpcq_scenario_params* sc);
+/* The scenario on its own, one tick for a batch.
+ *   first      [B] int32 or NULL: nonzero = a first tick for this robot; all_first != 0: for all
+ *   epoch, tick [B] int32 in/out
+ *   base       [B] the rows the constants are applied to; NULL = ctx's mpcq_params (a host table
+ *              is validated as in mpcq_set_robots, a device table is not)
+ *   wrench_in  [B][6] or NULL (zeros)
+ *   v_ref, push, wrench_out [B][6] out
+ *   robots_out [B] or NULL, draw [B][8] or NULL: in/out, written on a robot's first tick only
+ * sc NULL = mpcq_default_scenario_params.  Host pointers, or device pointers with
+ * MPCQ_FLAG_DEVICE_PTRS (then MPCQ_FLAG_ASYNC does not wait for the stream).
+ * MPCQ_E_INVALID, nothing launched: a NULL required pointer; a non-finite bound or lo > hi;
+ * mass_scale_lo <= 0 with (robots & 1), mu_lo <= 0 with (robots & 2); push_prob outside [0, 1];
+ * a negative integer field; push_ticks < 1 with pushes; cmd_period != 0 and cmd_period <
+ * cmd_start + cmd_ramp, or push_period != 0 and push_jitter + push_ticks > push_period (the
+ * two rules that keep a tick a function of one or two segments); robots beyond 3, push_flip
+ * beyond 63; reserved not zero.  The parameters are checked before anything else. */
+int mpcq_scenario_step_batch(mpcq_ctx* ctx, const mpcq_scenario_params* sc, int64_t batch,
+                             const int32_t* first, int all_first, int32_t* epoch, int32_t* tick,
+                             const mpcq_robot* base, const double* wrench_in, double* v_ref,
+                             double* push, double* wrench_out, mpcq_robot* robots_out,
+                             double* draw, uint32_t flags);
+
+/* Opt-in (sc NULL = mpcq_default_scenario_params; invalid parameters: MPCQ_E_INVALID, nothing is
+ * launched and the parameters in force stay): while enabled, every tick starts with one
+ * scenario launch, before its planner, on the context's stream.  A robot is first there exactly
+ * where the planner takes it as first (k == 0, or its MPCQ_SV_FIRST set by a reset or an
+ * auto-reset).  The base rows of the constants: the plant's table if set, else the model's
+ * table, else ctx's params, as they stand at the tick; the user's tables are never written.
+ * wrench_in is MPCQ_PV_WRENCH (zeros before any mpcq_session_set_wrench).
+ *   commands != 0: mpcq_session_tick and mpcq_session_run accept v_ref == NULL (v_ref_ticks is
+ *     then ignored): planner and monitor take MPCQ_CV_V_REF.  A non-NULL v_ref wins;
+ *     MPCQ_CV_V_REF is written all the same.  Without a scenario, or with commands == 0, a NULL
+ *     v_ref stays MPCQ_E_INVALID.
+ *   pushes != 0: the tick's plant launch takes MPCQ_CV_WRENCH in place of MPCQ_PV_WRENCH.
+ *   robots != 0: the tick's plant launch takes MPCQ_CV_ROBOTS as its table.
+ * Pushes and robots act only through an enabled plant; without one they are computed and unused.
+ * The first call makes the MPCQ_CV_* arrays (zero, MPCQ_CV_ROBOTS the base rows) and enqueues
+ * one launch that, for every robot, draws the constants of epoch 0 into MPCQ_CV_ROBOTS and
+ * MPCQ_CV_DRAW and evaluates commands and pushes at tau = 0 without advancing MPCQ_CV_TICK: a
+ * session enabled in mid-episode runs epoch 0 with tau counting from the enable; one enabled
+ * before its first tick starts epoch 1 there.  Calling it again replaces the parameters and
+ * keeps the arrays (the constants in force change at each robot's next first tick).  With
+ * auto-reset alone, the n-th ended episode of robot b (MPCQ_MV_EPISODES) ran under epoch n.
+ * A session that never enables it launches exactly what it did before. */
+int mpcq_session_enable_scenario(mpcq_session* s, const mpcq_scenario_params* sc);
+/* The ticks after it run without the scenario launch: the plant is back on the user's wrench
+ * and tables, a NULL v_ref is MPCQ_E_INVALID again; the arrays stay. */
+int mpcq_session_disable_scenario(mpcq_session* s);
+/* The scenario's arrays; they exist from the first mpcq_session_enable_scenario on (before:
+ * MPCQ_E_INVALID). */
+#define MPCQ_CV_EPOCH 0     /* [B] int32   the running episode's number */
+#define MPCQ_CV_TICK 1      /* [B] int32   the next tick's tau, unless that tick is a first one */
+#define MPCQ_CV_V_REF 2     /* [B][6]      the last tick's command */
+#define MPCQ_CV_PUSH 3      /* [B][6]      the last tick's push (zeros outside a window) */
+#define MPCQ_CV_WRENCH 4    /* [B][6]      MPCQ_PV_WRENCH + MPCQ_CV_PUSH (world frame) */
+#define MPCQ_CV_ROBOTS 5    /* [B] mpcq_robot  the running episode's true robots */
+#define MPCQ_CV_DRAW 6      /* [B][8]      mass_scale, mu, (double)epoch, five zeros */
+#define MPCQ_CV_COUNT 7
+/* Copy array `what` to dst (host, or device with MPCQ_FLAG_DEVICE_PTRS); blocking. */
+int mpcq_session_scenario_read(mpcq_session* s, int what, void* dst, uint32_t flags);
+/* Device address of array `what` (valid until mpcq_session_destroy). */
+int mpcq_session_scenario_device_ptr(mpcq_session* s, int what, void** out);
 
 /* ---- diagnostics -----------------------------------------------------------
  * Device buffer [B][16] (uint64) that a diagnostic build of the library

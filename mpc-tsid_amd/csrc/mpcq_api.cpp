@@ -4,7 +4,7 @@
 // Owns HIP contexts, device staging buffers for host-pointer calls, stream
 // and event handling.  All numerics run in the HIP kernels (mpcq_engine.hip,
 // mpcq_planner.hip, mpcq_session.hip, mpcq_order.hip, mpcq_swing.hip, mpcq_plant.hip,
-// mpcq_monitor.hip); there is no CPU fallback: a missing device is an error.
+// mpcq_monitor.hip, mpcq_scenario.hip); there is no CPU fallback: a missing device is an error.
 #include <math.h>
 #include <stdarg.h>
 #include <stdlib.h>
@@ -233,6 +233,37 @@ int mpcq::monitor_params(const mpcq_monitor_params* mp, mpcq_monitor_params* out
     return fail(MPCQ_E_INVALID, "the monitor needs a finite min_height (or -inf: no height test)");
   if (out->max_ticks < 0) return fail(MPCQ_E_INVALID, "the monitor needs max_ticks >= 0");
   if (out->auto_reset != 0 && out->auto_reset != 1) return fail(MPCQ_E_INVALID, "auto_reset must be 0 or 1");
+  return MPCQ_OK;
+}
+
+int mpcq::scenario_params(const mpcq_scenario_params* sc, mpcq_scenario_params* out) {
+  if (sc) *out = *sc;
+  else mpcq_default_scenario_params(out);
+  const mpcq_scenario_params& p = *out;
+  auto bounds = [](const double* lo, const double* hi, int n) {
+    for (int i = 0; i < n; ++i)
+      if (!isfinite(lo[i]) || !isfinite(hi[i]) || lo[i] > hi[i]) return false;
+    return true;
+  };
+  if (!bounds(p.v_lo, p.v_hi, 3) || !bounds(p.wrench_lo, p.wrench_hi, 6) ||
+      !bounds(&p.mass_scale_lo, &p.mass_scale_hi, 1) || !bounds(&p.mu_lo, &p.mu_hi, 1))
+    return fail(MPCQ_E_INVALID, "the scenario needs finite bounds with lo <= hi");
+  if ((p.robots & 1) && !(p.mass_scale_lo > 0)) return fail(MPCQ_E_INVALID, "the scenario needs mass_scale_lo > 0");
+  if ((p.robots & 2) && !(p.mu_lo > 0)) return fail(MPCQ_E_INVALID, "the scenario needs mu_lo > 0");
+  if (!(p.push_prob >= 0 && p.push_prob <= 1)) return fail(MPCQ_E_INVALID, "the scenario needs push_prob in [0, 1]");
+  const int32_t ints[] = {p.commands, p.cmd_start, p.cmd_ramp, p.cmd_period, p.pushes, p.push_first,
+                          p.push_period, p.push_jitter, p.push_ticks, p.push_flip, p.robots};
+  for (int32_t v : ints)
+    if (v < 0) return fail(MPCQ_E_INVALID, "the scenario's integer fields must be >= 0");
+  if (p.pushes && p.push_ticks < 1) return fail(MPCQ_E_INVALID, "the scenario's pushes need push_ticks >= 1");
+  if (p.cmd_period != 0 && (int64_t)p.cmd_period < (int64_t)p.cmd_start + p.cmd_ramp)
+    return fail(MPCQ_E_INVALID, "the scenario needs cmd_period == 0 or cmd_period >= cmd_start + cmd_ramp");
+  if (p.push_period != 0 && (int64_t)p.push_jitter + p.push_ticks > (int64_t)p.push_period)
+    return fail(MPCQ_E_INVALID, "the scenario needs push_period == 0 or push_jitter + push_ticks <= push_period");
+  if (p.robots > 3) return fail(MPCQ_E_INVALID, "the scenario's robots has bits beyond 3");
+  if (p.push_flip > 63) return fail(MPCQ_E_INVALID, "the scenario's push_flip has bits beyond 63");
+  for (int i = 0; i < 5; ++i)
+    if (p.reserved[i]) return fail(MPCQ_E_INVALID, "the scenario's reserved fields must be zero");
   return MPCQ_OK;
 }
 
@@ -924,6 +955,72 @@ int mpcq_monitor_step_batch(mpcq_ctx* c, const mpcq_monitor_params* mp, int64_t 
     a.totals = (unsigned long long*)totals; a.trace = trace;
   }
   HIP_TRY(mpcq::launch_monitor(P, a, c->stream));
+  if (!dev) return unstage(c, xs, NX);
+  if (!(flags & MPCQ_FLAG_ASYNC)) HIP_TRY(hipStreamSynchronize(c->stream));
+  return MPCQ_OK;
+}
+
+// Scenario: the reference's predefined joystick at MPC ticks (Joystick.py:82-83), no pushes,
+// the model's own robot.
+void mpcq_default_scenario_params(mpcq_scenario_params* sc) {
+  if (!sc) return;
+  memset(sc, 0, sizeof(*sc));
+  sc->commands = 1;
+  sc->v_lo[0] = sc->v_hi[0] = 1.0;
+  sc->cmd_start = 48;
+  sc->cmd_ramp = 175;
+  sc->push_prob = 1.0;
+  sc->push_ticks = 10;
+  sc->mass_scale_lo = sc->mass_scale_hi = 1.0;
+  sc->mu_lo = sc->mu_hi = 0.9;
+}
+
+int mpcq_scenario_step_batch(mpcq_ctx* c, const mpcq_scenario_params* sc, int64_t B, const int32_t* first,
+                             int all_first, int32_t* epoch, int32_t* tick, const mpcq_robot* base,
+                             const double* wrench_in, double* v_ref, double* push, double* wrench_out,
+                             mpcq_robot* robots_out, double* draw, uint32_t flags) {
+  mpcq_scenario_params P;
+  int rc = scenario_params(sc, &P);  // first: what is wrong with the parameters needs no context
+  if (rc) return rc;
+  rc = check_ctx(c, B);
+  if (rc) return rc;
+  if (!epoch || !tick || !v_ref || !push || !wrench_out)
+    return fail(MPCQ_E_INVALID, "epoch, tick, v_ref, push and wrench_out are required");
+  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
+  if (base && !dev) {
+    rc = check_robots(base, B);
+    if (rc) return rc;
+  }
+  if (B == 0) return MPCQ_OK;
+  DeviceGuard g(c->device);
+  mpcq::ScenarioArgs a{};
+  a.batch = B;
+  a.all_first = all_first != 0;
+  mpcq_default_robot(&c->p, &a.dflt);
+  const size_t b = (size_t)B;
+  enum { FI, EP, TI, BA, WI, VR, PU, WO, RO, DR, NX };
+  Xfer xs[NX] = {{first, nullptr, b * 4, nullptr},
+                 {epoch, epoch, b * 4, nullptr},
+                 {tick, tick, b * 4, nullptr},
+                 {base, nullptr, b * sizeof(mpcq_robot), nullptr},
+                 {wrench_in, nullptr, b * 48, nullptr},
+                 {nullptr, v_ref, b * 48, nullptr},
+                 {nullptr, push, b * 48, nullptr},
+                 {nullptr, wrench_out, b * 48, nullptr},
+                 {robots_out, robots_out, b * sizeof(mpcq_robot), nullptr},
+                 {draw, draw, b * 64, nullptr}};
+  if (!dev) {
+    rc = stage(c, xs, NX);
+    if (rc) return rc;
+    a.first = (const int32_t*)xs[FI].dev; a.epoch = (int32_t*)xs[EP].dev; a.tick = (int32_t*)xs[TI].dev;
+    a.base = (const mpcq_robot*)xs[BA].dev; a.wrench_in = (const double*)xs[WI].dev;
+    a.v_ref = (double*)xs[VR].dev; a.push = (double*)xs[PU].dev; a.wrench_out = (double*)xs[WO].dev;
+    a.robots_out = (mpcq_robot*)xs[RO].dev; a.draw = (double*)xs[DR].dev;
+  } else {
+    a.first = first; a.epoch = epoch; a.tick = tick; a.base = base; a.wrench_in = wrench_in;
+    a.v_ref = v_ref; a.push = push; a.wrench_out = wrench_out; a.robots_out = robots_out; a.draw = draw;
+  }
+  HIP_TRY(mpcq::launch_scenario(P, a, c->stream));
   if (!dev) return unstage(c, xs, NX);
   if (!(flags & MPCQ_FLAG_ASYNC)) HIP_TRY(hipStreamSynchronize(c->stream));
   return MPCQ_OK;

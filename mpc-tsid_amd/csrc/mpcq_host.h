@@ -83,5 +83,6 @@ int set_table(mpcq_ctx* c, RobotTable& t, int64_t count, const mpcq_robot* robot
 int swing_params(const mpcq_swing_params* sp, mpcq_swing_params* out);
 int plant_params(const mpcq_plant_params* pl, double dt_default, mpcq_plant_params* out);
 int monitor_params(const mpcq_monitor_params* mp, mpcq_monitor_params* out);
+int scenario_params(const mpcq_scenario_params* sc, mpcq_scenario_params* out);
 
 }  // namespace mpcq

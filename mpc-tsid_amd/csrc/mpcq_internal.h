@@ -281,6 +281,28 @@ struct MonitorArgs {
 };
 hipError_t launch_monitor(const mpcq_monitor_params& mp, const MonitorArgs& a, hipStream_t s);
 
+// Scenario stage (mpcq_scenario.hip); semantics and layouts in include/mpcq.h
+// (mpcq_scenario_step_batch, mpcq_session_enable_scenario).  One thread per robot.
+struct ScenarioArgs {
+  int64_t batch;
+  const int32_t* first;    // [B] or null: nonzero = a first tick
+  int all_first;           // every robot runs a first tick
+  // mpcq_session_enable_scenario's launch: the constants of the stored epoch and the tick's
+  // values at the stored tau, neither advanced
+  int init;
+  int32_t* epoch;          // [B] in/out
+  int32_t* tick;           // [B] in/out
+  const mpcq_robot* base;  // [B] or null: dflt
+  mpcq_robot dflt;
+  const double* wrench_in; // [B][6] or null: zeros
+  double* v_ref;           // [B][6]
+  double* push;            // [B][6]
+  double* wrench_out;      // [B][6]
+  mpcq_robot* robots_out;  // [B] or null
+  double* draw;            // [B][8] or null
+};
+hipError_t launch_scenario(const mpcq_scenario_params& sc, const ScenarioArgs& a, hipStream_t s);
+
 // Launchers (mpcq_engine.hip).  Return hipError_t.
 hipError_t launch_formulate(int N, const mpcq_params& p, const LaunchArgs& a, hipStream_t s);
 hipError_t launch_solve(int N, bool fused, const mpcq_params& p, const LaunchArgs& a, hipStream_t s);

@@ -2,8 +2,8 @@
 // sessions, per-robot state resident in HBM.
 //
 // A session's device arrays come in groups (alloc_group): the main one made by
-// mpcq_session_create, and one each for swing, plant and monitor, made when they are first
-// enabled.  A tick (session_tick) is a list of stages, each filling the argument struct of
+// mpcq_session_create, and one each for swing, plant, monitor and scenario, made when they are
+// first enabled.  A tick (session_tick) is a list of stages, each filling the argument struct of
 // its launch from the groups' arrays.  All numerics run in the HIP kernels.
 #include <math.h>
 #include <stdlib.h>
@@ -24,7 +24,7 @@ enum { SP_WARM_X = MPCQ_SV_COUNT, SP_PLAN_STATUS, SP_INFO, SP_IN_STATE, SP_IN_LF
 enum { PP_QW_PREV = MPCQ_PV_COUNT, PP_COUNT };
 
 // The arrays of one kind of id: MPCQ_SV_* (the swing slots are null until
-// mpcq_session_enable_swing), MPCQ_PV_*, MPCQ_MV_*.
+// mpcq_session_enable_swing), MPCQ_PV_*, MPCQ_MV_*, MPCQ_CV_*.
 struct Group {
   const char *kind, *enable;  // "<kind> array %d needs mpcq_session_enable_<enable>"
   int named;                  // the ids the _read / _write / _device_ptr entry points reach
@@ -44,14 +44,16 @@ struct mpcq_session {
   Group sv{"session", "swing", MPCQ_SV_COUNT};
   Group pv{"plant", "plant", MPCQ_PV_COUNT};      // made by the first enable_plant / set_wrench
   Group mv{"monitor", "monitor", MPCQ_MV_COUNT};  // made by the first enable_monitor
+  Group cv{"scenario", "scenario", MPCQ_CV_COUNT};  // made by the first enable_scenario
   void* swing_mem = nullptr;                      // MPCQ_SV_SWING_REF, _SWING_STATE, _FRAME
   bool have_order = false;  // MPCQ_SV_ORDER holds the next solve's order (longest previous first)
   bool use_order = true;    // MPCQ_DISPATCH_ORDER=0 turns it off (A/B timing only; results are identical)
   bool resets = false;      // mpcq_session_reset was called: from then on the ticks consult MPCQ_SV_FIRST
-  bool swing = false, plant = false, monitor = false;
+  bool swing = false, plant = false, monitor = false, scenario = false;
   mpcq_swing_params sp{};
   mpcq_plant_params pl{};
   mpcq_monitor_params mp{};
+  mpcq_scenario_params sc{};
   RobotTable robots;        // mpcq_session_set_robots (the session's own, not the context's)
   RobotTable plant_robots;  // mpcq_session_set_plant_robots
 };
@@ -186,6 +188,28 @@ int ensure_plant_mem(mpcq_session* s) {
   return alloc_group(s->ctx, "the plant arrays", PP_COUNT, nb, &s->pv.mem, s->pv.ptr, s->pv.bytes);
 }
 
+// The table of the robots the plant moves, or null (the context's params): the plant's own,
+// else the model's.
+const mpcq_robot* plant_table(const mpcq_session* s) {
+  return s->plant_robots.count ? s->plant_robots.dev : s->robots.count ? s->robots.dev : nullptr;
+}
+
+// The scenario launch: a tick's (first = MPCQ_SV_FIRST or null, all_first at k == 0), or with
+// init the one mpcq_session_enable_scenario enqueues.
+hipError_t enqueue_scenario(mpcq_session* s, const mpcq_scenario_params& sc, const int32_t* first, bool all_first,
+                            bool init) {
+  const Group& v = s->cv;
+  mpcq::ScenarioArgs a{};
+  a.batch = s->B; a.first = first; a.all_first = all_first; a.init = init;
+  a.epoch = v.i(MPCQ_CV_EPOCH); a.tick = v.i(MPCQ_CV_TICK);
+  a.base = plant_table(s);
+  mpcq_default_robot(&s->ctx->p, &a.dflt);
+  a.wrench_in = s->pv.mem ? s->pv.d(MPCQ_PV_WRENCH) : nullptr;
+  a.v_ref = v.d(MPCQ_CV_V_REF); a.push = v.d(MPCQ_CV_PUSH); a.wrench_out = v.d(MPCQ_CV_WRENCH);
+  a.robots_out = (mpcq_robot*)v.ptr[MPCQ_CV_ROBOTS]; a.draw = v.d(MPCQ_CV_DRAW);
+  return mpcq::launch_scenario(sc, a, s->ctx->stream);
+}
+
 }  // namespace
 
 extern "C" {
@@ -274,6 +298,7 @@ int mpcq_session_destroy(mpcq_session* s) {
     if (s->pv.mem) (void)hipFree(s->pv.mem);
     if (s->plant_robots.dev) (void)hipFree(s->plant_robots.dev);
     if (s->mv.mem) (void)hipFree(s->mv.mem);
+    if (s->cv.mem) (void)hipFree(s->cv.mem);
   }
   delete s;
   return MPCQ_OK;
@@ -412,6 +437,38 @@ int mpcq_session_disable_monitor(mpcq_session* s) {
   return MPCQ_OK;
 }
 
+int mpcq_session_enable_scenario(mpcq_session* s, const mpcq_scenario_params* sc) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  mpcq_scenario_params P;
+  int rc = scenario_params(sc, &P);
+  if (rc) return rc;
+  if (!s->cv.mem) {  // the arrays, zero; the launch gives every robot the draw of epoch 0
+    const size_t B = (size_t)s->B;
+    const size_t nb[MPCQ_CV_COUNT] = {B * 4, B * 4, B * 48, B * 48, B * 48, B * sizeof(mpcq_robot), B * 64};
+    DeviceGuard g(s->ctx->device);
+    Group cv = s->cv;
+    rc = alloc_group(s->ctx, "the scenario arrays", MPCQ_CV_COUNT, nb, &cv.mem, cv.ptr, cv.bytes);
+    if (rc) return rc;
+    s->cv = cv;
+    const hipError_t e = enqueue_scenario(s, P, nullptr, false, true);
+    if (e != hipSuccess) {
+      (void)hipStreamSynchronize(s->ctx->stream);
+      (void)hipFree(cv.mem);
+      s->cv = Group{"scenario", "scenario", MPCQ_CV_COUNT};
+      return fail(MPCQ_E_DEVICE, "initialising the scenario arrays failed: %s", hipGetErrorString(e));
+    }
+  }
+  s->sc = P;
+  s->scenario = true;
+  return MPCQ_OK;
+}
+
+int mpcq_session_disable_scenario(mpcq_session* s) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  s->scenario = false;
+  return MPCQ_OK;
+}
+
 }  // extern "C"
 
 namespace {
@@ -451,6 +508,14 @@ int tick_inputs(mpcq_session* s, const double* state, const double* l_feet, cons
   }
   t.first = s->resets ? v.i(MPCQ_SV_FIRST) : nullptr;
   t.first_k = t.k == 0 ? nullptr : t.first;
+  return MPCQ_OK;
+}
+
+// This tick's command, push and (on a first tick) true robots; it takes the first flags as
+// the planner will.
+int tick_scenario(mpcq_session* s, int k) {
+  const int32_t* first = s->resets && k != 0 ? s->sv.i(MPCQ_SV_FIRST) : nullptr;
+  HIP_TRY(enqueue_scenario(s, s->sc, first, k == 0, false));
   return MPCQ_OK;
 }
 
@@ -538,8 +603,10 @@ int tick_plant(mpcq_session* s, const Tick& t) {
   const Group& v = s->sv;
   mpcq::PlantArgs a{};
   a.batch = s->B;
-  a.state = t.state; a.fsteps = v.d(MPCQ_SV_FSTEPS); a.f = v.d(MPCQ_SV_F0); a.wrench = s->pv.d(MPCQ_PV_WRENCH);
-  a.robots = s->plant_robots.count ? s->plant_robots.dev : s->robots.count ? s->robots.dev : nullptr;
+  a.state = t.state; a.fsteps = v.d(MPCQ_SV_FSTEPS); a.f = v.d(MPCQ_SV_F0);
+  // a scenario's pushes ride on the user's wrench, its robots replace the table
+  a.wrench = s->scenario && s->sc.pushes ? s->cv.d(MPCQ_CV_WRENCH) : s->pv.d(MPCQ_PV_WRENCH);
+  a.robots = s->scenario && s->sc.robots ? (const mpcq_robot*)s->cv.ptr[MPCQ_CV_ROBOTS] : plant_table(s);
   mpcq_default_robot(&c->p, &a.dflt);
   a.state_out = s->pv.d(MPCQ_PV_STATE_END); a.f_eff = s->pv.d(MPCQ_PV_F_EFF);
   a.tail = 1;
@@ -585,11 +652,13 @@ int tick_swing(mpcq_session* s) {
   return MPCQ_OK;
 }
 
-// One tick: its stages in stream order.
+// One tick: its stages in stream order ([scenario] -> planner -> solve -> retrieve -> [plant]
+// -> [monitor] -> order -> [swing] -> [auto-reset]).
 int session_tick(mpcq_session* s, int k, const double* state, const double* l_feet, const double* v_ref,
                  const int32_t* reduced, uint32_t flags, double* trace) {
   if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
-  if (!v_ref) return fail(MPCQ_E_INVALID, "v_ref is required");
+  if (!v_ref && !(s->scenario && s->sc.commands))
+    return fail(MPCQ_E_INVALID, "v_ref is required (without a scenario that commands)");
   if (k < 0) return fail(MPCQ_E_INVALID, "k must be >= 0");
   mpcq_ctx* c = s->ctx;
   DeviceGuard g(c->device);
@@ -597,7 +666,9 @@ int session_tick(mpcq_session* s, int k, const double* state, const double* l_fe
   Tick t{};
   t.k = k;
   t.trace = trace;
-  int rc = tick_inputs(s, state, l_feet, v_ref, reduced, dev, t);
+  int rc = s->scenario ? tick_scenario(s, k) : MPCQ_OK;
+  if (!rc) rc = tick_inputs(s, state, l_feet, v_ref, reduced, dev, t);
+  if (!rc && !v_ref) t.v_ref = s->cv.d(MPCQ_CV_V_REF);
   if (!rc) rc = tick_plan(s, t);
   if (!rc) rc = tick_solve(s, t);
   if (!rc) rc = tick_retrieve(s, t);
@@ -626,14 +697,16 @@ int mpcq_session_run(mpcq_session* s, int k0, int n_ticks, const double* v_ref, 
                      uint32_t flags) {
   if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
   if (!(flags & MPCQ_FLAG_DEVICE_PTRS)) return fail(MPCQ_E_INVALID, "mpcq_session_run needs MPCQ_FLAG_DEVICE_PTRS");
-  if (!v_ref || v_ref_ticks < 1) return fail(MPCQ_E_INVALID, "v_ref [v_ref_ticks][B][6] with v_ref_ticks >= 1 is required");
+  if (!v_ref && !(s->scenario && s->sc.commands))
+    return fail(MPCQ_E_INVALID, "v_ref is required (without a scenario that commands)");
+  if (v_ref && v_ref_ticks < 1) return fail(MPCQ_E_INVALID, "v_ref [v_ref_ticks][B][6] needs v_ref_ticks >= 1");
   if (k0 < 0 || n_ticks < 1) return fail(MPCQ_E_INVALID, "need k0 >= 0 and n_ticks >= 1");
   if (k0 > INT32_MAX - n_ticks) return fail(MPCQ_E_INVALID, "k0 + n_ticks overflows");
   if (trace && !s->monitor) return fail(MPCQ_E_INVALID, "a trace needs mpcq_session_enable_monitor");
   const size_t B = (size_t)s->B;
   for (int t = 0; t < n_ticks; ++t) {
     const int row = t < v_ref_ticks ? t : v_ref_ticks - 1;
-    const int rc = session_tick(s, k0 + t, nullptr, nullptr, v_ref + (size_t)row * B * 6, nullptr,
+    const int rc = session_tick(s, k0 + t, nullptr, nullptr, v_ref ? v_ref + (size_t)row * B * 6 : nullptr, nullptr,
                                 MPCQ_FLAG_DEVICE_PTRS | MPCQ_FLAG_ASYNC,
                                 trace ? trace + (size_t)t * B * MPCQ_TRACE : nullptr);
     if (rc) {
@@ -683,6 +756,10 @@ int mpcq_session_monitor_read(mpcq_session* s, int what, void* dst, uint32_t fla
   return group_read(s, &mpcq_session::mv, what, dst, flags);
 }
 
+int mpcq_session_scenario_read(mpcq_session* s, int what, void* dst, uint32_t flags) {
+  return group_read(s, &mpcq_session::cv, what, dst, flags);
+}
+
 int mpcq_session_device_ptr(mpcq_session* s, int what, void** out) {
   return group_device_ptr(s, &mpcq_session::sv, what, out);
 }
@@ -693,6 +770,10 @@ int mpcq_session_plant_device_ptr(mpcq_session* s, int what, void** out) {
 
 int mpcq_session_monitor_device_ptr(mpcq_session* s, int what, void** out) {
   return group_device_ptr(s, &mpcq_session::mv, what, out);
+}
+
+int mpcq_session_scenario_device_ptr(mpcq_session* s, int what, void** out) {
+  return group_device_ptr(s, &mpcq_session::cv, what, out);
 }
 
 int mpcq_session_write(mpcq_session* s, int what, const void* src, uint32_t flags) {

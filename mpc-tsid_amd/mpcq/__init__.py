@@ -16,6 +16,9 @@ Public surface:
   Monitor           episodes on the device: per-robot termination, episode statistics, batch
                     totals (Session.enable_monitor: auto-reset; Session.run: whole rollouts
                     with a per-tick trace)
+  Scenario          per-episode random commands, pushes and payloads drawn on the device from a
+                    counter-based generator (Session.enable_scenario); mpcq.scenario restates
+                    the draws on the host, bit for bit
   synth             seeded synthetic inputs shaped like FootstepPlanner's
 """
 from . import synth  # noqa: F401
@@ -32,10 +35,14 @@ from ._lib import (FLAG_ASYNC, FLAG_DEVICE_PTRS, FLAG_ORDER_BY_CLASS, MODE_SETUP
                    Robot, default_robot,
                    PLANT_MODEL, PLANT_RIGID, PV_F_EFF, PV_STATE_END, PV_WRENCH, PlantParams, default_plant_params,
                    DONE_HEIGHT, DONE_NONFINITE, DONE_SOLVER, DONE_TILT, DONE_TIMEOUT, MV_DONE, MV_EP, MV_EP_TICKS,
-                   MV_EPISODES, MV_LAST, MV_TOTALS, TRACE, MonitorParams, default_monitor_params)
+                   MV_EPISODES, MV_LAST, MV_TOTALS, TRACE, MonitorParams, default_monitor_params,
+                   CV_DRAW, CV_EPOCH, CV_PUSH, CV_ROBOTS, CV_TICK, CV_V_REF, CV_WRENCH, ScenarioParams,
+                   default_scenario_params)
 from .engine import ROBOT_DTYPE, Engine, dims, pattern, robots  # noqa: F401
 from .monitor import Monitor  # noqa: F401
 from .plant import Plant  # noqa: F401
+from . import scenario  # noqa: F401
+from .scenario import Scenario  # noqa: F401
 from .session import Session  # noqa: F401
 from .swing import Swing  # noqa: F401
 

@@ -73,6 +73,8 @@ PV_STATE_END, PV_F_EFF, PV_WRENCH = 0, 1, 2
 DONE_NONFINITE, DONE_TILT, DONE_HEIGHT, DONE_SOLVER, DONE_TIMEOUT = 1, 2, 4, 8, 16
 MV_DONE, MV_EP, MV_EP_TICKS, MV_EPISODES, MV_LAST, MV_TOTALS = range(6)
 TRACE = 16
+# the scenario stage: a session's scenario arrays (MPCQ_CV_*)
+CV_EPOCH, CV_TICK, CV_V_REF, CV_PUSH, CV_WRENCH, CV_ROBOTS, CV_DRAW = range(7)
 
 EXPORTS = ("mpcq_abi_version", "mpcq_default_params", "mpcq_dims", "mpcq_pattern",
            "mpcq_supported_horizons", "mpcq_last_error", "mpcq_create", "mpcq_destroy",
@@ -93,7 +95,9 @@ EXPORTS = ("mpcq_abi_version", "mpcq_default_params", "mpcq_dims", "mpcq_pattern
            "mpcq_session_plant_read", "mpcq_session_plant_device_ptr",
            "mpcq_default_monitor_params", "mpcq_monitor_step_batch", "mpcq_session_enable_monitor",
            "mpcq_session_disable_monitor", "mpcq_session_monitor_read", "mpcq_session_monitor_device_ptr",
-           "mpcq_session_run")
+           "mpcq_session_run",
+           "mpcq_default_scenario_params", "mpcq_scenario_step_batch", "mpcq_session_enable_scenario",
+           "mpcq_session_disable_scenario", "mpcq_session_scenario_read", "mpcq_session_scenario_device_ptr")
 
 
 class MpcqError(RuntimeError):
@@ -197,6 +201,35 @@ class MonitorParams(C.Structure):
         ("max_ticks", C.c_int32),
         ("auto_reset", C.c_int32),
         ("reserved", C.c_int32 * 10),
+    ]
+
+
+class ScenarioParams(C.Structure):
+    """struct mpcq_scenario_params (include/mpcq.h)."""
+
+    _fields_ = [
+        ("seed", C.c_uint64),
+        ("v_lo", C.c_double * 3),
+        ("v_hi", C.c_double * 3),
+        ("wrench_lo", C.c_double * 6),
+        ("wrench_hi", C.c_double * 6),
+        ("push_prob", C.c_double),
+        ("mass_scale_lo", C.c_double),
+        ("mass_scale_hi", C.c_double),
+        ("mu_lo", C.c_double),
+        ("mu_hi", C.c_double),
+        ("commands", C.c_int32),
+        ("cmd_start", C.c_int32),
+        ("cmd_ramp", C.c_int32),
+        ("cmd_period", C.c_int32),
+        ("pushes", C.c_int32),
+        ("push_first", C.c_int32),
+        ("push_period", C.c_int32),
+        ("push_jitter", C.c_int32),
+        ("push_ticks", C.c_int32),
+        ("push_flip", C.c_int32),
+        ("robots", C.c_int32),
+        ("reserved", C.c_int32 * 5),
     ]
 
 
@@ -339,6 +372,17 @@ def lib():
     for name in ("mpcq_monitor_step_batch", "mpcq_session_enable_monitor", "mpcq_session_disable_monitor",
                  "mpcq_session_monitor_read", "mpcq_session_monitor_device_ptr", "mpcq_session_run"):
         getattr(L, name).restype = C.c_int
+    CP = C.POINTER(ScenarioParams)
+    L.mpcq_default_scenario_params.argtypes = [CP]
+    L.mpcq_default_scenario_params.restype = None
+    L.mpcq_scenario_step_batch.argtypes = [vp, CP, C.c_int64, vp, C.c_int] + [vp] * 9 + [C.c_uint32]
+    L.mpcq_session_enable_scenario.argtypes = [vp, CP]
+    L.mpcq_session_disable_scenario.argtypes = [vp]
+    L.mpcq_session_scenario_read.argtypes = [vp, C.c_int, vp, C.c_uint32]
+    L.mpcq_session_scenario_device_ptr.argtypes = [vp, C.c_int, C.POINTER(vp)]
+    for name in ("mpcq_scenario_step_batch", "mpcq_session_enable_scenario", "mpcq_session_disable_scenario",
+                 "mpcq_session_scenario_read", "mpcq_session_scenario_device_ptr"):
+        getattr(L, name).restype = C.c_int
     for name in ("mpcq_debug_class_table_read", "mpcq_debug_class_table_write", "mpcq_debug_class_order",
                  "mpcq_debug_class_learn", "mpcq_debug_suspended", "mpcq_debug_session_order",
                  "mpcq_debug_last_dispatch"):
@@ -409,6 +453,23 @@ def default_monitor_params(**overrides) -> MonitorParams:
     for k, v in overrides.items():
         if not hasattr(p, k):
             raise AttributeError(f"unknown monitor parameter {k}")
+        setattr(p, k, v)
+    return p
+
+
+def default_scenario_params(**overrides) -> ScenarioParams:
+    """mpcq_default_scenario_params; an array field takes a sequence of its length."""
+    p = ScenarioParams()
+    lib().mpcq_default_scenario_params(C.byref(p))
+    for k, v in overrides.items():
+        if not hasattr(p, k):
+            raise AttributeError(f"unknown scenario parameter {k}")
+        cur = getattr(p, k)
+        if hasattr(cur, "__len__"):
+            v = list(v)
+            if len(v) != len(cur):
+                raise ValueError(f"scenario parameter {k} takes {len(cur)} values")
+            v = type(cur)(*v)
         setattr(p, k, v)
     return p
 

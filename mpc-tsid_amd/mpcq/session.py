@@ -57,6 +57,7 @@ class Session:
         self.swing_params = None
         self.plant_params = None
         self.monitor_params = None
+        self.scenario_params = None
 
     def enable_swing(self, params: L.SwingParams | None = None):
         """Opt in to the swing-foot references: every later tick appends one swing launch over
@@ -177,6 +178,50 @@ class Session:
         self.engine._call("mpcq_session_monitor_device_ptr", self._h, what, C.byref(out))
         return int(out.value or 0)
 
+    # ------------------------------------------------------------------ scenarios
+    def enable_scenario(self, params: L.ScenarioParams | None = None, **overrides):
+        """Opt in to scenarios: every later tick starts with the scenario launch, which gives
+        each robot, for each of its episodes, a command profile relative to the episode's start
+        (CV_V_REF: with ``commands`` set, ``tick`` / ``run`` take ``v_ref=None``), push windows
+        on top of ``set_wrench`` (CV_PUSH, CV_WRENCH) and its own true mass and friction
+        (CV_ROBOTS, CV_DRAW), all reproducible on the host from (seed, robot, epoch) with
+        ``mpcq.scenario``; pushes and robots act through ``enable_plant``.  ``params`` None: the
+        defaults (the reference's predefined joystick), with ``overrides``.  Calling it again
+        replaces the parameters and keeps the arrays."""
+        if params is not None and overrides:
+            raise ValueError("pass params or overrides, not both")
+        sc = params or L.default_scenario_params(**overrides)
+        self.engine._call("mpcq_session_enable_scenario", self._h, C.byref(sc))
+        self.scenario_params = sc
+
+    def disable_scenario(self):
+        """The ticks after it run without the scenario launch: the plant is back on the user's
+        wrench and tables, ``v_ref=None`` is an error again; the arrays stay."""
+        self.engine._call("mpcq_session_disable_scenario", self._h)
+        self.scenario_params = None
+
+    def _scenario_shape(self, what: int):
+        B = self.batch
+        shapes = {L.CV_EPOCH: ((B,), np.int32), L.CV_TICK: ((B,), np.int32), L.CV_V_REF: ((B, 6), np.float64),
+                  L.CV_PUSH: ((B, 6), np.float64), L.CV_WRENCH: ((B, 6), np.float64), L.CV_ROBOTS: ((B,), ROBOT_DTYPE),
+                  L.CV_DRAW: ((B, 8), np.float64)}
+        if what not in shapes:
+            raise L.MpcqError(L.E_INVALID, f"unknown scenario array {what}")
+        return shapes[what]
+
+    def scenario_read(self, what: int):
+        """CV_EPOCH (B,) int32, CV_TICK (B,) int32, CV_V_REF / CV_PUSH / CV_WRENCH (B, 6),
+        CV_ROBOTS (B,) ROBOT_DTYPE or CV_DRAW (B, 8)."""
+        shape, dt = self._scenario_shape(what)
+        out = np.empty(shape, dt)
+        self.engine._call("mpcq_session_scenario_read", self._h, what, C.c_void_p(out.ctypes.data), 0)
+        return out
+
+    def scenario_device_ptr(self, what: int) -> int:
+        out = C.c_void_p()
+        self.engine._call("mpcq_session_scenario_device_ptr", self._h, what, C.byref(out))
+        return int(out.value or 0)
+
     # ------------------------------------------------------------------ rollouts
     def _to_device(self, a):
         """A host array on the engine's device through torch: (the tensor, which owns the memory,
@@ -194,25 +239,30 @@ class Session:
     def run(self, v_ref, n_ticks: int, trace: bool = False, k: int | None = None):
         """``n_ticks`` ticks of the virtual robot (or the plant) enqueued in one call.  ``v_ref``
         (host) is (6,) or (B, 6) for every tick, or a schedule (T, B, 6) whose last row is held
-        once the ticks outrun it.  ``trace=True`` (needs ``enable_monitor``) returns the
-        monitor's per-tick rows (n_ticks, B, TRACE), otherwise None."""
+        once the ticks outrun it; None: the commands of ``enable_scenario``.  ``trace=True``
+        (needs ``enable_monitor``) returns the monitor's per-tick rows (n_ticks, B, TRACE),
+        otherwise None."""
         B = self.batch
         n_ticks = int(n_ticks)
-        v = np.asarray(v_ref, np.float64)
-        if v.ndim < 3:
-            v = np.broadcast_to(v, (1, B, 6))
-        elif v.ndim != 3 or v.shape[0] < 1:
-            raise ValueError(f"v_ref must be (6,), ({B}, 6) or (T, {B}, 6); got {v.shape}")
-        v = np.ascontiguousarray(np.broadcast_to(v, (v.shape[0], B, 6)))
-        keep, v_ptr = self._to_device(v)
+        keep, v_ptr, v_ticks = None, 0, 1
+        if v_ref is not None:
+            v = np.asarray(v_ref, np.float64)
+            if v.ndim < 3:
+                v = np.broadcast_to(v, (1, B, 6))
+            elif v.ndim != 3 or v.shape[0] < 1:
+                raise ValueError(f"v_ref must be (6,), ({B}, 6) or (T, {B}, 6); got {v.shape}")
+            v = np.ascontiguousarray(np.broadcast_to(v, (v.shape[0], B, 6)))
+            keep, v_ptr = self._to_device(v)
+            v_ticks = v.shape[0]
         tr, tr_ptr, fetch = self._new_device((max(n_ticks, 0), B, L.TRACE)) if trace else (None, 0, None)
-        self.run_device(v_ptr, n_ticks, v_ref_ticks=v.shape[0], trace_ptr=tr_ptr, k=k, asynchronous=False)
+        self.run_device(v_ptr, n_ticks, v_ref_ticks=v_ticks, trace_ptr=tr_ptr, k=k, asynchronous=False)
         del keep
         return fetch() if trace else None
 
     def run_device(self, v_ref_ptr: int, n_ticks: int, v_ref_ticks: int = 1, trace_ptr: int = 0,
                    k: int | None = None, asynchronous: bool = True):
-        """``run`` on device arrays: v_ref (v_ref_ticks, B, 6), trace (n_ticks, B, TRACE) or 0."""
+        """``run`` on device arrays: v_ref (v_ref_ticks, B, 6) or 0 (the commands of
+        ``enable_scenario``), trace (n_ticks, B, TRACE) or 0."""
         k = self.k if k is None else int(k)
         v = lambda q: C.c_void_p(q) if q else None  # noqa: E731
         flags = L.FLAG_DEVICE_PTRS | (L.FLAG_ASYNC if asynchronous else 0)
@@ -243,8 +293,9 @@ class Session:
         a = np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype), shape))
         return a
 
-    def tick(self, v_ref, state=None, l_feet=None, reduced=None, k: int | None = None):
-        """One control tick for every robot (host arrays); returns f_applied (B, 12)."""
+    def tick(self, v_ref=None, state=None, l_feet=None, reduced=None, k: int | None = None):
+        """One control tick for every robot (host arrays); returns f_applied (B, 12).  ``v_ref``
+        None: the commands of ``enable_scenario``."""
         B = self.batch
         k = self.k if k is None else int(k)
         vr = self._in(v_ref, (B, 6))
@@ -258,7 +309,8 @@ class Session:
 
     def tick_device(self, v_ref_ptr: int, state_ptr: int = 0, l_feet_ptr: int = 0, reduced_ptr: int = 0,
                     k: int | None = None, asynchronous: bool = True):
-        """One tick on device-resident inputs (pointers on the engine's device)."""
+        """One tick on device-resident inputs (pointers on the engine's device; v_ref 0: the
+        commands of ``enable_scenario``)."""
         k = self.k if k is None else int(k)
         v = lambda q: C.c_void_p(q) if q else None  # noqa: E731
         flags = L.FLAG_DEVICE_PTRS | (L.FLAG_ASYNC if asynchronous else 0)
