@@ -632,9 +632,9 @@ static int solve_common(mpcq_ctx* c, int64_t B, bool fused, const double* xref, 
   // farthest from convergence (the iterations left, extrapolated from the residuals' decay)
   // first, and runs them to their end.  (Re-slicing the second launch too was slower: C3 39.0 k
   // against 44.1 k QP/s at 1200, profiles/r06r_*.)
-  // Only where the engine unit of this horizon holds the suspend / resume code (slice_supported:
-  // beyond 16 stages, or a -DMPCQ_SLICE16 build): a unit without it ignores the count on the
-  // device and would take the resumed launch's unwritten list for instance indices.
+  // Only where the engine holds the suspend / resume code (slice_supported: beyond 16 stages):
+  // a unit without it ignores the count on the device and would take the resumed launch's
+  // unwritten list for instance indices.
   const bool sliced = c->slice_iters > 0 && c->slice_iters < c->p.max_iter && mpcq::slice_supported(N);
   c->last_B = B;
   c->last_by_class = by_class;

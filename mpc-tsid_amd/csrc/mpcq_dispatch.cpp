@@ -14,22 +14,9 @@
 namespace mpcq {
 
 #define MPCQ_DECL(NN) \
-  hipError_t engine_launch_n##NN(bool fused, bool solve, const mpcq_params& p, const LaunchArgs& a, hipStream_t s); \
-  bool engine_slice_n##NN();
+  hipError_t engine_launch_n##NN(bool fused, bool solve, const mpcq_params& p, const LaunchArgs& a, hipStream_t s);
 MPCQ_HORIZONS(MPCQ_DECL)
 #undef MPCQ_DECL
-
-// Sliced solves: what horizon N's unit was compiled with (its kSlice<N>: beyond 16 stages, or
-// every horizon in a -DMPCQ_SLICE16 build).  A unit without the code ignores slice_iters,
-// resume and batch_dev, so the host must not run its two-launch path on it.
-bool slice_supported(int N) {
-#define MPCQ_CASE(NN) case NN: return engine_slice_n##NN();
-  switch (N) {
-    MPCQ_HORIZONS(MPCQ_CASE)
-    default: return false;
-  }
-#undef MPCQ_CASE
-}
 
 bool horizon_supported(int N) {
 #define MPCQ_CASE(NN) case NN:

@@ -112,14 +112,11 @@ constexpr int kRows = (N + 3) & ~3;
 // instance per CU there, so a long solve dispatched in a late round ends the launch late
 // (DESIGN.md section 8).  Up to 16 stages two instances share a CU and slicing does not
 // shorten the modelled launch (section 8b item 9): the code is compiled out and the ADMM
-// loop's allocation stays the unsliced one.
-// (-DMPCQ_SLICE16: at every horizon -- an experiment)
+// loop's allocation stays the unsliced one.  Slicing at 16 stages was built and measured
+// (round 6): slower than unsliced, as the model said, and removed; patch in
+// tools/attic/engine_variants_round6.patch, measurements in DESIGN.md section 8 item 1b.
 template <int N>
-#ifdef MPCQ_SLICE16
-constexpr bool kSlice = true;
-#else
-constexpr bool kSlice = N > 16;
-#endif
+constexpr bool kSlice = slice_supported(N);
 
 // ---------------------------------------------------------------------------
 // cross-lane helpers
@@ -690,81 +687,25 @@ __host__ __device__ constexpr int SLOT(int q) { return GS * q + (q > N / 2 ? kSl
 // termination check deferred into the next iteration) were measured slower and removed
 // in round 5; their code is kept as a patch, tools/attic/engine_cr_dc_round4.patch, and
 // their measurements in DESIGN.md section 8 (round 4) items 3-4.
+// Four more were measured slower and removed later, their code kept as
+// tools/attic/engine_variants_round6.patch: three or four 16-stage instances per CU in the
+// beyond-32-stage layout (round 5: C2 62.0 k / 35.3 k against 127.6 k QP/s; DESIGN.md section
+// 8b item 4), the explicit state-system inverse at 16 stages (round 5: 1.92 against 1.85 us per
+// iteration and one instance per CU, C2 86 k against 126 k QP/s; section 8b item 6), the
+// nested-dissection state solve (round 6: N = 32 2.976 against 2.875 us per iteration; section
+// 8 item 1) and slicing at 16 stages (kSlice above).
 // Horizons beyond 32 stages do not fit a CU's LDS (N = 48: 236 KB): S^{-1}, F W and
 // R^{-1} Q move to a per-instance global workspace (LaunchArgs::work, work_doubles(N)
 // doubles per instance, L2-resident), the rest stays in LDS (N = 48: 140 KB).
-// Occupancy experiment (round 5, -DMPCQ_OCC16=3 or 4): the 16-stage kernel with the
-// beyond-32-stage layout (S^{-1}, R^{-1} Q and the scaled constraint values in the global
-// workspace, the split sweep) and __launch_bounds__(..., 3 / 4), so that three or four
-// instances share a CU (LDS 39.5 KB; 168 / 128 VGPRs).  Not the default.
-#ifdef MPCQ_OCC16
 template <int N>
-constexpr int kOcc = N == 16 ? MPCQ_OCC16 : 2;
-#else
-template <int N>
-constexpr int kOcc = 2;
-#endif
-template <int N>
-constexpr bool kBig = N > 32 || kOcc<N> > 2;
+constexpr bool kBig = N > 32;
 // F W stays in LDS at every N (the ADMM loop reads it every iteration: from L2 at
 // N = 48 it cost the right-hand-side phase ~14 k cycles per iteration, r03d
 // stamps); beyond 49 stages the scaled constraint values (126 N - 18 doubles) leave
 // LDS instead (N = 64: 197 KB with them, 133 KB without); the engine reads them
 // through the same accessors, the stage-parallel phases from L2.
-// The nested-dissection state solve (round 6, nd_layout in mpcq_internal.h: N = 32).  The
-// state system (block tridiagonal, 12 x 12 blocks) is split at the separator stage s = N/2
-// into A = stages 0..s-1 and B = s+1..N-1; each half is factored two-ended on its own, and
-// the ADMM loop sweeps A on wave 0 and B on wave 1 at the same time (half the depth of the
-// whole-horizon sweep), then solves for the separator's states and corrects both halves by
-// the stored spikes W_k = K_A^{-1}[k, s-1] L_s' (k in A) / K_B^{-1}[k, s+1] L_{s+1} (k in B):
-//   z = K_A^{-1} b_A, K_B^{-1} b_B      x_s = Sigma^{-1} b_s + P z_{s-1} + Q z_{s+1}
-//   x_k = z_k - W_k x_s                 Sigma = D_s - L_s W_{s-1} - L_{s+1}' W_{s+1}
-//   P = -Sigma^{-1} L_s, Q = -Sigma^{-1} L_{s+1}'
-// The spikes (N x 144 doubles) take the LDS the scaled constraint values leave (they move
-// to the workspace, kAbG) with F W at the 72-double stride.
 template <int N>
-constexpr bool kND = nd_layout(N);
-template <int N>
-constexpr bool kAbG = N > 49 || kOcc<N> > 2 || kND<N>;
-// (kND) the halves: A = stages 0..NDS-1, the separator NDS = N/2, B = NDS+1..N-1 (NDB stages).
-// Both halves are swept as NDS-stage systems by one code path: B's sweep carries a phantom
-// stage after its last (local stage NDB: zero right-hand side, zero coupling, zero inverse
-// slot), which it steps through in parallel with A's real one and which leaves B's solution
-// unchanged (its bottom chain starts at the phantom with v = 0).
-template <int N> constexpr int NDS = N / 2;
-template <int N> constexpr int NDB = N - 1 - N / 2;  // B's real stages (A's: NDS)
-// Sweep slots of stage k's right-hand side / w (bo, na, yv) and of its states X_{k+1} (xs).
-// Whole-horizon sweep: SIG<N>(k) / SIGX<N>(k+1).  kND: each half in its own step-ordered
-// slots (SIG / SIGX of an NDS-stage system), A's first, then B's (B's phantom at
-// NDS + SIG<NDS>(NDB)), the separator's last (right-hand side slot N, states slot N+1; B's
-// slots start at NDS so that its local X_0 -- the separator, which B's sweep never writes --
-// would be A's slot NDS).
-template <int N>
-__device__ __forceinline__ int RSL(int k) {
-  if constexpr (kND<N>) {
-    constexpr int S = NDS<N>;
-    return k < S ? SIG<S>(k) : (k == S ? N : S + SIG<S>(k - S - 1));
-  } else {
-    return SIG<N>(k);
-  }
-}
-template <int N>
-__device__ __forceinline__ int XSL(int k) {
-  if constexpr (kND<N>) {
-    constexpr int S = NDS<N>;
-    return k < S ? SIGX<S>(k + 1) : (k == S ? N + 1 : S + SIGX<S>(k - S));
-  } else {
-    return SIGX<N>(k + 1);
-  }
-}
-// (kND) GH / Sm offset of half B's slots: after A's (SLOT<NDS>'s bottom shift included);
-// B's phantom's slot (its zero H coupling in GH, its zero inverse in Sm) and right-hand side slot
-template <int N> constexpr int kGhB = GS * NDS<N> + 2;
-template <int N> constexpr int kPhSlot = kGhB<N> + SLOT<NDS<N>>(SIG<NDS<N>>(NDB<N>));
-template <int N> constexpr int kPhRhs = NDS<N> + SIG<NDS<N>>(NDB<N>);
-// (kND) stage k's spike block (k != NDS)
-template <int N>
-__device__ __forceinline__ int WSI(int k) { return k < NDS<N> ? k : k - 1; }
+constexpr bool kAbG = N > 49;
 // Beyond 48 stages (13-16 waves: 128 VGPRs) the F_k row is read from the workspace in
 // the loop and the z update's constants are batch-loaded from private memory instead
 // of being held; from 33 to 48 stages (168 VGPRs) holding them is faster.  Measured at
@@ -799,8 +740,8 @@ template <int N> constexpr bool kLagOut = N <= 48;
 // x 3, stages 0 mod 16 units apart) the twelve rows of each group land in distinct banks.
 // Up to 32 stages, where the LDS has the 24 N doubles (N = 16: 80,048 B, still two
 // instances per CU).
-template <int N, bool KI = false>
-constexpr int kFWS = (!kBig<N> && !KI && !kND<N>) ? 96 : 72;  // (kKI: the LDS goes to Z's columns; kND: to the spikes)
+template <int N>
+constexpr int kFWS = kBig<N> ? 72 : 96;
 // Up to 16 stages the ADMM loop's exit status goes through LDS (Smem::flag[4]) instead of
 // a register carried across the loop: the N = 16 kernel then spills 27 instead of 43
 // VGPRs (scratch 256 -> 224 B per lane) and its C2 HBM traffic falls 127 -> 88 MB per
@@ -818,81 +759,15 @@ constexpr bool kXstLds = N <= 16;
 // us alone, 19.7 -> 21.2 at 256 in flight, r05v): there the status is carried as in round 4.
 template <int N>
 constexpr bool kXstRe = !kXstLds<N> && N <= 48;
-// ---- The explicit state-system inverse (kKI, round 5) ------------------------------
-// At 16 stages the ADMM loop solves the state system K_s x = r (192 x 192, block
-// tridiagonal) with an explicit inverse Z = K_s^{-1} instead of the two-ended sweep: one
-// dense matrix-vector product spread over every wave (no serial chain of N/2 dependent
-// 12 x 12 steps on one wave).  Z is formed once per factorisation from the sweep's own
-// factors (G / H / S^{-1} / M^{-1}): the sweep run on the identity's columns, 16 columns
-// at a time as 16 x 16 x 12 products on v_mfma_f64_16x16x4_f64, both chains of a tile in
-// one wave.  The workgroup doubles to eight waves (one instance per CU, 256 VGPRs): waves
-// 0-3 hold the stages as before, waves 4-7 ("helpers") hold 138 of Z's 192 columns in
-// registers (105 doubles per lane); the other 54 columns sit in LDS (KV) and waves 0-3
-// multiply them.  The helpers run the stage waves' barrier sequence with no stage work
-// (factor / checks with role std::true_type) and take part only in the formation and the
-// product.  The oracle's explicit-inverse restatement (full K^{-1} on the C2 and a mixed
-// 4096-instance batch) kept statuses and iteration counts identical to its factored solve,
-// forces within 1.5e-9.
-// Measured and NOT the default (round 5, profiles/r05b_*, r05e_*): parity green on the GPU
-// suite (79/79, statuses and iterations = the oracle's), but 1.92 us per iteration alone
-// against the sweep's 1.85, and one instance per CU instead of two: C2 86 k, C4 104 k, C5 135 k
-// QP/s against 126 k / 222 k / 285 k.  The product is 36,864 FMAs per iteration (ten times
-// the sweep's) and its FP64 issue, not a serial chain, then bounds the iteration; the stage
-// waves' own instruction stream (right-hand sides, forces, update: ~250 instructions) stays
-// on the critical path either way.  Build with -DMPCQ_KINV (make variants compiles it).
-#ifdef MPCQ_KINV
-template <int N>
-constexpr bool kKinv = N == 16;
-#else
-template <int N>
-constexpr bool kKinv = false;
-#endif
-template <int N, bool SOLVE, bool POLISH>
-constexpr bool kKI = kKinv<N> && SOLVE && !POLISH;
-template <int N>
-struct KinvLay {
-  static constexpr int R = 12 * N;             // states (rows / columns of Z)
-  static constexpr int KVS = R + 1;            // column stride of KV (odd: conflict-free columns)
-  static constexpr int HC = 34;                // helper register columns (per lane: rows l, l+64, l+128)
-  static constexpr int SC = 14;                // stage wave LDS columns
-  static constexpr int SP0 = 4 * HC, SPC = R - SP0;  // the LDS part: columns 136..191
-  // helper h's columns [hc0, hc0 + hcn), stage wave s's [sc0, sc0 + scn)
-  __host__ __device__ static constexpr int hc0(int h) { return HC * h; }
-  __host__ __device__ static constexpr int hcn(int) { return HC; }
-  __host__ __device__ static constexpr int sc0(int s_) { return SP0 + SC * s_; }
-  __host__ __device__ static constexpr int scn(int) { return SC; }
-  // formation passes: columns [pc0, pc0 + pcn) staged in KV (the last pass is KV's own part)
-  static constexpr int NPASS = 4;
-  __host__ __device__ static constexpr int pc0(int q) { return q < 3 ? 48 * q : SP0; }
-  __host__ __device__ static constexpr int pcn(int q) { return q < 2 ? 48 : (q == 2 ? SP0 - 96 : SPC); }
-};
-static_assert(KinvLay<16>::hc0(3) + KinvLay<16>::hcn(3) == KinvLay<16>::SP0 &&
-                  KinvLay<16>::sc0(3) + KinvLay<16>::scn(3) == KinvLay<16>::R && KinvLay<16>::pcn(3) <= 64 &&
-                  KinvLay<16>::pc0(2) + KinvLay<16>::pcn(2) == KinvLay<16>::SP0 && KinvLay<16>::pcn(3) <= 56 &&
-                  KinvLay<16>::hc0(3) + 47 < KinvLay<16>::R,
-              "Z's column split");
-typedef double dbl4 __attribute__((ext_vector_type(4)));
-
 template <int N>
 struct Work {  // offsets (doubles) inside one instance's workspace
   // SM starts two slots in (a pad kept from round 2; the sweep no longer reads it)
   // FR: each lane's row of F_k (12 doubles, lane-interleaved: entry i of thread t at 16 kRows i + t)
-  // (kND: only the zero block and the scaled constraint values)
-  static constexpr int SM = 2 * GS, FW = SM + N * GS + 2, QL = FW + 72 * N, ZERO = kND<N> ? 0 : QL + 36 * N, AB = ZERO + 72,
+  static constexpr int SM = 2 * GS, FW = SM + N * GS + 2, QL = FW + 72 * N, ZERO = QL + 36 * N, AB = ZERO + 72,
                        FR = AB + (kAbG<N> ? ((126 * N - 18 + 1) & ~1) : 0), SIZE = FR + (N > 48 ? 12 * 16 * kRows<N> : 0);
 };
 
-// (kND) the spikes W_k (stage k's 12 x 12 block, row-major; the separator's slot unused) and
-// Sigma^{-1}, P, Q of the separator (row-major)
 template <int N>
-struct NdSmem {
-  alignas(16) double Wsp[N - 1][GS];  // stage k's at WSI(k) (the separator has none)
-  alignas(16) double Sep[3][GS];
-  double Part[3][12];  // the separator's three terms of an iteration (ph_sweep_nd)
-};
-struct NoNdSmem {};
-
-template <int N, bool KI = false>
 struct Smem {
   double Ab[kAbG<N> ? 2 : 126 * N - 18];  // scaled constraint values, CSC order (N > 49: Work<N>::AB)
   // GH[0] = M^{-1}, GH[SIG(k)] = G_k (1 <= k <= m), GH[SIG(k+1)] = H_k (m <= k < N-1),
@@ -901,51 +776,47 @@ struct Smem {
   // dynamics-row rho of stage k [108,120); during scaling the row factors; in
   // the prologue xref / fsteps / the gait walk.
   alignas(16) double GH[N][GS];
-  double GHpad[kND<N> ? 4 : 2];  // the bottom slots' shift (SLOT; kND: both halves')
+  double GHpad[2];  // the bottom slots' shift (SLOT)
   // (N > 32: these three live in the global workspace, Work<N>)
   alignas(16) double Sm[kBig<N> ? 1 : N][GS];  // S_k^{-1} / U_k^{-1} of stage k at SLOT(SIG(k)), row-major (row stride RS)
-  double Smpad[kND<N> ? 4 : 2];
+  double Smpad[2];
   // F_k W_k (12x6, row psi at [6 psi]); W_k = B_k' R on rows 6..11: here beyond 32 stages
   // (stage stride 72), FWs at the end up to 32 stages (stride kFWS = 96)
-  alignas(16) double FWb[kBig<N> ? N : 1][(kBig<N> || (!KI && !kND<N>)) ? 72 : 2];  // (kKI / kND: no room for the placeholder)
+  alignas(16) double FWb[kBig<N> ? N : 1][72];
   double QL[kBig<N> ? 1 : N][36];   // B_k F_k W_k = R^{-1} W_k' F_k W_k (6x6)
   union {
     struct {
       // sweep right-hand side of stage k's states = bo[k] + na[k]: bo from stage k
       // itself, na from stage k+1's dynamics rows (Hd (w - beta) + H6 w, summed by
       // ph_rhs); nb is scratch of the checks
-      double bo[N + (kND<N> ? 1 : 0)][12];  // (kND: slot N the separator's, RSL)
-      double na[N + (kND<N> ? 1 : 0)][12];
+      double bo[N][12];
+      double na[N][12];
       double nb[N][12];
       double yv[N][12];      // w = S^{-1} y of the inward sweep (states / duals during the checks)
-      double xs[N + 1 + (kND<N> ? 1 : 0)][12];  // X_k (xs[k+1] = X_{k+1}, stage k's states; kND: sweep slots, XSL)
+      double xs[N + 1][12];  // X_k (xs[k+1] = X_{k+1}, stage k's states)
     } it;
     struct {
       alignas(16) double St[144];  // sweep hand-offs of the factorisation (16-B aligned: the
       alignas(16) double Sb[144];  // couplings read them as column pairs)
-      alignas(16) double St2[kND<N> ? 144 : 2];  // (kND) half B's two chains
-      alignas(16) double Sb2[kND<N> ? 144 : 2];
+      // (32 unused bytes, where the nested-dissection variant's two placeholders sat: at N = 4
+      // fa is the union's larger member, so they keep every later array's LDS offset there)
+      alignas(16) double fapad_[4];
     } fa;
   } u;
   // per-wave partial reductions (32 per wave); during the sweeps the sink of lanes
   // whose store is void (lane (t & 31) + 12 j, j <= N/2 + 1)
   double red[(8 * kRows<N> + 32 > 12 * (N / 2 + 2) + 32) ? 8 * kRows<N> + 32 : 12 * (N / 2 + 2) + 32];
-  double dump[kND<N> ? 1 : 64];  // sink of predicated stores (never read): lane & 63 (kND: red[], as the sweeps')
+  double dump[64];  // sink of predicated stores (never read): lane & 63
   // (13 unused doubles: where round 4's deferred-check arrays sat; they keep every later
   // array's LDS offset, and with it the compiler's register allocation, as measured)
-  double pad13_[(KI || kND<N>) ? 1 : 13];
+  double pad13_[13];
   alignas(16) double zero[72];  // zeros: masked coefficient reads point here instead of selecting
   // flag[4] (kXstLds): the ADMM loop's exit status, written by thread 0 at the (uniform)
   // exits and read by every thread after the loop
   int flag[kXstLds<N> ? 5 : 4];
   // (up to 32 stages) F W at its 96-double stride, last: its round-4 growth leaves every
   // other array's LDS offset -- and the compiler's register allocation -- as before
-  alignas(16) double FWs[kBig<N> ? 1 : N][kBig<N> ? 2 : kFWS<N, KI>];
-  // (kKI) Z's LDS part, column-major (column c - SP0 at KVS (c - SP0)); during the
-  // formation the staging of each pass.  The loop's partial products P[wave][row] sit in GH.
-  alignas(16) double KV[KI ? KinvLay<N>::SPC * KinvLay<N>::KVS : 1];
-  // (kND) the spikes and the separator's matrices (no room taken at the other horizons)
-  [[no_unique_address]] std::conditional_t<kND<N>, NdSmem<N>, NoNdSmem> nd;
+  alignas(16) double FWs[kBig<N> ? 1 : N][kBig<N> ? 2 : kFWS<N>];
 };
 
 // prologue aliases inside GH
@@ -965,11 +836,9 @@ struct Prologue {
 // for instruction what they were before the table existed (the formulation's kernels only: the
 // qp path takes Ax, l, u as given).
 template <int N, bool FUSED, bool SOLVE, bool POLISH, bool ROB = false>
-__global__ __launch_bounds__((16 * kRows<N> * (kKI<N, SOLVE, POLISH> ? 2 : 1)), (kKI<N, SOLVE, POLISH> ? 1 : kOcc<N>))
+__global__ __launch_bounds__(16 * kRows<N>, 2)
 void engine_kernel(mpcq_params p, LaunchArgs a) {
-  // KI: the explicit inverse (kKI): twice the threads, waves NW.. are the helpers
-  constexpr bool KI = kKI<N, SOLVE, POLISH>;
-  constexpr int NR = kRows<N>, NW = NR / 4, T = 16 * NR * (KI ? 2 : 1), n = 24 * N, m = 44 * N, nnz = 126 * N - 18,
+  constexpr int NR = kRows<N>, NW = NR / 4, T = 16 * NR, n = 24 * N, m = 44 * N, nnz = 126 * N - 18,
                 MID = N / 2;
 #ifndef MPCQ_STAMP_WAVE
 #define MPCQ_STAMP_WAVE 0
@@ -978,7 +847,7 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
   // the two chains of the state sweeps: top stages 0..MID-1, bottom N-1..MID+1
   // (BOT stages: MID - 1 for even N, MID for odd N), meeting at stage MID
   constexpr int BOT = N - 1 - MID;
-  __shared__ Smem<N, KI> sh;
+  __shared__ Smem<N> sh;
   const int t = threadIdx.x, wv = t >> 6, lane = t & 63;
   // lane coordinates; the loops launder them (see launder()) so that the
   // compiler recomputes the many LDS offsets derived from them instead of
@@ -1034,9 +903,6 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
     zQL = Work<N>::ZERO - Work<N>::QL;
     if (SOLVE && t < 72) wk[Work<N>::ZERO + t] = 0.0;
   } else {
-    if constexpr (ABG) {  // (kND) the zero block the masked coefficient reads of Ab point at
-      if (SOLVE && t < 72) a.work[b * Work<N>::SIZE + Work<N>::ZERO + t] = 0.0;
-    }
     SmW = (wdd*)&sh.Sm[0][0];
     FWW = (wdd*)&sh.FWs[0][0];
     QLW = (wdd*)&sh.QL[0][0];
@@ -1426,16 +1292,7 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
       }
     };
 
-      // NS: stages of the system swept (N, or a half of it under kND); RB: its right-hand
-      // side (RB[q] + RB[q + RO]), YVB: its y / w slots, XSB: its states, GHB / SMB: its G / H
-      // / M^{-1} and S^{-1} slots (ST: the stamp bucket of the wait for the right-hand sides,
-      // diagnostic builds).  ND (kND, a half on wave 0 or 1): the caller has passed the barrier
-      // that publishes the right-hand sides and runs this on the half's wave only.
-      auto ph_sweep_lag = [&](auto ns_tag, auto st_tag, auto nd_tag, lds_cd* const RB, int RO, double* const YVB,
-                              double* const XSB, lds_cd* const GHB, lds_cd* const SMB) __attribute__((always_inline)) {
-          constexpr int NS = decltype(ns_tag)::value, MID = NS / 2, BOT = NS - 1 - MID;
-          [[maybe_unused]] constexpr int ST = decltype(st_tag)::value;
-          constexpr bool ND = decltype(nd_tag)::value;
+      auto ph_sweep_lag = [&]() __attribute__((always_inline)) {
           // P5-P7: the state solve on wave 0 alone (no block barrier inside), up to 32
           // stages (beyond: ph_sweep_split).
           // Inward step j = 1..MID: top kk(j) = j, bottom kk(j) = N-1-j.  Half 0 (rows
@@ -1461,10 +1318,10 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
           // (N > 32: S^{-1} is global, so the row pointer is a generic one)
           using swp = lds_cd;
           using swp2 = lds_cd2;
-          swp* const GHs = GHB;
+          swp* const GHs = GHr;
           // (the bottom chain's slots are past N/2: +2, SLOT)
-          swp* const Mb = half == 0 ? GHs + (GS * (cr == 0 ? 0 : MID) + (cr == 0 ? 0 : kSlotPad<NS>) + RS * rr_)
-                                    : SMB + (GS * (cr == 0 ? -2 : MID - 1) + (cr == 0 ? 0 : kSlotPad<NS>) + RS * rr_);
+          swp* const Mb = half == 0 ? GHs + (GS * (cr == 0 ? 0 : MID) + (cr == 0 ? 0 : kSlotPad<N>) + RS * rr_)
+                                    : (swp*)&sh.Sm[0][0] + (GS * (cr == 0 ? -2 : MID - 1) + (cr == 0 ? 0 : kSlotPad<N>) + RS * rr_);
           double g[12];
           auto row12 = [&](swp* q) __attribute__((always_inline)) {  // 16-B aligned row: 6 ds_read_b128
 #pragma unroll
@@ -1485,19 +1342,14 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
             return Mb + GS * jj;
           };
           STAMP(15);  // (diagnostic builds: as in ph_sweep_split)
-          if constexpr (ND) {  // (the other waves pass their own barrier: nd_sweep_halves)
-            row12(rowp(1));
-            sync_all();
-          } else {
-            if (t < 64) row12(rowp(1));
-            sync_all();
-          }
-          STAMP(ST);
+          if (t < 64) row12(rowp(1));
+          sync_all();
+          STAMP(3);
           // outward step j reads G_{MID-j+1}' (top, slot MID+1-j) / H_{MID+j-1}'
           // (bottom, slot N-j) columns: Ob + (MID - j) GS (LDS offsets are unsigned,
           // so the bases sit at the lowest slot a chain reaches)
-          lds_cd* const Ob = GHB + (GS * (cr == 0 ? 1 : NS - MID) + (cr == 0 ? 0 : kSlotPad<NS>) + rr_);
-          if (ND || t < 64) {
+          lds_cd* const Ob = GHr + (GS * (cr == 0 ? 1 : N - MID) + (cr == 0 ? 0 : kSlotPad<N>) + rr_);
+          if (t < 64) {
             // the sweeps are every wave's critical path (the other waves of the
             // instance wait at the barrier): issue them ahead of a co-resident
             // instance's stage-parallel phases
@@ -1505,31 +1357,31 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
             // right-hand side of step j: top stage j (slot j), bottom stage N-1-j (slot
             // MID+1+j, except the meeting stage MID at the bottom's last step BOT, slot
             // MID, which the bottom re-reads in the steps it does not take); na at +12N
-            lds_cd* const Bb = RB + (12 * (cr == 0 ? 0 : MID + 1) + rr_);
-            lds_cd* const Bm = RB + (12 * MID + rr_);
+            lds_cd* const Bb = (lds_cd*)&sh.u.it.bo[0][0] + (12 * (cr == 0 ? 0 : MID + 1) + rr_);
+            lds_cd* const Bm = (lds_cd*)&sh.u.it.bo[0][0] + (12 * MID + rr_);
             auto rhs = [&](int j) __attribute__((always_inline)) -> lds_cd* {  // j: a constant
               return (j >= BOT && cr != 0) ? Bm : Bb + 12 * j;
             };
             // w of stage kk(j-2) (half 1): top slot j-2, bottom slot MID-1+j; the other
             // lanes store into the sink with the same stride
             lds_d* const sink = (lds_d*)&sh.red[0] + (t & 31);
-            lds_d* const Yb = (half == 1 && s < 12) ? (lds_d*)YVB + (12 * (cr == 0 ? -2 : MID - 1) + rr_)
+            lds_d* const Yb = (half == 1 && s < 12) ? (lds_d*)&sh.u.it.yv[0][0] + (12 * (cr == 0 ? -2 : MID - 1) + rr_)
                                                     : sink;
             // step MID+1's store: every lane has one target, so it is one store and no branch
-            lds_d* const Ym = ((NS & 1) || cr == 0) ? Yb + 12 * (MID + 1) : sink;
+            lds_d* const Ym = ((N & 1) || cr == 0) ? Yb + 12 * (MID + 1) : sink;
             lds_d* const Pm = (half == 0 && cr == 0 && s < 12)
-                                  ? (lds_d*)XSB + (12 * SIGX<NS>(MID + 1) + rr_) : Ym;
+                                  ? (lds_d*)&sh.u.it.xs[0][0] + (12 * SIGX<N>(MID + 1) + rr_) : Ym;
             // right-hand sides run two steps ahead: step j sums the one of step j+1
             // (loaded during step j-1) and loads the one of step j+2; half 1 (the w
             // products) starts its chain from 0.  The first two (y_kk(0) and step 1's)
             // are loaded together and waited for once: they were published by the
             // barrier just passed, so this round trip is on the critical path.
             const double m0 = half == 0 ? 1.0 : 0.0;
-            double s0 = rhs(0)[0], s1 = rhs(0)[RO];
-            double c0 = rhs(1)[0], c1 = rhs(1)[RO];
+            double s0 = rhs(0)[0], s1 = rhs(0)[12 * N];
+            double c0 = rhs(1)[0], c1 = rhs(1)[12 * N];
             double src = half == 0 ? s0 + s1 : 0.0;  // y_kk(0) (half 0)
             double bcn = add_mul_here(c0, c1, m0);
-            double b0 = rhs(2)[0], b1 = rhs(2)[RO];
+            double b0 = rhs(2)[0], b1 = rhs(2)[12 * N];
 #pragma unroll
             for (int j = 1; j <= MID + 1; ++j) {
               asm volatile("" : : : "memory");
@@ -1541,8 +1393,8 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
                 row12(rowp(j + 1));
               } else if (j == MID) {  // the meeting step: M^{-1} rows (half 0), the S walk (half 1)
                 row12(half == 0 ? GHs + RS * rr_ : rowp(MID + 1));
-                lds_cd* qb = RB + (12 * MID + rr_);
-                b0 = qb[0]; b1 = qb[RO];
+                lds_cd* qb = (lds_cd*)&sh.u.it.bo[0][0] + (12 * MID + rr_);
+                b0 = qb[0]; b1 = qb[12 * N];
               } else {  // the last step: the first outward step's columns
 #pragma unroll
                 for (int i = 0; i < 12; ++i) g[i] = Ob[RS * i + GS * (MID - 1)];
@@ -1559,7 +1411,7 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
               // compiler then copied the first pair and put a wait state in front of every sum)
               if (j < MID) bcn = add_mul_here(b0, b1, m0);
               if (j + 2 <= MID) {
-                b0 = rhs(j + 2)[0]; b1 = rhs(j + 2)[RO];
+                b0 = rhs(j + 2)[0]; b1 = rhs(j + 2)[12 * N];
               }
               if (j >= 2 && j <= MID) {  // half 1: w of stage kk(j-2)
                 Yb[12 * j] = acc;
@@ -1582,7 +1434,7 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
             }
             STAMP(6);
           }
-          if (ND || t < 64) {
+          if (t < 64) {
             // Outward step j: top kk = MID-j: X_kk = w_kk - G_{kk+1}' X_{kk+1}; bottom
             // kk = MID+j: X_kk = w_kk - H_{kk-1}' X_{kk-1} (columns from Ob - j GS).  Lane
             // rr reads column rr (a full 12-term product per lane; half 1 repeats half 0).
@@ -1590,9 +1442,9 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
             // top slot MID+1-j, bottom slot N-j (SIGX; Xb - 12 j).  The bottom row's last
             // step (kk = N) is idle: its store goes to the sink.
             // (bases at step MID's slot: step j at base + 12 (MID - j))
-            lds_cd* const Wb = (lds_cd*)YVB + (12 * (cr == 0 ? 0 : NS - MID) + rr_);
+            lds_cd* const Wb = (lds_cd*)&sh.u.it.yv[0][0] + (12 * (cr == 0 ? 0 : N - MID) + rr_);
             lds_d* const sinkO = (lds_d*)&sh.red[0] + (t & 31);
-            lds_d* const Xb = (half == 0 && s < 12) ? (lds_d*)XSB + (12 * (cr == 0 ? 1 : NS - MID) + rr_)
+            lds_d* const Xb = (half == 0 && s < 12) ? (lds_d*)&sh.u.it.xs[0][0] + (12 * (cr == 0 ? 1 : N - MID) + rr_)
                                                     : sinkO;
             wave_sync();  // the w written by half 1
             double bq = Wb[12 * (MID - 1)];
@@ -1615,7 +1467,7 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
               if (j < MID) {
                 xp = acc;
                 Xb[12 * (MID - j)] = acc;
-              } else if constexpr (NS & 1) {
+              } else if constexpr (N & 1) {
                 *Xb = acc;
               } else {  // even N: the bottom chain has no step MID
                 *(cr == 0 ? Xb : sinkO) = acc;
@@ -1626,43 +1478,18 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
           wave_sync();
           }  // MPCQ_REP_SWEEP
       };
-      // (kND) Both halves' sweeps, A on wave 0 and B on wave 1, one code path (B as an NDS-stage
-      // system with its phantom): the bases differ by a wave-uniform offset.  The barrier that
-      // publishes the right-hand sides is inside: the sweep waves read their first rows before
-      // theirs (as the whole-horizon sweep does), the other waves pass their own (a wave-uniform
-      // branch; every wave executes one s_barrier).
-      auto nd_sweep_halves = [&]() __attribute__((always_inline)) {
-        if constexpr (kND<N>) {
-          constexpr int S = NDS<N>;
-          const int wq = __builtin_amdgcn_readfirstlane(t >> 6);
-          if (wq < 2) {
-            const int o12 = wq ? 12 * S : 0, og = wq ? kGhB<N> : 0;
-            ph_sweep_lag(std::integral_constant<int, S>{}, std::integral_constant<int, 3>{}, std::true_type{},
-                         (lds_cd*)&sh.u.it.bo[0][0] + o12, 12 * (N + 1), &sh.u.it.yv[0][0] + o12,
-                         &sh.u.it.xs[0][0] + o12, GHr + og, (lds_cd*)&sh.Sm[0][0] + og);
-          } else {
-            sync_all();
-          }
-        }
-      };
     // pr: per-own-row rho override (polish: 1/delta on active rows, 0 elsewhere);
     // nullptr in the ADMM loop, where the class rho applies
-    // role: std::false_type for the stage waves; std::true_type (kKI's helper waves) runs the
-    // same barrier sequence with no work, so both roles pass every barrier together
-    auto factor = [&](auto role, double sigma, const double* pr) __attribute__((always_inline)) -> bool {
-      constexpr bool H = decltype(role)::value;
+    auto factor = [&](double sigma, const double* pr) __attribute__((always_inline)) -> bool {
       bool ok = true;
       launder();
       auto rho_of = [&](int j) __attribute__((always_inline)) -> double {
         return pr ? pr[j] : rho_of_cls(j);
       };
       double* gk = gh0 + GS * k;
-      if constexpr (!H) {
-        if (cl) gk[108 + ph] = rho_of(0);
-      }
+      if (cl) gk[108 + ph] = rho_of(0);
       sync_all();
-      // ---- phase P: F_k = K_ff^{-1} (row ph per column lane), F_k W_k, Q_k
-      if constexpr (!H) {
+      {  // ---- phase P: F_k = K_ff^{-1} (row ph per column lane), F_k W_k, Q_k
         double rd6[6];
 #pragma unroll
         for (int j = 0; j < 6; ++j) rd6[j] = gk[114 + j];
@@ -1714,7 +1541,7 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
         }
         if (cl) {
 #pragma unroll
-          for (int j = 0; j < 6; ++j) { gk[36 + 6 * ph + j] = fw[j]; FWW[kFWS<N, KI> * k + 6 * ph + j] = fw[j]; }
+          for (int j = 0; j < 6; ++j) { gk[36 + 6 * ph + j] = fw[j]; FWW[kFWS<N> * k + 6 * ph + j] = fw[j]; }
         }
         wave_sync();
         // Q = W' (F W): 36 entries over the row's 16 lanes
@@ -1802,156 +1629,6 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
         }
         schur_cols<!kBig<N>>(Ro, G, ca, c6, std::make_integer_sequence<int, 12>{});
       };
-      if constexpr (kND<N>) {
-        // (kND) Two two-ended factorisations, one per half, their steps interleaved (step j of
-        // both; B's meeting comes one step before A's at N = 32).  Half A's rows: stages
-        // 0..S-1, its top chain from stage 0, its bottom chain from S-1 (no coupling to the
-        // separator); half B's: S+1..N-1, its top chain from S+1 (no coupling to the separator).
-        // G / H / M^{-1} / S^{-1} in the half's slots (SLOT<NS>(SIG<NS>(local stage)), B's at
-        // kGhB); the chains hand off through St / Sb (A) and St2 / Sb2 (B).
-        constexpr int S = NDS<N>, NB = NDB<N>, MID2 = S / 2;
-        static_assert(S >= 4 && NB >= 3 && NB <= S, "the halves of the nested-dissection solve");
-        const int hh = k < S ? 0 : (k > S ? 1 : 2);  // 0: A, 1: B, 2: the separator
-        const int kl = hh == 0 ? k : k - S - 1;        // stage in the half
-        const int nreal = hh == 0 ? S : NB;            // (B's local stage NB is its phantom)
-        double* const Sth = hh == 0 ? St : sh.u.fa.St2;
-        double* const Sbh = hh == 0 ? Sb : sh.u.fa.Sb2;
-        const int hb = hh == 0 ? 0 : kGhB<N>;
-        auto hslot = [&](int q) __attribute__((always_inline)) -> int { return hb + SLOT<S>(SIG<S>(q)); };
-        // couple(): C S^{-1} from the given hand-off, G / H into the given slot row
-        auto couple_nd = [&](bool upper, double (&Ro)[12], const double* Sp, double* Gd)
-            __attribute__((always_inline)) {
-          const double ca = upper ? cta : cba;
-          double c6[6];
-#pragma unroll
-          for (int j = 0; j < 6; ++j) c6[j] = upper ? ct6[j] : cb6[j];
-          wave_sync();  // this row's reads of its G / H slots are done
-          const int ar = ph < 6 ? ph : ph - 6;
-          double G[12];
-#pragma unroll
-          for (int ci = 0; ci < 12; ci += 2) {
-            const dbl2 s0 = *(lds_cd2*)(Sp + 12 * ar + ci);
-            dbl2 su[6];
-#pragma unroll
-            for (int j = 0; j < 6; ++j) su[j] = *(lds_cd2*)(Sp + 12 * (6 + j) + ci);
-            double g0 = ca * s0.x, g1 = ca * s0.y;
-#pragma unroll
-            for (int j = 0; j < 6; ++j) {
-              g0 = fma(c6[j], su[j].x, g0);
-              g1 = fma(c6[j], su[j].y, g1);
-            }
-            G[ci] = g0;
-            G[ci + 1] = g1;
-            asm volatile("" ::: "memory");
-          }
-          if (cl) {
-#pragma unroll
-            for (int ci = 0; ci < 12; ++ci) Gd[ci] = -G[ci];  // stored negated
-          }
-          schur_cols<true>(Ro, G, ca, c6, std::make_integer_sequence<int, 12>{});
-        };
-        // B's phantom: zero coupling (its G / H slot) and zero inverse (its S^{-1} slot), once the
-        // stage-keyed factor scratch in GH (Q_k, F_k W_k, rho) has been read (Drow / Ctop / Cbot)
-        sync_all();
-        for (int e = t; e < GS; e += T) {
-          gh0[kPhSlot<N> + e] = 0.0;
-          SmW[kPhSlot<N> + e] = 0.0;
-        }
-#pragma nounroll
-        for (int j = 0; j <= MID2; ++j) {
-          launder();
-          const bool act = hh < 2;
-          const bool top = act && j < MID2 && kl == j;
-          const bool bot = act && j < MID2 && kl == S - 1 - j && kl > MID2;
-          const bool mrow = act && j == MID2 && kl == MID2;
-          if (!H && (top || bot || mrow)) {
-            const bool useT = (top && kl > 0) || mrow, useB = (bot && kl < nreal - 1) || mrow;
-            double Ro[12];
-#pragma unroll
-            for (int ci = 0; ci < 12; ++ci) Ro[ci] = Dr0[ci];
-            if (useT) couple_nd(true, Ro, Sth, gh0 + hslot(kl) + RS * ph);
-            if (useB) couple_nd(false, Ro, Sbh, gh0 + hslot(kl + 1) + RS * ph);
-            gj12<true>(Ro, ph, ok);
-            if (cl) {
-#pragma unroll
-              for (int ci = 0; ci < 12; ++ci) SmW[hslot(kl) + RS * ph + ci] = Ro[ci];
-            }
-            wave_sync();  // the previous inverse has been consumed by this row
-            if (cl) {
-              double* dst = mrow ? gh0 + hb + RS * ph : (bot ? Sbh : Sth) + 12 * ph;
-#pragma unroll
-              for (int ci = 0; ci < 12; ++ci) dst[ci] = Ro[ci];
-            }
-          }
-          sync_all();
-        }
-        // The spikes: each half solved with its coupling to the separator as the right-hand
-        // side, one column at a time through the ADMM loop's own half sweeps -- A with column
-        // cI of L_s' at stage S-1 (row ph of L_s' is stage S-1's lower coupling row, cba /
-        // cb6), B with column cI of L_{S+1} at stage S+1 (its upper coupling row, cta / ct6);
-        // W_k = the solution's block at stage k.  (u.fa's hand-offs are dead: u.it's right-hand
-        // sides, w and states take their place.)
-        {
-          const int ar = ph < 6 ? ph : ph - 6;
-#pragma nounroll
-          for (int cI = 0; cI < 12; ++cI) {
-            launder();
-            const bool lo = k == S - 1, up = k == S + 1;
-            double ca = lo ? cba : cta, cv = 0.0;
-#pragma unroll
-            for (int j = 0; j < 6; ++j)
-              if (cI == 6 + j) cv = lo ? cb6[j] : ct6[j];
-            const double rv = (lo || up) ? (cI == ar ? ca : 0.0) + cv : 0.0;
-            if (cl) {
-              sh.u.it.bo[RSL<N>(k)][ph] = rv;
-              sh.u.it.na[RSL<N>(k)][ph] = 0.0;
-              if (k == S) { sh.u.it.bo[kPhRhs<N>][ph] = 0.0; sh.u.it.na[kPhRhs<N>][ph] = 0.0; }
-            }
-            nd_sweep_halves();  // (its barrier publishes the right-hand sides)
-            sync_all();
-            if (cl && k != S) sh.nd.Wsp[WSI<N>(k)][RS * ph + cI] = sh.u.it.xs[XSL<N>(k)][ph];
-          }
-        }
-        sync_all();
-        // The separator: Sigma = D_S - L_S W_{S-1} - L_{S+1}' W_{S+1} (row ph: stage S's upper
-        // coupling row cta / ct6 against W_{S-1}, its lower one cba / cb6 against W_{S+1}), its
-        // inverse, P = -Sigma^{-1} L_S and Q = -Sigma^{-1} L_{S+1}' (rows of L_S / L_{S+1}' from
-        // the row's lanes by broadcast).
-        if (k == S) {
-          const int ar = ph < 6 ? ph : ph - 6;
-          double Ro[12];
-#pragma unroll
-          for (int ci = 0; ci < 12; ++ci) {
-            const double* const Wa = &sh.nd.Wsp[WSI<N>(S - 1)][0];
-            const double* const Wb = &sh.nd.Wsp[WSI<N>(S + 1)][0];
-            double ga = cta * Wa[12 * ar + ci], gb = cba * Wb[12 * ar + ci];
-#pragma unroll
-            for (int j = 0; j < 6; ++j) {
-              ga = fma(ct6[j], Wa[12 * (6 + j) + ci], ga);
-              gb = fma(cb6[j], Wb[12 * (6 + j) + ci], gb);
-            }
-            Ro[ci] = Dr0[ci] - ga - gb;
-          }
-          gj12<true>(Ro, ph, ok);
-          double Pr[12], Qr[12];
-#pragma unroll
-          for (int c = 0; c < 12; ++c) {
-            const double lt = (c == ar ? cta : 0.0) + (c >= 6 ? ct6[c >= 6 ? c - 6 : 0] : 0.0);
-            const double lb = (c == ar ? cba : 0.0) + (c >= 6 ? cb6[c >= 6 ? c - 6 : 0] : 0.0);
-            Pr[c] = -bdot_ln12(Ro, lt, 0.0);
-            Qr[c] = -bdot_ln12(Ro, lb, 0.0);
-          }
-          if (cl) {
-#pragma unroll
-            for (int ci = 0; ci < 12; ++ci) {
-              sh.nd.Sep[0][RS * ph + ci] = Ro[ci];
-              sh.nd.Sep[1][RS * ph + ci] = Pr[ci];
-              sh.nd.Sep[2][RS * ph + ci] = Qr[ci];
-            }
-          }
-        }
-        sync_all();
-      } else {
       // Step j < MID: top row k = j and bottom row k = N-1-j > MID in parallel; step
       // MID: the meeting row (both couplings).  M^{-1} -> GH[0].
 #pragma nounroll
@@ -1959,7 +1636,7 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
         launder();
         const bool mid = j == MID;
         const bool top = !mid && k == j, bot = !mid && k == N - 1 - j && k > MID, mrow = mid && k == MID;
-        if (!H && (top || bot || mrow)) {
+        if (top || bot || mrow) {
           const bool useT = (top && k > 0) || mrow, useB = (bot && k < N - 1) || mrow;
           double Ro[12];
 #pragma unroll
@@ -1980,7 +1657,6 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
         }
         sync_all();
       }
-      }  // kND
       STAMP(14);
       // a non-positive pivot anywhere fails the whole instance (uniform result)
       if (!ok) atomicOr(&sh.flag[2], 1);
@@ -2003,7 +1679,7 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
     if constexpr (ABG) zAb = Work<N>::ZERO - Work<N>::AB;
     else zAb = (int)(sh.zero - sh.Ab);
     lds_cd* XSr = (lds_cd*)&sh.u.it.xs[0][0];
-    double* const Wdump = kND<N> ? &sh.red[t & 63] : &sh.dump[t & 63];  // (red: no reduction is live in ph_rhs)
+    double* const Wdump = &sh.dump[t & 63];
     // The LDS offsets of the lane's coefficients, derived from its coordinates.  O0
     // is derived once and held (the loop phases up to 32 stages, where the ADMM loop
     // has the registers); a phase run between long stretches of other work -- the
@@ -2031,13 +1707,13 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
       o.oFa = FO<N>(k, f, ta >> 1) + 5 + (ta & 1);
       o.oFb = FO<N>(k, f, 2) + 5 + ta;
       o.oF4 = FO<N>(k, f, 2) + 9;
-      o.oFW = kFWS<N, KI> * k + 6 * ph;
-      const int oFWc = kFWS<N, KI> * k + (isv_ ? ph - 6 : 0);
+      o.oFW = kFWS<N> * k + 6 * ph;
+      const int oFWc = kFWS<N> * k + (isv_ ? ph - 6 : 0);
       o.oQL = 36 * k + 6 * (isv_ ? ph - 6 : 0);
       o.oXSp = 12 * k + ph;  // natural order (update_info)
       o.oXSp6 = 12 * k + (ph < 6 ? ph + 6 : ph);
       // the sweep's states in its slots (SIGX): own X_{k+1}, the previous stage's X_k
-      auto xsl = [](int kk) __attribute__((always_inline)) -> int { return 12 * XSL<N>(kk); };
+      auto xsl = [](int kk) __attribute__((always_inline)) -> int { return 12 * SIGX<N>(kk + 1); };
       o.rXS = xsl(k) + ph;
       o.rXSpm = hp_ ? xsl(k - 1) + ph : zXS;
       o.rXSp6m = hp_ ? xsl(k - 1) + (ph < 6 ? ph + 6 : ph) : zXS;
@@ -2046,13 +1722,8 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
       o.oFWcm = isv_ ? oFWc : zFW;
       o.oQLm = isv_ ? o.oQL : zQL;
       o.oB0 = FO<N>(k, 0, 0) + (ph >= 9 ? ph - 8 : 0);  // B row ph on force (fp, cp): + 24 fp + 7 cp
-      if constexpr (KI) {  // natural stage order: the product reads them by state index
-        o.Wbo = &sh.u.it.bo[k][ph];
-        o.Wna = &sh.u.it.na[hp_ ? k - 1 : N - 1][ph];
-      } else {
-        o.Wbo = &sh.u.it.bo[RSL<N>(k)][ph];
-        o.Wna = &sh.u.it.na[RSL<N>(hp_ ? k - 1 : N - 1)][ph];
-      }
+      o.Wbo = &sh.u.it.bo[SIG<N>(k)][ph];
+      o.Wna = &sh.u.it.na[SIG<N>(hp_ ? k - 1 : N - 1)][ph];
       return o;
     };
     LaneOffs O0 = offs();  // (re-derived at the top of every stretch of iterations up to 32 stages, below)
@@ -2067,7 +1738,7 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
   [[maybe_unused]] double* const Wbo = O_.Wbo;                                                             \
   [[maybe_unused]] double* const Wna = O_.Wna
     // beyond 32 stages the loop phases re-derive them too
-    constexpr bool kRecompLoop = BIG || KI;  // (kKI: the helpers' registers set the budget)
+    constexpr bool kRecompLoop = BIG;
     auto launder_p = [&]() __attribute__((always_inline)) {
       lds_uniform(Ab); lds_uniform(GHr); lds_uniform(SmR); lds_uniform(FWr); lds_uniform(QLr); lds_uniform(XSr);
     };
@@ -2345,13 +2016,10 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
     };
     // the products, where a cheap condition holds (inf_need != 0, uniform): A' dy for
     // the primal test, A dx for the dual one, on the deltas infeas_cheap published
-    // role: std::true_type (kKI's helpers) passes the barriers and forms the uniform bits only
-    auto infeas_products = [&](auto role, double dxf, double dxX, const double (&cv)[CK_COUNT])
+    auto infeas_products = [&](double dxf, double dxX, const double (&cv)[CK_COUNT])
         __attribute__((always_inline)) {
-      constexpr bool H = decltype(role)::value;
       MPCQ_CHECK_IDS();
       launder_p();
-      if constexpr (!H) {
       double vu = -INFINITY, vl = -INFINITY;
       {
         double adx[3], lob[3], hib[3];
@@ -2374,7 +2042,6 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
       // lanes 0 / 4 / 8 keep ||D^-1 A' dy|| / vu / vl, published in slots 1 / 4 / 5
       const double mine = pair_max(row_pair_max(tred3(naty, vu, vl, s)));
       if (lane == 0 || lane == 4 || lane == 8) sh.red[32 * wv + 16 + (lane == 0 ? 1 : 4 + (lane >> 3))] = mine;
-      }
       sync_all();
       const int e = s < 6 ? s : 0;  // slots 16..21 are all maxima (0 / 2 / 3 from infeas_cheap)
       double v = sh.red[16 + e];
@@ -2670,7 +2337,7 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
         }
       }
       // a resumed slice (mpcq_set_slice): the iterate every lane held when it was suspended
-      if constexpr (kSlice<N> && !KI) {
+      if constexpr (kSlice<N>) {
         if (a.resume) {
           constexpr int64_t RL = res_lanes(N);
           const double* const q = a.res + b * 8 * RL + t;
@@ -2703,7 +2370,7 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
       // 1.01e-7 from the oracle (its test allows 1e-7; r05r), and the loop reads its operands
       // per iteration there anyway.  Dropping the checks' laundering as well was slower at
       // N = 32 (3.06 us, r05q).
-      constexpr bool kColfFold = !KI && !BIG;
+      constexpr bool kColfFold = !BIG;
       struct RhsOps {
         double cf[10], fwc[12], cXd, cHd, cH6;
         double cf0m[kColfFold ? 3 : 1];
@@ -2725,11 +2392,8 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
       };
       // o: the operands held in registers (the ADMM loop), or null: read them here (polish,
       // whose loop would otherwise spill them)
-      // rsum (kKI): r = bo + na summed in LDS (two ds_add_f64 into a zeroed slot: its two
-      // addends commute, so the sum's bits do not depend on which lane adds first) instead of
-      // bo / na stored apart -- the product then loads one value per column, not two and an add
       auto ph_rhs = [&](bool admm, const RhsOps* op, const double (&pw)[3], double xcf, double xcX, double& uf,
-                        double& beta, lds_d* rsum = nullptr) __attribute__((always_inline)) {
+                        double& beta) __attribute__((always_inline)) {
           // (up to 48 stages no launder_p here since round 5: the laundered base pointers
           // cost ~40 instructions per iteration and the loop has no spill without them; beyond
           // 48 stages, at 128 VGPRs, the iteration was 15.0 -> 16.9 us without, r05r)
@@ -2815,26 +2479,12 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
             const double nb = cH6 * w[0];                // H6(k, ph): on X_k[ph+6] (ph < 6)
             // stage 0 zeroes the last stage's na / nb (that stage has no next stage:
             // its coefficients read zero)
-            if (!(KI && rsum)) *(cl ? Wbo : Wdump) = bo;
+            *(cl ? Wbo : Wdump) = bo;
             // stage k-1's component r takes na of lane r and nb of the lane 8 away in the
             // row (component r -+ 6, LN): summed here, one value and one add less per
             // sweep step
             const double nbx = dppd<0x128>(nb);  // row_ror:8
-            if (KI && rsum) {
-              if (cl) {
-                __hip_atomic_fetch_add(rsum + 12 * k + ph, bo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                __hip_atomic_fetch_add(rsum + 12 * (k >= 1 ? k - 1 : N - 1) + ph, na + nbx, __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_WORKGROUP);
-              }
-            } else {
-              *(cl ? Wna : Wdump) = na + nbx;
-            }
-            if constexpr (kND<N>) {  // B's phantom reads a zero right-hand side (the checks scribble on u.it)
-              if (k == NDS<N> && cl) {
-                sh.u.it.bo[kPhRhs<N>][ph] = 0.0;
-                sh.u.it.na[kPhRhs<N>][ph] = 0.0;
-              }
-            }
+            *(cl ? Wna : Wdump) = na + nbx;
           }
           // (the barrier that publishes bo / na / nb opens ph_sweep)
       };
@@ -3071,152 +2721,38 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
           wave_sync();
           }  // MPCQ_REP_SWEEP
       };
-      // ph_recover's iteration-invariant operands (F W and R^{-1} Q rows, friction coefficients)
-      struct RecPre {
-        double fwl[6], qll[6], cFb, cFa, cF4;
-      };
-      auto rec_pre = [&](RecPre& r) __attribute__((always_inline)) {
-        MPCQ_LANE_OFFS(kRecompLoop);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {  // 16-B aligned pairs: ds_read_b128 (twice ds_read2_b64's LDS rate)
-          using wcd2 = std::conditional_t<BIG, const dbl2, lds_cd2>;
-          const dbl2 fa = ((lds_cd2*)(FWr + oFW))[i], qa = ((wcd2*)(QLr + oQLm))[i];
-          r.fwl[2 * i] = fa.x; r.fwl[2 * i + 1] = fa.y;
-          r.qll[2 * i] = qa.x; r.qll[2 * i + 1] = qa.y;
-        }
-        r.cFb = Ab[oFb]; r.cFa = Ab[oFa]; r.cF4 = Ab[oF4];
-      };
-      // (kND) The state solve by nested dissection: the halves swept at once (A on wave 0, B on
-      // wave 1, each ph_sweep_lag's two-ended sweep on its own slots); wave 0 then forms
-      // P z_{S-1} and wave 1 Q z_{S+1} (each on its sweep lanes, lane r = component r: the half's
-      // separator-side state and the P / Q rows from LDS), the separator row's lanes Sigma^{-1}
-      // b_S meanwhile (b_S is published); one barrier; then every lane sums the separator's
-      // states x_S = Sigma^{-1} b_S + P z_{S-1} + Q z_{S+1} and corrects its own:
-      // x_k = z_k - W_k x_S.  ph_recover's barrier publishes the corrected states.  pre: the
-      // iteration-invariant operands of ph_recover, read right after the sweeps (their latency
-      // -- L2 for the constraint values -- behind the barrier and the correction).
-      auto ph_sweep_nd = [&](RecPre* pre) __attribute__((always_inline)) {
-        if constexpr (kND<N>) {
-          constexpr int S = NDS<N>;
-          const int wq = __builtin_amdgcn_readfirstlane(t >> 6);
-          lds_d* const part = (lds_d*)&sh.nd.Part[0][0];  // [0]: P z_{S-1}, [1]: Q z_{S+1}, [2]: Sigma^{-1} b_S
-          nd_sweep_halves();
-          STAMP(7);  // (diagnostic builds, kND: bucket 7 the outward sweep, 4 the separator terms, 5 the
-                     // barrier after them, 8 the correction; ph_recover's own wait joins bucket 7)
-          if (wq < 2) {  // (the sweep's own wave_sync has published its states to the wave)
-            // (lane ids from a laundered thread index: held across the loop, these addresses were
-            // spilled and each reload waited for)
-            int tl_ = t;
-            asm volatile("" : "+v"(tl_));
-            const int ri = (tl_ & 15) < 12 ? (tl_ & 15) : (tl_ & 15) - 12;
-            const double zv = sh.u.it.xs[XSL<N>(wq == 0 ? S - 1 : S + 1)][ri];
-            double pr[12];
-#pragma unroll
-            for (int i = 0; i < 6; ++i) {
-              const dbl2 v = ((lds_cd2*)&sh.nd.Sep[1 + wq][RS * ri])[i];
-              pr[2 * i] = v.x; pr[2 * i + 1] = v.y;
-            }
-            const double pz = bdot12(pr, zv, 0.0);
-            if (((tl_ >> 4) & 3) == 0 && (tl_ & 15) < 12) part[12 * wq + ri] = pz;
-          } else if (k == S) {
-            double Si[12];
-#pragma unroll
-            for (int i = 0; i < 6; ++i) {
-              const dbl2 v = ((lds_cd2*)&sh.nd.Sep[0][RS * ph])[i];
-              Si[2 * i] = v.x; Si[2 * i + 1] = v.y;
-            }
-            const double bs = sh.u.it.bo[RSL<N>(S)][ph] + sh.u.it.na[RSL<N>(S)][ph];  // b_S
-            const double sb = bdot_ln12(Si, bs, 0.0);
-            if (cl) part[24 + ph] = sb;
-          }
-          if (pre) rec_pre(*pre);
-          // this stage's spike row, read before the barrier (the waves that did not sweep have
-          // them in registers when it opens; after it, every wave's reads met in the LDS at once)
-          double Wr[12];
-#pragma unroll
-          for (int i = 0; i < 6; ++i) {
-            const dbl2 v = ((lds_cd2*)&sh.nd.Wsp[WSI<N>(k == NDS<N> ? k - 1 : k)][RS * ph])[i];  // (the separator's product is unused)
-            Wr[2 * i] = v.x; Wr[2 * i + 1] = v.y;
-          }
-          STAMP(4);
-          sync_all();  // z of both halves, the separator's three terms
-          STAMP(5);
-          const double xv = (part[24 + ph] + part[ph]) + part[12 + ph];
-          const double corr = bdot_ln12(Wr, xv, 0.0);
-          double* const zk = &sh.u.it.xs[XSL<N>(k)][ph];
-          const double zv = *zk;
-          if (cl) *zk = k == S ? xv : zv - corr;
-          STAMP(8);
-        }
-      };
       // the state sweep: the lagging form up to 32 stages, the split form beyond
-      // (kND: the nested-dissection solve)
       auto ph_sweep = [&]() __attribute__((always_inline)) {
-        if constexpr (kND<N>) {
-          ph_sweep_nd(nullptr);
-        } else if constexpr (BIG) {
-          ph_sweep_split();
-        } else {
-          ph_sweep_lag(std::integral_constant<int, N>{}, std::integral_constant<int, 3>{}, std::false_type{},
-                       (lds_cd*)&sh.u.it.bo[0][0], 12 * N, &sh.u.it.yv[0][0], &sh.u.it.xs[0][0], GHr,
-                       (lds_cd*)&sh.Sm[0][0]);
-        }
-      };
-      // (kKI) the state x_i = sum over the eight waves' partial products P[w][i] (in GH), always
-      // in wave order, so every lane that reads a state gets the same bits
-      auto ki_psum = [&](int i) __attribute__((always_inline)) -> double {
-        lds_cd* const q = GHr + i;
-        double v = q[0];
-#pragma unroll
-        for (int w = 1; w < 2 * NW; ++w) v += q[12 * N * w];
-        return v;
+        if constexpr (BIG) ph_sweep_split();
+        else ph_sweep_lag();
       };
       // ri0: 1/rho of the own slot-0 row (the ADMM loop's, or polish's)
       auto ph_recover = [&](const RhsOps* op, double ri0, double uf, double beta, double& sf, double& sX,
-                            double (&ax)[3], const RecPre* pre = nullptr)
-          __attribute__((always_inline)) {
+                            double (&ax)[3]) __attribute__((always_inline)) {
           // P8: forces f_k = F_k (b_f - R B' g) = u - (F W) g, with g = Xd X_{k+1} + Hd X_k
           // on the velocity rows (the states' part of those rows)
           double gv;
           MPCQ_LANE_OFFS(kRecompLoop);
           // the iteration-invariant LDS operands of P8 / P9 are read before the
           // barrier that ends the sweeps (their latency hides behind it), the
-          // sweep's states after it (kND: read by ph_sweep_nd, pre)
-          double fwl[6], qll[6], cFb, cFa, cF4;
-          if constexpr (kND<N>) {
-            RecPre own_;
-            if (!pre) rec_pre(own_);
-            const RecPre& q_ = pre ? *pre : own_;
+          // sweep's states after it
+          double fwl[6], qll[6];
 #pragma unroll
-            for (int i = 0; i < 6; ++i) { fwl[i] = q_.fwl[i]; qll[i] = q_.qll[i]; }
-            cFb = q_.cFb; cFa = q_.cFa; cF4 = q_.cF4;
-          } else {
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {  // 16-B aligned pairs: ds_read_b128 (twice ds_read2_b64's LDS rate)
-              using wcd2 = std::conditional_t<BIG, const dbl2, lds_cd2>;
-              const dbl2 fa = ((lds_cd2*)(FWr + oFW))[i], qa = ((wcd2*)(QLr + oQLm))[i];
-              fwl[2 * i] = fa.x; fwl[2 * i + 1] = fa.y;
-              qll[2 * i] = qa.x; qll[2 * i + 1] = qa.y;
-            }
+          for (int i = 0; i < 3; ++i) {  // 16-B aligned pairs: ds_read_b128 (twice ds_read2_b64's LDS rate)
+            using wcd2 = std::conditional_t<BIG, const dbl2, lds_cd2>;
+            const dbl2 fa = ((lds_cd2*)(FWr + oFW))[i], qa = ((wcd2*)(QLr + oQLm))[i];
+            fwl[2 * i] = fa.x; fwl[2 * i + 1] = fa.y;
+            qll[2 * i] = qa.x; qll[2 * i + 1] = qa.y;
           }
           // (the same coefficients as ph_rhs's, from the held set when there is one)
           const double eXd = op ? op->cXd : Ab[oXd], eHd = op ? op->cHd : Ab[oHdm], eH6 = op ? op->cH6 : Ab[oH6m];
-          if constexpr (!kND<N>) { cFb = Ab[oFb]; cFa = Ab[oFa]; cF4 = Ab[oF4]; }
+          const double cFb = Ab[oFb], cFa = Ab[oFa], cF4 = Ab[oF4];
           const double cSw = op ? op->cf[4] : Ab[oF + 4];
           sync_all();
           STAMP(7);
-          double xa, xb;
-          if constexpr (KI) {  // the explicit inverse's product (stage 0: X_0 = 0)
-            const int ip = 12 * (hp ? k - 1 : k);
-            sX = ki_psum(12 * k + ph);
-            const double a_ = ki_psum(ip + ph), b_ = ki_psum(ip + (ph < 6 ? ph + 6 : ph));
-            xa = hp ? a_ : 0.0;
-            xb = hp ? b_ : 0.0;
-          } else {
-            xa = XSr[rXSpm];  // (stage 0: X_0 = 0, a zero slot)
-            xb = XSr[rXSp6m];
-            sX = XSr[rXS];
-          }
+          const double xa = XSr[rXSpm];  // (stage 0: X_0 = 0, a zero slot)
+          const double xb = XSr[rXSp6m];
+          sX = XSr[rXS];
           asm volatile("" : : : "memory");
           {
             gv = eXd * sX + eHd * xa;  // used from the lanes of rows 6..11 only
@@ -3250,188 +2786,6 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
       };
       const double kNoW[3] = {0.0, 0.0, 0.0};
 
-      // ---- (kKI) the explicit inverse Z = K_s^{-1}: formation and product ----------------
-      using KL = KinvLay<N>;
-      // the wave index as a wave-uniform (scalar) value: the roles and column ranges branch on it
-      auto wvu = [&]() __attribute__((always_inline)) -> int { return __builtin_amdgcn_readfirstlane(t >> 6); };
-      // the summed right-hand side of iteration parity b (kKI): u.it.nb (b = 0) / u.it.yv (b = 1),
-      // free during the iterations (the checks publish there, then zero them again)
-      auto ki_rsum = [&](int b_) __attribute__((always_inline)) -> lds_d* {
-        return (lds_d*)(b_ ? &sh.u.it.yv[0][0] : &sh.u.it.nb[0][0]);
-      };
-      // One 16-column tile of Z (columns cb .. cb + 15) by the two-ended sweep on the
-      // identity's columns, both chains in this wave, every block product a 16 x 16 x 12
-      // MFMA (v_mfma_f64_16x16x4_f64 x 3).  Tiles in the D layout: lane l holds rows
-      // (l >> 4) + 4 r, r = 0..3, of column l & 15 (rows 12..15 are zero); a result's register
-      // s is the next product's B operand for K-slice s, so a chain step moves no data.
-      // A operands: lane l supplies M[l & 15][4 s + (l >> 4)] (transposed: M[4 s + (l >> 4)][l & 15]).
-      // The step's w = S^{-1} y tiles are parked in KV at the columns' own rows and read back
-      // by the outward steps, which overwrite them with the results (the pass's staging):
-      //   top    y_0 = e_0, y_k = e_k - G_k y_{k-1} (k <= MID), w_k = S_k^{-1} y_k (k < MID)
-      //   bottom v_{N-1} = e_{N-1}, v_k = e_k - H_k v_{k+1} (k >= MID), w_k = U_k^{-1} v_k (k > MID)
-      //   x_MID = M^{-1} (y_MID + v_MID - e_MID)
-      //   x_k = w_k - G_{k+1}' x_{k+1} (k < MID),  x_k = w_k - H_{k-1}' x_{k-1} (k > MID)
-      // (-G, -H are stored negated: every step is an accumulation.)
-      auto ki_tile = [&](int c0, int cn, int cb) __attribute__((always_inline)) {
-        const int l = lane, cc = l & 15, rb = l >> 4;
-        const int c = cb + cc;                    // this lane's column of Z
-        const bool keep = c < c0 + cn;            // columns past the pass are computed, not stored
-        double* const col = &sh.KV[0] + KL::KVS * (keep ? c - c0 : 0) + rb;  // + 12 k + 4 r: row 12 k + rb + 4 r
-        const dbl4 zero4 = {0.0, 0.0, 0.0, 0.0};
-        auto e_of = [&](int kk) __attribute__((always_inline)) -> dbl4 {  // the identity's rows of stage kk
-          dbl4 v;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = (r < 3 && 12 * kk + rb + 4 * r == c) ? 1.0 : 0.0;
-          return v;
-        };
-        // acc + M x (M 12 x 12 row-major in LDS at q; tr: M') for a tile x in the D layout
-        auto mm = [&](const double* q, bool tr, const dbl4& x, dbl4 acc) __attribute__((always_inline)) -> dbl4 {
-#pragma unroll
-          for (int s_ = 0; s_ < 3; ++s_) {
-            const int o = tr ? 12 * (4 * s_ + rb) + cc : 12 * cc + 4 * s_ + rb;
-            const double av = cc < 12 ? q[cc < 12 ? o : 0] : 0.0;
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, x[s_], acc, 0, 0, 0);
-          }
-          return acc;
-        };
-        auto park = [&](int kk, const dbl4& v) __attribute__((always_inline)) {
-          if (keep) {
-#pragma unroll
-            for (int r = 0; r < 3; ++r) col[12 * kk + 4 * r] = v[r];
-          }
-        };
-        auto unpark = [&](int kk) __attribute__((always_inline)) -> dbl4 {
-          dbl4 v = zero4;
-          if (keep) {
-#pragma unroll
-            for (int r = 0; r < 3; ++r) v[r] = col[12 * kk + 4 * r];
-          }
-          return v;
-        };
-        const double* const smp = &sh.Sm[0][0];
-        dbl4 yT = e_of(0), vB = e_of(N - 1);
-        park(0, mm(smp + SLOT<N>(SIG<N>(0)), false, yT, zero4));
-        park(N - 1, mm(smp + SLOT<N>(SIG<N>(N - 1)), false, vB, zero4));
-#pragma unroll
-        for (int kk = 1; kk <= MID; ++kk) {
-          yT = mm(gh0 + SLOT<N>(SIG<N>(kk)), false, yT, e_of(kk));
-          if (kk < MID) park(kk, mm(smp + SLOT<N>(SIG<N>(kk)), false, yT, zero4));
-          const int kb = N - 1 - kk;
-          if (kb >= MID) {
-            vB = mm(gh0 + SLOT<N>(SIG<N>(kb + 1)), false, vB, e_of(kb));
-            if (kb > MID) park(kb, mm(smp + SLOT<N>(SIG<N>(kb)), false, vB, zero4));
-          }
-        }
-        const dbl4 em = e_of(MID);
-        dbl4 t4;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) t4[r] = (yT[r] + vB[r]) - em[r];
-        const dbl4 xm = mm(gh0, false, t4, zero4);  // M^{-1} in GH slot 0
-        park(MID, xm);
-        dbl4 xT = xm, xB = xm;
-#pragma unroll
-        for (int j = 1; j <= (MID > N - 1 - MID ? MID : N - 1 - MID); ++j) {
-          const int kt = MID - j, kb = MID + j;
-          if (kt >= 0) {
-            xT = mm(gh0 + SLOT<N>(SIG<N>(kt + 1)), true, xT, unpark(kt));
-            park(kt, xT);
-          }
-          if (kb <= N - 1) {
-            xB = mm(gh0 + SLOT<N>(SIG<N>(kb)), true, xB, unpark(kb));
-            park(kb, xB);
-          }
-        }
-      };
-      // Z after a factorisation: four passes of at most 54 columns staged in KV (the last
-      // pass is KV's own part); a helper copies the columns it owns from each staged pass.
-      // Both roles run the same barriers.
-      auto kinv_form = [&](auto role, double (&kv)[3 * KL::HC]) __attribute__((always_inline)) {
-        constexpr bool H = decltype(role)::value;
-        if constexpr (!H) {  // the summed right-hand sides start from zero (their barriers follow)
-          if (cl) { ki_rsum(0)[12 * k + ph] = 0.0; ki_rsum(1)[12 * k + ph] = 0.0; }
-        }
-#pragma nounroll
-        for (int q = 0; q < KL::NPASS; ++q) {
-          const int c0 = KL::pc0(q), cn = KL::pcn(q);
-          if constexpr (!H) {
-            const int w_ = wvu();
-            if (w_ * 16 < cn) ki_tile(c0, cn, c0 + 16 * w_);
-          }
-          sync_all();
-          if constexpr (H) {
-            if (q < KL::NPASS - 1) {
-              const int h = wvu() - NW, hc = KL::hc0(h), hn = KL::hcn(h);
-#pragma unroll
-              for (int j = 0; j < KL::HC; ++j) {
-                const int cj = hc + j;
-                if (j < hn && cj >= c0 && cj < c0 + cn) {
-                  const double* const src = &sh.KV[0] + KL::KVS * (cj - c0) + lane;
-                  kv[3 * j] = src[0];
-                  kv[3 * j + 1] = src[64];
-                  kv[3 * j + 2] = src[128];
-                }
-              }
-            }
-          }
-          sync_all();
-        }
-      };
-      // x = Z r, r = bo + na (the state right-hand sides ph_rhs published): this wave's
-      // columns times r into P[wave][row] (rows lane, lane + 64, lane + 128), in column order.
-      // Helpers: their register columns; stage waves: their KV columns.
-      // x = Z r: r is loaded once, distributed (lane s of every 16-lane row holds r of the
-      // wave's column 16 u + s), and each column's three FMAs take it by row broadcast
-      // (v_fmac_f64_dpp row_newbcast:s): no per-column LDS load.  Helpers multiply their
-      // register columns; stage waves load their KV columns in two halves (all issued before
-      // the first half's FMAs).  Three accumulation chains (rows lane, lane + 64, lane + 128),
-      // each in column order.
-      auto kinv_mv = [&](auto role, const double (&kv)[3 * KL::HC], lds_cd* const rs) __attribute__((always_inline)) {
-        constexpr bool H = decltype(role)::value;
-        double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-        // (lane ids from a laundered thread index: held across the loop they were spilled)
-        int tl_ = t;
-        asm volatile("" : "+v"(tl_));
-        const int ln_ = tl_ & 63, s16 = tl_ & 15;
-        if constexpr (H) {
-          const int h = wvu() - NW, hn = KL::hcn(h);
-          lds_cd* const rq = rs + KL::hc0(h);  // (hc0 + 47 < 192: in the buffer)
-          double rv[3];
-#pragma unroll
-          for (int u = 0; u < 3; ++u) rv[u] = rq[16 * u + s16];
-          auto col = [&](auto jt) __attribute__((always_inline)) {
-            constexpr int j = decltype(jt)::value;
-            if (j < KL::HC - 1 || j < hn)
-              fmac3_bc<j % 16>(a0, a1, a2, rv[j / 16], kv[3 * j], kv[3 * j + 1], kv[3 * j + 2]);
-          };
-          for_each_j(col, std::make_integer_sequence<int, KL::HC>{});
-        } else {
-          const int w_ = wvu(), sc = KL::sc0(w_), sn = KL::scn(w_);
-          lds_cd* const kq = (lds_cd*)&sh.KV[0] + KL::KVS * (sc - KL::SP0) + ln_;
-          const double rv = rs[sc + (s16 < sn ? s16 : 0)];
-          constexpr int HALF = 7;
-          double ka[3 * HALF], kb[3 * HALF];
-#pragma unroll
-          for (int i = 0; i < HALF; ++i) {
-            const int ja = i, jb = HALF + i < sn ? HALF + i : sn - 1;  // (clamped: no read past KV)
-            ka[3 * i] = kq[KL::KVS * ja]; ka[3 * i + 1] = kq[KL::KVS * ja + 64]; ka[3 * i + 2] = kq[KL::KVS * ja + 128];
-            kb[3 * i] = kq[KL::KVS * jb]; kb[3 * i + 1] = kq[KL::KVS * jb + 64]; kb[3 * i + 2] = kq[KL::KVS * jb + 128];
-          }
-          asm volatile("" ::: "memory");
-          auto col = [&](auto jt, const double (&kk)[3 * HALF]) __attribute__((always_inline)) {
-            constexpr int j = decltype(jt)::value, i = j % HALF;
-            if (j < 2 * HALF - 1 || j < sn) fmac3_bc<j>(a0, a1, a2, rv, kk[3 * i], kk[3 * i + 1], kk[3 * i + 2]);
-          };
-          for_each_j([&](auto jt) __attribute__((always_inline)) { col(jt, ka); }, std::make_integer_sequence<int, HALF>{});
-          for_each_j([&](auto jt) __attribute__((always_inline)) {
-            col(std::integral_constant<int, HALF + decltype(jt)::value>{}, kb);
-          }, std::make_integer_sequence<int, HALF>{});
-        }
-        double* const P = gh0 + 12 * N * wvu() + ln_;
-        P[0] = a0;
-        P[64] = a1;
-        P[128] = a2;
-      };
-
       // ------------------------------------------------------------ ADMM
       // The factorisation sits outside the hot loop: the outer loop factors,
       // the inner loop iterates until convergence, max_iter or a rho update.
@@ -3441,136 +2795,6 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
 #define MPCQ_SET_XST(v_) do { if constexpr (kXstLds<N>) { if (t == 0) sh.flag[4] = (v_); } else if constexpr (!kXstRe<N>) { status = (v_); } } while (0)
       if constexpr (kXstLds<N>) MPCQ_SET_XST(0);
       int to_check = p.check_termination, to_adapt = p.adaptive_rho_interval;
-      if constexpr (KI) {
-        // (kKI) the loop of the explicit inverse: one driver for both roles, the helpers
-        // (waves NW..) with std::true_type -- the same barriers and the same uniform
-        // decisions (info_combine reads the stage waves' partials from LDS), no stage work
-        auto kinv_admm = [&](auto role) __attribute__((always_inline)) {
-          constexpr bool H = decltype(role)::value;
-          double kv[3 * KL::HC];  // (helpers) Z's columns hc0.. : rows lane, lane + 64, lane + 128
-#pragma unroll
-          for (int j = 0; j < 3 * KL::HC; ++j) kv[j] = 0.0;
-          const bool chk_on = p.check_termination > 0;
-          const bool adp_on = p.adaptive_rho && p.adaptive_rho_interval > 0;
-          for (;;) {
-            if (!factor(role, p.sigma, nullptr)) { MPCQ_SET_XST(MPCQ_STATUS_FACTOR_FAILED); break; }
-            kinv_form(role, kv);
-            STAMP(2);
-            bool refactor = false;
-            // one ADMM iteration: ph_rhs, barrier A, the product, ph_recover (barrier B), update
-            auto ki_iter = [&](auto mode_tag, const RhsOps& ops, double (&dyv)[3], double& dxf_, double& dxX_,
-                               double (&cvp)[CK_COUNT]) __attribute__((always_inline)) {
-              constexpr bool DELTA = decltype(mode_tag)::value == 1;
-              lds_d* const rs = ki_rsum(iter & 1);
-              if constexpr (H) {
-                STAMP(15);
-                sync_all();  // A
-                STAMP(3);
-                kinv_mv(role, kv, rs);
-                if constexpr (DELTA) ck_all(cvp);
-                STAMP(6);
-                sync_all();  // B
-                STAMP(7);
-              } else {
-                double uf, beta, sf, sX, ax[3];
-                ph_rhs(true, &ops, kNoW, 0.0, 0.0, uf, beta, rs);
-                STAMP(15);
-                sync_all();  // A: r = bo + na summed
-                STAMP(3);
-                kinv_mv(role, kv, rs);
-                STAMP(6);
-                if constexpr (DELTA) ck_all(cvp);
-                ph_recover(&ops, ri[0], uf, beta, sf, sX, ax);  // (B inside: the partial products)
-                // every read of this buffer preceded B; it is summed into again two iterations on
-                if (cl) rs[12 * k + ph] = 0.0;
-#pragma unroll
-                for (int j = 0; j < 3; ++j) {
-                  const double zr = p.alpha * ax[j] + (1.0 - p.alpha) * z[j];
-                  const double tt = zr + ri[j] * y[j];
-                  const double zn = fmin(fmax(tt, lo_of(j)), hi_of(j));  // osqp project
-                  const double d = rr[j] * (zr - zn);
-                  if constexpr (DELTA) dyv[j] = d;
-                  y[j] = y[j] + d;
-                  z[j] = zn;
-                }
-                const double nxf = p.alpha * sf + (1.0 - p.alpha) * xf;
-                const double nxX = p.alpha * sX + (1.0 - p.alpha) * xX;
-                if constexpr (DELTA) { dxf_ = nxf - xf; dxX_ = nxX - xX; }
-                xf = nxf;
-                xX = nxX;
-              }
-              STAMP(10);
-            };
-            while (iter <= p.max_iter) {
-              int until = p.max_iter - iter + 1;
-              if (chk_on && to_check < until) until = to_check;
-              if (adp_on && to_adapt < until) until = to_adapt;
-              double dyv[3], dxf_, dxX_;
-              RhsOps ops;
-              if constexpr (!H) load_rhs_ops(ops);
-              double cvp[CK_COUNT];
-#pragma nounroll
-              for (int r_ = 1; r_ < until; ++r_, ++iter)
-                ki_iter(std::integral_constant<int, 0>{}, ops, dyv, dxf_, dxX_, cvp);
-              ki_iter(std::integral_constant<int, 1>{}, ops, dyv, dxf_, dxX_, cvp);
-              const bool can_check = chk_on && (to_check -= until) == 0;
-              if (can_check) to_check = p.check_termination;
-              const bool adapt = adp_on && (to_adapt -= until) == 0;
-              if (adapt) to_adapt = p.adaptive_rho_interval;
-              last_checked = can_check;
-              if constexpr (H) {
-                sync_all();  // infeas_cheap's publication
-                sync_all();  // update_info: the stage waves' residual terms
-                info_combine(std::true_type{}, cvp, sh.red, 32);
-                sync_all();
-              } else {
-                infeas_cheap(dyv, dxf_, dxX_, cvp);
-                update_info(std::true_type{}, cvp);
-              }
-              if (inf_need) infeas_products(role, dxf_, dxX_, cvp);
-              // the checks published into the summed right-hand sides' buffers: zero them again,
-              // and a barrier before the next iteration sums into them
-              if constexpr (!H) {
-                if (cl) { ki_rsum(0)[12 * k + ph] = 0.0; ki_rsum(1)[12 * k + ph] = 0.0; }
-              }
-              sync_all();
-              if (!(isfinite(pri_res) && isfinite(dua_res))) { MPCQ_SET_XST(MPCQ_STATUS_NONFINITE); break; }
-              if (can_check) {
-                if (converged(1.0)) { MPCQ_SET_XST(MPCQ_STATUS_SOLVED); break; }
-                if (inf_bits & 1) { MPCQ_SET_XST(MPCQ_STATUS_PRIMAL_INFEASIBLE); break; }
-                if (inf_bits & 2) { MPCQ_SET_XST(MPCQ_STATUS_DUAL_INFEASIBLE); break; }
-              }
-              if (adapt) {
-                double rn = rho_s * sqrt(s_pri / (s_dua + kDivTol));
-                rn = fmin(fmax(rn, kRhoMin), kRhoMax);
-                if (rn > rho_s * p.adaptive_rho_tolerance || rn < rho_s / p.adaptive_rho_tolerance) {
-                  rho_s = rn;
-                  if constexpr (!H) {
-                    set_rho();
-                    zc_store();
-                  }
-                  refactor = true;
-                  ++n_upd;
-                  ++iter;
-                  sync_all();
-                  break;
-                }
-              }
-              STAMP(11);
-              ++iter;
-            }
-            if (!refactor) break;
-          }
-          sync_all();  // thread 0's exit status (kXstLds)
-          if constexpr (!H) status = sh.flag[4];
-        };
-        static_assert(!KI || kXstLds<N>, "the explicit inverse reads the exit status from LDS");
-        if (wvu() >= NW) {  // the helpers: nothing of theirs is an output
-          kinv_admm(std::true_type{});
-          return;
-        }
-        kinv_admm(std::false_type{});
-      } else {
       // a resumed slice continues the saved loop counters; slice_iters > 0 suspends at the
       // first segment end slice_iters iterations on (mpcq_set_slice)
       if (kSlice<N> && a.resume) {
@@ -3592,7 +2816,7 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
         const uint64_t ft0_ = __builtin_amdgcn_s_memtime();
 #endif
 #pragma nounroll
-        for (int rep_ = 0; rep_ < MPCQ_REP_FACTOR; ++rep_) fac_ok = factor(std::false_type{}, p.sigma, nullptr);  // > 1: timing only
+        for (int rep_ = 0; rep_ < MPCQ_REP_FACTOR; ++rep_) fac_ok = factor(p.sigma, nullptr);  // > 1: timing only
 #ifdef MPCQ_FACTIME
         fac_cycles += __builtin_amdgcn_s_memtime() - ft0_;
 #endif
@@ -3616,9 +2840,7 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
           // register budget of the 9..16-wave workgroups -- N = 48: scratch 840 -> 712 B
           // per lane, 17.68 -> 16.75 us per iteration, profiles/r03c_iterbench.txt)
           ph_rhs(true, kBig<N> ? nullptr : &ops, kNoW, 0.0, 0.0, uf, beta);
-          [[maybe_unused]] RecPre pre_;
-          if constexpr (kND<N>) ph_sweep_nd(&pre_);
-          else ph_sweep();
+          ph_sweep();
           // DELTA (the last iteration before a check): the check's constant block is read
           // here, its memory latency behind the force recovery and the z / y / x update
           if constexpr (DELTA) ck_all(cvp);
@@ -3631,7 +2853,7 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
               zl[j] = q[ZC_LO + j]; zh[j] = q[ZC_HI + j]; zrr[j] = q[ZC_RR + j]; zri[j] = q[ZC_RI + j];
             }
           } else {
-            ph_recover(kBig<N> ? nullptr : &ops, ri[0], uf, beta, sf, sX, ax, kND<N> ? &pre_ : nullptr);
+            ph_recover(kBig<N> ? nullptr : &ops, ri[0], uf, beta, sf, sX, ax);
 #pragma unroll
             for (int j = 0; j < 3; ++j) { zl[j] = lo_of(j); zh[j] = hi_of(j); zrr[j] = rr[j]; zri[j] = ri[j]; }
           }
@@ -3687,7 +2909,7 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
           // live (osqp's update_info after the loop when the last iteration was unchecked)
           infeas_cheap(dyv, dxf_, dxX_, cvp);
           update_info(std::true_type{}, cvp);
-          if (inf_need) infeas_products(std::false_type{}, dxf_, dxX_, cvp);
+          if (inf_need) infeas_products(dxf_, dxX_, cvp);
           if (!(isfinite(pri_res) && isfinite(dua_res))) { MPCQ_SET_XST(MPCQ_STATUS_NONFINITE); break; }
           if (can_check) {  // osqp check_termination
             if (converged(1.0)) { MPCQ_SET_XST(MPCQ_STATUS_SOLVED); break; }
@@ -3756,7 +2978,6 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
         sync_all();  // thread 0's exit status
         status = sh.flag[4];
       }
-      }  // !KI
       if constexpr (kXstRe<N>) {  // the exit's reason, as the loop tested it (kXstRe)
         if (sh.flag[2] != 0) status = MPCQ_STATUS_FACTOR_FAILED;
         else if (iter <= p.max_iter) {
@@ -3852,7 +3073,7 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
               if (same) break;
             }
             ++pol_rounds;
-            if (!factor(std::false_type{}, p.sigma, prho)) break;
+            if (!factor(p.sigma, prho)) break;
 #pragma unroll
             for (int j = 0; j < 3; ++j) { rr[j] = prho[j]; ri[j] = act[j] ? 1.0 / kPolishRho : 0.0; }
             // one proximal multiplier step from the ADMM point (x, y on the active rows),
@@ -4005,20 +3226,20 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
 template <int N>
 hipError_t launch_t(bool fused, bool solve, const mpcq_params& p, const LaunchArgs& a,
                     hipStream_t s) {
-  const dim3 grid((unsigned)a.batch), block(16 * kRows<N>), block2(16 * kRows<N> * (kKinv<N> ? 2 : 1));
-  if ((kBig<N> || kND<N>) && solve && !a.work) return hipErrorInvalidValue;  // the caller sizes it with work_doubles(N)
+  const dim3 grid((unsigned)a.batch), block(16 * kRows<N>);
+  if (kBig<N> && solve && !a.work) return hipErrorInvalidValue;  // the caller sizes it with work_doubles(N)
   // polish lives in its own instantiation: the production kernel's code (and its
   // register allocation in the ADMM loop) does not carry it
   const bool pol = p.polish != 0;
   const bool rob = a.robots != nullptr && (fused || !solve);
   if (rob && !solve) hipLaunchKernelGGL((engine_kernel<N, true, false, false, true>), grid, block, 0, s, p, a);
   else if (rob && pol) hipLaunchKernelGGL((engine_kernel<N, true, true, true, true>), grid, block, 0, s, p, a);
-  else if (rob) hipLaunchKernelGGL((engine_kernel<N, true, true, false, true>), grid, block2, 0, s, p, a);
+  else if (rob) hipLaunchKernelGGL((engine_kernel<N, true, true, false, true>), grid, block, 0, s, p, a);
   else if (!solve) hipLaunchKernelGGL((engine_kernel<N, true, false, false>), grid, block, 0, s, p, a);
   else if (fused && pol) hipLaunchKernelGGL((engine_kernel<N, true, true, true>), grid, block, 0, s, p, a);
-  else if (fused) hipLaunchKernelGGL((engine_kernel<N, true, true, false>), grid, block2, 0, s, p, a);
+  else if (fused) hipLaunchKernelGGL((engine_kernel<N, true, true, false>), grid, block, 0, s, p, a);
   else if (pol) hipLaunchKernelGGL((engine_kernel<N, false, true, true>), grid, block, 0, s, p, a);
-  else hipLaunchKernelGGL((engine_kernel<N, false, true, false>), grid, block2, 0, s, p, a);
+  else hipLaunchKernelGGL((engine_kernel<N, false, true, false>), grid, block, 0, s, p, a);
   return hipGetLastError();
 }
 
@@ -4031,9 +3252,7 @@ hipError_t launch_t(bool fused, bool solve, const mpcq_params& p, const LaunchAr
 #endif
 static_assert(MPCQ_ENGINE_N >= 4 && kRows<MPCQ_ENGINE_N> <= 64, "horizons 4..64 (1024 threads at most)");
 static_assert(sizeof(Smem<MPCQ_ENGINE_N>) <= 160 * 1024, "Smem<N> exceeds the CU's LDS");
-static_assert(sizeof(Smem<MPCQ_ENGINE_N, kKinv<MPCQ_ENGINE_N>>) <= 160 * 1024, "Smem<N, KI> exceeds the CU's LDS");
-static_assert(Work<MPCQ_ENGINE_N>::SIZE == ((kBig<MPCQ_ENGINE_N> || kND<MPCQ_ENGINE_N>) ? work_doubles(MPCQ_ENGINE_N)
-                                                                                   : 72 + Work<MPCQ_ENGINE_N>::ZERO),
+static_assert(!kBig<MPCQ_ENGINE_N> || Work<MPCQ_ENGINE_N>::SIZE == work_doubles(MPCQ_ENGINE_N),
               "work_doubles(N) (mpcq_internal.h) and Work<N> disagree");
 static_assert(kRows<MPCQ_ENGINE_N> > 16 || sizeof(Smem<MPCQ_ENGINE_N>) <= 80 * 1024,
               "Smem<N> must fit twice in a CU for N <= 16");
@@ -4044,8 +3263,5 @@ hipError_t MPCQ_CAT(engine_launch_n, MPCQ_ENGINE_N)(bool fused, bool solve, cons
                                                    const LaunchArgs& a, hipStream_t s) {
   return launch_t<MPCQ_ENGINE_N>(fused, solve, p, a, s);
 }
-// whether this unit holds the sliced-solve code (mpcq_dispatch.cpp slice_supported: the host
-// slices a solve only where the engine can suspend and resume)
-bool MPCQ_CAT(engine_slice_n, MPCQ_ENGINE_N)() { return kSlice<MPCQ_ENGINE_N>; }
 
 }  // namespace mpcq

@@ -31,7 +31,7 @@ struct LaunchArgs {
   double* rho_out;     // [B]
   int32_t* info;       // [B][4]: rho updates, polish status, polish rounds, reserved
   uint64_t* stamps;    // [B][16] diagnostic build only (MPCQ_STAMPS): cycles per phase
-  double* work;        // [B][work_doubles(N)] engine workspace (N > 32 and the nested-dissection horizons)
+  double* work;        // [B][work_doubles(N)] engine workspace (N > 32)
   const int32_t* order; // [B] instance solved by workgroup i (a permutation of 0..B-1), or null: i
   // sliced solves (mpcq_set_slice): slice_iters > 0 suspends an instance at the first segment
   // end (a check / adaptive-rho / max_iter boundary of the ADMM loop) after slice_iters more
@@ -68,36 +68,23 @@ constexpr int64_t res_lanes(int N) { return 16 * (int64_t)((N + 3) & ~3); }
 // a zero block (72), beyond 49 stages the scaled constraint values (126 N - 18,
 // rounded up to even), beyond 48 every lane's row of F_k (12 x 16 x the stage rows, N
 // rounded up to 4); the F W block stays reserved (F W lives in LDS since round 3)
-// (-DMPCQ_OCC16=3/4, an experiment: the 16-stage kernel in the beyond-32 layout, its
-// scaled constraint values in the workspace too -- mpcq_engine.hip kOcc)
-#if defined(MPCQ_OCC3) && !defined(MPCQ_OCC16)
-#define MPCQ_OCC16 3
-#elif defined(MPCQ_OCC4) && !defined(MPCQ_OCC16)
-#define MPCQ_OCC16 4
-#endif
-#ifdef MPCQ_OCC16
-constexpr bool work_occ16(int N) { return N == 16 && MPCQ_OCC16 > 2; }
-#else
-constexpr bool work_occ16(int) { return false; }
-#endif
-// The nested-dissection state solve (mpcq_engine.hip kND, round 6; an opt-in variant: measured
-// slower than the two-ended sweep): at these horizons the scaled
-// constraint values live in the workspace (72-double zero block + 126 N - 18, rounded up to
-// even), which frees the LDS for the separator's spikes.  -DMPCQ_ND: N = 32; -DMPCQ_ND16: N = 16
-// and 32.  Without either (the production build) the round-5 two-ended sweep at every horizon.
-#if defined(MPCQ_ND16)
-constexpr bool nd_layout(int N) { return N == 32 || N == 16; }
-#elif defined(MPCQ_ND)
-constexpr bool nd_layout(int N) { return N == 32; }
-#else
-constexpr bool nd_layout(int) { return false; }
-#endif
+// (One formula: the layouts that had their own -- three or four 16-stage instances per CU, the
+// nested-dissection solve -- were measured slower and removed; their code is kept as
+// tools/attic/engine_variants_round6.patch, their measurements in DESIGN.md sections 8b item 4
+// and 8 item 1.)
 constexpr int64_t work_doubles(int N) {
-  if (nd_layout(N)) return 72 + ((126 * (int64_t)N - 18 + 1) & ~1);
-  return (N > 32 || work_occ16(N)) ? 288 + (int64_t)N * (144 + 72 + 36) + 2 + 72 + ((N > 49 || work_occ16(N)) ? ((126 * N - 18 + 1) & ~1) : 0) +
+  return N > 32 ? 288 + (int64_t)N * (144 + 72 + 36) + 2 + 72 + (N > 49 ? ((126 * N - 18 + 1) & ~1) : 0) +
                       (N > 48 ? (int64_t)12 * 16 * ((N + 3) & ~3) : 0)
                 : 0;
 }
+static_assert(work_doubles(16) == 0 && work_doubles(32) == 0 && work_doubles(33) == 8678 && work_doubles(48) == 12458 &&
+                  work_doubles(49) == 22694 && work_doubles(50) == 29228 && work_doubles(64) == 36824,
+              "the engine workspace per instance (doubles)");
+// Sliced solves (LaunchArgs::slice_iters / resume): the engine holds the suspend / resume code
+// beyond 16 stages only (mpcq_engine.hip kSlice), and the host takes its two-launch path only
+// there: a unit without the code ignores slice_iters, resume and batch_dev.
+constexpr bool slice_supported(int N) { return N > 16; }
+static_assert(!slice_supported(16) && slice_supported(17), "slicing starts at 17 stages");
 
 // Planner launch (mpcq_planner.hip); layouts in include/mpcq.h (mpcq_plan_batch).
 struct PlanArgs {
@@ -313,8 +300,6 @@ hipError_t launch_solve(int N, bool fused, const mpcq_params& p, const LaunchArg
   X(41) X(42) X(43) X(44) X(45) X(46) X(47) X(48) X(49) X(50) X(51) X(52) X(53) X(54) X(55) X(56) X(57) X(58)  \
   X(59) X(60) X(61) X(62) X(63) X(64)
 bool horizon_supported(int N);
-// whether horizon N's engine unit was compiled with the sliced-solve code (its kSlice<N>)
-bool slice_supported(int N);
 int supported_horizons(int32_t* out, int cap);
 
 }  // namespace mpcq

@@ -410,9 +410,10 @@ def test_short_slice_of_a_warm_solve_ignores_a_cold_call_s_samples(trot20):
 
 
 def test_slice16_in_the_environment_does_not_slice_the_default_library(monkeypatch):
-    """MPCQ_SLICE16=1 (the switch of an experiment build) against the default library, whose
-    16-stage engine holds no suspend / resume code: the solve must not take the two-launch
-    path (its second launch would read a list nobody wrote) -- one launch, the same bits."""
+    """MPCQ_SLICE16=1 (once the switch of an experiment build; nothing reads it any more) against
+    the library, whose 16-stage engine holds no suspend / resume code: the solve must not take
+    the two-launch path (its second launch would read a list nobody wrote) -- one launch, the
+    same bits."""
     import mpcq
     from mpcq import synth
     # the library that answers this query is the one that gates slicing on the engine's build

@@ -1,7 +1,5 @@
 """CPU: round-6 host logic -- the bench line's workload label for shard runs, the reference25
-reading's mode, the class-order flag's value in the header and the bindings, and the
-nested-dissection horizons' workspace size (mpcq_internal.h) as the engine's static layout
-states it."""
+reading's mode, and the class-order flag's value in the header and the bindings."""
 import os
 import re
 import sys
@@ -36,14 +34,3 @@ def test_class_order_flag_matches_the_header():
     from mpcq import _lib
     assert _lib.FLAG_ORDER_BY_CLASS == int(m.group(1))
     assert _lib.FLAG_ORDER_BY_CLASS & (_lib.FLAG_DEVICE_PTRS | _lib.FLAG_ASYNC) == 0
-
-
-def test_nd_workspace_size_formula():
-    """work_doubles(N) at the nested-dissection horizons: a 72-double zero block and the
-    scaled constraint values (126 N - 18, rounded up to even) -- mirrored from
-    mpcq_internal.h (the engine static_asserts Work<N>::SIZE against it)."""
-    src = open(os.path.join(REPO, "mpc-tsid_amd", "csrc", "mpcq_internal.h")).read()
-    m = re.search(r"#elif defined\(MPCQ_ND\)\nconstexpr bool nd_layout\(int N\) \{ return N == (\d+); \}", src)
-    assert m and int(m.group(1)) == 32
-    assert "#else\nconstexpr bool nd_layout(int) { return false; }" in src  # the production build
-    assert "if (nd_layout(N)) return 72 + ((126 * (int64_t)N - 18 + 1) & ~1);" in src

@@ -1,6 +1,6 @@
 """CPU: the engine's opt-in compile switches still build (mpc-tsid_amd/csrc/Makefile
 `variants`: MPCQ_FR_HELD / ZC_HELD / SPLIT_OUT / NO_LDS_ZERO / FACTIME / STAMPS /
-DEBUG_* at horizons where each changes the code).  Compile only, nothing runs: the
+DEBUG_PIVOT / DEBUG_POLISH / GJ_NORM at horizons where each changes the code).  Compile only, nothing runs: the
 objects are rebuilt when the engine source is newer than them (a few minutes after an
 engine edit, seconds otherwise)."""
 import os
