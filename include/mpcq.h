@@ -61,7 +61,11 @@ extern "C" {
  *      mpcq_scenario_step_batch, mpcq_session_enable_scenario / _disable_scenario /
  *      _scenario_read / _scenario_device_ptr (per-episode random commands, pushes and payloads
  *      drawn on the device); its arrays have ids of their own, MPCQ_CV_*; with a scenario that
- *      commands, mpcq_session_tick and mpcq_session_run accept v_ref == NULL */
+ *      commands, mpcq_session_tick and mpcq_session_run accept v_ref == NULL
+ *   3 (additions, no bump): mpcq_snapshot, mpcq_session_snapshot_create / _destroy / _save /
+ *      _restore / _bytes / _export / _import, mpcq_session_fork, mpcq_debug_gather_rows (save,
+ *      restore and branch a session's robots on the device); no new array id: MPCQ_SV_COUNT
+ *      stays 21 */
 #define MPCQ_ABI_VERSION 3
 
 /* error codes (return values) */
@@ -832,6 +836,89 @@ int mpcq_session_scenario_read(mpcq_session* s, int what, void* dst, uint32_t fl
 /* Device address of array `what` (valid until mpcq_session_destroy). */
 int mpcq_session_scenario_device_ptr(mpcq_session* s, int what, void** out);
 
+/* ---- snapshots: save, restore and branch robots on the device ---------------
+ * A snapshot is a device-resident copy of everything per-robot that a session holds, plus the
+ * few host flags that decide what the next tick launches.  Every call below runs on the
+ * context's stream: behind the ticks already queued, ahead of later ones.  No reference
+ * counterpart (the reference runs one robot forward).
+ *
+ * What a snapshot holds: every array of every group the session has allocated when it is
+ * saved -- the main group (MPCQ_SV_F0 .. _H_ROT, MPCQ_SV_FIRST, the warm start, the planner's
+ * status, the engine's info, the creation gait table), the swing arrays (after
+ * mpcq_session_enable_swing), MPCQ_PV_* (after _enable_plant / _set_wrench), MPCQ_MV_* (after
+ * _enable_monitor), MPCQ_CV_* (after _enable_scenario), and the tables of
+ * mpcq_session_set_robots / _set_plant_robots where in force -- and its shape: N, B, which of
+ * these exist, the swing k_mpc; and whether a tick has run since create and whether a reset
+ * was ever called.  Not held: the staging of host inputs and the plant's copy of q_w (every
+ * tick rewrites them before reading), and MPCQ_SV_ORDER (a permutation, not a per-robot row;
+ * the restore rebuilds it, and results do not depend on it).  Parameters and enable flags
+ * (swing, plant, monitor, scenario parameters; _enable_* / _disable_*) are configuration, not
+ * robots' state: the session's own, never touched.
+ *
+ * create: no device memory until the first save.  The snapshot belongs to s's context (hence
+ * its N and stream) and may be restored into any session of that context.  A snapshot may be
+ * destroyed after its session; one whose session is gone is good for _destroy, _bytes and
+ * _export, and for a restore into another session of the context.  Destroy every snapshot
+ * before mpcq_destroy of the context.  destroy(NULL) is MPCQ_OK. */
+typedef struct mpcq_snapshot mpcq_snapshot;
+int mpcq_session_snapshot_create(mpcq_session* s, mpcq_snapshot** out);
+int mpcq_session_snapshot_destroy(mpcq_snapshot* snap);
+/* Capture s as it stands behind the queued ticks: whole-array device-to-device copies.
+ * Saving again re-captures, and reallocates when the shape changed (one allocation per group;
+ * a failed one leaves the snapshot as it was).  Blocking unless flags has MPCQ_FLAG_ASYNC (a
+ * save that has to allocate blocks all the same). */
+int mpcq_session_snapshot_save(mpcq_session* s, mpcq_snapshot* snap, uint32_t flags);
+/* Robot b of s takes row map[b] of snap; map [B_session] int32, -1 = leave this robot alone
+ * (not one byte of it is written).  The same row may appear any number of times (branching);
+ * the snapshot's batch may differ from the session's (seeding).  map == NULL: the identity
+ * over every robot; it needs B_snapshot == B_session and also restores the batch-wide
+ * MPCQ_MV_TOTALS, which a mapped restore leaves alone.
+ * Requirements, else MPCQ_E_INVALID naming the first difference, with nothing launched and
+ * the session as it was: snap saved; the same context; the same shape as at the save (the same
+ * groups allocated, the same swing k_mpc, each table in force or not as then); a host map's
+ * entries -1 or in [0, B_snapshot) (the message names the first offending index); and a mapped
+ * restore of ticked state into a session that has not ticked yet covers every robot (no -1;
+ * the others would run a warm tick on creation state), from a host map.
+ * map is a host pointer (the call blocks) or, with MPCQ_FLAG_DEVICE_PTRS, a device pointer
+ * (with | MPCQ_FLAG_ASYNC the call enqueues and returns, as mpcq_session_reset).  A device
+ * map cannot be validated: an entry outside [0, B_snapshot) acts as -1.
+ * A restored robot gets its row of every array the snapshot holds, in ONE launch
+ * (gather_rows_kernel).  After it, where the session or the snapshot has a dispatch order in
+ * use, MPCQ_SV_ORDER is rebuilt from the restored iteration counts and pending resets.  A
+ * reset recorded in the snapshot stays recorded in the session.
+ * A snapshot saved before any tick holds creation state, which only a first tick may consume:
+ * its rows come with MPCQ_SV_FIRST[b] = 1, so restoring such a row is exactly a pending
+ * mpcq_session_reset of that robot.
+ * k stays the caller's: after restoring ticked state, call the next tick with k > 0 (the
+ * planner and the engine read k only as zero or non-zero).
+ * Scenarios: the draws are a function of (seed, slot b, epoch, tau).  A robot restored into
+ * slot b inherits the source's MPCQ_CV_EPOCH, _TICK and the running episode's true robot
+ * (MPCQ_CV_ROBOTS, MPCQ_CV_DRAW); from the next tick on it draws slot b's own commands and
+ * pushes at that (epoch, tau): branches of one robot live through different futures from one
+ * state.  On the host a branch's constants are those of (map[b], epoch) for the running
+ * episode and of (b, epoch) from its next restart on. */
+int mpcq_session_snapshot_restore(mpcq_session* s, const mpcq_snapshot* snap, const int32_t* map,
+                                  uint32_t flags);
+/* Save into a snapshot the session owns (made on first use, freed by mpcq_session_destroy),
+ * then restore from it with map (not NULL): the one-call form of branching inside a live
+ * session.  The source is never the live arrays: map may be any mapping. */
+int mpcq_session_fork(mpcq_session* s, const int32_t* map, uint32_t flags);
+/* Checkpoint to the host.  One blob = a 128-byte header, then the groups' arrays unpadded, in
+ * the order main, swing, plant, monitor, scenario, robots table, plant robots table, inside a
+ * group by array id (the private main arrays behind the named ones).  The header, little
+ * endian: char magic[8] "MPCQSNP1"; uint32 version (1); int32 N; int64 B; int32 k_mpc (0: no
+ * swing arrays); uint32 flags (bit 0 a tick had run, 1 a reset was recorded, 2 swing, 3 plant,
+ * 4 monitor, 5 scenario, 6 robots table, 7 plant robots table); int64 group_bytes[7]; int64
+ * total (header included); int64 user (0; for the caller, ignored by import); zeros.
+ * _bytes: the size of snap's blob (snap saved).  _export: dst is a host buffer of exactly
+ * that many bytes; blocking.  _import: makes snap the snapshot the blob describes, for s's
+ * context; before it touches the device it checks the magic, the version, N against the
+ * context, and that the group byte counts follow from the header's shape and sum to `bytes`: a
+ * truncated or foreign blob is MPCQ_E_INVALID and snap stays as it was. */
+int mpcq_session_snapshot_bytes(const mpcq_snapshot* snap, int64_t* bytes);
+int mpcq_session_snapshot_export(const mpcq_snapshot* snap, void* dst, int64_t bytes);
+int mpcq_session_snapshot_import(mpcq_session* s, mpcq_snapshot* snap, const void* src, int64_t bytes);
+
 /* ---- diagnostics -----------------------------------------------------------
  * Device buffer [B][16] (uint64) that a diagnostic build of the library
  * (compiled with -DMPCQ_STAMPS, libmpcq_stamps.so) fills with per-phase
@@ -875,6 +962,16 @@ int mpcq_debug_session_order(mpcq_ctx* ctx, int64_t batch, const int32_t* iters,
  * listed instance is the key it was ranked by (sliced only; otherwise untouched). */
 int mpcq_debug_last_dispatch(mpcq_ctx* ctx, int64_t* batch, int32_t* sliced, int32_t* by_class,
                              int32_t* cls, int32_t* order, int32_t* list, int32_t* count, double* key);
+
+/* The restore's gather kernel on its own (tests/test_gpu_snapshot.py pins it to numpy's fancy
+ * indexing): n arrays (at most 48); array i has rows of row_bytes[i] bytes (a multiple of 4),
+ * src[i] rows_src of them, dst[i] rows_dst; dst row b <- src row map[b] for every i, in one
+ * launch; an entry outside [0, rows_src) leaves row b alone; map NULL = the identity.  src,
+ * dst and row_bytes are host tables; what src[i], dst[i] and map point to is host memory, or
+ * device memory (4-byte aligned) with MPCQ_FLAG_DEVICE_PTRS (| MPCQ_FLAG_ASYNC: not blocking). */
+int mpcq_debug_gather_rows(mpcq_ctx* ctx, int n, const void* const* src, void* const* dst,
+                           const int64_t* row_bytes, int64_t rows_src, int64_t rows_dst,
+                           const int32_t* map, uint32_t flags);
 
 #ifdef __cplusplus
 }

@@ -290,6 +290,31 @@ struct ScenarioArgs {
 };
 hipError_t launch_scenario(const mpcq_scenario_params& sc, const ScenarioArgs& a, hipStream_t s);
 
+// Row gather of a snapshot restore (mpcq_snapshot.hip; semantics in include/mpcq.h,
+// mpcq_session_snapshot_restore / mpcq_debug_gather_rows): row b of every dst array <- row
+// map[b] of its src array, in one launch.  The table travels in the kernel arguments.
+constexpr int kGatherMax = 48;      // arrays per launch
+constexpr int kGatherNarrow = 32;   // rows up to this many bytes: one lane per robot; above: one wave
+struct GatherDesc {
+  const void* src;    // rows_src rows of row_bytes
+  void* dst;          // rows_dst rows of row_bytes
+  int32_t row_bytes;  // a multiple of vec
+  int32_t vec;        // bytes per access: 16, 8 or 4 (what row_bytes and both bases are aligned to)
+};
+struct GatherArgs {
+  int64_t rows_src, rows_dst;
+  const int32_t* map;  // [rows_dst] or null: the identity; an entry outside [0, rows_src) = skip this robot
+  int32_t* first;      // [rows_dst] or null: set to 1 for every robot that is written
+  // d[0 .. n_wide): row_bytes > kGatherNarrow, sorted by vec: [0, n_wide16) 16, [n_wide16, n_wide8) 8,
+  // [n_wide8, n_wide) 4; d[n_wide .. n): the others
+  int32_t n_wide16, n_wide8, n_wide, n;
+  GatherDesc d[kGatherMax];
+};
+// The access width for an array: the widest of 16 / 8 / 4 that divides row_bytes and both
+// addresses, or 0 (not a multiple of 4).
+int gather_vec(const void* src, const void* dst, int64_t row_bytes);
+hipError_t launch_gather_rows(const GatherArgs& a, hipStream_t s);
+
 // Launchers (mpcq_engine.hip).  Return hipError_t.
 hipError_t launch_formulate(int N, const mpcq_params& p, const LaunchArgs& a, hipStream_t s);
 hipError_t launch_solve(int N, bool fused, const mpcq_params& p, const LaunchArgs& a, hipStream_t s);

@@ -7,6 +7,7 @@
 // its launch from the groups' arrays.  All numerics run in the HIP kernels.
 #include <math.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include "mpcq_host.h"
 
@@ -56,6 +57,7 @@ struct mpcq_session {
   mpcq_scenario_params sc{};
   RobotTable robots;        // mpcq_session_set_robots (the session's own, not the context's)
   RobotTable plant_robots;  // mpcq_session_set_plant_robots
+  mpcq_snapshot* fork_snap = nullptr;  // mpcq_session_fork's own, made on first use
 };
 
 namespace {
@@ -79,6 +81,23 @@ size_t sv_bytes(int what, int64_t B, int N) {
     case SP_INFO: return b * 16;
   }
   return 0;  // (the swing arrays exist from mpcq_session_enable_swing on)
+}
+
+// Bytes of the arrays of the other groups: the one statement, for the enables that allocate them
+// and for the snapshots that mirror them.
+void swing_bytes(size_t B, int k_mpc, size_t nb[3]) {  // MPCQ_SV_SWING_REF, _SWING_STATE, _FRAME
+  nb[0] = B * k_mpc * 36 * 8; nb[1] = B * 4 * MPCQ_SWING_STATE * 8; nb[2] = B * 24;
+}
+void plant_bytes(size_t B, size_t nb[PP_COUNT]) {  // STATE_END, F_EFF, WRENCH, qw_prev
+  nb[MPCQ_PV_STATE_END] = B * 96; nb[MPCQ_PV_F_EFF] = B * 96; nb[MPCQ_PV_WRENCH] = B * 48; nb[PP_QW_PREV] = B * 48;
+}
+void monitor_bytes(size_t B, size_t nb[MPCQ_MV_COUNT]) {  // DONE, EP, EP_TICKS, EPISODES, LAST, TOTALS
+  const size_t m[MPCQ_MV_COUNT] = {B * 4, B * 64, B * 4, B * 4, B * 128, 64};
+  for (int w = 0; w < MPCQ_MV_COUNT; ++w) nb[w] = m[w];
+}
+void scenario_bytes(size_t B, size_t nb[MPCQ_CV_COUNT]) {  // EPOCH, TICK, V_REF, PUSH, WRENCH, ROBOTS, DRAW
+  const size_t c[MPCQ_CV_COUNT] = {B * 4, B * 4, B * 48, B * 48, B * 48, B * sizeof(mpcq_robot), B * 64};
+  for (int w = 0; w < MPCQ_CV_COUNT; ++w) nb[w] = c[w];
 }
 
 // n arrays of nb[i] bytes, each 256-B aligned, in one allocation zeroed on the context's
@@ -183,8 +202,8 @@ hipError_t enqueue_reset(mpcq_session* s, const int32_t* mask, const double* gai
 // The plant's arrays, all zero: made by the first mpcq_session_enable_plant / _set_wrench.
 int ensure_plant_mem(mpcq_session* s) {
   if (s->pv.mem) return MPCQ_OK;
-  const size_t B = (size_t)s->B;
-  const size_t nb[PP_COUNT] = {B * 96, B * 96, B * 48, B * 48};  // STATE_END, F_EFF, WRENCH, qw_prev
+  size_t nb[PP_COUNT];
+  plant_bytes((size_t)s->B, nb);
   return alloc_group(s->ctx, "the plant arrays", PP_COUNT, nb, &s->pv.mem, s->pv.ptr, s->pv.bytes);
 }
 
@@ -299,6 +318,7 @@ int mpcq_session_destroy(mpcq_session* s) {
     if (s->plant_robots.dev) (void)hipFree(s->plant_robots.dev);
     if (s->mv.mem) (void)hipFree(s->mv.mem);
     if (s->cv.mem) (void)hipFree(s->cv.mem);
+    (void)mpcq_session_snapshot_destroy(s->fork_snap);
   }
   delete s;
   return MPCQ_OK;
@@ -347,8 +367,8 @@ int mpcq_session_enable_swing(mpcq_session* s, const mpcq_swing_params* sp) {
     s->sp = P;
     return MPCQ_OK;
   }
-  const size_t B = (size_t)s->B;
-  const size_t nb[3] = {B * P.k_mpc * 36 * 8, B * 4 * MPCQ_SWING_STATE * 8, B * 24};  // all-zero state = new generators
+  size_t nb[3];  // all-zero state = new generators
+  swing_bytes((size_t)s->B, P.k_mpc, nb);
   DeviceGuard g(s->ctx->device);
   rc = alloc_group(s->ctx, "the swing arrays", 3, nb, &s->swing_mem, s->sv.ptr + MPCQ_SV_SWING_REF,
                    s->sv.bytes + MPCQ_SV_SWING_REF);
@@ -409,7 +429,8 @@ int mpcq_session_enable_monitor(mpcq_session* s, const mpcq_monitor_params* mp) 
     mpcq_ctx* c = s->ctx;
     DeviceGuard g(c->device);
     const size_t B = (size_t)s->B;
-    const size_t nb[MPCQ_MV_COUNT] = {B * 4, B * 64, B * 4, B * 4, B * 128, 64};
+    size_t nb[MPCQ_MV_COUNT];
+    monitor_bytes(B, nb);
     double* h = (double*)malloc(nb[MPCQ_MV_EP]);
     if (!h) return fail(MPCQ_E_NOMEM, "host malloc failed");
     for (size_t e = 0; e < B * 8; ++e) h[e] = e % 8 == 4 ? INFINITY : 0.0;
@@ -443,8 +464,8 @@ int mpcq_session_enable_scenario(mpcq_session* s, const mpcq_scenario_params* sc
   int rc = scenario_params(sc, &P);
   if (rc) return rc;
   if (!s->cv.mem) {  // the arrays, zero; the launch gives every robot the draw of epoch 0
-    const size_t B = (size_t)s->B;
-    const size_t nb[MPCQ_CV_COUNT] = {B * 4, B * 4, B * 48, B * 48, B * 48, B * sizeof(mpcq_robot), B * 64};
+    size_t nb[MPCQ_CV_COUNT];
+    scenario_bytes((size_t)s->B, nb);
     DeviceGuard g(s->ctx->device);
     Group cv = s->cv;
     rc = alloc_group(s->ctx, "the scenario arrays", MPCQ_CV_COUNT, nb, &cv.mem, cv.ptr, cv.bytes);
@@ -790,6 +811,505 @@ int mpcq_session_write(mpcq_session* s, int what, const void* src, uint32_t flag
   const hipMemcpyKind kind = (flags & MPCQ_FLAG_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   HIP_TRY(hipMemcpyAsync(s->sv.ptr[what], src, s->sv.bytes[what], kind, s->ctx->stream));
   HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+  return MPCQ_OK;
+}
+
+}  // extern "C"
+
+// ---- snapshots: save, restore and branch robots on the device (include/mpcq.h) ------------
+
+namespace {
+
+// The parts of a snapshot, in the blob's order; each is one allocation (alloc_group).
+enum { G_MAIN, G_SWING, G_PLANT, G_MONITOR, G_SCENARIO, G_ROBOTS, G_PLANT_ROBOTS, G_COUNT };
+const char* const kPartName[G_COUNT] = {"the snapshot's session arrays", "the snapshot's swing arrays",
+                                        "the snapshot's plant arrays", "the snapshot's monitor arrays",
+                                        "the snapshot's scenario arrays", "the snapshot's robots table",
+                                        "the snapshot's plant robots table"};
+
+// What a snapshot's allocations follow from, with the context's N.
+struct SnapShape {
+  int64_t B = 0;
+  int k_mpc = 0;  // 0: no swing arrays
+  bool pv = false, mv = false, cv = false, robots = false, plant_robots = false;
+};
+
+}  // namespace
+
+struct mpcq_snapshot {
+  mpcq_ctx* ctx = nullptr;
+  bool saved = false;
+  SnapShape sh;
+  Group g[G_COUNT];         // ptr / bytes by the part's own array ids; mem null: the part is absent
+  bool have_order = false;  // a tick had run since create
+  bool resets = false;      // mpcq_session_reset had been called
+};
+
+namespace {
+
+SnapShape shape_of(const mpcq_session* s) {
+  SnapShape sh;
+  sh.B = s->B;
+  sh.k_mpc = s->swing ? s->sp.k_mpc : 0;
+  sh.pv = s->pv.mem; sh.mv = s->mv.mem; sh.cv = s->cv.mem;
+  sh.robots = s->robots.count > 0; sh.plant_robots = s->plant_robots.count > 0;
+  return sh;
+}
+
+// The main group's arrays a snapshot holds: not the staging of host inputs (every tick
+// rewrites it before reading), not MPCQ_SV_ORDER (a permutation: rebuilt, never copied by
+// rows), not the swing slots (a part of their own).
+bool main_held(int w) {
+  return w != MPCQ_SV_ORDER && w != MPCQ_SV_SWING_REF && w != MPCQ_SV_SWING_STATE && w != MPCQ_SV_FRAME &&
+         w != SP_IN_STATE && w != SP_IN_LFEET && w != SP_IN_VREF && w != SP_IN_REDUCED && w != SP_IN_GAIT;
+}
+
+// Bytes of every array of every part of a snapshot of this shape (0: not held).
+void snap_sizes(const SnapShape& sh, int N, size_t nb[G_COUNT][SP_COUNT]) {
+  const size_t B = (size_t)sh.B;
+  memset(nb, 0, sizeof(size_t) * G_COUNT * SP_COUNT);
+  for (int w = 0; w < SP_COUNT; ++w)
+    if (main_held(w)) nb[G_MAIN][w] = sv_bytes(w, sh.B, N);
+  if (sh.k_mpc > 0) swing_bytes(B, sh.k_mpc, nb[G_SWING]);
+  if (sh.pv) {
+    plant_bytes(B, nb[G_PLANT]);
+    nb[G_PLANT][PP_QW_PREV] = 0;  // (a tick with the plant takes it before its retrieve)
+  }
+  if (sh.mv) monitor_bytes(B, nb[G_MONITOR]);
+  if (sh.cv) scenario_bytes(B, nb[G_SCENARIO]);
+  if (sh.robots) nb[G_ROBOTS][0] = B * sizeof(mpcq_robot);
+  if (sh.plant_robots) nb[G_PLANT_ROBOTS][0] = B * sizeof(mpcq_robot);
+}
+
+// The session's arrays seen as a snapshot's parts (the arrays a snapshot does not hold: null).
+void session_parts(const mpcq_session* s, Group out[G_COUNT]) {
+  for (int w = 0; w < SP_COUNT; ++w)
+    if (main_held(w)) { out[G_MAIN].ptr[w] = s->sv.ptr[w]; out[G_MAIN].bytes[w] = s->sv.bytes[w]; }
+  if (s->swing)
+    for (int i = 0; i < 3; ++i) {
+      out[G_SWING].ptr[i] = s->sv.ptr[MPCQ_SV_SWING_REF + i]; out[G_SWING].bytes[i] = s->sv.bytes[MPCQ_SV_SWING_REF + i];
+    }
+  if (s->pv.mem)
+    for (int w = 0; w < MPCQ_PV_COUNT; ++w) { out[G_PLANT].ptr[w] = s->pv.ptr[w]; out[G_PLANT].bytes[w] = s->pv.bytes[w]; }
+  if (s->mv.mem)
+    for (int w = 0; w < MPCQ_MV_COUNT; ++w) { out[G_MONITOR].ptr[w] = s->mv.ptr[w]; out[G_MONITOR].bytes[w] = s->mv.bytes[w]; }
+  if (s->cv.mem)
+    for (int w = 0; w < MPCQ_CV_COUNT; ++w) { out[G_SCENARIO].ptr[w] = s->cv.ptr[w]; out[G_SCENARIO].bytes[w] = s->cv.bytes[w]; }
+  const size_t tb = (size_t)s->B * sizeof(mpcq_robot);
+  if (s->robots.count > 0) { out[G_ROBOTS].ptr[0] = s->robots.dev; out[G_ROBOTS].bytes[0] = tb; }
+  if (s->plant_robots.count > 0) { out[G_PLANT_ROBOTS].ptr[0] = s->plant_robots.dev; out[G_PLANT_ROBOTS].bytes[0] = tb; }
+}
+
+// One array of a snapshot (a) next to its counterpart (b; null without one), in the blob's order.
+struct SnapItem {
+  void *a, *b;
+  size_t bytes_a, bytes_b;
+  bool rows;  // per-robot rows (all but MPCQ_MV_TOTALS)
+};
+
+// The table save, restore, fork, export and import all walk: every array parts `a` hold, with
+// the same array of parts `b` (null: none).  An array `a` holds and `b` lacks is an error (-1).
+int list_arrays(const Group a[G_COUNT], const Group* b, SnapItem out[kGatherMax]) {
+  int n = 0;
+  for (int gi = 0; gi < G_COUNT; ++gi)
+    for (int w = 0; w < SP_COUNT; ++w) {
+      if (!a[gi].ptr[w]) continue;
+      if (n == kGatherMax || (b && !b[gi].ptr[w])) return -1;
+      out[n++] = SnapItem{a[gi].ptr[w], b ? b[gi].ptr[w] : nullptr, a[gi].bytes[w], b ? b[gi].bytes[w] : 0,
+                          !(gi == G_MONITOR && w == MPCQ_MV_TOTALS)};
+    }
+  return n;
+}
+
+void free_parts(mpcq_snapshot* p) {
+  for (int gi = 0; gi < G_COUNT; ++gi) {
+    if (p->g[gi].mem) (void)hipFree(p->g[gi].mem);
+    p->g[gi] = Group{};
+  }
+  p->saved = false;
+}
+
+// The allocations of a snapshot of this shape into *p (which holds none): all or nothing.
+int alloc_parts(mpcq_ctx* c, const SnapShape& sh, mpcq_snapshot* p) {
+  size_t nb[G_COUNT][SP_COUNT];
+  snap_sizes(sh, c->N, nb);
+  for (int gi = 0; gi < G_COUNT; ++gi) {
+    size_t tot = 0;
+    for (int w = 0; w < SP_COUNT; ++w) tot += nb[gi][w];
+    if (!tot) continue;
+    const int rc = alloc_group(c, kPartName[gi], SP_COUNT, nb[gi], &p->g[gi].mem, p->g[gi].ptr, p->g[gi].bytes);
+    if (rc) {
+      free_parts(p);
+      return rc;
+    }
+  }
+  p->ctx = c;
+  p->sh = sh;
+  return MPCQ_OK;
+}
+
+// The first difference between a snapshot's shape and a session's, as text; or null.
+const char* shape_difference(const SnapShape& a, const SnapShape& b, bool batch_too) {
+  if (batch_too && a.B != b.B) return "the batch sizes differ (a restore without a map needs the same batch)";
+  if ((a.k_mpc > 0) != (b.k_mpc > 0)) return "the swing arrays exist on one side only";
+  if (a.k_mpc != b.k_mpc) return "the swing k_mpc differs";
+  if (a.pv != b.pv) return "the plant arrays exist on one side only";
+  if (a.mv != b.mv) return "the monitor arrays exist on one side only";
+  if (a.cv != b.cv) return "the scenario arrays exist on one side only";
+  if (a.robots != b.robots) return "the robots table is in force on one side only";
+  if (a.plant_robots != b.plant_robots) return "the plant robots table is in force on one side only";
+  return nullptr;
+}
+
+// A host map: every entry -1 or in [0, rows_src); with `full`, no -1 either.
+int check_host_map(const int32_t* map, int64_t n, int64_t rows_src, bool full) {
+  for (int64_t b = 0; b < n; ++b) {
+    if (map[b] < -1 || map[b] >= rows_src)
+      return fail(MPCQ_E_INVALID, "map[%lld] = %d is neither -1 nor a row of the snapshot (0..%lld)", (long long)b,
+                  map[b], (long long)rows_src - 1);
+    if (full && map[b] == -1)
+      return fail(MPCQ_E_INVALID, "map[%lld] = -1: restoring ticked state into a session that has not ticked yet "
+                  "must cover every robot", (long long)b);
+  }
+  return MPCQ_OK;
+}
+
+// The launch's table from the arrays: the wide ones first, by access width, then the narrow ones.
+int gather_table(const SnapItem* it, int n, int64_t rows_src, int64_t rows_dst, mpcq::GatherArgs* a) {
+  a->n = 0;
+  const int widths[4] = {16, 8, 4, 0};  // the passes: wide by width, then narrow
+  for (int pass = 0; pass < 4; ++pass) {
+    for (int i = 0; i < n; ++i) {
+      if (!it[i].rows) continue;
+      const int64_t rb = (int64_t)(it[i].bytes_a / (size_t)rows_src);
+      if (rb < 4 || rb > INT32_MAX || (size_t)rb * (size_t)rows_src != it[i].bytes_a ||
+          (size_t)rb * (size_t)rows_dst != it[i].bytes_b)
+        return fail(MPCQ_E_INVALID, "array %d: %zu bytes for %lld rows against %zu bytes for %lld rows", i,
+                    it[i].bytes_a, (long long)rows_src, it[i].bytes_b, (long long)rows_dst);
+      const int vec = mpcq::gather_vec(it[i].a, it[i].b, rb);
+      if (!vec) return fail(MPCQ_E_INVALID, "array %d: rows of %lld bytes at %p / %p are not 4-byte aligned", i,
+                            (long long)rb, it[i].a, it[i].b);
+      if (rb > mpcq::kGatherNarrow ? vec != widths[pass] : pass != 3) continue;
+      if (a->n == mpcq::kGatherMax) return fail(MPCQ_E_INVALID, "more than %d arrays", mpcq::kGatherMax);
+      a->d[a->n++] = mpcq::GatherDesc{it[i].a, it[i].b, (int32_t)rb, vec};
+    }
+    if (pass == 0) a->n_wide16 = a->n;
+    if (pass == 1) a->n_wide8 = a->n;
+    if (pass == 2) a->n_wide = a->n;
+  }
+  a->rows_src = rows_src;
+  a->rows_dst = rows_dst;
+  return MPCQ_OK;
+}
+
+int snapshot_save(mpcq_session* s, mpcq_snapshot* p, uint32_t flags) {
+  mpcq_ctx* c = s->ctx;
+  if (p->ctx != c) return fail(MPCQ_E_INVALID, "the snapshot belongs to another context");
+  DeviceGuard dg(c->device);
+  const SnapShape sh = shape_of(s);
+  if (!p->g[G_MAIN].mem || shape_difference(p->sh, sh, true)) {  // the new allocations first
+    mpcq_snapshot fresh;
+    const int rc = alloc_parts(c, sh, &fresh);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));  // a queued restore may still read the old ones
+    free_parts(p);
+    for (int gi = 0; gi < G_COUNT; ++gi) p->g[gi] = fresh.g[gi];
+    p->sh = sh;
+  }
+  Group live[G_COUNT];
+  session_parts(s, live);
+  SnapItem it[mpcq::kGatherMax];
+  const int n = list_arrays(p->g, live, it);
+  if (n < 0) return fail(MPCQ_E_DEVICE, "the snapshot's arrays do not match the session's");
+  for (int i = 0; i < n; ++i)
+    if (it[i].bytes_a != it[i].bytes_b)
+      return fail(MPCQ_E_DEVICE, "the snapshot's array %d has %zu bytes, the session's %zu", i, it[i].bytes_a, it[i].bytes_b);
+  p->saved = false;
+  for (int i = 0; i < n; ++i)
+    HIP_TRY(hipMemcpyAsync(it[i].a, it[i].b, it[i].bytes_a, hipMemcpyDeviceToDevice, c->stream));
+  p->have_order = s->have_order;
+  p->resets = s->resets;
+  p->saved = true;
+  if (!(flags & MPCQ_FLAG_ASYNC)) HIP_TRY(hipStreamSynchronize(c->stream));
+  return MPCQ_OK;
+}
+
+int snapshot_restore(mpcq_session* s, const mpcq_snapshot* p, const int32_t* map, uint32_t flags) {
+  mpcq_ctx* c = s->ctx;
+  if (!p->saved) return fail(MPCQ_E_INVALID, "the snapshot holds nothing: save into it first");
+  if (p->ctx != c) return fail(MPCQ_E_INVALID, "the snapshot belongs to another context");
+  const char* diff = shape_difference(p->sh, shape_of(s), !map);
+  if (diff) return fail(MPCQ_E_INVALID, "the snapshot's shape is not the session's: %s", diff);
+  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
+  // ticked state into a session that has not ticked: a robot left out would run a warm tick on
+  // creation state
+  const bool full = p->have_order && !s->have_order;
+  if (map && dev && full)
+    return fail(MPCQ_E_INVALID, "restoring ticked state into a session that has not ticked yet needs a host map "
+                "(it must cover every robot)");
+  if (map && !dev) {
+    const int rc = check_host_map(map, s->B, p->sh.B, full);
+    if (rc) return rc;
+  }
+  Group live[G_COUNT];
+  session_parts(s, live);
+  SnapItem it[mpcq::kGatherMax];
+  const int n = list_arrays(p->g, live, it);
+  if (n < 0) return fail(MPCQ_E_INVALID, "the snapshot's arrays do not match the session's");
+  mpcq::GatherArgs a{};
+  int rc = gather_table(it, n, p->sh.B, s->B, &a);
+  if (rc) return rc;
+  DeviceGuard dg(c->device);
+  hipError_t e = hipSuccess;
+  a.map = staged(s, dev, map, SP_IN_REDUCED, &e);
+  // creation state, which only a first tick may consume: the rows come with a pending reset
+  a.first = p->have_order ? nullptr : s->sv.i(MPCQ_SV_FIRST);
+  if (e == hipSuccess) e = mpcq::launch_gather_rows(a, c->stream);
+  if (e == hipSuccess && !map && p->sh.mv)  // the batch-wide totals go with the whole batch only
+    e = hipMemcpyAsync(s->mv.ptr[MPCQ_MV_TOTALS], p->g[G_MONITOR].ptr[MPCQ_MV_TOTALS], s->mv.bytes[MPCQ_MV_TOTALS],
+                       hipMemcpyDeviceToDevice, c->stream);
+  if (e == hipSuccess) {
+    if (!p->have_order || p->resets) s->resets = true;
+    if (s->have_order || p->have_order) {  // as enqueue_reset: the pending resets to the front
+      e = mpcq::launch_order(s->sv.i(MPCQ_SV_ITERS), s->resets ? s->sv.i(MPCQ_SV_FIRST) : nullptr, s->B,
+                             s->sv.i(MPCQ_SV_ORDER), c->stream);
+      s->have_order = true;
+    }
+  }
+  if (!(flags & MPCQ_FLAG_ASYNC) || (map && !dev)) {
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = es;
+  }
+  HIP_TRY(e);
+  return MPCQ_OK;
+}
+
+// The blob's header (include/mpcq.h, mpcq_session_snapshot_export).
+struct BlobHeader {
+  char magic[8];
+  uint32_t version;
+  int32_t N;
+  int64_t B;
+  int32_t k_mpc;
+  uint32_t flags;
+  int64_t group_bytes[G_COUNT];
+  int64_t total;
+  int64_t user;
+  int64_t zero[3];
+};
+static_assert(sizeof(BlobHeader) == 128 && G_COUNT == 7, "the blob's header is 128 bytes");
+const char kMagic[8] = {'M', 'P', 'C', 'Q', 'S', 'N', 'P', '1'};
+
+void blob_header(const SnapShape& sh, int N, bool have_order, bool resets, BlobHeader* h) {
+  size_t nb[G_COUNT][SP_COUNT];
+  snap_sizes(sh, N, nb);
+  memset(h, 0, sizeof(*h));
+  memcpy(h->magic, kMagic, 8);
+  h->version = 1; h->N = N; h->B = sh.B; h->k_mpc = sh.k_mpc;
+  h->flags = (have_order ? 1u : 0u) | (resets ? 2u : 0u) | (sh.k_mpc > 0 ? 4u : 0u) | (sh.pv ? 8u : 0u) |
+             (sh.mv ? 16u : 0u) | (sh.cv ? 32u : 0u) | (sh.robots ? 64u : 0u) | (sh.plant_robots ? 128u : 0u);
+  h->total = sizeof(*h);
+  for (int gi = 0; gi < G_COUNT; ++gi) {
+    for (int w = 0; w < SP_COUNT; ++w) h->group_bytes[gi] += (int64_t)nb[gi][w];
+    h->total += h->group_bytes[gi];
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int mpcq_session_snapshot_create(mpcq_session* s, mpcq_snapshot** out) {
+  if (!out) return fail(MPCQ_E_INVALID, "out is NULL");
+  *out = nullptr;
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  mpcq_snapshot* p = new mpcq_snapshot();
+  p->ctx = s->ctx;
+  *out = p;
+  return MPCQ_OK;
+}
+
+int mpcq_session_snapshot_destroy(mpcq_snapshot* p) {
+  if (!p) return MPCQ_OK;
+  if (p->g[G_MAIN].mem) {
+    DeviceGuard g(p->ctx->device);
+    (void)hipStreamSynchronize(p->ctx->stream);
+    free_parts(p);
+  }
+  delete p;
+  return MPCQ_OK;
+}
+
+int mpcq_session_snapshot_save(mpcq_session* s, mpcq_snapshot* p, uint32_t flags) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  if (!p) return fail(MPCQ_E_INVALID, "snapshot is NULL");
+  return snapshot_save(s, p, flags);
+}
+
+int mpcq_session_snapshot_restore(mpcq_session* s, const mpcq_snapshot* p, const int32_t* map, uint32_t flags) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  if (!p) return fail(MPCQ_E_INVALID, "snapshot is NULL");
+  return snapshot_restore(s, p, map, flags);
+}
+
+int mpcq_session_fork(mpcq_session* s, const int32_t* map, uint32_t flags) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  if (!map) return fail(MPCQ_E_INVALID, "map is NULL (a fork needs one)");
+  if (!(flags & MPCQ_FLAG_DEVICE_PTRS)) {  // before anything is launched
+    const int rc = check_host_map(map, s->B, s->B, false);
+    if (rc) return rc;
+  }
+  if (!s->fork_snap) {
+    const int rc = mpcq_session_snapshot_create(s, &s->fork_snap);
+    if (rc) return rc;
+  }
+  const int rc = snapshot_save(s, s->fork_snap, MPCQ_FLAG_ASYNC);
+  if (rc) return rc;
+  return snapshot_restore(s, s->fork_snap, map, flags);
+}
+
+int mpcq_session_snapshot_bytes(const mpcq_snapshot* p, int64_t* bytes) {
+  if (!p || !bytes) return fail(MPCQ_E_INVALID, "NULL argument");
+  if (!p->saved) return fail(MPCQ_E_INVALID, "the snapshot holds nothing: save into it first");
+  BlobHeader h;
+  blob_header(p->sh, p->ctx->N, p->have_order, p->resets, &h);
+  *bytes = h.total;
+  return MPCQ_OK;
+}
+
+int mpcq_session_snapshot_export(const mpcq_snapshot* p, void* dst, int64_t bytes) {
+  if (!p || !dst) return fail(MPCQ_E_INVALID, "NULL argument");
+  if (!p->saved) return fail(MPCQ_E_INVALID, "the snapshot holds nothing: save into it first");
+  BlobHeader h;
+  blob_header(p->sh, p->ctx->N, p->have_order, p->resets, &h);
+  if (bytes != h.total) return fail(MPCQ_E_INVALID, "the blob has %lld bytes, dst %lld", (long long)h.total, (long long)bytes);
+  SnapItem it[mpcq::kGatherMax];
+  const int n = list_arrays(p->g, nullptr, it);
+  if (n < 0) return fail(MPCQ_E_DEVICE, "the snapshot holds more than %d arrays", mpcq::kGatherMax);
+  mpcq_ctx* c = p->ctx;
+  DeviceGuard dg(c->device);
+  memcpy(dst, &h, sizeof(h));
+  size_t off = sizeof(h);
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < n && e == hipSuccess; ++i) {
+    e = hipMemcpyAsync((char*)dst + off, it[i].a, it[i].bytes_a, hipMemcpyDeviceToHost, c->stream);
+    off += it[i].bytes_a;
+  }
+  const hipError_t es = hipStreamSynchronize(c->stream);
+  HIP_TRY(e);
+  HIP_TRY(es);
+  if ((int64_t)off != h.total) return fail(MPCQ_E_DEVICE, "wrote %zu of %lld bytes", off, (long long)h.total);
+  return MPCQ_OK;
+}
+
+int mpcq_session_snapshot_import(mpcq_session* s, mpcq_snapshot* p, const void* src, int64_t bytes) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  if (!p || !src) return fail(MPCQ_E_INVALID, "NULL argument");
+  mpcq_ctx* c = s->ctx;
+  if (p->ctx != c) return fail(MPCQ_E_INVALID, "the snapshot belongs to another context");
+  BlobHeader h;
+  if (bytes < (int64_t)sizeof(h)) return fail(MPCQ_E_INVALID, "%lld bytes are less than a header", (long long)bytes);
+  memcpy(&h, src, sizeof(h));
+  if (memcmp(h.magic, kMagic, 8) != 0) return fail(MPCQ_E_INVALID, "not a snapshot blob (magic)");
+  if (h.version != 1) return fail(MPCQ_E_INVALID, "blob format version %u, this library reads 1", h.version);
+  if (h.N != c->N) return fail(MPCQ_E_INVALID, "the blob is of a context with N = %d, this one has N = %d", h.N, c->N);
+  if (h.B < 1 || h.B > (int64_t)0x7fffffff || h.k_mpc < 0 || h.k_mpc > 65536 || (h.flags >> 8) ||
+      ((h.flags & 4u) != 0) != (h.k_mpc > 0))
+    return fail(MPCQ_E_INVALID, "the blob's header is inconsistent (B %lld, k_mpc %d, flags %#x)", (long long)h.B,
+                h.k_mpc, h.flags);
+  SnapShape sh;
+  sh.B = h.B; sh.k_mpc = h.k_mpc;
+  sh.pv = h.flags & 8u; sh.mv = h.flags & 16u; sh.cv = h.flags & 32u;
+  sh.robots = h.flags & 64u; sh.plant_robots = h.flags & 128u;
+  BlobHeader want;
+  blob_header(sh, c->N, h.flags & 1u, h.flags & 2u, &want);
+  for (int gi = 0; gi < G_COUNT; ++gi)
+    if (h.group_bytes[gi] != want.group_bytes[gi])
+      return fail(MPCQ_E_INVALID, "the blob's part %d has %lld bytes, its shape says %lld", gi,
+                  (long long)h.group_bytes[gi], (long long)want.group_bytes[gi]);
+  if (h.total != want.total || bytes != want.total)
+    return fail(MPCQ_E_INVALID, "the blob says %lld bytes, its shape %lld, the caller %lld (truncated?)",
+                (long long)h.total, (long long)want.total, (long long)bytes);
+  DeviceGuard dg(c->device);
+  mpcq_snapshot fresh;
+  int rc = alloc_parts(c, sh, &fresh);
+  if (rc) return rc;
+  SnapItem it[mpcq::kGatherMax];
+  const int n = list_arrays(fresh.g, nullptr, it);
+  size_t off = sizeof(h);
+  hipError_t e = n < 0 ? hipErrorInvalidValue : hipSuccess;
+  for (int i = 0; i < n && e == hipSuccess; ++i) {
+    e = hipMemcpyAsync(it[i].a, (const char*)src + off, it[i].bytes_a, hipMemcpyHostToDevice, c->stream);
+    off += it[i].bytes_a;
+  }
+  const hipError_t es = hipStreamSynchronize(c->stream);  // (also: a queued restore may still read p's arrays)
+  if (e != hipSuccess || es != hipSuccess) {
+    free_parts(&fresh);
+    return fail(MPCQ_E_DEVICE, "copying the blob to the device failed");
+  }
+  free_parts(p);
+  for (int gi = 0; gi < G_COUNT; ++gi) p->g[gi] = fresh.g[gi];
+  p->sh = sh;
+  p->have_order = h.flags & 1u;
+  p->resets = h.flags & 2u;
+  p->saved = true;
+  return MPCQ_OK;
+}
+
+int mpcq_debug_gather_rows(mpcq_ctx* c, int n, const void* const* src, void* const* dst, const int64_t* row_bytes,
+                           int64_t rows_src, int64_t rows_dst, const int32_t* map, uint32_t flags) {
+  int rc = check_ctx(c, rows_dst);
+  if (!rc) rc = check_ctx(c, rows_src);
+  if (rc) return rc;
+  if (n < 1 || n > mpcq::kGatherMax || !src || !dst || !row_bytes)
+    return fail(MPCQ_E_INVALID, "1..%d arrays and their three tables are required", mpcq::kGatherMax);
+  for (int i = 0; i < n; ++i)
+    if (!src[i] || !dst[i] || row_bytes[i] < 4 || row_bytes[i] % 4 || row_bytes[i] > (1 << 24))
+      return fail(MPCQ_E_INVALID, "array %d: NULL, or rows of %lld bytes (a multiple of 4 is required)", i,
+                  (long long)row_bytes[i]);
+  if (rows_src == 0 || rows_dst == 0) return MPCQ_OK;
+  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
+  DeviceGuard dg(c->device);
+  auto padded = [](size_t b) { return (b + 255) & ~size_t(255); };
+  SnapItem it[mpcq::kGatherMax];
+  void* mem = nullptr;
+  const int32_t* dmap = map;
+  if (!dev) {  // the arrays, destinations included (their other rows must come back as they were), and the map
+    size_t tot = map ? padded((size_t)rows_dst * 4) : 0;
+    for (int i = 0; i < n; ++i) tot += padded((size_t)rows_src * row_bytes[i]) + padded((size_t)rows_dst * row_bytes[i]);
+    if (hipMalloc(&mem, tot) != hipSuccess) return fail(MPCQ_E_NOMEM, "hipMalloc(%zu) failed", tot);
+  }
+  hipError_t e = hipSuccess;
+  size_t off = 0;
+  for (int i = 0; i < n; ++i) {
+    const size_t sb = (size_t)rows_src * row_bytes[i], db = (size_t)rows_dst * row_bytes[i];
+    it[i] = SnapItem{const_cast<void*>(src[i]), dst[i], sb, db, true};
+    if (dev) continue;
+    it[i].a = (char*)mem + off; off += padded(sb);
+    it[i].b = (char*)mem + off; off += padded(db);
+    if (e == hipSuccess) e = hipMemcpyAsync(it[i].a, src[i], sb, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(it[i].b, dst[i], db, hipMemcpyHostToDevice, c->stream);
+  }
+  if (!dev && map) {
+    dmap = (const int32_t*)((char*)mem + off);
+    if (e == hipSuccess) e = hipMemcpyAsync((char*)mem + off, map, (size_t)rows_dst * 4, hipMemcpyHostToDevice, c->stream);
+  }
+  mpcq::GatherArgs a{};
+  rc = e == hipSuccess ? gather_table(it, n, rows_src, rows_dst, &a) : MPCQ_OK;
+  if (!rc && e == hipSuccess) {
+    a.map = dmap;
+    e = mpcq::launch_gather_rows(a, c->stream);
+  }
+  if (!dev)
+    for (int i = 0; i < n && !rc && e == hipSuccess; ++i)
+      e = hipMemcpyAsync(dst[i], it[i].b, it[i].bytes_b, hipMemcpyDeviceToHost, c->stream);
+  if (!dev || !(flags & MPCQ_FLAG_ASYNC)) {
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = es;
+  }
+  if (mem) (void)hipFree(mem);
+  if (rc) return rc;
+  HIP_TRY(e);
   return MPCQ_OK;
 }
 

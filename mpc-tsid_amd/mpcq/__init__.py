@@ -19,6 +19,10 @@ Public surface:
   Scenario          per-episode random commands, pushes and payloads drawn on the device from a
                     counter-based generator (Session.enable_scenario); mpcq.scenario restates
                     the draws on the host, bit for bit
+  Snapshot          a session's robots saved on the device (Session.snapshot): restore them, seed
+                    another session from them, branch one robot into many (Session.restore,
+                    Session.fork), checkpoint them to the host (Snapshot.tobytes,
+                    Session.snapshot_from)
   synth             seeded synthetic inputs shaped like FootstepPlanner's
 """
 from . import synth  # noqa: F401
@@ -43,7 +47,7 @@ from .monitor import Monitor  # noqa: F401
 from .plant import Plant  # noqa: F401
 from . import scenario  # noqa: F401
 from .scenario import Scenario  # noqa: F401
-from .session import Session  # noqa: F401
+from .session import Session, Snapshot  # noqa: F401
 from .swing import Swing  # noqa: F401
 
 __version__ = "0.1.0"

@@ -75,6 +75,7 @@ MV_DONE, MV_EP, MV_EP_TICKS, MV_EPISODES, MV_LAST, MV_TOTALS = range(6)
 TRACE = 16
 # the scenario stage: a session's scenario arrays (MPCQ_CV_*)
 CV_EPOCH, CV_TICK, CV_V_REF, CV_PUSH, CV_WRENCH, CV_ROBOTS, CV_DRAW = range(7)
+SNAPSHOT_USER_OFFSET = 96  # a snapshot blob's header: the int64 left to the caller (include/mpcq.h)
 
 EXPORTS = ("mpcq_abi_version", "mpcq_default_params", "mpcq_dims", "mpcq_pattern",
            "mpcq_supported_horizons", "mpcq_last_error", "mpcq_create", "mpcq_destroy",
@@ -97,7 +98,10 @@ EXPORTS = ("mpcq_abi_version", "mpcq_default_params", "mpcq_dims", "mpcq_pattern
            "mpcq_session_disable_monitor", "mpcq_session_monitor_read", "mpcq_session_monitor_device_ptr",
            "mpcq_session_run",
            "mpcq_default_scenario_params", "mpcq_scenario_step_batch", "mpcq_session_enable_scenario",
-           "mpcq_session_disable_scenario", "mpcq_session_scenario_read", "mpcq_session_scenario_device_ptr")
+           "mpcq_session_disable_scenario", "mpcq_session_scenario_read", "mpcq_session_scenario_device_ptr",
+           "mpcq_session_snapshot_create", "mpcq_session_snapshot_destroy", "mpcq_session_snapshot_save",
+           "mpcq_session_snapshot_restore", "mpcq_session_fork", "mpcq_session_snapshot_bytes",
+           "mpcq_session_snapshot_export", "mpcq_session_snapshot_import", "mpcq_debug_gather_rows")
 
 
 class MpcqError(RuntimeError):
@@ -382,6 +386,19 @@ def lib():
     L.mpcq_session_scenario_device_ptr.argtypes = [vp, C.c_int, C.POINTER(vp)]
     for name in ("mpcq_scenario_step_batch", "mpcq_session_enable_scenario", "mpcq_session_disable_scenario",
                  "mpcq_session_scenario_read", "mpcq_session_scenario_device_ptr"):
+        getattr(L, name).restype = C.c_int
+    L.mpcq_session_snapshot_create.argtypes = [vp, C.POINTER(vp)]
+    L.mpcq_session_snapshot_destroy.argtypes = [vp]
+    L.mpcq_session_snapshot_save.argtypes = [vp, vp, C.c_uint32]
+    L.mpcq_session_snapshot_restore.argtypes = [vp, vp, vp, C.c_uint32]
+    L.mpcq_session_fork.argtypes = [vp, vp, C.c_uint32]
+    L.mpcq_session_snapshot_bytes.argtypes = [vp, C.POINTER(C.c_int64)]
+    L.mpcq_session_snapshot_export.argtypes = [vp, vp, C.c_int64]
+    L.mpcq_session_snapshot_import.argtypes = [vp, vp, vp, C.c_int64]
+    L.mpcq_debug_gather_rows.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int64, C.c_int64, vp, C.c_uint32]
+    for name in ("mpcq_session_snapshot_create", "mpcq_session_snapshot_destroy", "mpcq_session_snapshot_save",
+                 "mpcq_session_snapshot_restore", "mpcq_session_fork", "mpcq_session_snapshot_bytes",
+                 "mpcq_session_snapshot_export", "mpcq_session_snapshot_import", "mpcq_debug_gather_rows"):
         getattr(L, name).restype = C.c_int
     for name in ("mpcq_debug_class_table_read", "mpcq_debug_class_table_write", "mpcq_debug_class_order",
                  "mpcq_debug_class_learn", "mpcq_debug_suspended", "mpcq_debug_session_order",

@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import ctypes as C
 import threading
+import weakref
 
 import numpy as np
 
@@ -95,6 +96,7 @@ class Engine:
         h = C.c_void_p()
         L.check(L.lib().mpcq_create(self.device, self.n_steps, C.byref(self.params), C.byref(h)))
         self._h = h
+        self._snapshots = weakref.WeakSet()  # live mpcq.Snapshot objects: closed before the context
 
     def _call(self, name: str, *args):
         """One C-ABI call on this context.  A context is used by one host thread at a
@@ -105,6 +107,8 @@ class Engine:
 
     def close(self):
         if getattr(self, "_h", None):
+            for snap in list(getattr(self, "_snapshots", ())):  # their destroy needs the context
+                snap.close()
             with self.lock:
                 L.lib().mpcq_destroy(self._h)
                 self._h = None

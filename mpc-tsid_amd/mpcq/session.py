@@ -17,6 +17,7 @@ tick under the forces the MPC applied: a robot that can disagree with the model.
 from __future__ import annotations
 
 import ctypes as C
+import struct
 
 import numpy as np
 
@@ -35,6 +36,66 @@ def _shapes(B, N):
         L.SV_L_FEET: ((B, 3, 4), np.float64), L.SV_ROT_FLAG: ((B,), np.int32), L.SV_H_ROT: ((B,), np.float64),
         L.SV_ORDER: ((B,), np.int32), L.SV_FIRST: ((B,), np.int32),
     }
+
+
+class Snapshot:
+    """A device-resident copy of a session's robots (``Session.snapshot``): every per-robot array
+    of every group the session holds, and ``Session.k`` at the save.  It belongs to the
+    session's engine and may be restored into any session on it with the same groups enabled.
+    A context manager: leaving it frees the device memory."""
+
+    def __init__(self, session: "Session"):
+        self.engine = session.engine
+        self.session = session
+        self.k = 0
+        self.batch = 0
+        h = C.c_void_p()
+        self.engine._call("mpcq_session_snapshot_create", session._h, C.byref(h))
+        self._h = h
+        live = getattr(self.engine, "_snapshots", None)
+        if live is not None:
+            live.add(self)  # Engine.close frees it first
+
+    def save(self):
+        """Capture the session again, as it stands now (behind every queued tick)."""
+        self.engine._call("mpcq_session_snapshot_save", self.session._h, self._h, 0)
+        self.k = self.session.k
+        self.batch = self.session.batch
+        return self
+
+    def nbytes(self) -> int:
+        n = C.c_int64()
+        self.engine._call("mpcq_session_snapshot_bytes", self._h, C.byref(n))
+        return int(n.value)
+
+    def tobytes(self) -> bytes:
+        """The snapshot as one blob on the host (``Session.snapshot_from`` reads it back);
+        ``Snapshot.k`` travels in the header's caller field."""
+        buf = bytearray(self.nbytes())
+        addr = C.addressof((C.c_char * len(buf)).from_buffer(buf))
+        self.engine._call("mpcq_session_snapshot_export", self._h, C.c_void_p(addr), len(buf))
+        struct.pack_into("<q", buf, L.SNAPSHOT_USER_OFFSET, int(self.k))
+        return bytes(buf)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            # the native destroy needs the context: Engine.close closes its live snapshots first,
+            # and one that outlives the engine all the same is only forgotten
+            if getattr(self.engine, "_h", True):
+                L.lib().mpcq_session_snapshot_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 class Session:
@@ -338,6 +399,65 @@ class Session:
         v = lambda q: C.c_void_p(q) if q else None  # noqa: E731
         flags = L.FLAG_DEVICE_PTRS | (L.FLAG_ASYNC if asynchronous else 0)
         self.engine._call("mpcq_session_reset", self._h, v(mask_ptr), v(gait0_ptr), v(q_w0_ptr), flags)
+
+    # ------------------------------------------------------------------ snapshots
+    def snapshot(self) -> Snapshot:
+        """Save every robot's state on the device and return the ``Snapshot``."""
+        return Snapshot(self).save()
+
+    def snapshot_from(self, blob: bytes) -> Snapshot:
+        """The snapshot ``Snapshot.tobytes`` wrote, on this session's engine (the same horizon)."""
+        blob = bytes(blob)
+        snap = Snapshot(self)
+        try:
+            self.engine._call("mpcq_session_snapshot_import", self._h, snap._h, blob, len(blob))
+        except L.MpcqError:
+            snap.close()
+            raise
+        snap.batch, = struct.unpack_from("<q", blob, 16)
+        snap.k, = struct.unpack_from("<q", blob, L.SNAPSHOT_USER_OFFSET)
+        return snap
+
+    def _map(self, map):  # noqa: A002
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(map, np.int32), (self.batch,)))
+
+    def _restored(self, snap: Snapshot, full: bool):
+        # a full restore goes back to the snapshot's tick index; a mapped one keeps counting,
+        # unless this session has not ticked: its robots then hold the snapshot's state
+        if full or self.k == 0:
+            self.k = snap.k
+
+    def restore(self, snap: Snapshot, map=None):  # noqa: A002
+        """Slot b takes row ``map[b]`` of ``snap``; -1 leaves the robot alone.  ``map`` broadcasts
+        to (B,) int32: a scalar r means every slot from row r.  None: the identity over every
+        robot (the same batch), which also restores MV_TOTALS and sets ``Session.k`` back to the
+        snapshot's.  A mapped restore leaves ``Session.k`` alone, unless this session has not
+        ticked yet: it then takes the snapshot's."""
+        m = None if map is None else self._map(map)
+        self.engine._call("mpcq_session_snapshot_restore", self._h, snap._h,
+                          None if m is None else C.c_void_p(m.ctypes.data), 0)
+        self._restored(snap, m is None)
+
+    def restore_device(self, snap: Snapshot, map_ptr: int, asynchronous: bool = True):
+        """``restore`` from a device map (int32 [B]; 0: the identity), enqueued on the engine's
+        stream; an entry outside the snapshot's rows acts as -1.  Ticked state into a session that
+        has not ticked yet is refused from a device map (it would have to cover every robot, which
+        only a host map lets the library check): use ``restore``."""
+        flags = L.FLAG_DEVICE_PTRS | (L.FLAG_ASYNC if asynchronous else 0)
+        self.engine._call("mpcq_session_snapshot_restore", self._h, snap._h, C.c_void_p(map_ptr) if map_ptr else None,
+                          flags)
+        self._restored(snap, not map_ptr)
+
+    def fork(self, map):  # noqa: A002
+        """Branch inside the live session: slot b continues from robot ``map[b]`` as it stands now
+        (-1: untouched; a scalar r: every slot from robot r).  ``Session.k`` keeps counting."""
+        m = self._map(map)
+        self.engine._call("mpcq_session_fork", self._h, C.c_void_p(m.ctypes.data), 0)
+
+    def fork_device(self, map_ptr: int, asynchronous: bool = True):
+        """``fork`` from a device map (int32 [B])."""
+        flags = L.FLAG_DEVICE_PTRS | (L.FLAG_ASYNC if asynchronous else 0)
+        self.engine._call("mpcq_session_fork", self._h, C.c_void_p(map_ptr) if map_ptr else None, flags)
 
     def _shape(self, what: int):
         if what not in self._shapes and what in (L.SV_SWING_REF, L.SV_SWING_STATE, L.SV_FRAME):
