@@ -65,7 +65,14 @@ extern "C" {
  *   3 (additions, no bump): mpcq_snapshot, mpcq_session_snapshot_create / _destroy / _save /
  *      _restore / _bytes / _export / _import, mpcq_session_fork, mpcq_debug_gather_rows (save,
  *      restore and branch a session's robots on the device); no new array id: MPCQ_SV_COUNT
- *      stays 21 */
+ *      stays 21
+ *   3 (additions, no bump): mpcq_channel_params, mpcq_default_channel_params,
+ *      mpcq_channel_observe_batch, mpcq_channel_actuate_batch, mpcq_session_enable_channel /
+ *      _disable_channel / _channel_read / _channel_device_ptr (noisy, delayed, biased state
+ *      feedback in front of the planner; delayed, scaled, noisy forces in front of the plant);
+ *      its arrays have ids of their own, MPCQ_HV_*: MPCQ_SV_COUNT stays 21.  A snapshot of a
+ *      session with a channel writes blob format version 2 (one more part); one without writes
+ *      version 1 as before, and import reads both */
 #define MPCQ_ABI_VERSION 3
 
 /* error codes (return values) */
@@ -836,6 +843,141 @@ int mpcq_session_scenario_read(mpcq_session* s, int what, void* dst, uint32_t fl
 /* Device address of array `what` (valid until mpcq_session_destroy). */
 int mpcq_session_scenario_device_ptr(mpcq_session* s, int what, void** out);
 
+/* ---- channel: noisy, delayed state feedback and delayed forces ---------------
+ * What lies between the plant and the controller, on the device: a measurement model in front
+ * of the planner (delay, per-episode bias, per-tick noise, dropped frames) and an actuation
+ * model in front of the plant (latency, per-episode leg gain, per-tick force noise).  One tick
+ * of latency is the reference's asynchronous mode, where get_latest_result hands back the
+ * previous solve and, on the first call, [0, 0, 8] * 4 (MPC_Wrapper.py:57-78; processing.py:
+ * 133-145).  Everything else has no reference counterpart.  Every draw is a pure function of
+ * (seed, robot, epoch, tau): a host restatement (mpcq/channel.py) agrees bit for bit.
+ *
+ * Clock [B][2] int32: the episode's number `epoch` and the next tick's `tau`, the channel's own
+ * (no scenario needed) under the scenario's rule: on a tick where the robot is first, epoch += 1
+ * and tau = 0; otherwise tau is the stored value; after the observe stage the stored value is
+ * tau + 1.  A scenario enabled before the first tick has the same clock by construction.
+ * A NEGATIVE stored tau is the bitwise complement of the tau to continue from and says that the
+ * robot's rings are not filled yet: the next observe stage `primes` it (below).
+ *
+ * Generator: the scenario's Philox4x32-10 under the channel's seed, philox((b, epoch, c2,
+ * stream), key), u(wa, wb) and prob(w, p) as above.  Streams (none shared with the scenario's):
+ *   0x100 + i  state noise of component i             c2 = tau
+ *   0x110      hold decision (w1)                     c2 = tau
+ *   0x120 + j  force noise of force component j < 12  c2 = tau
+ *   0x200 + i  episode bias of component i            c2 = 0
+ *   0x210 + q  episode gain of leg q                  c2 = 0
+ * Draw shapes:
+ *   n(w)   = (double)((int64)(w0 + w1 + w2 + w3) - 8589934590) * (1.7320508075688772 * 2^-32)
+ *   sym(w) = 2 * u(w0, w1) - 1
+ * n is the centred sum of the four words at unit variance (Irwin-Hall of order 4: near-Gaussian,
+ * |n| <= 2 sqrt(3)), exact up to one rounding; it needs no log / cos of a device library.  sym
+ * is exact, in [-1, 1).
+ *
+ * Observe stage (per robot; truth [12] = the state the tick would have handed the planner).
+ *   init = first or priming.  On an init tick: draw[i] = bias[i] * sym(stream 0x200 + i) for
+ *     i < 12 and gain_q = 1 + f_gain * sym(stream 0x210 + q) for the epoch; every slot of the
+ *     state ring <- truth; on a FIRST tick every slot of the force ring <- [0, 0, 8] * 4 and
+ *     draw[12 + q] = gain_q; on a priming tick that is not first the force ring is left to the
+ *     actuate stage, which fills it with that tick's own f0: until then draw[12] holds -gain_0
+ *     (the gains are positive: the sign of draw[12] is that pending mark, nothing else).
+ *   delayed = truth if delay == 0, else ring slot tau % delay read before truth is written into
+ *     it: the truth of tick tau - delay, or the episode's (or the priming tick's) first truth
+ *     before that.  The record is reported as it was written, in that tick's yaw-free local
+ *     frame: it is not re-expressed in the current one.
+ *   obs_i = (delayed_i + draw_i) + sigma[i] * n(stream 0x100 + i), no contraction.  A term whose
+ *     amplitude (bias[i], sigma[i]) is exactly 0 is not added at all: -0.0 and NaN pass through,
+ *     and a zero channel is a bitwise pass-through.
+ *   hold: with hold_prob > 0, on a tick that is not init, prob(w1 of stream 0x110, hold_prob)
+ *     makes obs the previous obs row (a dropped frame); the ring is advanced all the same.
+ *   obs is written; the clock becomes (epoch, tau + 1).
+ * Actuate stage (per robot; tau = stored - 1, taken as 0 where no observe stage has run).
+ *   cmd = f0 if latency == 0, else force-ring slot tau % latency read before this tick's f0 is
+ *     written there: the f0 of tick tau - latency, applied in the current local frame as
+ *     commanded (as the reference applies a late result); before that the initial result above.
+ *     With the pending mark set, every slot <- f0 first (so cmd = f0) and the mark is cleared.
+ *   f_cmd[3q + a] = cmd * gain_q + f_sigma[a] * n(stream 0x120 + 3q + a), no contraction, the
+ *     same zero-amplitude rule (f_gain == 0: no product; f_sigma[a] == 0: no sum). */
+typedef struct mpcq_channel_params {   /* 256 bytes */
+  uint64_t seed;                        /* the channel's own */
+  int32_t delay;                        /* 0..8 ticks between a state and its observation */
+  int32_t latency;                      /* 0..4 ticks between a solve and its forces */
+  double hold_prob;                     /* in [0, 1]: a tick repeats the previous observation */
+  double sigma[12];                     /* per-tick noise amplitude per state component */
+  double bias[12];                      /* per-episode bias amplitude per state component */
+  double f_sigma[3];                    /* per-tick force noise, x / y / z of every foot */
+  double f_gain;                        /* per-episode leg gain amplitude, 0 <= f_gain < 1 */
+  int32_t reserved[2];
+} mpcq_channel_params;
+#define MPCQ_CHANNEL_MAX_DELAY 8
+#define MPCQ_CHANNEL_MAX_LATENCY 4
+#ifdef __cplusplus
+static_assert(sizeof(mpcq_channel_params) == 256, "mpcq_channel_params is 256 bytes");
+#else
+_Static_assert(sizeof(mpcq_channel_params) == 256, "mpcq_channel_params is 256 bytes");
+#endif
+/* Everything zero: a channel that changes nothing. */
+void mpcq_default_channel_params(mpcq_channel_params* ch);
+/* The observe stage on its own, one tick for a batch.
+ *   first   [B] int32 or NULL: nonzero = a first tick for this robot; all_first != 0: for all
+ *   truth   [B][12]
+ *   clock   [B][2] int32 in/out;  obs [B][12] in/out (a held tick reads it);  draw [B][16]
+ *   in/out;  s_ring [B][8][12] in/out;  f_ring [B][4][12] in/out (written on a first tick only)
+ * All are required but first.  ch NULL = mpcq_default_channel_params.  Host pointers, or device
+ * pointers with MPCQ_FLAG_DEVICE_PTRS (then MPCQ_FLAG_ASYNC does not wait for the stream).
+ * MPCQ_E_INVALID, nothing launched, the message naming the field: delay outside 0..8, latency
+ * outside 0..4, hold_prob outside [0, 1] or NaN, a negative, NaN or infinite sigma, bias,
+ * f_sigma or f_gain, f_gain >= 1, reserved not zero; a NULL required pointer.  The parameters
+ * are checked before anything else. */
+int mpcq_channel_observe_batch(mpcq_ctx* ctx, const mpcq_channel_params* ch, int64_t batch,
+                               const int32_t* first, int all_first, const double* truth,
+                               int32_t* clock, double* obs, double* draw, double* s_ring,
+                               double* f_ring, uint32_t flags);
+/* The actuate stage on its own, after the observe stage of the same tick.
+ *   f0 [B][12];  clock [B][2] int32 (read);  draw [B][16] in/out (the pending mark);
+ *   f_ring [B][4][12] in/out;  f_cmd [B][12] out.  All required; flags and errors as above. */
+int mpcq_channel_actuate_batch(mpcq_ctx* ctx, const mpcq_channel_params* ch, int64_t batch,
+                               const double* f0, const int32_t* clock, double* draw,
+                               double* f_ring, double* f_cmd, uint32_t flags);
+
+/* Opt-in (ch NULL = mpcq_default_channel_params; invalid parameters: MPCQ_E_INVALID naming the
+ * field, nothing is launched and the parameters in force stay).  While enabled a tick runs
+ *   - the observe stage after its scenario stage and the staging of its inputs, before the
+ *     planner: truth = the staged copy of MPCQ_SV_STATE, or the caller's state; a robot is
+ *     first exactly where the planner takes it as first (k == 0, or its MPCQ_SV_FIRST set).
+ *     The planner takes MPCQ_HV_OBS as its state: column 0 of MPCQ_SV_XREF is the observation,
+ *     bit for bit.  l_feet is not disturbed.  Whatever else reads the tick's state, the plant,
+ *     keeps reading the truth;
+ *   - the actuate stage directly before the plant launch, only in ticks that run the plant:
+ *     the plant takes MPCQ_HV_F_CMD in place of MPCQ_SV_F0, and its own rules then apply (a
+ *     swing foot applies none, clamp to the true robot's cone): MPCQ_PV_F_EFF is what acted,
+ *     MPCQ_SV_F0 stays the MPC's.
+ * Without a plant the retrieve makes the prediction from the OBSERVATION the next state, so
+ * measurement error enters the virtual robot's state and accumulates; that is allowed.
+ * The first call makes the MPCQ_HV_* arrays, zero.  Whenever the channel was not enabled, or
+ * delay or latency differ from those in force, the call enqueues one small launch that
+ * complements every non-negative stored tau (on new arrays: -1), so the next observe stage
+ * primes every robot: rings filled, draw drawn for the stored epoch, tau continuing; a robot
+ * that is first there starts its new epoch as usual.  Calling it again with the same delay and
+ * latency only replaces the amplitudes (a bias or gain in force changes at the robot's next
+ * first tick).  A reset or an auto-reset needs nothing of its own: the first flags carry it.
+ * A session that never enables it launches exactly what it did before. */
+int mpcq_session_enable_channel(mpcq_session* s, const mpcq_channel_params* ch);
+/* The ticks after it run without the two launches; the arrays stay. */
+int mpcq_session_disable_channel(mpcq_session* s);
+/* The channel's arrays; they exist from the first mpcq_session_enable_channel on (before:
+ * MPCQ_E_INVALID).  The ring depths are the maxima whatever delay and latency are. */
+#define MPCQ_HV_CLOCK 0     /* [B][2] int32  epoch, the next tick's tau (negative: see above) */
+#define MPCQ_HV_OBS 1       /* [B][12]       the last tick's observation */
+#define MPCQ_HV_F_CMD 2     /* [B][12]       the last plant tick's commanded forces */
+#define MPCQ_HV_DRAW 3      /* [B][16]       the episode's 12 biases and 4 leg gains */
+#define MPCQ_HV_S_RING 4    /* [B][8][12]    the last truths, slot tau % delay */
+#define MPCQ_HV_F_RING 5    /* [B][4][12]    the last f0, slot tau % latency */
+#define MPCQ_HV_COUNT 6
+/* Copy array `what` to dst (host, or device with MPCQ_FLAG_DEVICE_PTRS); blocking. */
+int mpcq_session_channel_read(mpcq_session* s, int what, void* dst, uint32_t flags);
+/* Device address of array `what` (valid until mpcq_session_destroy). */
+int mpcq_session_channel_device_ptr(mpcq_session* s, int what, void** out);
+
 /* ---- snapshots: save, restore and branch robots on the device ---------------
  * A snapshot is a device-resident copy of everything per-robot that a session holds, plus the
  * few host flags that decide what the next tick launches.  Every call below runs on the
@@ -846,10 +988,11 @@ int mpcq_session_scenario_device_ptr(mpcq_session* s, int what, void** out);
  * saved -- the main group (MPCQ_SV_F0 .. _H_ROT, MPCQ_SV_FIRST, the warm start, the planner's
  * status, the engine's info, the creation gait table), the swing arrays (after
  * mpcq_session_enable_swing), MPCQ_PV_* (after _enable_plant / _set_wrench), MPCQ_MV_* (after
- * _enable_monitor), MPCQ_CV_* (after _enable_scenario), and the tables of
- * mpcq_session_set_robots / _set_plant_robots where in force -- and its shape: N, B, which of
- * these exist, the swing k_mpc; and whether a tick has run since create and whether a reset
- * was ever called.  Not held: the staging of host inputs and the plant's copy of q_w (every
+ * _enable_monitor), MPCQ_CV_* (after _enable_scenario), MPCQ_HV_* (after _enable_channel), and
+ * the tables of mpcq_session_set_robots / _set_plant_robots where in force -- and its shape: N,
+ * B, which of these exist, the swing k_mpc, the channel's delay and latency in force at the
+ * save (the rings mean nothing under others: a restore into a session whose values differ is
+ * MPCQ_E_INVALID); and whether a tick has run since create and whether a reset was ever called.  Not held: the staging of host inputs and the plant's copy of q_w (every
  * tick rewrites them before reading), and MPCQ_SV_ORDER (a permutation, not a per-robot row;
  * the restore rebuilds it, and results do not depend on it).  Parameters and enable flags
  * (swing, plant, monitor, scenario parameters; _enable_* / _disable_*) are configuration, not
@@ -904,12 +1047,15 @@ int mpcq_session_snapshot_restore(mpcq_session* s, const mpcq_snapshot* snap, co
  * session.  The source is never the live arrays: map may be any mapping. */
 int mpcq_session_fork(mpcq_session* s, const int32_t* map, uint32_t flags);
 /* Checkpoint to the host.  One blob = a 128-byte header, then the groups' arrays unpadded, in
- * the order main, swing, plant, monitor, scenario, robots table, plant robots table, inside a
- * group by array id (the private main arrays behind the named ones).  The header, little
- * endian: char magic[8] "MPCQSNP1"; uint32 version (1); int32 N; int64 B; int32 k_mpc (0: no
- * swing arrays); uint32 flags (bit 0 a tick had run, 1 a reset was recorded, 2 swing, 3 plant,
- * 4 monitor, 5 scenario, 6 robots table, 7 plant robots table); int64 group_bytes[7]; int64
- * total (header included); int64 user (0; for the caller, ignored by import); zeros.
+ * the order main, swing, plant, monitor, scenario, robots table, plant robots table, channel,
+ * inside a group by array id (the private main arrays behind the named ones).  The header,
+ * little endian: char magic[8] "MPCQSNP1"; uint32 version (2 with a channel part, else 1: a
+ * session without a channel writes the version-1 blob byte for byte; import reads both); int32
+ * N; int64 B; int32 k_mpc (0: no swing arrays); uint32 flags (bit 0 a tick had run, 1 a reset
+ * was recorded, 2 swing, 3 plant, 4 monitor, 5 scenario, 6 robots table, 7 plant robots table,
+ * 8 channel); int64 group_bytes[7]; int64 total (header included); int64 user (0; for the
+ * caller, ignored by import); at offset 104 int64 bytes of the channel part; at 112 int32
+ * delay, latency in force at the save; zeros.
  * _bytes: the size of snap's blob (snap saved).  _export: dst is a host buffer of exactly
  * that many bytes; blocking.  _import: makes snap the snapshot the blob describes, for s's
  * context; before it touches the device it checks the magic, the version, N against the

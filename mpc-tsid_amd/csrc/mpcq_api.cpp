@@ -4,7 +4,8 @@
 // Owns HIP contexts, device staging buffers for host-pointer calls, stream
 // and event handling.  All numerics run in the HIP kernels (mpcq_engine.hip,
 // mpcq_planner.hip, mpcq_session.hip, mpcq_order.hip, mpcq_swing.hip, mpcq_plant.hip,
-// mpcq_monitor.hip, mpcq_scenario.hip); there is no CPU fallback: a missing device is an error.
+// mpcq_monitor.hip, mpcq_scenario.hip, mpcq_channel.hip); there is no CPU fallback: a missing
+// device is an error.
 #include <math.h>
 #include <stdarg.h>
 #include <stdlib.h>
@@ -264,6 +265,28 @@ int mpcq::scenario_params(const mpcq_scenario_params* sc, mpcq_scenario_params* 
   if (p.push_flip > 63) return fail(MPCQ_E_INVALID, "the scenario's push_flip has bits beyond 63");
   for (int i = 0; i < 5; ++i)
     if (p.reserved[i]) return fail(MPCQ_E_INVALID, "the scenario's reserved fields must be zero");
+  return MPCQ_OK;
+}
+
+int mpcq::channel_params(const mpcq_channel_params* ch, mpcq_channel_params* out) {
+  if (ch) *out = *ch;
+  else mpcq_default_channel_params(out);
+  const mpcq_channel_params& p = *out;
+  if (p.delay < 0 || p.delay > MPCQ_CHANNEL_MAX_DELAY)
+    return fail(MPCQ_E_INVALID, "the channel needs delay in 0..%d (got %d)", MPCQ_CHANNEL_MAX_DELAY, p.delay);
+  if (p.latency < 0 || p.latency > MPCQ_CHANNEL_MAX_LATENCY)
+    return fail(MPCQ_E_INVALID, "the channel needs latency in 0..%d (got %d)", MPCQ_CHANNEL_MAX_LATENCY, p.latency);
+  if (!(p.hold_prob >= 0 && p.hold_prob <= 1)) return fail(MPCQ_E_INVALID, "the channel needs hold_prob in [0, 1]");
+  auto amplitude = [](double v) { return isfinite(v) && v >= 0; };
+  for (int i = 0; i < 12; ++i)
+    if (!amplitude(p.sigma[i])) return fail(MPCQ_E_INVALID, "the channel needs a finite sigma[%d] >= 0", i);
+  for (int i = 0; i < 12; ++i)
+    if (!amplitude(p.bias[i])) return fail(MPCQ_E_INVALID, "the channel needs a finite bias[%d] >= 0", i);
+  for (int i = 0; i < 3; ++i)
+    if (!amplitude(p.f_sigma[i])) return fail(MPCQ_E_INVALID, "the channel needs a finite f_sigma[%d] >= 0", i);
+  if (!amplitude(p.f_gain) || !(p.f_gain < 1)) return fail(MPCQ_E_INVALID, "the channel needs 0 <= f_gain < 1");
+  for (int i = 0; i < 2; ++i)
+    if (p.reserved[i]) return fail(MPCQ_E_INVALID, "the channel's reserved fields must be zero");
   return MPCQ_OK;
 }
 
@@ -1021,6 +1044,88 @@ int mpcq_scenario_step_batch(mpcq_ctx* c, const mpcq_scenario_params* sc, int64_
     a.v_ref = v_ref; a.push = push; a.wrench_out = wrench_out; a.robots_out = robots_out; a.draw = draw;
   }
   HIP_TRY(mpcq::launch_scenario(P, a, c->stream));
+  if (!dev) return unstage(c, xs, NX);
+  if (!(flags & MPCQ_FLAG_ASYNC)) HIP_TRY(hipStreamSynchronize(c->stream));
+  return MPCQ_OK;
+}
+
+// Channel: everything zero, a channel that changes nothing.
+void mpcq_default_channel_params(mpcq_channel_params* ch) {
+  if (!ch) return;
+  memset(ch, 0, sizeof(*ch));
+}
+
+int mpcq_channel_observe_batch(mpcq_ctx* c, const mpcq_channel_params* ch, int64_t B, const int32_t* first,
+                               int all_first, const double* truth, int32_t* clock, double* obs, double* draw,
+                               double* s_ring, double* f_ring, uint32_t flags) {
+  mpcq_channel_params P;
+  int rc = channel_params(ch, &P);  // first: what is wrong with the parameters needs no context
+  if (rc) return rc;
+  rc = check_ctx(c, B);
+  if (rc) return rc;
+  if (!truth || !clock || !obs || !draw || !s_ring || !f_ring)
+    return fail(MPCQ_E_INVALID, "truth, clock, obs, draw, s_ring and f_ring are required");
+  if (B == 0) return MPCQ_OK;
+  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
+  DeviceGuard g(c->device);
+  mpcq::ObserveArgs a{};
+  a.batch = B;
+  a.all_first = all_first != 0;
+  const size_t b = (size_t)B;
+  enum { FI, TR, CL, OB, DR, SR, FR, NX };
+  Xfer xs[NX] = {{first, nullptr, b * 4, nullptr},
+                 {truth, nullptr, b * 96, nullptr},
+                 {clock, clock, b * 8, nullptr},
+                 {obs, obs, b * 96, nullptr},
+                 {draw, draw, b * 128, nullptr},
+                 {s_ring, s_ring, b * MPCQ_CHANNEL_MAX_DELAY * 96, nullptr},
+                 {f_ring, f_ring, b * MPCQ_CHANNEL_MAX_LATENCY * 96, nullptr}};
+  if (!dev) {
+    rc = stage(c, xs, NX);
+    if (rc) return rc;
+    a.first = (const int32_t*)xs[FI].dev; a.truth = (const double*)xs[TR].dev; a.clock = (int32_t*)xs[CL].dev;
+    a.obs = (double*)xs[OB].dev; a.draw = (double*)xs[DR].dev; a.s_ring = (double*)xs[SR].dev;
+    a.f_ring = (double*)xs[FR].dev;
+  } else {
+    a.first = first; a.truth = truth; a.clock = clock; a.obs = obs; a.draw = draw; a.s_ring = s_ring;
+    a.f_ring = f_ring;
+  }
+  HIP_TRY(mpcq::launch_observe(P, a, c->stream));
+  if (!dev) return unstage(c, xs, NX);
+  if (!(flags & MPCQ_FLAG_ASYNC)) HIP_TRY(hipStreamSynchronize(c->stream));
+  return MPCQ_OK;
+}
+
+int mpcq_channel_actuate_batch(mpcq_ctx* c, const mpcq_channel_params* ch, int64_t B, const double* f0,
+                               const int32_t* clock, double* draw, double* f_ring, double* f_cmd, uint32_t flags) {
+  mpcq_channel_params P;
+  int rc = channel_params(ch, &P);
+  if (rc) return rc;
+  rc = check_ctx(c, B);
+  if (rc) return rc;
+  if (!f0 || !clock || !draw || !f_ring || !f_cmd)
+    return fail(MPCQ_E_INVALID, "f0, clock, draw, f_ring and f_cmd are required");
+  if (B == 0) return MPCQ_OK;
+  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
+  DeviceGuard g(c->device);
+  mpcq::ActuateArgs a{};
+  a.batch = B;
+  const size_t b = (size_t)B;
+  enum { F0, CL, DR, FR, FC, NX };
+  Xfer xs[NX] = {{f0, nullptr, b * 96, nullptr},
+                 {clock, nullptr, b * 8, nullptr},
+                 {draw, draw, b * 128, nullptr},
+                 {f_ring, f_ring, b * MPCQ_CHANNEL_MAX_LATENCY * 96, nullptr},
+                 {nullptr, f_cmd, b * 96, nullptr}};
+  if (!dev) {
+    rc = stage(c, xs, NX);
+    if (rc) return rc;
+    a.f0 = (const double*)xs[F0].dev; a.clock = (const int32_t*)xs[CL].dev; a.draw = (double*)xs[DR].dev;
+    a.f_ring = (double*)xs[FR].dev; a.f_cmd = (double*)xs[FC].dev;
+  } else {
+    a.f0 = f0; a.clock = clock; a.draw = draw; a.f_ring = f_ring; a.f_cmd = f_cmd;
+  }
+  HIP_TRY(mpcq::launch_actuate(P, a, c->stream));
   if (!dev) return unstage(c, xs, NX);
   if (!(flags & MPCQ_FLAG_ASYNC)) HIP_TRY(hipStreamSynchronize(c->stream));
   return MPCQ_OK;

@@ -84,5 +84,6 @@ int swing_params(const mpcq_swing_params* sp, mpcq_swing_params* out);
 int plant_params(const mpcq_plant_params* pl, double dt_default, mpcq_plant_params* out);
 int monitor_params(const mpcq_monitor_params* mp, mpcq_monitor_params* out);
 int scenario_params(const mpcq_scenario_params* sc, mpcq_scenario_params* out);
+int channel_params(const mpcq_channel_params* ch, mpcq_channel_params* out);
 
 }  // namespace mpcq

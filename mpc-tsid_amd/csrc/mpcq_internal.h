@@ -290,6 +290,33 @@ struct ScenarioArgs {
 };
 hipError_t launch_scenario(const mpcq_scenario_params& sc, const ScenarioArgs& a, hipStream_t s);
 
+// Channel stages (mpcq_channel.hip); semantics and layouts in include/mpcq.h
+// (mpcq_channel_observe_batch / _actuate_batch, mpcq_session_enable_channel).  Sixteen lanes
+// per robot, lane c < 12 owns component c.
+struct ObserveArgs {
+  int64_t batch;
+  const int32_t* first;  // [B] or null: nonzero = a first tick
+  int all_first;         // every robot runs a first tick
+  const double* truth;   // [B][12]
+  int32_t* clock;        // [B][2] in/out
+  double* obs;           // [B][12] in/out
+  double* draw;          // [B][16] in/out
+  double* s_ring;        // [B][8][12] in/out
+  double* f_ring;        // [B][4][12]: written on a first tick
+};
+struct ActuateArgs {
+  int64_t batch;
+  const double* f0;      // [B][12]
+  const int32_t* clock;  // [B][2]
+  double* draw;          // [B][16]: the pending mark in the sign of draw[12]
+  double* f_ring;        // [B][4][12] in/out
+  double* f_cmd;         // [B][12] out
+};
+hipError_t launch_observe(const mpcq_channel_params& ch, const ObserveArgs& a, hipStream_t s);
+hipError_t launch_actuate(const mpcq_channel_params& ch, const ActuateArgs& a, hipStream_t s);
+// mpcq_session_enable_channel's launch: every non-negative stored tau to its complement
+hipError_t launch_channel_arm(int32_t* clock, int64_t batch, hipStream_t s);
+
 // Row gather of a snapshot restore (mpcq_snapshot.hip; semantics in include/mpcq.h,
 // mpcq_session_snapshot_restore / mpcq_debug_gather_rows): row b of every dst array <- row
 // map[b] of its src array, in one launch.  The table travels in the kernel arguments.

@@ -16,34 +16,10 @@
 
 #pragma clang fp contract(off)
 
+#include "mpcq_philox.h"  // philox, u01, range (shared with mpcq_channel.hip)
+
 namespace mpcq {
 namespace {
-
-struct W4 {
-  uint32_t w0, w1, w2, w3;
-};
-
-__device__ inline W4 philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0;
-    c1 = lo1;
-    c2 = hi0 ^ c3 ^ k1;
-    c3 = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return W4{c0, c1, c2, c3};
-}
-
-// 53 bits of two words as a double in [0, 1): both products and the sum are exact
-__device__ inline double u01(uint32_t wa, uint32_t wb) {
-  return ((double)(wa >> 5) * 67108864.0 + (double)(wb >> 6)) * 0x1p-53;
-}
-
-__device__ inline double range(double lo, double hi, double u) { return lo + (hi - lo) * u; }
 
 // the command target of segment j: vx, vy, wyaw
 __device__ inline void target(const mpcq_scenario_params& sc, uint32_t b, uint32_t epoch, uint32_t j, uint32_t k0,

@@ -2,8 +2,8 @@
 // sessions, per-robot state resident in HBM.
 //
 // A session's device arrays come in groups (alloc_group): the main one made by
-// mpcq_session_create, and one each for swing, plant, monitor and scenario, made when they are
-// first enabled.  A tick (session_tick) is a list of stages, each filling the argument struct of
+// mpcq_session_create, and one each for swing, plant, monitor, scenario and channel, made when
+// they are first enabled.  A tick (session_tick) is a list of stages, each filling the argument struct of
 // its launch from the groups' arrays.  All numerics run in the HIP kernels.
 #include <math.h>
 #include <stdlib.h>
@@ -25,7 +25,7 @@ enum { SP_WARM_X = MPCQ_SV_COUNT, SP_PLAN_STATUS, SP_INFO, SP_IN_STATE, SP_IN_LF
 enum { PP_QW_PREV = MPCQ_PV_COUNT, PP_COUNT };
 
 // The arrays of one kind of id: MPCQ_SV_* (the swing slots are null until
-// mpcq_session_enable_swing), MPCQ_PV_*, MPCQ_MV_*, MPCQ_CV_*.
+// mpcq_session_enable_swing), MPCQ_PV_*, MPCQ_MV_*, MPCQ_CV_*, MPCQ_HV_*.
 struct Group {
   const char *kind, *enable;  // "<kind> array %d needs mpcq_session_enable_<enable>"
   int named;                  // the ids the _read / _write / _device_ptr entry points reach
@@ -46,15 +46,17 @@ struct mpcq_session {
   Group pv{"plant", "plant", MPCQ_PV_COUNT};      // made by the first enable_plant / set_wrench
   Group mv{"monitor", "monitor", MPCQ_MV_COUNT};  // made by the first enable_monitor
   Group cv{"scenario", "scenario", MPCQ_CV_COUNT};  // made by the first enable_scenario
+  Group hv{"channel", "channel", MPCQ_HV_COUNT};    // made by the first enable_channel
   void* swing_mem = nullptr;                      // MPCQ_SV_SWING_REF, _SWING_STATE, _FRAME
   bool have_order = false;  // MPCQ_SV_ORDER holds the next solve's order (longest previous first)
   bool use_order = true;    // MPCQ_DISPATCH_ORDER=0 turns it off (A/B timing only; results are identical)
   bool resets = false;      // mpcq_session_reset was called: from then on the ticks consult MPCQ_SV_FIRST
-  bool swing = false, plant = false, monitor = false, scenario = false;
+  bool swing = false, plant = false, monitor = false, scenario = false, channel = false;
   mpcq_swing_params sp{};
   mpcq_plant_params pl{};
   mpcq_monitor_params mp{};
   mpcq_scenario_params sc{};
+  mpcq_channel_params ch{};  // (delay and latency: what the rings in hv were primed under)
   RobotTable robots;        // mpcq_session_set_robots (the session's own, not the context's)
   RobotTable plant_robots;  // mpcq_session_set_plant_robots
   mpcq_snapshot* fork_snap = nullptr;  // mpcq_session_fork's own, made on first use
@@ -98,6 +100,12 @@ void monitor_bytes(size_t B, size_t nb[MPCQ_MV_COUNT]) {  // DONE, EP, EP_TICKS,
 void scenario_bytes(size_t B, size_t nb[MPCQ_CV_COUNT]) {  // EPOCH, TICK, V_REF, PUSH, WRENCH, ROBOTS, DRAW
   const size_t c[MPCQ_CV_COUNT] = {B * 4, B * 4, B * 48, B * 48, B * 48, B * sizeof(mpcq_robot), B * 64};
   for (int w = 0; w < MPCQ_CV_COUNT; ++w) nb[w] = c[w];
+}
+
+void channel_bytes(size_t B, size_t nb[MPCQ_HV_COUNT]) {  // CLOCK, OBS, F_CMD, DRAW, S_RING, F_RING
+  const size_t h[MPCQ_HV_COUNT] = {B * 8, B * 96, B * 96, B * 128, B * MPCQ_CHANNEL_MAX_DELAY * 96,
+                                   B * MPCQ_CHANNEL_MAX_LATENCY * 96};
+  for (int w = 0; w < MPCQ_HV_COUNT; ++w) nb[w] = h[w];
 }
 
 // n arrays of nb[i] bytes, each 256-B aligned, in one allocation zeroed on the context's
@@ -318,6 +326,7 @@ int mpcq_session_destroy(mpcq_session* s) {
     if (s->plant_robots.dev) (void)hipFree(s->plant_robots.dev);
     if (s->mv.mem) (void)hipFree(s->mv.mem);
     if (s->cv.mem) (void)hipFree(s->cv.mem);
+    if (s->hv.mem) (void)hipFree(s->hv.mem);
     (void)mpcq_session_snapshot_destroy(s->fork_snap);
   }
   delete s;
@@ -490,6 +499,43 @@ int mpcq_session_disable_scenario(mpcq_session* s) {
   return MPCQ_OK;
 }
 
+int mpcq_session_enable_channel(mpcq_session* s, const mpcq_channel_params* ch) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  mpcq_channel_params P;
+  int rc = channel_params(ch, &P);
+  if (rc) return rc;
+  DeviceGuard g(s->ctx->device);
+  const bool fresh = !s->hv.mem;
+  Group hv = s->hv;
+  if (fresh) {  // the arrays, zero
+    size_t nb[MPCQ_HV_COUNT];
+    channel_bytes((size_t)s->B, nb);
+    rc = alloc_group(s->ctx, "the channel arrays", MPCQ_HV_COUNT, nb, &hv.mem, hv.ptr, hv.bytes);
+    if (rc) return rc;
+  }
+  // the rings hold nothing the coming ticks may read: every robot primes at its next observe
+  if (!s->channel || P.delay != s->ch.delay || P.latency != s->ch.latency) {
+    const hipError_t e = mpcq::launch_channel_arm(hv.i(MPCQ_HV_CLOCK), s->B, s->ctx->stream);
+    if (e != hipSuccess) {
+      if (fresh) {
+        (void)hipStreamSynchronize(s->ctx->stream);
+        (void)hipFree(hv.mem);
+      }
+      return fail(MPCQ_E_DEVICE, "arming the channel's clock failed: %s", hipGetErrorString(e));
+    }
+  }
+  s->hv = hv;
+  s->ch = P;
+  s->channel = true;
+  return MPCQ_OK;
+}
+
+int mpcq_session_disable_channel(mpcq_session* s) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  s->channel = false;
+  return MPCQ_OK;
+}
+
 }  // extern "C"
 
 namespace {
@@ -498,6 +544,7 @@ namespace {
 struct Tick {
   int k;
   const double *state, *l_feet, *v_ref;
+  const double* plan_state;  // what the planner takes as the state: state, or the channel's observation
   const int32_t* reduced;  // or null
   // after a mpcq_session_reset: a robot whose MPCQ_SV_FIRST is set runs this tick as a first
   // tick whatever k says (the planner's extra pass then touches those robots only)
@@ -527,6 +574,7 @@ int tick_inputs(mpcq_session* s, const double* state, const double* l_feet, cons
     HIP_TRY(hipMemcpyAsync(v.ptr[SP_IN_LFEET], v.ptr[MPCQ_SV_L_FEET], v.bytes[SP_IN_LFEET], hipMemcpyDeviceToDevice, st));
     t.l_feet = v.d(SP_IN_LFEET);
   }
+  t.plan_state = t.state;
   t.first = s->resets ? v.i(MPCQ_SV_FIRST) : nullptr;
   t.first_k = t.k == 0 ? nullptr : t.first;
   return MPCQ_OK;
@@ -540,13 +588,36 @@ int tick_scenario(mpcq_session* s, int k) {
   return MPCQ_OK;
 }
 
+// The channel's measurement model: the planner's state becomes the observation of the truth
+// (t.state, which the plant keeps); it takes the first flags as the planner will.
+int tick_observe(mpcq_session* s, Tick& t) {
+  const Group& h = s->hv;
+  mpcq::ObserveArgs a{};
+  a.batch = s->B; a.first = t.first_k; a.all_first = t.k == 0; a.truth = t.state;
+  a.clock = h.i(MPCQ_HV_CLOCK); a.obs = h.d(MPCQ_HV_OBS); a.draw = h.d(MPCQ_HV_DRAW);
+  a.s_ring = h.d(MPCQ_HV_S_RING); a.f_ring = h.d(MPCQ_HV_F_RING);
+  HIP_TRY(mpcq::launch_observe(s->ch, a, s->ctx->stream));
+  t.plan_state = h.d(MPCQ_HV_OBS);
+  return MPCQ_OK;
+}
+
+// The channel's actuation model: MPCQ_HV_F_CMD from this tick's (and earlier) MPCQ_SV_F0.
+int tick_actuate(mpcq_session* s) {
+  const Group& h = s->hv;
+  mpcq::ActuateArgs a{};
+  a.batch = s->B; a.f0 = s->sv.d(MPCQ_SV_F0); a.clock = h.i(MPCQ_HV_CLOCK); a.draw = h.d(MPCQ_HV_DRAW);
+  a.f_ring = h.d(MPCQ_HV_F_RING); a.f_cmd = h.d(MPCQ_HV_F_CMD);
+  HIP_TRY(mpcq::launch_actuate(s->ch, a, s->ctx->stream));
+  return MPCQ_OK;
+}
+
 // The planner (processing.py:80-89, 131), between ev[0] and ev[1].
 int tick_plan(mpcq_session* s, const Tick& t) {
   mpcq_ctx* c = s->ctx;
   const Group& v = s->sv;
   mpcq::PlanArgs a{};
   a.batch = s->B; a.N = c->N; a.k = t.k; a.first = t.first_k;
-  a.state = t.state; a.l_feet = t.l_feet; a.v_ref = t.v_ref; a.reduced = t.reduced;
+  a.state = t.plan_state; a.l_feet = t.l_feet; a.v_ref = t.v_ref; a.reduced = t.reduced;
   a.gait = v.d(MPCQ_SV_GAIT); a.rot_flag = v.i(MPCQ_SV_ROT_FLAG); a.h_rot = v.d(MPCQ_SV_H_ROT);
   a.xref = v.d(MPCQ_SV_XREF); a.fsteps = v.d(MPCQ_SV_FSTEPS); a.status = v.i(SP_PLAN_STATUS);
   HIP_TRY(hipEventRecord(c->ev[0], c->stream));
@@ -624,7 +695,8 @@ int tick_plant(mpcq_session* s, const Tick& t) {
   const Group& v = s->sv;
   mpcq::PlantArgs a{};
   a.batch = s->B;
-  a.state = t.state; a.fsteps = v.d(MPCQ_SV_FSTEPS); a.f = v.d(MPCQ_SV_F0);
+  a.state = t.state; a.fsteps = v.d(MPCQ_SV_FSTEPS);
+  a.f = s->channel ? s->hv.d(MPCQ_HV_F_CMD) : v.d(MPCQ_SV_F0);  // (tick_actuate has run)
   // a scenario's pushes ride on the user's wrench, its robots replace the table
   a.wrench = s->scenario && s->sc.pushes ? s->cv.d(MPCQ_CV_WRENCH) : s->pv.d(MPCQ_PV_WRENCH);
   a.robots = s->scenario && s->sc.robots ? (const mpcq_robot*)s->cv.ptr[MPCQ_CV_ROBOTS] : plant_table(s);
@@ -673,8 +745,8 @@ int tick_swing(mpcq_session* s) {
   return MPCQ_OK;
 }
 
-// One tick: its stages in stream order ([scenario] -> planner -> solve -> retrieve -> [plant]
-// -> [monitor] -> order -> [swing] -> [auto-reset]).
+// One tick: its stages in stream order ([scenario] -> inputs -> [observe] -> planner -> solve ->
+// retrieve -> [actuate -> plant] -> [monitor] -> order -> [swing] -> [auto-reset]).
 int session_tick(mpcq_session* s, int k, const double* state, const double* l_feet, const double* v_ref,
                  const int32_t* reduced, uint32_t flags, double* trace) {
   if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
@@ -690,9 +762,11 @@ int session_tick(mpcq_session* s, int k, const double* state, const double* l_fe
   int rc = s->scenario ? tick_scenario(s, k) : MPCQ_OK;
   if (!rc) rc = tick_inputs(s, state, l_feet, v_ref, reduced, dev, t);
   if (!rc && !v_ref) t.v_ref = s->cv.d(MPCQ_CV_V_REF);
+  if (!rc && s->channel) rc = tick_observe(s, t);
   if (!rc) rc = tick_plan(s, t);
   if (!rc) rc = tick_solve(s, t);
   if (!rc) rc = tick_retrieve(s, t);
+  if (!rc && s->plant && s->channel) rc = tick_actuate(s);
   if (!rc && s->plant) rc = tick_plant(s, t);
   if (!rc && s->monitor) rc = tick_monitor(s, t);
   if (!rc) rc = tick_order(s);
@@ -781,6 +855,10 @@ int mpcq_session_scenario_read(mpcq_session* s, int what, void* dst, uint32_t fl
   return group_read(s, &mpcq_session::cv, what, dst, flags);
 }
 
+int mpcq_session_channel_read(mpcq_session* s, int what, void* dst, uint32_t flags) {
+  return group_read(s, &mpcq_session::hv, what, dst, flags);
+}
+
 int mpcq_session_device_ptr(mpcq_session* s, int what, void** out) {
   return group_device_ptr(s, &mpcq_session::sv, what, out);
 }
@@ -795,6 +873,10 @@ int mpcq_session_monitor_device_ptr(mpcq_session* s, int what, void** out) {
 
 int mpcq_session_scenario_device_ptr(mpcq_session* s, int what, void** out) {
   return group_device_ptr(s, &mpcq_session::cv, what, out);
+}
+
+int mpcq_session_channel_device_ptr(mpcq_session* s, int what, void** out) {
+  return group_device_ptr(s, &mpcq_session::hv, what, out);
 }
 
 int mpcq_session_write(mpcq_session* s, int what, const void* src, uint32_t flags) {
@@ -821,17 +903,19 @@ int mpcq_session_write(mpcq_session* s, int what, const void* src, uint32_t flag
 namespace {
 
 // The parts of a snapshot, in the blob's order; each is one allocation (alloc_group).
-enum { G_MAIN, G_SWING, G_PLANT, G_MONITOR, G_SCENARIO, G_ROBOTS, G_PLANT_ROBOTS, G_COUNT };
+enum { G_MAIN, G_SWING, G_PLANT, G_MONITOR, G_SCENARIO, G_ROBOTS, G_PLANT_ROBOTS, G_CHANNEL, G_COUNT };
 const char* const kPartName[G_COUNT] = {"the snapshot's session arrays", "the snapshot's swing arrays",
                                         "the snapshot's plant arrays", "the snapshot's monitor arrays",
                                         "the snapshot's scenario arrays", "the snapshot's robots table",
-                                        "the snapshot's plant robots table"};
+                                        "the snapshot's plant robots table", "the snapshot's channel arrays"};
 
 // What a snapshot's allocations follow from, with the context's N.
 struct SnapShape {
   int64_t B = 0;
   int k_mpc = 0;  // 0: no swing arrays
   bool pv = false, mv = false, cv = false, robots = false, plant_robots = false;
+  bool hv = false;              // the channel arrays, primed under
+  int delay = 0, latency = 0;   // these depths
 };
 
 }  // namespace
@@ -853,6 +937,8 @@ SnapShape shape_of(const mpcq_session* s) {
   sh.k_mpc = s->swing ? s->sp.k_mpc : 0;
   sh.pv = s->pv.mem; sh.mv = s->mv.mem; sh.cv = s->cv.mem;
   sh.robots = s->robots.count > 0; sh.plant_robots = s->plant_robots.count > 0;
+  sh.hv = s->hv.mem;
+  if (sh.hv) { sh.delay = s->ch.delay; sh.latency = s->ch.latency; }
   return sh;
 }
 
@@ -879,6 +965,7 @@ void snap_sizes(const SnapShape& sh, int N, size_t nb[G_COUNT][SP_COUNT]) {
   if (sh.cv) scenario_bytes(B, nb[G_SCENARIO]);
   if (sh.robots) nb[G_ROBOTS][0] = B * sizeof(mpcq_robot);
   if (sh.plant_robots) nb[G_PLANT_ROBOTS][0] = B * sizeof(mpcq_robot);
+  if (sh.hv) channel_bytes(B, nb[G_CHANNEL]);
 }
 
 // The session's arrays seen as a snapshot's parts (the arrays a snapshot does not hold: null).
@@ -898,6 +985,8 @@ void session_parts(const mpcq_session* s, Group out[G_COUNT]) {
   const size_t tb = (size_t)s->B * sizeof(mpcq_robot);
   if (s->robots.count > 0) { out[G_ROBOTS].ptr[0] = s->robots.dev; out[G_ROBOTS].bytes[0] = tb; }
   if (s->plant_robots.count > 0) { out[G_PLANT_ROBOTS].ptr[0] = s->plant_robots.dev; out[G_PLANT_ROBOTS].bytes[0] = tb; }
+  if (s->hv.mem)
+    for (int w = 0; w < MPCQ_HV_COUNT; ++w) { out[G_CHANNEL].ptr[w] = s->hv.ptr[w]; out[G_CHANNEL].bytes[w] = s->hv.bytes[w]; }
 }
 
 // One array of a snapshot (a) next to its counterpart (b; null without one), in the blob's order.
@@ -958,6 +1047,9 @@ const char* shape_difference(const SnapShape& a, const SnapShape& b, bool batch_
   if (a.cv != b.cv) return "the scenario arrays exist on one side only";
   if (a.robots != b.robots) return "the robots table is in force on one side only";
   if (a.plant_robots != b.plant_robots) return "the plant robots table is in force on one side only";
+  if (a.hv != b.hv) return "the channel arrays exist on one side only";
+  if (a.delay != b.delay) return "the channel's delay differs (the rings were filled under another)";
+  if (a.latency != b.latency) return "the channel's latency differs (the rings were filled under another)";
   return nullptr;
 }
 
@@ -1092,12 +1184,14 @@ struct BlobHeader {
   int64_t B;
   int32_t k_mpc;
   uint32_t flags;
-  int64_t group_bytes[G_COUNT];
+  int64_t group_bytes[G_CHANNEL];  // the seven parts of format version 1
   int64_t total;
   int64_t user;
-  int64_t zero[3];
+  int64_t channel_bytes;   // format version 2: the eighth part,
+  int32_t delay, latency;  // and the depths its rings were filled under
+  int64_t zero;
 };
-static_assert(sizeof(BlobHeader) == 128 && G_COUNT == 7, "the blob's header is 128 bytes");
+static_assert(sizeof(BlobHeader) == 128 && G_CHANNEL == 7 && G_COUNT == 8, "the blob's header is 128 bytes");
 const char kMagic[8] = {'M', 'P', 'C', 'Q', 'S', 'N', 'P', '1'};
 
 void blob_header(const SnapShape& sh, int N, bool have_order, bool resets, BlobHeader* h) {
@@ -1105,13 +1199,16 @@ void blob_header(const SnapShape& sh, int N, bool have_order, bool resets, BlobH
   snap_sizes(sh, N, nb);
   memset(h, 0, sizeof(*h));
   memcpy(h->magic, kMagic, 8);
-  h->version = 1; h->N = N; h->B = sh.B; h->k_mpc = sh.k_mpc;
+  h->version = sh.hv ? 2 : 1; h->N = N; h->B = sh.B; h->k_mpc = sh.k_mpc;
   h->flags = (have_order ? 1u : 0u) | (resets ? 2u : 0u) | (sh.k_mpc > 0 ? 4u : 0u) | (sh.pv ? 8u : 0u) |
-             (sh.mv ? 16u : 0u) | (sh.cv ? 32u : 0u) | (sh.robots ? 64u : 0u) | (sh.plant_robots ? 128u : 0u);
+             (sh.mv ? 16u : 0u) | (sh.cv ? 32u : 0u) | (sh.robots ? 64u : 0u) | (sh.plant_robots ? 128u : 0u) |
+             (sh.hv ? 256u : 0u);
+  h->delay = sh.delay; h->latency = sh.latency;
   h->total = sizeof(*h);
   for (int gi = 0; gi < G_COUNT; ++gi) {
-    for (int w = 0; w < SP_COUNT; ++w) h->group_bytes[gi] += (int64_t)nb[gi][w];
-    h->total += h->group_bytes[gi];
+    int64_t& gb = gi == G_CHANNEL ? h->channel_bytes : h->group_bytes[gi];
+    for (int w = 0; w < SP_COUNT; ++w) gb += (int64_t)nb[gi][w];
+    h->total += gb;
   }
 }
 
@@ -1211,22 +1308,30 @@ int mpcq_session_snapshot_import(mpcq_session* s, mpcq_snapshot* p, const void* 
   if (bytes < (int64_t)sizeof(h)) return fail(MPCQ_E_INVALID, "%lld bytes are less than a header", (long long)bytes);
   memcpy(&h, src, sizeof(h));
   if (memcmp(h.magic, kMagic, 8) != 0) return fail(MPCQ_E_INVALID, "not a snapshot blob (magic)");
-  if (h.version != 1) return fail(MPCQ_E_INVALID, "blob format version %u, this library reads 1", h.version);
+  if (h.version != 1 && h.version != 2)
+    return fail(MPCQ_E_INVALID, "blob format version %u, this library reads 1 and 2", h.version);
   if (h.N != c->N) return fail(MPCQ_E_INVALID, "the blob is of a context with N = %d, this one has N = %d", h.N, c->N);
-  if (h.B < 1 || h.B > (int64_t)0x7fffffff || h.k_mpc < 0 || h.k_mpc > 65536 || (h.flags >> 8) ||
-      ((h.flags & 4u) != 0) != (h.k_mpc > 0))
+  const bool chan = h.flags & 256u;
+  if (h.B < 1 || h.B > (int64_t)0x7fffffff || h.k_mpc < 0 || h.k_mpc > 65536 || (h.flags >> 9) ||
+      ((h.flags & 4u) != 0) != (h.k_mpc > 0) || chan != (h.version == 2) ||
+      (chan ? h.delay < 0 || h.delay > MPCQ_CHANNEL_MAX_DELAY || h.latency < 0 || h.latency > MPCQ_CHANNEL_MAX_LATENCY
+            : h.delay != 0 || h.latency != 0 || h.channel_bytes != 0))
     return fail(MPCQ_E_INVALID, "the blob's header is inconsistent (B %lld, k_mpc %d, flags %#x)", (long long)h.B,
                 h.k_mpc, h.flags);
   SnapShape sh;
   sh.B = h.B; sh.k_mpc = h.k_mpc;
   sh.pv = h.flags & 8u; sh.mv = h.flags & 16u; sh.cv = h.flags & 32u;
   sh.robots = h.flags & 64u; sh.plant_robots = h.flags & 128u;
+  sh.hv = chan; sh.delay = h.delay; sh.latency = h.latency;
   BlobHeader want;
   blob_header(sh, c->N, h.flags & 1u, h.flags & 2u, &want);
-  for (int gi = 0; gi < G_COUNT; ++gi)
-    if (h.group_bytes[gi] != want.group_bytes[gi])
-      return fail(MPCQ_E_INVALID, "the blob's part %d has %lld bytes, its shape says %lld", gi,
-                  (long long)h.group_bytes[gi], (long long)want.group_bytes[gi]);
+  for (int gi = 0; gi < G_COUNT; ++gi) {
+    const int64_t have = gi == G_CHANNEL ? h.channel_bytes : h.group_bytes[gi];
+    const int64_t need = gi == G_CHANNEL ? want.channel_bytes : want.group_bytes[gi];
+    if (have != need)
+      return fail(MPCQ_E_INVALID, "the blob's part %d has %lld bytes, its shape says %lld", gi, (long long)have,
+                  (long long)need);
+  }
   if (h.total != want.total || bytes != want.total)
     return fail(MPCQ_E_INVALID, "the blob says %lld bytes, its shape %lld, the caller %lld (truncated?)",
                 (long long)h.total, (long long)want.total, (long long)bytes);

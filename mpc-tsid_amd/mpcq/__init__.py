@@ -19,6 +19,10 @@ Public surface:
   Scenario          per-episode random commands, pushes and payloads drawn on the device from a
                     counter-based generator (Session.enable_scenario); mpcq.scenario restates
                     the draws on the host, bit for bit
+  Channel           what lies between plant and controller, on the device: delayed, biased, noisy
+                    state feedback with dropped frames in front of the planner, delayed, scaled,
+                    noisy forces in front of the plant (Session.enable_channel); mpcq.channel
+                    restates the draws on the host, bit for bit
   Snapshot          a session's robots saved on the device (Session.snapshot): restore them, seed
                     another session from them, branch one robot into many (Session.restore,
                     Session.fork), checkpoint them to the host (Snapshot.tobytes,
@@ -41,7 +45,11 @@ from ._lib import (FLAG_ASYNC, FLAG_DEVICE_PTRS, FLAG_ORDER_BY_CLASS, MODE_SETUP
                    DONE_HEIGHT, DONE_NONFINITE, DONE_SOLVER, DONE_TILT, DONE_TIMEOUT, MV_DONE, MV_EP, MV_EP_TICKS,
                    MV_EPISODES, MV_LAST, MV_TOTALS, TRACE, MonitorParams, default_monitor_params,
                    CV_DRAW, CV_EPOCH, CV_PUSH, CV_ROBOTS, CV_TICK, CV_V_REF, CV_WRENCH, ScenarioParams,
-                   default_scenario_params)
+                   default_scenario_params,
+                   HV_CLOCK, HV_DRAW, HV_F_CMD, HV_F_RING, HV_OBS, HV_S_RING, CHANNEL_MAX_DELAY,
+                   CHANNEL_MAX_LATENCY, ChannelParams, default_channel_params)
+from . import channel  # noqa: F401
+from .channel import Channel  # noqa: F401
 from .engine import ROBOT_DTYPE, Engine, dims, pattern, robots  # noqa: F401
 from .monitor import Monitor  # noqa: F401
 from .plant import Plant  # noqa: F401

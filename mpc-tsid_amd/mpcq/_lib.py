@@ -75,6 +75,9 @@ MV_DONE, MV_EP, MV_EP_TICKS, MV_EPISODES, MV_LAST, MV_TOTALS = range(6)
 TRACE = 16
 # the scenario stage: a session's scenario arrays (MPCQ_CV_*)
 CV_EPOCH, CV_TICK, CV_V_REF, CV_PUSH, CV_WRENCH, CV_ROBOTS, CV_DRAW = range(7)
+# the channel: a session's channel arrays (MPCQ_HV_*), the ring depths
+HV_CLOCK, HV_OBS, HV_F_CMD, HV_DRAW, HV_S_RING, HV_F_RING = range(6)
+CHANNEL_MAX_DELAY, CHANNEL_MAX_LATENCY = 8, 4
 SNAPSHOT_USER_OFFSET = 96  # a snapshot blob's header: the int64 left to the caller (include/mpcq.h)
 
 EXPORTS = ("mpcq_abi_version", "mpcq_default_params", "mpcq_dims", "mpcq_pattern",
@@ -99,6 +102,9 @@ EXPORTS = ("mpcq_abi_version", "mpcq_default_params", "mpcq_dims", "mpcq_pattern
            "mpcq_session_run",
            "mpcq_default_scenario_params", "mpcq_scenario_step_batch", "mpcq_session_enable_scenario",
            "mpcq_session_disable_scenario", "mpcq_session_scenario_read", "mpcq_session_scenario_device_ptr",
+           "mpcq_default_channel_params", "mpcq_channel_observe_batch", "mpcq_channel_actuate_batch",
+           "mpcq_session_enable_channel", "mpcq_session_disable_channel", "mpcq_session_channel_read",
+           "mpcq_session_channel_device_ptr",
            "mpcq_session_snapshot_create", "mpcq_session_snapshot_destroy", "mpcq_session_snapshot_save",
            "mpcq_session_snapshot_restore", "mpcq_session_fork", "mpcq_session_snapshot_bytes",
            "mpcq_session_snapshot_export", "mpcq_session_snapshot_import", "mpcq_debug_gather_rows")
@@ -234,6 +240,22 @@ class ScenarioParams(C.Structure):
         ("push_flip", C.c_int32),
         ("robots", C.c_int32),
         ("reserved", C.c_int32 * 5),
+    ]
+
+
+class ChannelParams(C.Structure):
+    """struct mpcq_channel_params (include/mpcq.h)."""
+
+    _fields_ = [
+        ("seed", C.c_uint64),
+        ("delay", C.c_int32),
+        ("latency", C.c_int32),
+        ("hold_prob", C.c_double),
+        ("sigma", C.c_double * 12),
+        ("bias", C.c_double * 12),
+        ("f_sigma", C.c_double * 3),
+        ("f_gain", C.c_double),
+        ("reserved", C.c_int32 * 2),
     ]
 
 
@@ -387,6 +409,18 @@ def lib():
     for name in ("mpcq_scenario_step_batch", "mpcq_session_enable_scenario", "mpcq_session_disable_scenario",
                  "mpcq_session_scenario_read", "mpcq_session_scenario_device_ptr"):
         getattr(L, name).restype = C.c_int
+    HP = C.POINTER(ChannelParams)
+    L.mpcq_default_channel_params.argtypes = [HP]
+    L.mpcq_default_channel_params.restype = None
+    L.mpcq_channel_observe_batch.argtypes = [vp, HP, C.c_int64, vp, C.c_int] + [vp] * 6 + [C.c_uint32]
+    L.mpcq_channel_actuate_batch.argtypes = [vp, HP, C.c_int64] + [vp] * 5 + [C.c_uint32]
+    L.mpcq_session_enable_channel.argtypes = [vp, HP]
+    L.mpcq_session_disable_channel.argtypes = [vp]
+    L.mpcq_session_channel_read.argtypes = [vp, C.c_int, vp, C.c_uint32]
+    L.mpcq_session_channel_device_ptr.argtypes = [vp, C.c_int, C.POINTER(vp)]
+    for name in ("mpcq_channel_observe_batch", "mpcq_channel_actuate_batch", "mpcq_session_enable_channel",
+                 "mpcq_session_disable_channel", "mpcq_session_channel_read", "mpcq_session_channel_device_ptr"):
+        getattr(L, name).restype = C.c_int
     L.mpcq_session_snapshot_create.argtypes = [vp, C.POINTER(vp)]
     L.mpcq_session_snapshot_destroy.argtypes = [vp]
     L.mpcq_session_snapshot_save.argtypes = [vp, vp, C.c_uint32]
@@ -519,3 +553,21 @@ def supported_horizons():
     buf = (C.c_int32 * 64)()
     n = lib().mpcq_supported_horizons(buf, 64)
     return [buf[i] for i in range(min(n, 64))]
+
+
+def default_channel_params(**overrides) -> ChannelParams:
+    """mpcq_default_channel_params (all zero: a channel that changes nothing); an array field
+    takes a sequence of its length, or one number for every entry."""
+    p = ChannelParams()
+    lib().mpcq_default_channel_params(C.byref(p))
+    for k, v in overrides.items():
+        if not hasattr(p, k):
+            raise AttributeError(f"unknown channel parameter {k}")
+        cur = getattr(p, k)
+        if hasattr(cur, "__len__"):
+            v = [v] * len(cur) if not hasattr(v, "__len__") else list(v)
+            if len(v) != len(cur):
+                raise ValueError(f"channel parameter {k} takes {len(cur)} values")
+            v = type(cur)(*v)
+        setattr(p, k, v)
+    return p

@@ -119,6 +119,7 @@ class Session:
         self.plant_params = None
         self.monitor_params = None
         self.scenario_params = None
+        self.channel_params = None
 
     def enable_swing(self, params: L.SwingParams | None = None):
         """Opt in to the swing-foot references: every later tick appends one swing launch over
@@ -281,6 +282,51 @@ class Session:
     def scenario_device_ptr(self, what: int) -> int:
         out = C.c_void_p()
         self.engine._call("mpcq_session_scenario_device_ptr", self._h, what, C.byref(out))
+        return int(out.value or 0)
+
+    # ------------------------------------------------------------------ channel
+    def enable_channel(self, params: L.ChannelParams | None = None, **overrides):
+        """Opt in to the channel between plant and controller: every later tick observes the
+        state it would have handed the planner through a measurement model (``delay`` ticks
+        late, a per-episode ``bias``, per-tick noise ``sigma``, frames dropped with
+        ``hold_prob``; HV_OBS is what the planner sees, the plant keeps the truth) and, with a
+        plant, hands it the forces through an actuation model (``latency`` ticks late, a
+        per-episode leg gain ``f_gain``, per-tick noise ``f_sigma``; HV_F_CMD).  Every draw is
+        reproducible on the host from (seed, robot, epoch, tau) with ``mpcq.channel``.
+        ``params`` None: the defaults (all zero: a channel that changes nothing), with
+        ``overrides``.  Calling it again with the same delay and latency only replaces the
+        amplitudes; other depths refill the rings at the next tick."""
+        if params is not None and overrides:
+            raise ValueError("pass params or overrides, not both")
+        ch = params or L.default_channel_params(**overrides)
+        self.engine._call("mpcq_session_enable_channel", self._h, C.byref(ch))
+        self.channel_params = ch
+
+    def disable_channel(self):
+        """The ticks after it run without the channel's two launches; the arrays stay."""
+        self.engine._call("mpcq_session_disable_channel", self._h)
+        self.channel_params = None
+
+    def _channel_shape(self, what: int):
+        B = self.batch
+        shapes = {L.HV_CLOCK: ((B, 2), np.int32), L.HV_OBS: ((B, 12), np.float64), L.HV_F_CMD: ((B, 12), np.float64),
+                  L.HV_DRAW: ((B, 16), np.float64), L.HV_S_RING: ((B, L.CHANNEL_MAX_DELAY, 12), np.float64),
+                  L.HV_F_RING: ((B, L.CHANNEL_MAX_LATENCY, 12), np.float64)}
+        if what not in shapes:
+            raise L.MpcqError(L.E_INVALID, f"unknown channel array {what}")
+        return shapes[what]
+
+    def channel_read(self, what: int):
+        """HV_CLOCK (B, 2) int32 (epoch, next tau), HV_OBS / HV_F_CMD (B, 12), HV_DRAW (B, 16),
+        HV_S_RING (B, 8, 12) or HV_F_RING (B, 4, 12)."""
+        shape, dt = self._channel_shape(what)
+        out = np.empty(shape, dt)
+        self.engine._call("mpcq_session_channel_read", self._h, what, C.c_void_p(out.ctypes.data), 0)
+        return out
+
+    def channel_device_ptr(self, what: int) -> int:
+        out = C.c_void_p()
+        self.engine._call("mpcq_session_channel_device_ptr", self._h, what, C.byref(out))
         return int(out.value or 0)
 
     # ------------------------------------------------------------------ rollouts
