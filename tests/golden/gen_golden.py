@@ -6,6 +6,8 @@
     python tests/golden/gen_golden.py horizons_r3  # golden_horizons_r3.npz: N = 5, 6, 10, 13, 33,
                                                    # 36, 40, 57, 64
     python tests/golden/gen_golden.py horizons_r4  # golden_horizons_r4.npz: N = 49, 50
+    python tests/golden/gen_golden.py horizons_rest  # golden_horizons_rest_a.npz / _b.npz: the 41
+                                                     # remaining horizons of 4 ... 64 (reduced field set)
     python tests/golden/gen_golden.py params       # golden_params.npz: formulation only, under
                                                    # non-default mass / mu / gI / dt / footholds
 
@@ -234,10 +236,14 @@ def exact_optimum(Pd, A, l, u, rounds=40, delta=1e-9, refine=30):
 
 
 # --------------------------------------------------------------------------- driver
-def build(N: int, per_gait: int, seed: int, extra=True):
+def build(N: int, per_gait: int, seed: int, extra=True, gaits=None):
+    """``gaits``: the subset of synth.GAITS to build (None: all); a gait keeps its index in
+    synth.GAITS, and with it its seed and its ``gait`` field, whatever the subset."""
     MPC = import_reference_mpc()
     insts = []
     for gi, g in enumerate(synth.GAITS):
+        if gaits is not None and g not in gaits:
+            continue
         b = synth.make_batch(per_gait, N, gaits=(g,), seed=seed + 7 * gi)
         for i in range(per_gait):
             insts.append((b["xref"][i], b["fsteps"][i], gi))
@@ -287,41 +293,37 @@ HORIZONS_R3 = ((5, 1, 505), (6, 2, 606), (10, 2, 1010), (13, 1, 1313), (33, 1, 3
 HORIZONS_R4 = ((49, 1, 4949), (50, 1, 5050))
 
 
-def main_horizons():
-    """The other horizons the engine compiles (N = 4j <= 32) plus N = 48 (three
-    16-step periods at dt = 0.02: n_periods = 3 in FootstepPlanner.py:55)."""
+# every remaining compiled horizon (the engine is one code object per N = 4 ... 64): with these
+# the fixtures cover all 61.  One instance per gait up to 32 stages, one instance (gait N mod 3)
+# beyond; seed 101 N as above
+HORIZONS_REST_A = tuple((N, 1, 101 * N) for N in (7, 9, 11, 14, 15, 17, 18, 19, 21, 22, 23, 25, 26, 27, 29, 30, 31))
+HORIZONS_REST_B = tuple((N, 1, 101 * N, (synth.GAITS[N % 3],))
+                        for N in (34, 35, 37, 38, 39, *range(41, 48), *range(51, 57), *range(58, 64)))
+# left out of the horizons_rest files to keep them small: setup mode at these horizons is
+# checked against the oracle, whose setup mode the other fixtures pin
+REST_DROP = ("Ax_setup", "l_setup", "u_setup", "y_star")
+
+
+def main_horizons(horizons, name, extra=True, drop=()):
+    """One horizon fixture file: build() per (N, per_gait, seed[, gaits]) entry, keys
+    n<N>_<field> plus ``horizons``; fields named in ``drop`` are not written.
+    golden_horizons.npz: the other N = 4j <= 32 plus N = 48 (three 16-step periods at
+    dt = 0.02: n_periods = 3 in FootstepPlanner.py:55)."""
     out = {}
-    for N, per_gait, seed in HORIZONS:
-        arrs = build(N, per_gait, seed)
+    for N, per_gait, seed, *rest in horizons:
+        arrs = build(N, per_gait, seed, extra=extra, gaits=rest[0] if rest else None)
         for k, v in arrs.items():
-            out[f"n{N}_{k}"] = v
-    path = os.path.join(HERE, "golden_horizons.npz")
-    np.savez_compressed(path, horizons=np.array([h[0] for h in HORIZONS]), **out)
+            if k not in drop:
+                out[f"n{N}_{k}"] = v
+    path = os.path.join(HERE, name)
+    np.savez_compressed(path, horizons=np.array([h[0] for h in horizons]), **out)
     print("wrote", path, os.path.getsize(path), "bytes")
 
 
-def main_horizons_r3():
-    """golden_horizons_r3.npz: HORIZONS_R3, same fields and key scheme as main_horizons."""
-    out = {}
-    for N, per_gait, seed in HORIZONS_R3:
-        arrs = build(N, per_gait, seed)
-        for k, v in arrs.items():
-            out[f"n{N}_{k}"] = v
-    path = os.path.join(HERE, "golden_horizons_r3.npz")
-    np.savez_compressed(path, horizons=np.array([h[0] for h in HORIZONS_R3]), **out)
-    print("wrote", path, os.path.getsize(path), "bytes")
-
-
-def main_horizons_r4():
-    """golden_horizons_r4.npz: HORIZONS_R4, same fields and key scheme as main_horizons."""
-    out = {}
-    for N, per_gait, seed in HORIZONS_R4:
-        arrs = build(N, per_gait, seed)
-        for k, v in arrs.items():
-            out[f"n{N}_{k}"] = v
-    path = os.path.join(HERE, "golden_horizons_r4.npz")
-    np.savez_compressed(path, horizons=np.array([h[0] for h in HORIZONS_R4]), **out)
-    print("wrote", path, os.path.getsize(path), "bytes")
+def main_horizons_rest():
+    """golden_horizons_rest_a.npz (N <= 32) and golden_horizons_rest_b.npz (N > 32)."""
+    main_horizons(HORIZONS_REST_A, "golden_horizons_rest_a.npz", extra=False, drop=REST_DROP)
+    main_horizons(HORIZONS_REST_B, "golden_horizons_rest_b.npz", extra=False, drop=REST_DROP)
 
 
 # non-default formulation constants: the attributes MPC.py keeps on the object (mass, mu, gI,
@@ -367,17 +369,13 @@ def main_params():
 
 
 def main():
-    if len(sys.argv) > 1 and sys.argv[1] == "params":
-        main_params()
-        return
-    if len(sys.argv) > 1 and sys.argv[1] == "horizons_r4":
-        main_horizons_r4()
-        return
-    if len(sys.argv) > 1 and sys.argv[1] == "horizons":
-        main_horizons()
-        return
-    if len(sys.argv) > 1 and sys.argv[1] == "horizons_r3":
-        main_horizons_r3()
+    modes = dict(params=main_params,
+                 horizons=lambda: main_horizons(HORIZONS, "golden_horizons.npz"),
+                 horizons_r3=lambda: main_horizons(HORIZONS_R3, "golden_horizons_r3.npz"),
+                 horizons_r4=lambda: main_horizons(HORIZONS_R4, "golden_horizons_r4.npz"),
+                 horizons_rest=main_horizons_rest)
+    if len(sys.argv) > 1:
+        modes[sys.argv[1]]()
         return
     for N, per_gait, seed in ((16, 16, 1234), (32, 4, 4321)):
         arrs = build(N, per_gait, seed)

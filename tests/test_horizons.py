@@ -4,7 +4,7 @@ fixtures captured from the unmodified reference MPC.py (tests/golden/gen_golden.
 horizons / horizons_r3): the CSC pattern, the
 A / l / u handed to OSQP in both modes, and the polished solve on the certified
 optimum x*.  The reference takes any n_steps (MPC.py:22-26; FootstepPlanner.py:55
-n_steps = n_periods T_gait / dt)."""
+n_steps = n_periods T_gait / dt).  The 41 other compiled horizons: test_horizons_rest.py."""
 import numpy as np
 import pytest
 from conftest import FIXTURE_HORIZONS as HORIZONS
