@@ -978,6 +978,133 @@ int mpcq_session_channel_read(mpcq_session* s, int what, void* dst, uint32_t fla
 /* Device address of array `what` (valid until mpcq_session_destroy). */
 int mpcq_session_channel_device_ptr(mpcq_session* s, int what, void** out);
 
+/* ---- estimator: a delay-compensating state estimator in front of the planner --
+ * The controller's side of the channel, on the device: per robot a Kalman filter on the MPC's
+ * own discrete model that keeps its posterior at the time the measurement was taken (`lag`
+ * ticks ago) and predicts forward to now through the forces the MPC commanded and the
+ * footholds it planned.  No reference counterpart (the reference reads the simulator's ground
+ * truth); tests/estimator_model.py restates every rule below on the host.
+ *
+ * Model step M(x, feet, f): the plant's MPCQ_PLANT_MODEL step (mpcq_plant_step_batch above)
+ * without clamp and without wrench, with dt and gravity of the context's mpcq_params and the
+ * robot row the CONTROLLER believes (the robots argument / the session's mpcq_session_set_robots
+ * table, else the context's params; never the plant's table), followed by the state part of
+ * the tick's frame change: x, y and yaw <- 0, (vx, vy) and (wx, wy) rotated by Rz(-yaw_end).
+ * The operation order is that of those two, no contraction, sums over feet left to right in
+ * foot order; a foot with any NaN coordinate is a swing foot and applies no force.
+ *
+ * Filter state, one row of MPCQ_EST_ROW doubles per robot (nothing in it depends on a
+ * parameter: no launch arms it, a snapshot needs no depth fields):
+ *   [MPCQ_EST_POST  .. +12)  the posterior mean at filter time s
+ *   [MPCQ_EST_PREV  .. +12)  the previous tick's observation row
+ *   [MPCQ_EST_P     .. +18)  six symmetric 2x2 blocks (p_pp, p_pv, p_vv): block i couples
+ *                            components i and i + 6 (a pose and its rate)
+ *   [MPCQ_EST_CLOCK .. +2)   four int32: valid, s, tau_next, zero
+ *   [MPCQ_EST_RING  .. +288) 12 slots of 24 doubles: slot j % 12 holds tick j's f0 [12] and
+ *                            stance feet [3][4] (laid out as l_feet, NaN = swing)
+ * tau is the filter's own count of ticks since its last initialisation.
+ *
+ * One robot-tick (obs [12] the measurement; f_prev, feet_prev the PREVIOUS tick's f0 and feet):
+ *  1. Init, when any of: the robot is first; valid == 0; the previous tick failed; the stored
+ *     s is not max(tau_next - 1 - lag, 0) (the lag changed under it).  Then post = obs, block
+ *     P_i = diag(p0[i], p0[i + 6]), s = 0, tau = 0, valid = 1, est = obs bit for bit; the ring is
+ *     not read before it is written.
+ *  2. Otherwise tau = tau_next, and in this order:
+ *     time update, with s* = max(tau - lag, 0): if s* == s + 1, post <- M(post, feet of tick s,
+ *       force of tick s) and every block <- A P A^T + diag(q[i], q[i + 6]), A = [[1, dt], [0, 1]]
+ *       (the MPC's own A): t = p_pv + dt p_vv; p_pp = ((p_pp + dt p_pv) + dt t) + q[i]; p_pv = t;
+ *       p_vv = p_vv + q[i + 6]; for i in {0, 1, 5} the frame change pins the pose: p_pp = q[i],
+ *       p_pv = 0.  The covariance ignores the small rotation of (vx, vy) and (wx, wy).  Its ring
+ *       slots are read BEFORE the record below (at lag 8, f_lag 4 the force of tick tau - 13
+ *       shares its slot with tick tau - 1).
+ *     record: slot (tau - 1) % 12 <- f_prev, feet_prev.
+ *     measurement update, skipped on a missing frame (a row with any non-finite component;
+ *       with skip_repeats a row equal bit for bit to the previous tick's row: the channel's
+ *       hold): per block S = P + diag(r[i], r[i + 6]), det = s00 s11 - s01 s01,
+ *       K = P S^-1 (k00 = (p_pp s11 - p_pv s01) / det, k01 = (p_pv s00 - p_pp s01) / det,
+ *       k10 = (p_pv s11 - p_vv s01) / det, k11 = (p_vv s00 - p_pv s01) / det), e = obs - post,
+ *       post_i += k00 e_i + k01 e_{i+6}, post_{i+6} += k10 e_i + k11 e_{i+6}, and P -= K P
+ *       (p_pp -= k00 p_pp + k01 p_pv; p_pv -= k00 p_pv + k01 p_vv; p_vv -= k10 p_pv + k11 p_vv).
+ *     forecast: est = post taken tau - s* times (at most 8) through M over ticks s* .. tau - 1.
+ *     `The force of tick j` is the f0 recorded for tick j - f_lag, and before that tick 0 the
+ *     reference's initial result [0, 0, 8] * 4 (MPC_Wrapper.py:78).
+ *  3. prev = obs, s = s*, tau_next = tau + 1 are stored.
+ * With p0 = q = 0 every gain is exactly 0 (a pure model rollout from the first observation);
+ * with an exact model and exact measurements every innovation is exactly 0 and est is the
+ * truth.  A bias is unobservable with H = I and is not estimated. */
+#define MPCQ_ESTIMATOR_MAX_LAG 8
+#define MPCQ_ESTIMATOR_MAX_F_LAG 4
+#define MPCQ_EST_POST 0
+#define MPCQ_EST_PREV 12
+#define MPCQ_EST_P 24
+#define MPCQ_EST_CLOCK 42
+#define MPCQ_EST_RING 44
+#define MPCQ_EST_SLOTS 12   /* MPCQ_ESTIMATOR_MAX_LAG + MPCQ_ESTIMATOR_MAX_F_LAG */
+#define MPCQ_EST_ROW 332    /* doubles: 2656 bytes, a multiple of 16 */
+typedef struct mpcq_estimator_params {   /* 320 bytes */
+  int32_t lag;                          /* 0..8: the age in ticks of a measurement (the channel's delay) */
+  int32_t f_lag;                        /* 0..4: ticks between a solve and its forces (the channel's latency) */
+  int32_t skip_repeats;                 /* nonzero: a repeated observation row is a missing frame */
+  int32_t reserved[5];                  /* zero */
+  double q[12];                         /* process variance per state component (c, rpy, v, w) */
+  double r[12];                         /* measurement variance, > 0 */
+  double p0[12];                        /* initial variance */
+} mpcq_estimator_params;
+#ifdef __cplusplus
+static_assert(sizeof(mpcq_estimator_params) == 320, "mpcq_estimator_params is 320 bytes");
+#else
+_Static_assert(sizeof(mpcq_estimator_params) == 320, "mpcq_estimator_params is 320 bytes");
+#endif
+/* lag 0, f_lag 0, skip_repeats 1, p0 = 1e-2, q = 1e-6 (components 0..5) and 1e-4 (6..11),
+ * r = 1e-4: starting values, not tuned; set r to the channel's sigma^2. */
+void mpcq_default_estimator_params(mpcq_estimator_params* ep);
+/* One tick of the filter for a batch, on its own.
+ *   first       [B] int32 or NULL: nonzero = a first tick for this robot; all_first != 0: all
+ *   obs         [B][12]
+ *   f_prev      [B][12], feet_prev [B][3][4]: the previous tick's f0 and feet (not read by a
+ *               robot that initialises)
+ *   failed_prev [B] int32 or NULL: nonzero = the previous tick failed
+ *   robots      [B] mpcq_robot or NULL (the context's params); a host table is validated as in
+ *               mpcq_set_robots
+ *   row         [B][MPCQ_EST_ROW] in/out (all zero: a new filter);  est [B][12] out
+ * ep NULL = the defaults.  Host pointers, or device pointers with MPCQ_FLAG_DEVICE_PTRS (then
+ * MPCQ_FLAG_ASYNC does not wait for the stream).  MPCQ_E_INVALID, nothing launched, the message
+ * naming the field: lag outside 0..8, f_lag outside 0..4, r[i] <= 0, a negative q[i] or p0[i],
+ * any NaN or infinity, reserved not zero; a NULL obs, f_prev, feet_prev, row or est.  The
+ * parameters are checked before anything else. */
+int mpcq_estimator_step_batch(mpcq_ctx* ctx, const mpcq_estimator_params* ep, int64_t batch,
+                              const int32_t* first, int all_first, const double* obs,
+                              const double* f_prev, const double* feet_prev,
+                              const int32_t* failed_prev, const mpcq_robot* robots, double* row,
+                              double* est, uint32_t flags);
+/* Opt-in (ep NULL = the defaults; invalid parameters: MPCQ_E_INVALID naming the field, nothing
+ * is launched and the parameters in force stay).  While enabled a tick runs the estimate stage
+ * after its observe stage (or, without a channel, after the staging of its inputs) and before
+ * the planner: obs = what the planner would have taken as its state (MPCQ_HV_OBS, or the staged
+ * state); f_prev = MPCQ_SV_F0 and feet_prev = row 0 of MPCQ_SV_FSTEPS as they stand before this
+ * tick's planner; the previous tick failed by the plant's rule (MPCQ_SV_STATUS none of SOLVED,
+ * SOLVED_INACCURATE, MAX_ITER_REACHED, or a planner status); a robot is first exactly where the
+ * planner takes it as first.  The planner takes MPCQ_EV_EST as its state: column 0 of
+ * MPCQ_SV_XREF is the estimate, bit for bit.  The plant and the monitor keep reading the truth.
+ * It works without a channel and without a plant.  A reset or an auto-reset needs nothing of its
+ * own: the first flags carry it.
+ * The first call makes the MPCQ_EV_* arrays, zero (valid = 0).  Enabling while not enabled
+ * zeroes the rows again (a ring that missed ticks is stale).  Calling it while enabled only
+ * replaces the parameters; a changed lag re-initialises each robot at its next tick by rule 1.
+ * A session that never enables it launches exactly what it did before. */
+int mpcq_session_enable_estimator(mpcq_session* s, const mpcq_estimator_params* ep);
+/* The ticks after it run without the launch; the arrays stay. */
+int mpcq_session_disable_estimator(mpcq_session* s);
+/* The estimator's arrays; they exist from the first mpcq_session_enable_estimator on (before:
+ * MPCQ_E_INVALID). */
+#define MPCQ_EV_EST 0       /* [B][12]            the last tick's estimate (derived: not in snapshots) */
+#define MPCQ_EV_ROW 1       /* [B][MPCQ_EST_ROW]  the filter state */
+#define MPCQ_EV_COUNT 2
+/* Copy array `what` to dst (host, or device with MPCQ_FLAG_DEVICE_PTRS); blocking. */
+int mpcq_session_estimator_read(mpcq_session* s, int what, void* dst, uint32_t flags);
+/* Device address of array `what` (valid until mpcq_session_destroy). */
+int mpcq_session_estimator_device_ptr(mpcq_session* s, int what, void** out);
+
 /* ---- snapshots: save, restore and branch robots on the device ---------------
  * A snapshot is a device-resident copy of everything per-robot that a session holds, plus the
  * few host flags that decide what the next tick launches.  Every call below runs on the
@@ -988,8 +1115,11 @@ int mpcq_session_channel_device_ptr(mpcq_session* s, int what, void** out);
  * saved -- the main group (MPCQ_SV_F0 .. _H_ROT, MPCQ_SV_FIRST, the warm start, the planner's
  * status, the engine's info, the creation gait table), the swing arrays (after
  * mpcq_session_enable_swing), MPCQ_PV_* (after _enable_plant / _set_wrench), MPCQ_MV_* (after
- * _enable_monitor), MPCQ_CV_* (after _enable_scenario), MPCQ_HV_* (after _enable_channel), and
- * the tables of mpcq_session_set_robots / _set_plant_robots where in force -- and its shape: N,
+ * _enable_monitor), MPCQ_CV_* (after _enable_scenario), MPCQ_HV_* (after _enable_channel), MPCQ_EV_ROW (after
+ * _enable_estimator; the row is self-describing, so a restore into a session with another lag is
+ * legal and re-initialises by the filter's rule 1; MPCQ_EV_EST is derived, rewritten by every
+ * tick before anything reads it, and left out: after a restore it shows the session's last tick
+ * until the next one), and the tables of mpcq_session_set_robots / _set_plant_robots where in force -- and its shape: N,
  * B, which of these exist, the swing k_mpc, the channel's delay and latency in force at the
  * save (the rings mean nothing under others: a restore into a session whose values differ is
  * MPCQ_E_INVALID); and whether a tick has run since create and whether a reset was ever called.  Not held: the staging of host inputs and the plant's copy of q_w (every
@@ -1048,14 +1178,15 @@ int mpcq_session_snapshot_restore(mpcq_session* s, const mpcq_snapshot* snap, co
 int mpcq_session_fork(mpcq_session* s, const int32_t* map, uint32_t flags);
 /* Checkpoint to the host.  One blob = a 128-byte header, then the groups' arrays unpadded, in
  * the order main, swing, plant, monitor, scenario, robots table, plant robots table, channel,
- * inside a group by array id (the private main arrays behind the named ones).  The header,
- * little endian: char magic[8] "MPCQSNP1"; uint32 version (2 with a channel part, else 1: a
- * session without a channel writes the version-1 blob byte for byte; import reads both); int32
+ * estimator, inside a group by array id (the private main arrays behind the named ones).  The
+ * header, little endian: char magic[8] "MPCQSNP1"; uint32 version (3 with an estimator part, else
+ * 2 with a channel part, else 1: a session without either writes the version-1 blob byte for
+ * byte, one with a channel and no estimator the version-2 blob; import reads all three); int32
  * N; int64 B; int32 k_mpc (0: no swing arrays); uint32 flags (bit 0 a tick had run, 1 a reset
  * was recorded, 2 swing, 3 plant, 4 monitor, 5 scenario, 6 robots table, 7 plant robots table,
- * 8 channel); int64 group_bytes[7]; int64 total (header included); int64 user (0; for the
+ * 8 channel, 9 estimator); int64 group_bytes[7]; int64 total (header included); int64 user (0; for the
  * caller, ignored by import); at offset 104 int64 bytes of the channel part; at 112 int32
- * delay, latency in force at the save; zeros.
+ * delay, latency in force at the save; at 120 int64 bytes of the estimator part (MPCQ_EV_ROW).
  * _bytes: the size of snap's blob (snap saved).  _export: dst is a host buffer of exactly
  * that many bytes; blocking.  _import: makes snap the snapshot the blob describes, for s's
  * context; before it touches the device it checks the magic, the version, N against the

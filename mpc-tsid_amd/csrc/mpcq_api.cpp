@@ -290,6 +290,25 @@ int mpcq::channel_params(const mpcq_channel_params* ch, mpcq_channel_params* out
   return MPCQ_OK;
 }
 
+int mpcq::estimator_params(const mpcq_estimator_params* ep, mpcq_estimator_params* out) {
+  if (ep) *out = *ep;
+  else mpcq_default_estimator_params(out);
+  const mpcq_estimator_params& p = *out;
+  if (p.lag < 0 || p.lag > MPCQ_ESTIMATOR_MAX_LAG)
+    return fail(MPCQ_E_INVALID, "the estimator needs lag in 0..%d (got %d)", MPCQ_ESTIMATOR_MAX_LAG, p.lag);
+  if (p.f_lag < 0 || p.f_lag > MPCQ_ESTIMATOR_MAX_F_LAG)
+    return fail(MPCQ_E_INVALID, "the estimator needs f_lag in 0..%d (got %d)", MPCQ_ESTIMATOR_MAX_F_LAG, p.f_lag);
+  for (int i = 0; i < 12; ++i)
+    if (!(isfinite(p.q[i]) && p.q[i] >= 0)) return fail(MPCQ_E_INVALID, "the estimator needs a finite q[%d] >= 0", i);
+  for (int i = 0; i < 12; ++i)
+    if (!(isfinite(p.r[i]) && p.r[i] > 0)) return fail(MPCQ_E_INVALID, "the estimator needs a finite r[%d] > 0", i);
+  for (int i = 0; i < 12; ++i)
+    if (!(isfinite(p.p0[i]) && p.p0[i] >= 0)) return fail(MPCQ_E_INVALID, "the estimator needs a finite p0[%d] >= 0", i);
+  for (int i = 0; i < 5; ++i)
+    if (p.reserved[i]) return fail(MPCQ_E_INVALID, "the estimator's reserved fields must be zero");
+  return MPCQ_OK;
+}
+
 int mpcq::check_ctx(mpcq_ctx* c, int64_t batch) {
   if (!c) return fail(MPCQ_E_INVALID, "ctx is NULL");
   if (batch < 0 || batch > (int64_t)0x7fffffff) return fail(MPCQ_E_INVALID, "bad batch %lld", (long long)batch);
@@ -1126,6 +1145,68 @@ int mpcq_channel_actuate_batch(mpcq_ctx* c, const mpcq_channel_params* ch, int64
     a.f0 = f0; a.clock = clock; a.draw = draw; a.f_ring = f_ring; a.f_cmd = f_cmd;
   }
   HIP_TRY(mpcq::launch_actuate(P, a, c->stream));
+  if (!dev) return unstage(c, xs, NX);
+  if (!(flags & MPCQ_FLAG_ASYNC)) HIP_TRY(hipStreamSynchronize(c->stream));
+  return MPCQ_OK;
+}
+
+// Estimator: starting values, not tuned (include/mpcq.h).
+void mpcq_default_estimator_params(mpcq_estimator_params* ep) {
+  if (!ep) return;
+  memset(ep, 0, sizeof(*ep));
+  ep->skip_repeats = 1;
+  for (int i = 0; i < 12; ++i) {
+    ep->q[i] = i < 6 ? 1e-6 : 1e-4;
+    ep->r[i] = 1e-4;
+    ep->p0[i] = 1e-2;
+  }
+}
+
+int mpcq_estimator_step_batch(mpcq_ctx* c, const mpcq_estimator_params* ep, int64_t B, const int32_t* first,
+                              int all_first, const double* obs, const double* f_prev, const double* feet_prev,
+                              const int32_t* failed_prev, const mpcq_robot* robots, double* row, double* est,
+                              uint32_t flags) {
+  mpcq_estimator_params P;
+  int rc = estimator_params(ep, &P);  // first: what is wrong with the parameters needs no context
+  if (rc) return rc;
+  rc = check_ctx(c, B);
+  if (rc) return rc;
+  if (!obs || !f_prev || !feet_prev || !row || !est)
+    return fail(MPCQ_E_INVALID, "obs, f_prev, feet_prev, row and est are required");
+  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
+  if (robots && !dev) {
+    rc = check_robots(robots, B);
+    if (rc) return rc;
+  }
+  if (B == 0) return MPCQ_OK;
+  DeviceGuard g(c->device);
+  mpcq::EstimateArgs a{};
+  a.batch = B;
+  a.all_first = all_first != 0;
+  a.dt = c->p.dt;
+  a.gravity = c->p.gravity;
+  mpcq_default_robot(&c->p, &a.dflt);
+  const size_t b = (size_t)B;
+  enum { FI, OB, FP, FT, FA, RB, RO, ES, NX };
+  Xfer xs[NX] = {{first, nullptr, b * 4, nullptr},
+                 {obs, nullptr, b * 96, nullptr},
+                 {f_prev, nullptr, b * 96, nullptr},
+                 {feet_prev, nullptr, b * 96, nullptr},
+                 {failed_prev, nullptr, b * 4, nullptr},
+                 {robots, nullptr, b * sizeof(mpcq_robot), nullptr},
+                 {row, row, b * MPCQ_EST_ROW * 8, nullptr},
+                 {nullptr, est, b * 96, nullptr}};
+  if (!dev) {
+    rc = stage(c, xs, NX);
+    if (rc) return rc;
+    a.first = (const int32_t*)xs[FI].dev; a.obs = (const double*)xs[OB].dev; a.f_prev = (const double*)xs[FP].dev;
+    a.feet_prev = (const double*)xs[FT].dev; a.failed = (const int32_t*)xs[FA].dev;
+    a.robots = (const mpcq_robot*)xs[RB].dev; a.row = (double*)xs[RO].dev; a.est = (double*)xs[ES].dev;
+  } else {
+    a.first = first; a.obs = obs; a.f_prev = f_prev; a.feet_prev = feet_prev; a.failed = failed_prev;
+    a.robots = robots; a.row = row; a.est = est;
+  }
+  HIP_TRY(mpcq::launch_estimate(P, a, c->stream));
   if (!dev) return unstage(c, xs, NX);
   if (!(flags & MPCQ_FLAG_ASYNC)) HIP_TRY(hipStreamSynchronize(c->stream));
   return MPCQ_OK;

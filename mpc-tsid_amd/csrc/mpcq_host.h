@@ -85,5 +85,5 @@ int plant_params(const mpcq_plant_params* pl, double dt_default, mpcq_plant_para
 int monitor_params(const mpcq_monitor_params* mp, mpcq_monitor_params* out);
 int scenario_params(const mpcq_scenario_params* sc, mpcq_scenario_params* out);
 int channel_params(const mpcq_channel_params* ch, mpcq_channel_params* out);
-
+int estimator_params(const mpcq_estimator_params* ep, mpcq_estimator_params* out);
 }  // namespace mpcq

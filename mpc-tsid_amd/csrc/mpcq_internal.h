@@ -317,6 +317,28 @@ hipError_t launch_actuate(const mpcq_channel_params& ch, const ActuateArgs& a, h
 // mpcq_session_enable_channel's launch: every non-negative stored tau to its complement
 hipError_t launch_channel_arm(int32_t* clock, int64_t batch, hipStream_t s);
 
+// Estimate stage (mpcq_estimator.hip); semantics and layouts in include/mpcq.h
+// (mpcq_estimator_step_batch, mpcq_session_enable_estimator).  Sixteen lanes per robot.
+struct EstimateArgs {
+  int64_t batch;
+  const int32_t* first;    // [B] or null: nonzero = a first tick
+  int all_first;           // every robot runs a first tick
+  const double* obs;       // [B][12]
+  const double* f_prev;    // [B][12]
+  const double* feet_prev; // [B][3][4], or null with fsteps
+  const double* fsteps;    // [B][20][13] (a session's tick): the feet are row 0's
+  const int32_t* failed;   // [B] or null: nonzero = the previous tick failed
+  // a session's tick: the previous tick's statuses, failed by the plant's rule (failed null)
+  const int32_t* status;      // [B] or null
+  const int32_t* plan_status; // [B]
+  const mpcq_robot* robots;// [B] or null: dflt
+  mpcq_robot dflt;
+  double dt, gravity;      // the context's
+  double* row;             // [B][MPCQ_EST_ROW] in/out
+  double* est;             // [B][12] out
+};
+hipError_t launch_estimate(const mpcq_estimator_params& ep, const EstimateArgs& a, hipStream_t s);
+
 // Row gather of a snapshot restore (mpcq_snapshot.hip; semantics in include/mpcq.h,
 // mpcq_session_snapshot_restore / mpcq_debug_gather_rows): row b of every dst array <- row
 // map[b] of its src array, in one launch.  The table travels in the kernel arguments.

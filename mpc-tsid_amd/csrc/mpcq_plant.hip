@@ -13,21 +13,11 @@
 
 #pragma clang fp contract(off)
 
+#include "mpcq_model.h"
 #include "mpcq_virtual.h"
 
 namespace mpcq {
 namespace {
-
-// x = inv(m) b by the adjugate (m row-major 3x3)
-__device__ __forceinline__ void solve3(const double* m, const double* b, double* x) {
-  const double c00 = m[4] * m[8] - m[5] * m[7], c01 = m[2] * m[7] - m[1] * m[8], c02 = m[1] * m[5] - m[2] * m[4];
-  const double c10 = m[5] * m[6] - m[3] * m[8], c11 = m[0] * m[8] - m[2] * m[6], c12 = m[2] * m[3] - m[0] * m[5];
-  const double c20 = m[3] * m[7] - m[4] * m[6], c21 = m[1] * m[6] - m[0] * m[7], c22 = m[0] * m[4] - m[1] * m[3];
-  const double det = (m[0] * c00 + m[1] * c10) + m[2] * c20;
-  x[0] = ((c00 * b[0] + c01 * b[1]) + c02 * b[2]) / det;
-  x[1] = ((c10 * b[0] + c11 * b[1]) + c12 * b[2]) / det;
-  x[2] = ((c20 * b[0] + c21 * b[1]) + c22 * b[2]) / det;
-}
 
 // One tick of one robot: x [12] in/out; px, py, pz [4] the feet (NaN = swing); f [12] in,
 // the effective forces out; w [6] the wrench in x's frame.

@@ -2,7 +2,7 @@
 // sessions, per-robot state resident in HBM.
 //
 // A session's device arrays come in groups (alloc_group): the main one made by
-// mpcq_session_create, and one each for swing, plant, monitor, scenario and channel, made when
+// mpcq_session_create, and one each for swing, plant, monitor, scenario, channel and estimator, made when
 // they are first enabled.  A tick (session_tick) is a list of stages, each filling the argument struct of
 // its launch from the groups' arrays.  All numerics run in the HIP kernels.
 #include <math.h>
@@ -25,7 +25,7 @@ enum { SP_WARM_X = MPCQ_SV_COUNT, SP_PLAN_STATUS, SP_INFO, SP_IN_STATE, SP_IN_LF
 enum { PP_QW_PREV = MPCQ_PV_COUNT, PP_COUNT };
 
 // The arrays of one kind of id: MPCQ_SV_* (the swing slots are null until
-// mpcq_session_enable_swing), MPCQ_PV_*, MPCQ_MV_*, MPCQ_CV_*, MPCQ_HV_*.
+// mpcq_session_enable_swing), MPCQ_PV_*, MPCQ_MV_*, MPCQ_CV_*, MPCQ_HV_*, MPCQ_EV_*.
 struct Group {
   const char *kind, *enable;  // "<kind> array %d needs mpcq_session_enable_<enable>"
   int named;                  // the ids the _read / _write / _device_ptr entry points reach
@@ -47,16 +47,18 @@ struct mpcq_session {
   Group mv{"monitor", "monitor", MPCQ_MV_COUNT};  // made by the first enable_monitor
   Group cv{"scenario", "scenario", MPCQ_CV_COUNT};  // made by the first enable_scenario
   Group hv{"channel", "channel", MPCQ_HV_COUNT};    // made by the first enable_channel
+  Group ev{"estimator", "estimator", MPCQ_EV_COUNT};  // made by the first enable_estimator
   void* swing_mem = nullptr;                      // MPCQ_SV_SWING_REF, _SWING_STATE, _FRAME
   bool have_order = false;  // MPCQ_SV_ORDER holds the next solve's order (longest previous first)
   bool use_order = true;    // MPCQ_DISPATCH_ORDER=0 turns it off (A/B timing only; results are identical)
   bool resets = false;      // mpcq_session_reset was called: from then on the ticks consult MPCQ_SV_FIRST
-  bool swing = false, plant = false, monitor = false, scenario = false, channel = false;
+  bool swing = false, plant = false, monitor = false, scenario = false, channel = false, estimator = false;
   mpcq_swing_params sp{};
   mpcq_plant_params pl{};
   mpcq_monitor_params mp{};
   mpcq_scenario_params sc{};
   mpcq_channel_params ch{};  // (delay and latency: what the rings in hv were primed under)
+  mpcq_estimator_params ep{};
   RobotTable robots;        // mpcq_session_set_robots (the session's own, not the context's)
   RobotTable plant_robots;  // mpcq_session_set_plant_robots
   mpcq_snapshot* fork_snap = nullptr;  // mpcq_session_fork's own, made on first use
@@ -106,6 +108,10 @@ void channel_bytes(size_t B, size_t nb[MPCQ_HV_COUNT]) {  // CLOCK, OBS, F_CMD, 
   const size_t h[MPCQ_HV_COUNT] = {B * 8, B * 96, B * 96, B * 128, B * MPCQ_CHANNEL_MAX_DELAY * 96,
                                    B * MPCQ_CHANNEL_MAX_LATENCY * 96};
   for (int w = 0; w < MPCQ_HV_COUNT; ++w) nb[w] = h[w];
+}
+
+void estimator_bytes(size_t B, size_t nb[MPCQ_EV_COUNT]) {  // EST, ROW
+  nb[MPCQ_EV_EST] = B * 96; nb[MPCQ_EV_ROW] = B * MPCQ_EST_ROW * 8;
 }
 
 // n arrays of nb[i] bytes, each 256-B aligned, in one allocation zeroed on the context's
@@ -327,6 +333,7 @@ int mpcq_session_destroy(mpcq_session* s) {
     if (s->mv.mem) (void)hipFree(s->mv.mem);
     if (s->cv.mem) (void)hipFree(s->cv.mem);
     if (s->hv.mem) (void)hipFree(s->hv.mem);
+    if (s->ev.mem) (void)hipFree(s->ev.mem);
     (void)mpcq_session_snapshot_destroy(s->fork_snap);
   }
   delete s;
@@ -536,6 +543,33 @@ int mpcq_session_disable_channel(mpcq_session* s) {
   return MPCQ_OK;
 }
 
+int mpcq_session_enable_estimator(mpcq_session* s, const mpcq_estimator_params* ep) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  mpcq_estimator_params P;
+  int rc = estimator_params(ep, &P);
+  if (rc) return rc;
+  DeviceGuard g(s->ctx->device);
+  if (!s->ev.mem) {  // the arrays, zero: every filter invalid
+    size_t nb[MPCQ_EV_COUNT];
+    estimator_bytes((size_t)s->B, nb);
+    Group ev = s->ev;
+    rc = alloc_group(s->ctx, "the estimator arrays", MPCQ_EV_COUNT, nb, &ev.mem, ev.ptr, ev.bytes);
+    if (rc) return rc;
+    s->ev = ev;
+  } else if (!s->estimator) {  // the rings missed the ticks since the disable: every filter invalid again
+    HIP_TRY(hipMemsetAsync(s->ev.ptr[MPCQ_EV_ROW], 0, s->ev.bytes[MPCQ_EV_ROW], s->ctx->stream));
+  }
+  s->ep = P;
+  s->estimator = true;
+  return MPCQ_OK;
+}
+
+int mpcq_session_disable_estimator(mpcq_session* s) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  s->estimator = false;
+  return MPCQ_OK;
+}
+
 }  // extern "C"
 
 namespace {
@@ -544,7 +578,8 @@ namespace {
 struct Tick {
   int k;
   const double *state, *l_feet, *v_ref;
-  const double* plan_state;  // what the planner takes as the state: state, or the channel's observation
+  const double* plan_state;  // what the planner takes as the state: state, the channel's observation, or
+                             // the estimator's estimate
   const int32_t* reduced;  // or null
   // after a mpcq_session_reset: a robot whose MPCQ_SV_FIRST is set runs this tick as a first
   // tick whatever k says (the planner's extra pass then touches those robots only)
@@ -598,6 +633,25 @@ int tick_observe(mpcq_session* s, Tick& t) {
   a.s_ring = h.d(MPCQ_HV_S_RING); a.f_ring = h.d(MPCQ_HV_F_RING);
   HIP_TRY(mpcq::launch_observe(s->ch, a, s->ctx->stream));
   t.plan_state = h.d(MPCQ_HV_OBS);
+  return MPCQ_OK;
+}
+
+// The estimator: the planner's state becomes the filter's estimate from what it would have
+// taken (t.plan_state), the previous tick's f0, feet and statuses as they stand before this
+// tick's planner, and the model's robots; it takes the first flags as the planner will.
+int tick_estimate(mpcq_session* s, Tick& t) {
+  mpcq_ctx* c = s->ctx;
+  const Group &v = s->sv, &e = s->ev;
+  mpcq::EstimateArgs a{};
+  a.batch = s->B; a.first = t.first_k; a.all_first = t.k == 0; a.obs = t.plan_state;
+  a.f_prev = v.d(MPCQ_SV_F0); a.fsteps = v.d(MPCQ_SV_FSTEPS);
+  a.status = v.i(MPCQ_SV_STATUS); a.plan_status = v.i(SP_PLAN_STATUS);
+  a.robots = s->robots.count ? s->robots.dev : nullptr;
+  mpcq_default_robot(&c->p, &a.dflt);
+  a.dt = c->p.dt; a.gravity = c->p.gravity;
+  a.row = e.d(MPCQ_EV_ROW); a.est = e.d(MPCQ_EV_EST);
+  HIP_TRY(mpcq::launch_estimate(s->ep, a, c->stream));
+  t.plan_state = e.d(MPCQ_EV_EST);
   return MPCQ_OK;
 }
 
@@ -745,7 +799,7 @@ int tick_swing(mpcq_session* s) {
   return MPCQ_OK;
 }
 
-// One tick: its stages in stream order ([scenario] -> inputs -> [observe] -> planner -> solve ->
+// One tick: its stages in stream order ([scenario] -> inputs -> [observe] -> [estimate] -> planner -> solve ->
 // retrieve -> [actuate -> plant] -> [monitor] -> order -> [swing] -> [auto-reset]).
 int session_tick(mpcq_session* s, int k, const double* state, const double* l_feet, const double* v_ref,
                  const int32_t* reduced, uint32_t flags, double* trace) {
@@ -763,6 +817,7 @@ int session_tick(mpcq_session* s, int k, const double* state, const double* l_fe
   if (!rc) rc = tick_inputs(s, state, l_feet, v_ref, reduced, dev, t);
   if (!rc && !v_ref) t.v_ref = s->cv.d(MPCQ_CV_V_REF);
   if (!rc && s->channel) rc = tick_observe(s, t);
+  if (!rc && s->estimator) rc = tick_estimate(s, t);
   if (!rc) rc = tick_plan(s, t);
   if (!rc) rc = tick_solve(s, t);
   if (!rc) rc = tick_retrieve(s, t);
@@ -859,6 +914,10 @@ int mpcq_session_channel_read(mpcq_session* s, int what, void* dst, uint32_t fla
   return group_read(s, &mpcq_session::hv, what, dst, flags);
 }
 
+int mpcq_session_estimator_read(mpcq_session* s, int what, void* dst, uint32_t flags) {
+  return group_read(s, &mpcq_session::ev, what, dst, flags);
+}
+
 int mpcq_session_device_ptr(mpcq_session* s, int what, void** out) {
   return group_device_ptr(s, &mpcq_session::sv, what, out);
 }
@@ -877,6 +936,10 @@ int mpcq_session_scenario_device_ptr(mpcq_session* s, int what, void** out) {
 
 int mpcq_session_channel_device_ptr(mpcq_session* s, int what, void** out) {
   return group_device_ptr(s, &mpcq_session::hv, what, out);
+}
+
+int mpcq_session_estimator_device_ptr(mpcq_session* s, int what, void** out) {
+  return group_device_ptr(s, &mpcq_session::ev, what, out);
 }
 
 int mpcq_session_write(mpcq_session* s, int what, const void* src, uint32_t flags) {
@@ -903,11 +966,13 @@ int mpcq_session_write(mpcq_session* s, int what, const void* src, uint32_t flag
 namespace {
 
 // The parts of a snapshot, in the blob's order; each is one allocation (alloc_group).
-enum { G_MAIN, G_SWING, G_PLANT, G_MONITOR, G_SCENARIO, G_ROBOTS, G_PLANT_ROBOTS, G_CHANNEL, G_COUNT };
+enum { G_MAIN, G_SWING, G_PLANT, G_MONITOR, G_SCENARIO, G_ROBOTS, G_PLANT_ROBOTS, G_CHANNEL, G_ESTIMATOR,
+       G_COUNT };
 const char* const kPartName[G_COUNT] = {"the snapshot's session arrays", "the snapshot's swing arrays",
                                         "the snapshot's plant arrays", "the snapshot's monitor arrays",
                                         "the snapshot's scenario arrays", "the snapshot's robots table",
-                                        "the snapshot's plant robots table", "the snapshot's channel arrays"};
+                                        "the snapshot's plant robots table", "the snapshot's channel arrays",
+                                        "the snapshot's estimator row"};
 
 // What a snapshot's allocations follow from, with the context's N.
 struct SnapShape {
@@ -916,6 +981,7 @@ struct SnapShape {
   bool pv = false, mv = false, cv = false, robots = false, plant_robots = false;
   bool hv = false;              // the channel arrays, primed under
   int delay = 0, latency = 0;   // these depths
+  bool ev = false;              // the estimator's row (self-describing: no parameter travels)
 };
 
 }  // namespace
@@ -939,6 +1005,7 @@ SnapShape shape_of(const mpcq_session* s) {
   sh.robots = s->robots.count > 0; sh.plant_robots = s->plant_robots.count > 0;
   sh.hv = s->hv.mem;
   if (sh.hv) { sh.delay = s->ch.delay; sh.latency = s->ch.latency; }
+  sh.ev = s->ev.mem;
   return sh;
 }
 
@@ -966,6 +1033,10 @@ void snap_sizes(const SnapShape& sh, int N, size_t nb[G_COUNT][SP_COUNT]) {
   if (sh.robots) nb[G_ROBOTS][0] = B * sizeof(mpcq_robot);
   if (sh.plant_robots) nb[G_PLANT_ROBOTS][0] = B * sizeof(mpcq_robot);
   if (sh.hv) channel_bytes(B, nb[G_CHANNEL]);
+  if (sh.ev) {
+    estimator_bytes(B, nb[G_ESTIMATOR]);
+    nb[G_ESTIMATOR][MPCQ_EV_EST] = 0;  // (derived: every tick rewrites it before anything reads it)
+  }
 }
 
 // The session's arrays seen as a snapshot's parts (the arrays a snapshot does not hold: null).
@@ -987,6 +1058,7 @@ void session_parts(const mpcq_session* s, Group out[G_COUNT]) {
   if (s->plant_robots.count > 0) { out[G_PLANT_ROBOTS].ptr[0] = s->plant_robots.dev; out[G_PLANT_ROBOTS].bytes[0] = tb; }
   if (s->hv.mem)
     for (int w = 0; w < MPCQ_HV_COUNT; ++w) { out[G_CHANNEL].ptr[w] = s->hv.ptr[w]; out[G_CHANNEL].bytes[w] = s->hv.bytes[w]; }
+  if (s->ev.mem) { out[G_ESTIMATOR].ptr[MPCQ_EV_ROW] = s->ev.ptr[MPCQ_EV_ROW]; out[G_ESTIMATOR].bytes[MPCQ_EV_ROW] = s->ev.bytes[MPCQ_EV_ROW]; }
 }
 
 // One array of a snapshot (a) next to its counterpart (b; null without one), in the blob's order.
@@ -996,14 +1068,18 @@ struct SnapItem {
   bool rows;  // per-robot rows (all but MPCQ_MV_TOTALS)
 };
 
+// The listing's bound: what one gather launch takes, and MPCQ_MV_TOTALS, which is listed and
+// never gathered.
+constexpr int kListMax = kGatherMax + 1;
+
 // The table save, restore, fork, export and import all walk: every array parts `a` hold, with
 // the same array of parts `b` (null: none).  An array `a` holds and `b` lacks is an error (-1).
-int list_arrays(const Group a[G_COUNT], const Group* b, SnapItem out[kGatherMax]) {
+int list_arrays(const Group a[G_COUNT], const Group* b, SnapItem out[kListMax]) {
   int n = 0;
   for (int gi = 0; gi < G_COUNT; ++gi)
     for (int w = 0; w < SP_COUNT; ++w) {
       if (!a[gi].ptr[w]) continue;
-      if (n == kGatherMax || (b && !b[gi].ptr[w])) return -1;
+      if (n == kListMax || (b && !b[gi].ptr[w])) return -1;
       out[n++] = SnapItem{a[gi].ptr[w], b ? b[gi].ptr[w] : nullptr, a[gi].bytes[w], b ? b[gi].bytes[w] : 0,
                           !(gi == G_MONITOR && w == MPCQ_MV_TOTALS)};
     }
@@ -1050,6 +1126,7 @@ const char* shape_difference(const SnapShape& a, const SnapShape& b, bool batch_
   if (a.hv != b.hv) return "the channel arrays exist on one side only";
   if (a.delay != b.delay) return "the channel's delay differs (the rings were filled under another)";
   if (a.latency != b.latency) return "the channel's latency differs (the rings were filled under another)";
+  if (a.ev != b.ev) return "the estimator arrays exist on one side only";
   return nullptr;
 }
 
@@ -1110,7 +1187,7 @@ int snapshot_save(mpcq_session* s, mpcq_snapshot* p, uint32_t flags) {
   }
   Group live[G_COUNT];
   session_parts(s, live);
-  SnapItem it[mpcq::kGatherMax];
+  SnapItem it[kListMax];
   const int n = list_arrays(p->g, live, it);
   if (n < 0) return fail(MPCQ_E_DEVICE, "the snapshot's arrays do not match the session's");
   for (int i = 0; i < n; ++i)
@@ -1145,7 +1222,7 @@ int snapshot_restore(mpcq_session* s, const mpcq_snapshot* p, const int32_t* map
   }
   Group live[G_COUNT];
   session_parts(s, live);
-  SnapItem it[mpcq::kGatherMax];
+  SnapItem it[kListMax];
   const int n = list_arrays(p->g, live, it);
   if (n < 0) return fail(MPCQ_E_INVALID, "the snapshot's arrays do not match the session's");
   mpcq::GatherArgs a{};
@@ -1189,9 +1266,15 @@ struct BlobHeader {
   int64_t user;
   int64_t channel_bytes;   // format version 2: the eighth part,
   int32_t delay, latency;  // and the depths its rings were filled under
-  int64_t zero;
+  int64_t estimator_bytes; // format version 3: the ninth part
 };
-static_assert(sizeof(BlobHeader) == 128 && G_CHANNEL == 7 && G_COUNT == 8, "the blob's header is 128 bytes");
+static_assert(sizeof(BlobHeader) == 128 && G_CHANNEL == 7 && G_ESTIMATOR == 8 && G_COUNT == 9,
+              "the blob's header is 128 bytes");
+
+// The header's byte count of part gi.
+int64_t& part_bytes(BlobHeader& h, int gi) {
+  return gi == G_ESTIMATOR ? h.estimator_bytes : gi == G_CHANNEL ? h.channel_bytes : h.group_bytes[gi];
+}
 const char kMagic[8] = {'M', 'P', 'C', 'Q', 'S', 'N', 'P', '1'};
 
 void blob_header(const SnapShape& sh, int N, bool have_order, bool resets, BlobHeader* h) {
@@ -1199,14 +1282,14 @@ void blob_header(const SnapShape& sh, int N, bool have_order, bool resets, BlobH
   snap_sizes(sh, N, nb);
   memset(h, 0, sizeof(*h));
   memcpy(h->magic, kMagic, 8);
-  h->version = sh.hv ? 2 : 1; h->N = N; h->B = sh.B; h->k_mpc = sh.k_mpc;
+  h->version = sh.ev ? 3 : sh.hv ? 2 : 1; h->N = N; h->B = sh.B; h->k_mpc = sh.k_mpc;
   h->flags = (have_order ? 1u : 0u) | (resets ? 2u : 0u) | (sh.k_mpc > 0 ? 4u : 0u) | (sh.pv ? 8u : 0u) |
              (sh.mv ? 16u : 0u) | (sh.cv ? 32u : 0u) | (sh.robots ? 64u : 0u) | (sh.plant_robots ? 128u : 0u) |
-             (sh.hv ? 256u : 0u);
+             (sh.hv ? 256u : 0u) | (sh.ev ? 512u : 0u);
   h->delay = sh.delay; h->latency = sh.latency;
   h->total = sizeof(*h);
   for (int gi = 0; gi < G_COUNT; ++gi) {
-    int64_t& gb = gi == G_CHANNEL ? h->channel_bytes : h->group_bytes[gi];
+    int64_t& gb = part_bytes(*h, gi);
     for (int w = 0; w < SP_COUNT; ++w) gb += (int64_t)nb[gi][w];
     h->total += gb;
   }
@@ -1280,9 +1363,9 @@ int mpcq_session_snapshot_export(const mpcq_snapshot* p, void* dst, int64_t byte
   BlobHeader h;
   blob_header(p->sh, p->ctx->N, p->have_order, p->resets, &h);
   if (bytes != h.total) return fail(MPCQ_E_INVALID, "the blob has %lld bytes, dst %lld", (long long)h.total, (long long)bytes);
-  SnapItem it[mpcq::kGatherMax];
+  SnapItem it[kListMax];
   const int n = list_arrays(p->g, nullptr, it);
-  if (n < 0) return fail(MPCQ_E_DEVICE, "the snapshot holds more than %d arrays", mpcq::kGatherMax);
+  if (n < 0) return fail(MPCQ_E_DEVICE, "the snapshot holds more than %d arrays", kListMax);
   mpcq_ctx* c = p->ctx;
   DeviceGuard dg(c->device);
   memcpy(dst, &h, sizeof(h));
@@ -1308,12 +1391,13 @@ int mpcq_session_snapshot_import(mpcq_session* s, mpcq_snapshot* p, const void* 
   if (bytes < (int64_t)sizeof(h)) return fail(MPCQ_E_INVALID, "%lld bytes are less than a header", (long long)bytes);
   memcpy(&h, src, sizeof(h));
   if (memcmp(h.magic, kMagic, 8) != 0) return fail(MPCQ_E_INVALID, "not a snapshot blob (magic)");
-  if (h.version != 1 && h.version != 2)
-    return fail(MPCQ_E_INVALID, "blob format version %u, this library reads 1 and 2", h.version);
+  if (h.version < 1 || h.version > 3)
+    return fail(MPCQ_E_INVALID, "blob format version %u, this library reads 1 to 3", h.version);
   if (h.N != c->N) return fail(MPCQ_E_INVALID, "the blob is of a context with N = %d, this one has N = %d", h.N, c->N);
-  const bool chan = h.flags & 256u;
-  if (h.B < 1 || h.B > (int64_t)0x7fffffff || h.k_mpc < 0 || h.k_mpc > 65536 || (h.flags >> 9) ||
-      ((h.flags & 4u) != 0) != (h.k_mpc > 0) || chan != (h.version == 2) ||
+  const bool chan = h.flags & 256u, est = h.flags & 512u;
+  if (h.B < 1 || h.B > (int64_t)0x7fffffff || h.k_mpc < 0 || h.k_mpc > 65536 || (h.flags >> 10) ||
+      ((h.flags & 4u) != 0) != (h.k_mpc > 0) || h.version != (est ? 3u : chan ? 2u : 1u) ||
+      (!est && h.estimator_bytes != 0) ||
       (chan ? h.delay < 0 || h.delay > MPCQ_CHANNEL_MAX_DELAY || h.latency < 0 || h.latency > MPCQ_CHANNEL_MAX_LATENCY
             : h.delay != 0 || h.latency != 0 || h.channel_bytes != 0))
     return fail(MPCQ_E_INVALID, "the blob's header is inconsistent (B %lld, k_mpc %d, flags %#x)", (long long)h.B,
@@ -1323,11 +1407,11 @@ int mpcq_session_snapshot_import(mpcq_session* s, mpcq_snapshot* p, const void* 
   sh.pv = h.flags & 8u; sh.mv = h.flags & 16u; sh.cv = h.flags & 32u;
   sh.robots = h.flags & 64u; sh.plant_robots = h.flags & 128u;
   sh.hv = chan; sh.delay = h.delay; sh.latency = h.latency;
+  sh.ev = est;
   BlobHeader want;
   blob_header(sh, c->N, h.flags & 1u, h.flags & 2u, &want);
   for (int gi = 0; gi < G_COUNT; ++gi) {
-    const int64_t have = gi == G_CHANNEL ? h.channel_bytes : h.group_bytes[gi];
-    const int64_t need = gi == G_CHANNEL ? want.channel_bytes : want.group_bytes[gi];
+    const int64_t have = part_bytes(h, gi), need = part_bytes(want, gi);
     if (have != need)
       return fail(MPCQ_E_INVALID, "the blob's part %d has %lld bytes, its shape says %lld", gi, (long long)have,
                   (long long)need);
@@ -1339,7 +1423,7 @@ int mpcq_session_snapshot_import(mpcq_session* s, mpcq_snapshot* p, const void* 
   mpcq_snapshot fresh;
   int rc = alloc_parts(c, sh, &fresh);
   if (rc) return rc;
-  SnapItem it[mpcq::kGatherMax];
+  SnapItem it[kListMax];
   const int n = list_arrays(fresh.g, nullptr, it);
   size_t off = sizeof(h);
   hipError_t e = n < 0 ? hipErrorInvalidValue : hipSuccess;

@@ -23,6 +23,9 @@ Public surface:
                     state feedback with dropped frames in front of the planner, delayed, scaled,
                     noisy forces in front of the plant (Session.enable_channel); mpcq.channel
                     restates the draws on the host, bit for bit
+  Estimator         the controller's side of the channel, on the device: a per-robot Kalman filter
+                    on the MPC's own model that compensates the measurement's delay through the
+                    recorded forces and footholds (Session.enable_estimator)
   Snapshot          a session's robots saved on the device (Session.snapshot): restore them, seed
                     another session from them, branch one robot into many (Session.restore,
                     Session.fork), checkpoint them to the host (Snapshot.tobytes,
@@ -47,9 +50,13 @@ from ._lib import (FLAG_ASYNC, FLAG_DEVICE_PTRS, FLAG_ORDER_BY_CLASS, MODE_SETUP
                    CV_DRAW, CV_EPOCH, CV_PUSH, CV_ROBOTS, CV_TICK, CV_V_REF, CV_WRENCH, ScenarioParams,
                    default_scenario_params,
                    HV_CLOCK, HV_DRAW, HV_F_CMD, HV_F_RING, HV_OBS, HV_S_RING, CHANNEL_MAX_DELAY,
-                   CHANNEL_MAX_LATENCY, ChannelParams, default_channel_params)
+                   CHANNEL_MAX_LATENCY, ChannelParams, default_channel_params,
+                   EV_EST, EV_ROW, EST_CLOCK, EST_P, EST_POST, EST_PREV, EST_RING, EST_ROW, EST_SLOTS,
+                   ESTIMATOR_MAX_F_LAG, ESTIMATOR_MAX_LAG, EstimatorParams, default_estimator_params)
 from . import channel  # noqa: F401
 from .channel import Channel  # noqa: F401
+from . import estimator  # noqa: F401
+from .estimator import Estimator  # noqa: F401
 from .engine import ROBOT_DTYPE, Engine, dims, pattern, robots  # noqa: F401
 from .monitor import Monitor  # noqa: F401
 from .plant import Plant  # noqa: F401

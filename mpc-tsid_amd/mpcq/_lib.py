@@ -78,6 +78,11 @@ CV_EPOCH, CV_TICK, CV_V_REF, CV_PUSH, CV_WRENCH, CV_ROBOTS, CV_DRAW = range(7)
 # the channel: a session's channel arrays (MPCQ_HV_*), the ring depths
 HV_CLOCK, HV_OBS, HV_F_CMD, HV_DRAW, HV_S_RING, HV_F_RING = range(6)
 CHANNEL_MAX_DELAY, CHANNEL_MAX_LATENCY = 8, 4
+# the estimator: a session's estimator arrays (MPCQ_EV_*), the filter row's offsets in doubles
+# (MPCQ_EST_*), the greatest lags
+EV_EST, EV_ROW = range(2)
+EST_POST, EST_PREV, EST_P, EST_CLOCK, EST_RING, EST_SLOTS, EST_ROW = 0, 12, 24, 42, 44, 12, 332
+ESTIMATOR_MAX_LAG, ESTIMATOR_MAX_F_LAG = 8, 4
 SNAPSHOT_USER_OFFSET = 96  # a snapshot blob's header: the int64 left to the caller (include/mpcq.h)
 
 EXPORTS = ("mpcq_abi_version", "mpcq_default_params", "mpcq_dims", "mpcq_pattern",
@@ -105,6 +110,8 @@ EXPORTS = ("mpcq_abi_version", "mpcq_default_params", "mpcq_dims", "mpcq_pattern
            "mpcq_default_channel_params", "mpcq_channel_observe_batch", "mpcq_channel_actuate_batch",
            "mpcq_session_enable_channel", "mpcq_session_disable_channel", "mpcq_session_channel_read",
            "mpcq_session_channel_device_ptr",
+           "mpcq_default_estimator_params", "mpcq_estimator_step_batch", "mpcq_session_enable_estimator",
+           "mpcq_session_disable_estimator", "mpcq_session_estimator_read", "mpcq_session_estimator_device_ptr",
            "mpcq_session_snapshot_create", "mpcq_session_snapshot_destroy", "mpcq_session_snapshot_save",
            "mpcq_session_snapshot_restore", "mpcq_session_fork", "mpcq_session_snapshot_bytes",
            "mpcq_session_snapshot_export", "mpcq_session_snapshot_import", "mpcq_debug_gather_rows")
@@ -256,6 +263,20 @@ class ChannelParams(C.Structure):
         ("f_sigma", C.c_double * 3),
         ("f_gain", C.c_double),
         ("reserved", C.c_int32 * 2),
+    ]
+
+
+class EstimatorParams(C.Structure):
+    """struct mpcq_estimator_params (include/mpcq.h)."""
+
+    _fields_ = [
+        ("lag", C.c_int32),
+        ("f_lag", C.c_int32),
+        ("skip_repeats", C.c_int32),
+        ("reserved", C.c_int32 * 5),
+        ("q", C.c_double * 12),
+        ("r", C.c_double * 12),
+        ("p0", C.c_double * 12),
     ]
 
 
@@ -421,6 +442,17 @@ def lib():
     for name in ("mpcq_channel_observe_batch", "mpcq_channel_actuate_batch", "mpcq_session_enable_channel",
                  "mpcq_session_disable_channel", "mpcq_session_channel_read", "mpcq_session_channel_device_ptr"):
         getattr(L, name).restype = C.c_int
+    EP = C.POINTER(EstimatorParams)
+    L.mpcq_default_estimator_params.argtypes = [EP]
+    L.mpcq_default_estimator_params.restype = None
+    L.mpcq_estimator_step_batch.argtypes = [vp, EP, C.c_int64, vp, C.c_int] + [vp] * 7 + [C.c_uint32]
+    L.mpcq_session_enable_estimator.argtypes = [vp, EP]
+    L.mpcq_session_disable_estimator.argtypes = [vp]
+    L.mpcq_session_estimator_read.argtypes = [vp, C.c_int, vp, C.c_uint32]
+    L.mpcq_session_estimator_device_ptr.argtypes = [vp, C.c_int, C.POINTER(vp)]
+    for name in ("mpcq_estimator_step_batch", "mpcq_session_enable_estimator", "mpcq_session_disable_estimator",
+                 "mpcq_session_estimator_read", "mpcq_session_estimator_device_ptr"):
+        getattr(L, name).restype = C.c_int
     L.mpcq_session_snapshot_create.argtypes = [vp, C.POINTER(vp)]
     L.mpcq_session_snapshot_destroy.argtypes = [vp]
     L.mpcq_session_snapshot_save.argtypes = [vp, vp, C.c_uint32]
@@ -568,6 +600,25 @@ def default_channel_params(**overrides) -> ChannelParams:
             v = [v] * len(cur) if not hasattr(v, "__len__") else list(v)
             if len(v) != len(cur):
                 raise ValueError(f"channel parameter {k} takes {len(cur)} values")
+            v = type(cur)(*v)
+        setattr(p, k, v)
+    return p
+
+
+def default_estimator_params(**overrides) -> EstimatorParams:
+    """mpcq_default_estimator_params (lag 0, f_lag 0, skip_repeats 1, p0 1e-2, q 1e-6 / 1e-4,
+    r 1e-4: starting values, not tuned); an array field takes a sequence of its length, or one
+    number for every entry."""
+    p = EstimatorParams()
+    lib().mpcq_default_estimator_params(C.byref(p))
+    for k, v in overrides.items():
+        if not hasattr(p, k):
+            raise AttributeError(f"unknown estimator parameter {k}")
+        cur = getattr(p, k)
+        if hasattr(cur, "__len__"):
+            v = [v] * len(cur) if not hasattr(v, "__len__") else list(v)
+            if len(v) != len(cur):
+                raise ValueError(f"estimator parameter {k} takes {len(cur)} values")
             v = type(cur)(*v)
         setattr(p, k, v)
     return p

@@ -120,6 +120,7 @@ class Session:
         self.monitor_params = None
         self.scenario_params = None
         self.channel_params = None
+        self.estimator_params = None
 
     def enable_swing(self, params: L.SwingParams | None = None):
         """Opt in to the swing-foot references: every later tick appends one swing launch over
@@ -327,6 +328,48 @@ class Session:
     def channel_device_ptr(self, what: int) -> int:
         out = C.c_void_p()
         self.engine._call("mpcq_session_channel_device_ptr", self._h, what, C.byref(out))
+        return int(out.value or 0)
+
+    # ------------------------------------------------------------------ estimator
+    def enable_estimator(self, params: L.EstimatorParams | None = None, **overrides):
+        """Opt in to the state estimator: every later tick runs, between the channel's observe
+        stage and the planner, a per-robot Kalman filter on the MPC's own model that takes what
+        the planner would have read (HV_OBS, or the state as staged) as a measurement ``lag``
+        ticks old and predicts forward to now through the recorded SV_F0 (acting ``f_lag`` ticks
+        late) and footholds; the planner reads EV_EST, the plant and the monitor keep the
+        truth.  Set ``lag`` / ``f_lag`` to the channel's ``delay`` / ``latency`` and ``r`` to its
+        ``sigma**2``.  ``params`` None: the defaults, with ``overrides``.  Calling it while
+        enabled only replaces the parameters (another ``lag`` re-initialises every robot at its
+        next tick); enabling after a disable starts every filter anew."""
+        if params is not None and overrides:
+            raise ValueError("pass params or overrides, not both")
+        ep = params or L.default_estimator_params(**overrides)
+        self.engine._call("mpcq_session_enable_estimator", self._h, C.byref(ep))
+        self.estimator_params = ep
+
+    def disable_estimator(self):
+        """The ticks after it run without the estimator's launch; the arrays stay."""
+        self.engine._call("mpcq_session_disable_estimator", self._h)
+        self.estimator_params = None
+
+    def _estimator_shape(self, what: int):
+        B = self.batch
+        shapes = {L.EV_EST: ((B, 12), np.float64), L.EV_ROW: ((B, L.EST_ROW), np.float64)}
+        if what not in shapes:
+            raise L.MpcqError(L.E_INVALID, f"unknown estimator array {what}")
+        return shapes[what]
+
+    def estimator_read(self, what: int):
+        """EV_EST (B, 12) the last tick's estimate, or EV_ROW (B, EST_ROW) the filter state
+        (``mpcq.estimator.unpack`` names its parts)."""
+        shape, dt = self._estimator_shape(what)
+        out = np.empty(shape, dt)
+        self.engine._call("mpcq_session_estimator_read", self._h, what, C.c_void_p(out.ctypes.data), 0)
+        return out
+
+    def estimator_device_ptr(self, what: int) -> int:
+        out = C.c_void_p()
+        self.engine._call("mpcq_session_estimator_device_ptr", self._h, what, C.byref(out))
         return int(out.value or 0)
 
     # ------------------------------------------------------------------ rollouts
