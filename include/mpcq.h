@@ -46,6 +46,8 @@ extern "C" {
  *      17 -> 20; MPCQ_E_INVALID on a session that has not enabled swing)
  *   3 (additions, no bump): mpcq_robot, mpcq_default_robot, mpcq_set_robots,
  *      mpcq_session_set_robots, mpcq_session_get_robots (per-instance mass, gI, mu, fz_max)
+ *   3 (additions, no bump): mpcq_weights, mpcq_default_weights, mpcq_set_weights,
+ *      mpcq_session_set_weights, mpcq_session_get_weights (per-instance diagonal of P)
  *   3 (additions, no bump): mpcq_session_reset (any subset of a session's robots back to their
  *      state after create, between two ticks); MPCQ_SV_FIRST (MPCQ_SV_COUNT 20 -> 21, read-only)
  *   3 (additions, no bump): mpcq_plant_params, mpcq_default_plant_params, mpcq_plant_step_batch,
@@ -204,9 +206,10 @@ int mpcq_set_slice(mpcq_ctx* ctx, int32_t slice_iters);
 
 /* ---- per-robot constants ----------------------------------------------------
  * No reference counterpart (the reference is one robot): the four physical constants of
- * mpcq_params that may differ between the instances of one batch.  Every other field (dt,
- * gravity, weights, footholds, OSQP settings) shapes P, the scaling or the loop counters and
- * stays per context. */
+ * mpcq_params that may differ between the instances of one batch.  The diagonal of P
+ * (state_weights, force_weight) has a table of its own, mpcq_weights below.  Every other
+ * field (dt, gravity, footholds, OSQP settings) shapes the horizon's meaning, the scaling or
+ * the loop counters and stays per context. */
 typedef struct mpcq_robot {      /* 16 doubles = 128 bytes */
   double mass;      /* > 0 */
   double gI[9];     /* row-major 3x3, as mpcq_params.gI */
@@ -238,6 +241,44 @@ void mpcq_default_robot(const mpcq_params* p, mpcq_robot* r);
  * mpcq_qp_solve_batch is untouched by the table: its caller has formulated already, and P
  * comes from the context. */
 int mpcq_set_robots(mpcq_ctx* ctx, int64_t count, const mpcq_robot* robots, uint32_t flags);
+
+/* ---- per-instance cost weights ------------------------------------------------
+ * No reference counterpart (the reference is one controller): the 13 numbers of P's diagonal,
+ * so that every instance of a batch, and every robot of a session, may carry its own tuning. */
+typedef struct mpcq_weights {    /* 16 doubles = 128 bytes */
+  double state[12];  /* as mpcq_params.state_weights, each > 0 */
+  double force;      /* as mpcq_params.force_weight, > 0 */
+  double reserved[3];            /* zero */
+} mpcq_weights;
+#ifdef __cplusplus
+static_assert(sizeof(mpcq_weights) == 128, "mpcq_weights is 16 doubles");
+#else
+_Static_assert(sizeof(mpcq_weights) == 128, "mpcq_weights is 16 doubles");
+#endif
+/* state_weights and force_weight of p (NULL = mpcq_default_params), reserved zero.  A NULL w
+ * is ignored. */
+void mpcq_default_weights(const mpcq_params* p, mpcq_weights* w);
+/* Copies weights [count] into memory the context owns: from a host pointer the call blocks;
+ * with MPCQ_FLAG_DEVICE_PTRS the copy is device to device on ctx's stream, behind the
+ * launches that still read the table it replaces.  In every later mpcq_solve_batch of ctx
+ * (both formulation modes, polish, sliced and class-ordered solves included) instance b takes
+ * the diagonal of P from weights[b] -- b is the instance index, whatever order the workgroups
+ * are dispatched in -- and with it q = -P xref, the scaling and the KKT diagonal; everything
+ * else comes from ctx's mpcq_params, or from the robots table where one is set (the two
+ * tables are independent).  count == 0 or weights == NULL clears the table (the context's
+ * mpcq_params again: a context that never sets one launches exactly what it did before).
+ * While a table is set, a launch with batch > count returns MPCQ_E_INVALID and launches
+ * nothing.
+ * A host table is validated: every state weight and the force weight finite and > 0, reserved
+ * zero; otherwise MPCQ_E_INVALID (the message names the first offending index and field) and
+ * the table in force stays, as it does when the memory for a larger table cannot be
+ * allocated (MPCQ_E_NOMEM).  A device table is not validated: a NaN or Inf among the values
+ * of a row is caught by the solver's non-finite data check and ends as MPCQ_STATUS_NONFINITE
+ * on that instance alone.
+ * mpcq_formulate_batch does not look at the table: Ax, l, u hold no entry of P.
+ * mpcq_qp_solve_batch does not look at it either, as with the robots table: its P comes
+ * from the context's mpcq_params. */
+int mpcq_set_weights(mpcq_ctx* ctx, int64_t count, const mpcq_weights* weights, uint32_t flags);
 
 /* ---- formulation -----------------------------------------------------------
  * Replaces MPC.construct_gait + update_matrices (MPC.py:635-652, 290-378) in
@@ -422,6 +463,17 @@ int mpcq_session_set_robots(mpcq_session* s, const mpcq_robot* robots, uint32_t 
 /* The table in force, robots [B] (host, or device with MPCQ_FLAG_DEVICE_PTRS); blocking.
  * Without a table: mpcq_default_robot(the context's params) for every robot. */
 int mpcq_session_get_robots(mpcq_session* s, mpcq_robot* robots, uint32_t flags);
+/* The session's own table of cost weights, weights [B] (mpcq_set_weights: the same copy,
+ * validation and flags); independent of the context's table.  The ticks after the call solve
+ * robot b under weights[b], and MPCQ_SV_COST is robot b's cost under weights[b].  NULL clears
+ * it.  The table persists across mpcq_session_reset and the monitor's auto-reset.  It is the
+ * controller's tuning, not the robot's state: snapshots do not carry it, and restore,
+ * restore_map and fork leave the table in force untouched -- fork(r) followed by
+ * mpcq_session_set_weights is a tuning sweep from one state. */
+int mpcq_session_set_weights(mpcq_session* s, const mpcq_weights* weights, uint32_t flags);
+/* The table in force, weights [B] (host, or device with MPCQ_FLAG_DEVICE_PTRS); blocking.
+ * Without a table: mpcq_default_weights(the context's params) for every robot. */
+int mpcq_session_get_weights(mpcq_session* s, mpcq_weights* weights, uint32_t flags);
 /* Restart a subset of the robots between two ticks; the others are not written at all.
  *   mask  [B] int32, nonzero = reset this robot; NULL = every robot
  *   gait0 [B][20][5] or NULL (the table the session was created with, of which it keeps a
@@ -1126,7 +1178,9 @@ int mpcq_session_estimator_device_ptr(mpcq_session* s, int what, void** out);
  * tick rewrites them before reading), and MPCQ_SV_ORDER (a permutation, not a per-robot row;
  * the restore rebuilds it, and results do not depend on it).  Parameters and enable flags
  * (swing, plant, monitor, scenario parameters; _enable_* / _disable_*) are configuration, not
- * robots' state: the session's own, never touched.
+ * robots' state: the session's own, never touched.  So is the table of
+ * mpcq_session_set_weights, the controller's tuning: a snapshot does not hold it (the blob of
+ * a session with a table is byte for byte the blob without one) and no restore touches it.
  *
  * create: no device memory until the first save.  The snapshot belongs to s's context (hence
  * its N and stream) and may be restored into any session of that context.  A snapshot may be

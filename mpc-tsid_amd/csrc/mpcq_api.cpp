@@ -192,14 +192,81 @@ int check_robots(const mpcq_robot* r, int64_t count) {
   return MPCQ_OK;
 }
 
+// The first entry of a host table that mpcq_set_weights rejects, named in the message.
+int check_weights(const mpcq_weights* w, int64_t count) {
+  for (int64_t i = 0; i < count; ++i) {
+    for (int j = 0; j < 12; ++j)
+      if (!(isfinite(w[i].state[j]) && w[i].state[j] > 0))
+        return fail(MPCQ_E_INVALID, "weights[%lld]: state[%d] must be finite and > 0", (long long)i, j);
+    if (!(isfinite(w[i].force) && w[i].force > 0))
+      return fail(MPCQ_E_INVALID, "weights[%lld]: force must be finite and > 0", (long long)i);
+    for (int j = 0; j < 3; ++j)
+      if (!(w[i].reserved[j] == 0.0))
+        return fail(MPCQ_E_INVALID, "weights[%lld]: reserved must be zero", (long long)i);
+  }
+  return MPCQ_OK;
+}
+
 // The table a launch of `batch` instances reads: null without one, an error if it is too short.
-int launch_table(const RobotTable& t, int64_t batch, const mpcq_robot** out) {
+template <class R>
+int launch_table(const Table<R>& t, const char* what, int64_t batch, const R** out) {
   *out = nullptr;
   if (t.count == 0) return MPCQ_OK;
   if (batch > t.count)
-    return fail(MPCQ_E_INVALID, "batch %lld > the robot table's count %lld", (long long)batch, (long long)t.count);
+    return fail(MPCQ_E_INVALID, "batch %lld > the %s table's count %lld", (long long)batch, what, (long long)t.count);
   *out = t.dev;
   return MPCQ_OK;
+}
+
+// set_table over either record type (both 128 bytes); check: the host table's validation.
+template <class R>
+int set_table_t(mpcq_ctx* c, Table<R>& t, int64_t count, const R* rows, uint32_t flags, const char* what,
+                int (*check)(const R*, int64_t)) {
+  if (count < 0 || count > (int64_t)0x7fffffff) return fail(MPCQ_E_INVALID, "bad %s count %lld", what, (long long)count);
+  if (count == 0 || !rows) {
+    t.count = 0;
+    return MPCQ_OK;
+  }
+  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
+  if (!dev) {
+    const int rc = check(rows, count);
+    if (rc) return rc;
+  }
+  DeviceGuard g(c->device);
+  if (count > t.cap) {  // the new buffer first: a failed allocation leaves the table in force as it was
+    const size_t nb = (size_t)count * sizeof(R);
+    R* grown = nullptr;
+    if (hipMalloc(&grown, nb) != hipSuccess)
+      return fail(MPCQ_E_NOMEM, "hipMalloc(%zu) for the %s table failed", nb, what);
+    if (t.dev) {
+      hipError_t e = hipStreamSynchronize(c->stream);  // a queued launch may still read it
+      if (e == hipSuccess) e = hipFree(t.dev);
+      if (e != hipSuccess) {
+        (void)hipFree(grown);
+        return fail(MPCQ_E_DEVICE, "releasing the previous %s table failed: %s", what, hipGetErrorString(e));
+      }
+    }
+    t.dev = grown;
+    t.cap = count;
+    t.count = 0;  // (nothing copied yet)
+  }
+  HIP_TRY(hipMemcpyAsync(t.dev, rows, (size_t)count * sizeof(R), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                         c->stream));
+  t.count = count;
+  if (!dev) HIP_TRY(hipStreamSynchronize(c->stream));
+  return MPCQ_OK;
+}
+
+// `rows` copies of the context's own record in a fill table (mpcq_host.h FillTables).
+template <class R>
+int ensure_fill(mpcq_ctx* c, Table<R>& t, int64_t rows, const R& rec) {
+  if (t.count >= rows) return MPCQ_OK;
+  R* h = (R*)malloc((size_t)rows * sizeof(R));
+  if (!h) return fail(MPCQ_E_NOMEM, "malloc for a table of the context's values failed");
+  for (int64_t i = 0; i < rows; ++i) h[i] = rec;
+  const int rc = mpcq::set_table(c, t, rows, h, 0);
+  free(h);
+  return rc;
 }
 
 }  // namespace
@@ -341,39 +408,39 @@ int mpcq::ensure_work(mpcq_ctx* c, int64_t B, double** out) {
 }
 
 int mpcq::set_table(mpcq_ctx* c, RobotTable& t, int64_t count, const mpcq_robot* robots, uint32_t flags) {
-  if (count < 0 || count > (int64_t)0x7fffffff) return fail(MPCQ_E_INVALID, "bad robot count %lld", (long long)count);
-  if (count == 0 || !robots) {
-    t.count = 0;
-    return MPCQ_OK;
+  return set_table_t(c, t, count, robots, flags, "robot", check_robots);
+}
+
+int mpcq::set_table(mpcq_ctx* c, WeightsTable& t, int64_t count, const mpcq_weights* weights, uint32_t flags) {
+  return set_table_t(c, t, count, weights, flags, "weights", check_weights);
+}
+
+int mpcq::launch_tables(mpcq_ctx* c, const RobotTable& robots, const WeightsTable& weights, FillTables& fill,
+                        int64_t batch, const mpcq_robot** r, const mpcq_weights** w) {
+  *r = nullptr;
+  *w = nullptr;
+  int rc = launch_table(robots, "robot", batch, r);
+  if (rc) return rc;
+  rc = launch_table(weights, "weights", batch, w);
+  if (rc) return rc;
+  if (*r && !*w) {
+    mpcq_weights d;
+    mpcq_default_weights(&c->p, &d);
+    rc = ensure_fill(c, fill.weights, batch, d);
+    *w = fill.weights.dev;
+  } else if (*w && !*r) {
+    mpcq_robot d;
+    mpcq_default_robot(&c->p, &d);
+    rc = ensure_fill(c, fill.robots, batch, d);
+    *r = fill.robots.dev;
   }
-  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
-  if (!dev) {
-    const int rc = check_robots(robots, count);
-    if (rc) return rc;
-  }
-  DeviceGuard g(c->device);
-  if (count > t.cap) {  // the new buffer first: a failed allocation leaves the table in force as it was
-    const size_t nb = (size_t)count * sizeof(mpcq_robot);
-    mpcq_robot* grown = nullptr;
-    if (hipMalloc(&grown, nb) != hipSuccess)
-      return fail(MPCQ_E_NOMEM, "hipMalloc(%zu) for the robot table failed", nb);
-    if (t.dev) {
-      hipError_t e = hipStreamSynchronize(c->stream);  // a queued launch may still read it
-      if (e == hipSuccess) e = hipFree(t.dev);
-      if (e != hipSuccess) {
-        (void)hipFree(grown);
-        return fail(MPCQ_E_DEVICE, "releasing the previous robot table failed: %s", hipGetErrorString(e));
-      }
-    }
-    t.dev = grown;
-    t.cap = count;
-    t.count = 0;  // (nothing copied yet)
-  }
-  HIP_TRY(hipMemcpyAsync(t.dev, robots, (size_t)count * sizeof(mpcq_robot),
-                         dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
-  t.count = count;
-  if (!dev) HIP_TRY(hipStreamSynchronize(c->stream));
-  return MPCQ_OK;
+  return rc;
+}
+
+void mpcq::free_tables(FillTables& fill) {
+  if (fill.robots.dev) (void)hipFree(fill.robots.dev);
+  if (fill.weights.dev) (void)hipFree(fill.weights.dev);
+  fill = FillTables{};
 }
 
 extern "C" {
@@ -475,6 +542,18 @@ void mpcq_default_robot(const mpcq_params* p, mpcq_robot* r) {
   r->fz_max = p->fz_max;
 }
 
+void mpcq_default_weights(const mpcq_params* p, mpcq_weights* w) {
+  if (!w) return;
+  mpcq_params d;
+  if (!p) {
+    mpcq_default_params(&d);
+    p = &d;
+  }
+  memset(w, 0, sizeof(*w));
+  memcpy(w->state, p->state_weights, sizeof(w->state));
+  w->force = p->force_weight;
+}
+
 int mpcq_supported_horizons(int32_t* out, int cap) { return mpcq::supported_horizons(out, cap); }
 
 const char* mpcq_last_error(void) { return g_err.c_str(); }
@@ -524,6 +603,8 @@ int mpcq_destroy(mpcq_ctx* c) {
   if (c->sl_buf) (void)hipFree(c->sl_buf);
   if (c->sl_count) (void)hipFree(c->sl_count);
   if (c->robots.dev) (void)hipFree(c->robots.dev);
+  if (c->weights.dev) (void)hipFree(c->weights.dev);
+  mpcq::free_tables(c->fill);
   for (auto& e : c->ev)
     if (e) (void)hipEventDestroy(e);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -547,6 +628,11 @@ int mpcq_set_slice(mpcq_ctx* c, int32_t slice_iters) {
 int mpcq_set_robots(mpcq_ctx* c, int64_t count, const mpcq_robot* robots, uint32_t flags) {
   if (!c) return fail(MPCQ_E_INVALID, "ctx is NULL");
   return set_table(c, c->robots, count, robots, flags);
+}
+
+int mpcq_set_weights(mpcq_ctx* c, int64_t count, const mpcq_weights* weights, uint32_t flags) {
+  if (!c) return fail(MPCQ_E_INVALID, "ctx is NULL");
+  return set_table(c, c->weights, count, weights, flags);
 }
 
 int mpcq_last_kernel_ms(mpcq_ctx* c, double* fms, double* sms) {
@@ -585,7 +671,7 @@ int mpcq_formulate_batch(mpcq_ctx* c, int64_t B, const double* xref, const doubl
   mpcq::LaunchArgs a{};
   a.batch = B;
   a.mode = mode;
-  rc = launch_table(c->robots, B, &a.robots);
+  rc = launch_table(c->robots, "robot", B, &a.robots);  // (no P here: the weights table is not looked at)
   if (rc) return rc;
   const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
   Xfer xs[6] = {{xref, nullptr, B * n12 * 8, nullptr}, {fsteps, nullptr, (size_t)B * 260 * 8, nullptr},
@@ -624,7 +710,7 @@ static int solve_common(mpcq_ctx* c, int64_t B, bool fused, const double* xref, 
   a.batch = B;
   a.mode = mode;
   if (fused) {  // (the qp path has formulated already)
-    rc = launch_table(c->robots, B, &a.robots);
+    rc = mpcq::launch_tables(c, c->robots, c->weights, c->fill, B, &a.robots, &a.weights);
     if (rc) return rc;
   }
   const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;

@@ -604,6 +604,20 @@ __device__ __forceinline__ void load_robot(const mpcq_robot* r, RobotK& rb) {
   rb.mu = uni(r->mu);
 }
 
+// The diagonal of P of the workgroup's instance (ROB solve kernels: LaunchArgs::weights[b],
+// mpcq_set_weights; the others keep the launch's mpcq_params, the code they always had): the force
+// weight uniform in SGPRs, the lane's own state weight (ph = its state index) as one global load.
+template <bool TABLE>
+__device__ __forceinline__ double weight_f(const LaunchArgs& a, int64_t b, double dflt) {
+  if constexpr (TABLE) return uni(a.weights[b].force);
+  else return dflt;
+}
+template <bool TABLE>
+__device__ __forceinline__ double weight_x(const LaunchArgs& a, int64_t b, int ph, double dflt) {
+  if constexpr (TABLE) return a.weights[b].state[ph];
+  else return dflt;
+}
+
 // The 24 CSC values of one foot's three force columns in one stage: dt/m row,
 // B rows 9..11 = dt inv(Rz(yaw) gI) [lever]x (MPC.py:339-345), swing flag S
 // (MPC.py:628), friction-cone coefficients (MPC.py:136-148).
@@ -831,7 +845,9 @@ struct Prologue {
 // The engine kernel.  FUSED: formulate from (xref, fsteps) then solve.
 // !FUSED: solve the given (Ax, l, u).  SOLVE=false: formulation only.
 
-// ROB: the per-robot table (LaunchArgs::robots, not null) in place of p.mass / gI / mu / fz_max.
+// ROB: the per-instance tables, both not null: LaunchArgs::robots in place of p.mass / gI / mu /
+// fz_max, LaunchArgs::weights in place of p.state_weights / force_weight (the solving kernels
+// only; the host fills a table that is not set with the context's values).
 // An instantiation of its own, so that the kernels of a launch without a table are instruction
 // for instruction what they were before the table existed (the formulation's kernels only: the
 // qp path takes Ax, l, u as given).
@@ -968,12 +984,17 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
   };
   const int colF = 12 * N + 12 * k + ph, colX = 12 * k + ph;
 
-  // P diagonal of the own columns (MPC.py:255-275)
-  const double P0f = p.force_weight;
+  // P diagonal of the own columns (MPC.py:255-275).  ROB: row b of the weights table
+  // (LaunchArgs::weights, mpcq_set_weights), read here once -- the lane's own state weight as one
+  // global load, the workgroup-uniform force weight into SGPRs -- and held like the params'
+  // values: q, the Ruiz passes, the cost scaling, K's diagonal and polish read these two.
+  // (The formulation-only kernel has no P and does not touch the table.)
+  const double P0f = weight_f<ROB && SOLVE>(a, b, p.force_weight);
   double P0X = p.state_weights[0];
 #pragma unroll
   for (int e = 1; e < 12; ++e)
     if (ph == e) P0X = p.state_weights[e];
+  P0X = weight_x<ROB && SOLVE>(a, b, ph, P0X);
 
   // Bounds.  FUSED: the dynamics row keeps one value (l = u, MPC.py:410); swing
   // rows are 0 = 0; friction rows u = 0, l = -inf (-OSQP_INFTY) or -fz_max.
@@ -1103,6 +1124,10 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
       int bad = 0;
       for (int e = t; e < nnz; e += T)
         if (!isfinite(AbW[e])) bad = 1;
+      // (a device weights table is not validated on the way in, unlike mpcq_params' P)
+      if constexpr (ROB) {
+        if (!(isfinite(P0X) && isfinite(P0f))) bad = 1;
+      }
       int lgu = 0;  // l > u on an own row (osqp rejects the data)
       if constexpr (FUSED) {
         if (cl && isnan(bnd)) bad = 1;
@@ -3232,6 +3257,9 @@ hipError_t launch_t(bool fused, bool solve, const mpcq_params& p, const LaunchAr
   // register allocation in the ADMM loop) does not carry it
   const bool pol = p.polish != 0;
   const bool rob = a.robots != nullptr && (fused || !solve);
+  // the solving ROB kernels read both tables (mpcq_api.cpp launch_tables passes both or neither)
+  if (rob && solve && !a.weights) return hipErrorInvalidValue;
+  if (!rob && a.weights) return hipErrorInvalidValue;
   if (rob && !solve) hipLaunchKernelGGL((engine_kernel<N, true, false, false, true>), grid, block, 0, s, p, a);
   else if (rob && pol) hipLaunchKernelGGL((engine_kernel<N, true, true, true, true>), grid, block, 0, s, p, a);
   else if (rob) hipLaunchKernelGGL((engine_kernel<N, true, true, false, true>), grid, block, 0, s, p, a);

@@ -4,12 +4,24 @@
 #pragma once
 #include "mpcq_internal.h"
 
-// A table of per-robot constants on the device (mpcq_set_robots, mpcq_session_set_robots):
+// A table of per-instance records on the device -- the robots' constants (mpcq_set_robots,
+// mpcq_session_set_robots) or the cost weights (mpcq_set_weights, mpcq_session_set_weights):
 // count > 0 = in force.
-struct RobotTable {
-  mpcq_robot* dev = nullptr;
+template <class R>
+struct Table {
+  static_assert(sizeof(R) == 128, "a table record is 16 doubles");
+  R* dev = nullptr;
   int64_t cap = 0;
   int64_t count = 0;
+};
+using RobotTable = Table<mpcq_robot>;
+using WeightsTable = Table<mpcq_weights>;
+// The engine's ROB kernels read both tables.  Where only one is set, the other is one of these:
+// a device table of the context's own values, made at the first launch that needs it and grown
+// with the batch (the context's mpcq_params never change after mpcq_create).
+struct FillTables {
+  RobotTable robots;
+  WeightsTable weights;
 };
 
 struct mpcq_ctx {
@@ -48,6 +60,8 @@ struct mpcq_ctx {
   int64_t sl_cap = 0;
   int32_t* sl_count = nullptr;
   RobotTable robots;  // mpcq_set_robots
+  WeightsTable weights;  // mpcq_set_weights
+  FillTables fill;
 };
 
 namespace mpcq {
@@ -79,6 +93,13 @@ int ensure_work(mpcq_ctx* c, int64_t B, double** out);
 // Replace (count > 0) or clear a table.  The copy runs on the context's stream, behind any
 // queued launch that still reads the old values; from a host pointer the call then blocks.
 int set_table(mpcq_ctx* c, RobotTable& t, int64_t count, const mpcq_robot* robots, uint32_t flags);
+int set_table(mpcq_ctx* c, WeightsTable& t, int64_t count, const mpcq_weights* weights, uint32_t flags);
+// The tables a fused launch of `batch` instances reads: both null where neither is set (the
+// kernels of a launch without a table), else both not null, the missing one from `fill`.
+// MPCQ_E_INVALID, and nothing to launch, where a table in force is shorter than the batch.
+int launch_tables(mpcq_ctx* c, const RobotTable& robots, const WeightsTable& weights, FillTables& fill, int64_t batch,
+                  const mpcq_robot** r, const mpcq_weights** w);
+void free_tables(FillTables& fill);
 // The caller's parameters (null: the defaults) into *out, or MPCQ_E_INVALID.
 int swing_params(const mpcq_swing_params* sp, mpcq_swing_params* out);
 int plant_params(const mpcq_plant_params* pl, double dt_default, mpcq_plant_params* out);

@@ -53,12 +53,17 @@ struct LaunchArgs {
   // [B] per-instance mass, gI, mu, fz_max (mpcq_set_robots), or null: the launch's mpcq_params.
   // Indexed by the instance (after the order[] mapping), never by the workgroup; read by the
   // formulation only: not null selects the engine's ROB instantiations.
-  // (Last, so that the other arguments keep their offsets.)
   const mpcq_robot* robots;
   // [B] or null (a session after mpcq_session_reset): nonzero = this instance (after the
   // order[] mapping) runs a first tick -- MPCQ_MODE_SETUP and a cold start that reads none of
   // warm_x, warm_y, rho_in -- whatever mode and the warm pointers say.  Batch solves: null.
   const int32_t* first;
+  // [B] per-instance diagonal of P (mpcq_set_weights, mpcq_session_set_weights), indexed by the
+  // instance like robots.  The ROB instantiations read both tables, so the host passes both or
+  // neither: where one table is set and the other is not, the missing one is a device table of
+  // the context's values (mpcq_api.cpp launch_tables).  Null with robots null.
+  // (Last, so that the other arguments keep their offsets.)
+  const mpcq_weights* weights;
 };
 constexpr int32_t kStatusSuspended = 100;  // (internal: the host loop resumes these)
 constexpr int64_t res_lanes(int N) { return 16 * (int64_t)((N + 3) & ~3); }
@@ -132,6 +137,7 @@ struct SessionArgs {
   double* next_l_feet;   // [B][3][4]
   double state_weights[12];
   double force_weight;
+  const mpcq_weights* weights;  // [B] or null: the two by-value fields above (mpcq_session_set_weights)
   double shoulders[8];
   int32_t* first;        // [B] or null: cleared (the robot's pending reset is served)
 };

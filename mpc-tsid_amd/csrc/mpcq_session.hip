@@ -67,7 +67,9 @@ __global__ __launch_bounds__(64) void retrieve_kernel(SessionArgs a) {
   for (int e = lane; e < n; e += 64) {
     const double v = gx[e];
     xs[e] = v;
-    const double w = e < 12 * N ? a.state_weights[e % 12] : a.force_weight;
+    double w;  // the robot's own diagonal of P where a table is in force (mpcq_session_set_weights)
+    if (a.weights) w = e < 12 * N ? a.weights[b].state[e % 12] : a.weights[b].force;
+    else w = e < 12 * N ? a.state_weights[e % 12] : a.force_weight;
     cost[e] = (v * w) * v;  // (diag(x) @ diag(P)) @ x
   }
   __syncthreads();

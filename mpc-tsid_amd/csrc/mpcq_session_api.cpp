@@ -61,6 +61,8 @@ struct mpcq_session {
   mpcq_estimator_params ep{};
   RobotTable robots;        // mpcq_session_set_robots (the session's own, not the context's)
   RobotTable plant_robots;  // mpcq_session_set_plant_robots
+  WeightsTable weights;     // mpcq_session_set_weights (the controller's tuning: no snapshot holds it)
+  FillTables fill;          // the table a ROB launch reads in place of the one that is not set
   mpcq_snapshot* fork_snap = nullptr;  // mpcq_session_fork's own, made on first use
 };
 
@@ -330,6 +332,8 @@ int mpcq_session_destroy(mpcq_session* s) {
     if (s->robots.dev) (void)hipFree(s->robots.dev);
     if (s->pv.mem) (void)hipFree(s->pv.mem);
     if (s->plant_robots.dev) (void)hipFree(s->plant_robots.dev);
+    if (s->weights.dev) (void)hipFree(s->weights.dev);
+    mpcq::free_tables(s->fill);
     if (s->mv.mem) (void)hipFree(s->mv.mem);
     if (s->cv.mem) (void)hipFree(s->cv.mem);
     if (s->hv.mem) (void)hipFree(s->hv.mem);
@@ -368,6 +372,39 @@ int mpcq_session_get_robots(mpcq_session* s, mpcq_robot* robots, uint32_t flags)
   if (!h) return fail(MPCQ_E_NOMEM, "host malloc failed");
   for (int64_t b = 0; b < s->B; ++b) h[b] = d;
   const hipError_t e = hipMemcpy(robots, h, nb, hipMemcpyHostToDevice);
+  free(h);
+  HIP_TRY(e);
+  return MPCQ_OK;
+}
+
+int mpcq_session_set_weights(mpcq_session* s, const mpcq_weights* weights, uint32_t flags) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  return set_table(s->ctx, s->weights, weights ? s->B : 0, weights, flags);
+}
+
+int mpcq_session_get_weights(mpcq_session* s, mpcq_weights* weights, uint32_t flags) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  if (!weights) return fail(MPCQ_E_INVALID, "weights is NULL");
+  mpcq_ctx* c = s->ctx;
+  DeviceGuard g(c->device);
+  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
+  const size_t nb = (size_t)s->B * sizeof(mpcq_weights);
+  if (s->weights.count) {
+    HIP_TRY(hipMemcpyAsync(weights, s->weights.dev, nb, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
+                           c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MPCQ_OK;
+  }
+  mpcq_weights d;
+  mpcq_default_weights(&c->p, &d);
+  if (!dev) {
+    for (int64_t b = 0; b < s->B; ++b) weights[b] = d;
+    return MPCQ_OK;
+  }
+  mpcq_weights* h = (mpcq_weights*)malloc(nb);
+  if (!h) return fail(MPCQ_E_NOMEM, "host malloc failed");
+  for (int64_t b = 0; b < s->B; ++b) h[b] = d;
+  const hipError_t e = hipMemcpy(weights, h, nb, hipMemcpyHostToDevice);
   free(h);
   HIP_TRY(e);
   return MPCQ_OK;
@@ -704,9 +741,10 @@ int tick_solve(mpcq_session* s, const Tick& t) {
   // longest-first by the previous tick's iteration counts (a tick k == 0 restarts cold)
   if (t.k == 0) s->have_order = false;
   a.order = s->have_order && s->use_order ? v.i(MPCQ_SV_ORDER) : nullptr;
-  a.robots = s->robots.count ? s->robots.dev : nullptr;
+  int rc = mpcq::launch_tables(c, s->robots, s->weights, s->fill, s->B, &a.robots, &a.weights);
+  if (rc) return rc;
   a.first = t.first_k;
-  const int rc = ensure_work(c, s->B, &a.work);
+  rc = ensure_work(c, s->B, &a.work);
   if (rc) return rc;
   HIP_TRY(hipEventRecord(c->ev[2], c->stream));
   HIP_TRY(mpcq::launch_solve(c->N, true, c->p, a, c->stream));
@@ -730,6 +768,7 @@ int tick_retrieve(mpcq_session* s, const Tick& t) {
   a.next_state = v.d(MPCQ_SV_STATE); a.next_l_feet = v.d(MPCQ_SV_L_FEET);
   for (int i = 0; i < 12; ++i) a.state_weights[i] = c->p.state_weights[i];
   a.force_weight = c->p.force_weight;
+  a.weights = s->weights.count ? s->weights.dev : nullptr;
   for (int i = 0; i < 8; ++i) a.shoulders[i] = s->pp.shoulders[i];
   a.first = t.first;
   if (s->swing) {  // the frame of this tick's fsteps: q_w's x, y, yaw

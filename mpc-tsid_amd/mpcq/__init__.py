@@ -10,6 +10,8 @@ Public surface:
                     (Session.reset: any subset of them back to their initial state)
   robots            per-robot mass / inertia / friction / force limit tables
                     (Engine.set_robots, Session.set_robots)
+  weights           per-instance cost weights, the diagonal of P (Engine.set_weights,
+                    Session.set_weights): a tuning sweep in one launch
   Swing             batched swing-foot trajectories between two ticks (Session.enable_swing)
   Plant             batched rigid-body plant under the stance feet's forces: true robots that
                     differ from the model, external pushes (Session.enable_plant)
@@ -43,7 +45,7 @@ from ._lib import (FLAG_ASYNC, FLAG_DEVICE_PTRS, FLAG_ORDER_BY_CLASS, MODE_SETUP
                    STATUS_DUAL_INFEASIBLE_INACCURATE, STATUS_BAD_BOUNDS, MpcqError,
                    Params, build, build_info, default_params, lib, source_sha, supported_horizons,
                    SV_FRAME, SV_SWING_REF, SV_SWING_STATE, SWING_STATE, SwingParams, default_swing_params,
-                   Robot, default_robot,
+                   Robot, default_robot, Weights, default_weights,
                    PLANT_MODEL, PLANT_RIGID, PV_F_EFF, PV_STATE_END, PV_WRENCH, PlantParams, default_plant_params,
                    DONE_HEIGHT, DONE_NONFINITE, DONE_SOLVER, DONE_TILT, DONE_TIMEOUT, MV_DONE, MV_EP, MV_EP_TICKS,
                    MV_EPISODES, MV_LAST, MV_TOTALS, TRACE, MonitorParams, default_monitor_params,
@@ -57,7 +59,7 @@ from . import channel  # noqa: F401
 from .channel import Channel  # noqa: F401
 from . import estimator  # noqa: F401
 from .estimator import Estimator  # noqa: F401
-from .engine import ROBOT_DTYPE, Engine, dims, pattern, robots  # noqa: F401
+from .engine import ROBOT_DTYPE, WEIGHTS_DTYPE, Engine, dims, pattern, robots, weights  # noqa: F401
 from .monitor import Monitor  # noqa: F401
 from .plant import Plant  # noqa: F401
 from . import scenario  # noqa: F401

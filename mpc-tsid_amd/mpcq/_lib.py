@@ -98,6 +98,7 @@ EXPORTS = ("mpcq_abi_version", "mpcq_default_params", "mpcq_dims", "mpcq_pattern
            "mpcq_default_swing_params", "mpcq_swing_step_batch", "mpcq_swing_batch",
            "mpcq_session_enable_swing",
            "mpcq_default_robot", "mpcq_set_robots", "mpcq_session_set_robots", "mpcq_session_get_robots",
+           "mpcq_default_weights", "mpcq_set_weights", "mpcq_session_set_weights", "mpcq_session_get_weights",
            "mpcq_session_reset",
            "mpcq_default_plant_params", "mpcq_plant_step_batch", "mpcq_session_enable_plant",
            "mpcq_session_disable_plant", "mpcq_session_set_plant_robots", "mpcq_session_set_wrench",
@@ -292,6 +293,16 @@ class Robot(C.Structure):
     ]
 
 
+class Weights(C.Structure):
+    """struct mpcq_weights (include/mpcq.h): the per-instance diagonal of P."""
+
+    _fields_ = [
+        ("state", C.c_double * 12),
+        ("force", C.c_double),
+        ("reserved", C.c_double * 3),
+    ]
+
+
 def build(force: bool = False) -> str:
     """Compile libmpcq.so for gfx950 with hipcc (csrc/Makefile)."""
     if force or not os.path.exists(LIB_PATH):
@@ -399,6 +410,13 @@ def lib():
     L.mpcq_plant_step_batch.argtypes = [vp, PL, C.c_int64] + [vp] * 7 + [C.c_uint32]
     L.mpcq_session_enable_plant.argtypes = [vp, PL]
     L.mpcq_session_disable_plant.argtypes = [vp]
+    L.mpcq_default_weights.argtypes = [PP, C.POINTER(Weights)]
+    L.mpcq_default_weights.restype = None
+    L.mpcq_set_weights.argtypes = [vp, C.c_int64, vp, C.c_uint32]
+    L.mpcq_session_set_weights.argtypes = [vp, vp, C.c_uint32]
+    L.mpcq_session_get_weights.argtypes = [vp, vp, C.c_uint32]
+    for name in ("mpcq_set_weights", "mpcq_session_set_weights", "mpcq_session_get_weights"):
+        getattr(L, name).restype = C.c_int
     L.mpcq_session_set_plant_robots.argtypes = [vp, vp, C.c_uint32]
     L.mpcq_session_set_wrench.argtypes = [vp, vp, C.c_uint32]
     L.mpcq_session_plant_read.argtypes = [vp, C.c_int, vp, C.c_uint32]
@@ -555,6 +573,13 @@ def default_scenario_params(**overrides) -> ScenarioParams:
             v = type(cur)(*v)
         setattr(p, k, v)
     return p
+
+
+def default_weights(params: Params | None = None) -> Weights:
+    """mpcq_default_weights: state_weights and force_weight of ``params`` (None: the defaults)."""
+    w = Weights()
+    lib().mpcq_default_weights(C.byref(params) if params is not None else None, C.byref(w))
+    return w
 
 
 def default_robot(params: Params | None = None) -> Robot:

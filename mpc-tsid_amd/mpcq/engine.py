@@ -81,6 +81,33 @@ def _robot_table(table, count=None):
     return np.ascontiguousarray(table)
 
 
+# numpy mirror of struct mpcq_weights (L.Weights)
+WEIGHTS_DTYPE = np.dtype([("state", np.float64, (12,)), ("force", np.float64), ("reserved", np.float64, (3,))])
+
+
+def weights(B: int, state=None, force=None, params: L.Params | None = None):
+    """A table of per-instance cost weights for ``Engine.set_weights`` / ``Session.set_weights``:
+    a contiguous (B,) array of WEIGHTS_DTYPE.  state: a scalar, (12,) or (B,12); force: a scalar or
+    (B,).  A field left None comes from ``params`` (None: the default parameters)."""
+    B = int(B)
+    d = L.default_weights(params)
+    out = np.zeros(B, WEIGHTS_DTYPE)
+    out["state"] = np.broadcast_to(np.asarray(d.state[:] if state is None else state, np.float64), (B, 12))
+    out["force"] = np.broadcast_to(np.asarray(d.force if force is None else force, np.float64), (B,))
+    return out
+
+
+def _weights_table(table, count=None):
+    """(B,) WEIGHTS_DTYPE, contiguous, from a WEIGHTS_DTYPE array or a ctypes array of L.Weights."""
+    if not isinstance(table, np.ndarray):
+        table = np.frombuffer(bytes(table), WEIGHTS_DTYPE)
+    if table.dtype != WEIGHTS_DTYPE or table.ndim != 1:
+        raise ValueError("a weights table is a (B,) array of mpcq.WEIGHTS_DTYPE (mpcq.weights())")
+    if count is not None and table.shape[0] != count:
+        raise ValueError(f"expected {count} weight rows, got {table.shape[0]}")
+    return np.ascontiguousarray(table)
+
+
 class Engine:
     """One HIP context (device, horizon N, parameters)."""
 
@@ -93,6 +120,7 @@ class Engine:
         self.n, self.m, self.nnz = dims(self.n_steps)
         self.lock = threading.RLock()
         self.has_robots = False  # whether a per-robot table is in force (set_robots / set_robots_device)
+        self.has_weights = False  # whether a weights table is in force (set_weights / set_weights_device)
         h = C.c_void_p()
         L.check(L.lib().mpcq_create(self.device, self.n_steps, C.byref(self.params), C.byref(h)))
         self._h = h
@@ -256,6 +284,24 @@ class Engine:
         t = _robot_table(table)
         self._call("mpcq_set_robots", self._h, t.shape[0], _p(t), 0)
         self.has_robots = t.shape[0] > 0
+
+    def set_weights(self, table):
+        """Per-instance diagonal of P (mpcq_set_weights): instance b of every later solve takes
+        state_weights and force_weight from ``table[b]`` (``mpcq.weights()``), everything else from
+        the engine's parameters (and the robots table, where set).  None clears the table."""
+        if table is None:
+            self._call("mpcq_set_weights", self._h, 0, None, 0)
+            self.has_weights = False
+            return
+        t = _weights_table(table)
+        self._call("mpcq_set_weights", self._h, t.shape[0], _p(t), 0)
+        self.has_weights = t.shape[0] > 0
+
+    def set_weights_device(self, ptr: int, count: int):
+        """The same from ``count`` mpcq_weights records in device memory (copied on the engine's
+        stream, not validated).  ``count`` 0 or a null ``ptr`` clears the table."""
+        self._call("mpcq_set_weights", self._h, int(count), C.c_void_p(ptr) if ptr else None, L.FLAG_DEVICE_PTRS)
+        self.has_weights = bool(ptr) and int(count) > 0
 
     def set_robots_device(self, ptr: int, count: int):
         """The same from ``count`` mpcq_robot records in device memory (copied on the engine's

@@ -22,7 +22,7 @@ import struct
 import numpy as np
 
 from . import _lib as L
-from .engine import ROBOT_DTYPE, Engine, _robot_table
+from .engine import ROBOT_DTYPE, WEIGHTS_DTYPE, Engine, _robot_table, _weights_table
 
 
 def _shapes(B, N):
@@ -140,6 +140,20 @@ class Session:
         the next tick on; independent of the engine's table.  None clears it."""
         t = None if table is None else _robot_table(table, self.batch)
         self.engine._call("mpcq_session_set_robots", self._h, None if t is None else C.c_void_p(t.ctypes.data), 0)
+
+    def set_weights(self, table):
+        """The session's own per-robot cost weights (``mpcq.weights(B, ...)``), used from the next
+        tick on by the solve and by SV_COST; None clears them.  The table is the controller's
+        tuning: it persists across ``reset``, and no snapshot, ``restore`` or ``fork`` touches it
+        (``fork(r)`` then ``set_weights(table)`` is a tuning sweep from one state)."""
+        t = None if table is None else _weights_table(table, self.batch)
+        self.engine._call("mpcq_session_set_weights", self._h, None if t is None else C.c_void_p(t.ctypes.data), 0)
+
+    def get_weights(self):
+        """The weights table in force, (B,) WEIGHTS_DTYPE (without one: the engine's parameters)."""
+        out = np.zeros(self.batch, WEIGHTS_DTYPE)
+        self.engine._call("mpcq_session_get_weights", self._h, C.c_void_p(out.ctypes.data), 0)
+        return out
 
     def get_robots(self):
         """The table in force, (B,) ROBOT_DTYPE (without one: the engine's parameters)."""
