@@ -74,7 +74,13 @@ extern "C" {
  *      feedback in front of the planner; delayed, scaled, noisy forces in front of the plant);
  *      its arrays have ids of their own, MPCQ_HV_*: MPCQ_SV_COUNT stays 21.  A snapshot of a
  *      session with a channel writes blob format version 2 (one more part); one without writes
- *      version 1 as before, and import reads both */
+ *      version 1 as before, and import reads both
+ *   3 (additions, no bump): mpcq_gait_params, mpcq_default_gait_params, mpcq_gait_roll_batch,
+ *      mpcq_session_enable_gait / _disable_gait / _set_gait / _gait_read / _gait_device_ptr
+ *      (per-robot target gaits: the step that enters the horizon comes from a desired gait
+ *      cycle); its array has an id of its own, MPCQ_GV_STATE: MPCQ_SV_COUNT stays 21.  A
+ *      snapshot of a session with the gait array writes blob format version 4 (a 144-byte
+ *      header, one more part); one without writes what it wrote before, and import reads all */
 #define MPCQ_ABI_VERSION 3
 
 /* error codes (return values) */
@@ -1157,6 +1163,112 @@ int mpcq_session_estimator_read(mpcq_session* s, int what, void* dst, uint32_t f
 /* Device address of array `what` (valid until mpcq_session_destroy). */
 int mpcq_session_estimator_device_ptr(mpcq_session* s, int what, void** out);
 
+/* ---- gait transitions: per-robot target gaits through the roll ----------------
+ * The reference's roll (FootstepPlanner.py:401-425) appends to the end of the horizon a copy of
+ * the step it consumes at the front, so a gait table repeats itself for ever.  The gait stage
+ * replaces that roll: the step that enters the horizon comes from a desired gait cycle, per
+ * robot (mpcq_gait.hip).  tests/gait_model.py restates every rule below on the host; all
+ * quantities are small integers, every comparison against it is exact.
+ *
+ * Library: n_gaits cycles (1..MPCQ_GAIT_MAX), each a [20][5] table in the gait table's own
+ * format -- rows [count, c0, c1, c2, c3], ended by a row whose count is 0 -- holding ONE period
+ * of a gait (its period P_g = the sum of its counts; no relation to N).  A valid cycle has 1 to
+ * 19 rows, every count an integer in 1..64, every contact exactly 0.0 or 1.0, and everything
+ * after the terminator row zero.  The one-row cycle [1, 1,1,1,1] is "stand".
+ *
+ * Per-robot state, [B][4] int32 (want, active, phase, switches); (-1, -1, 0, 0) after enable and
+ * after any reset of the robot.  want: the requested library entry (-1: none).  active: the
+ * entry whose cycle is being appended (-1: the table repeats itself, the reference's roll).
+ * phase: the next step of that cycle, in [0, P_active).  switches: how many switches were taken.
+ * The kernel is defensive about what it reads: an active or a want outside [-1, n_gaits) is read
+ * as -1, and phase is taken mod P_active, so a restored or hand-written row cannot index outside
+ * a cycle.
+ *
+ * One call per robot (a session: once per tick, tick 0 included):
+ * 1. selection, with select = MPCQ_GAIT_BY_SPEED only: s = sqrt(vx vx + vy vy) + yaw_weight |wz|
+ *    of this call's v_ref (no contraction).  want < 0 (and s not NaN): want = the number of
+ *    thresholds[i], i < n_gaits - 1, with s >= thresholds[i].  Otherwise want moves up while
+ *    want < n_gaits - 1 and s > thresholds[want] + hysteresis; if it did not move up, it moves
+ *    down while want > 0 and s < thresholds[want - 1] - hysteresis.  A NaN s leaves want alone.
+ * 2. switch: index = the first row whose count is 0, last = index - 1 (row 19 for index 0, as
+ *    the reference's gait[index - 1] wraps).  A table without a zero row: NOTHING is written,
+ *    neither table nor state (the planner's own test then ends the tick as
+ *    MPCQ_STATUS_BAD_GAIT).  With want >= 0 and want != active: boundary = (active >= 0) ? phase
+ *    is the first step of a row of the active cycle : the contacts of row 0 differ from those
+ *    of row last (the reference's "create a new phase" branch: the step about to be appended
+ *    starts a phase of the running gait), or index == 1.  If boundary, or align == 0: active =
+ *    want, phase = 0, switches += 1.
+ * 3. roll: the new contacts are step `phase` of cycle `active`, then phase = (phase + 1) mod
+ *    P_active; with active = -1 they are the contacts of row 0.  The rest is the reference's
+ *    roll: equal to row last's contacts: that row's count += 1, else row index = [1, contacts];
+ *    then the front row's count is decremented where it is > 1, else the rows shift up and row
+ *    19 is zeroed.  The sum of the counts never changes.
+ * With align = 1 the running gait contributes only whole phases to the horizon and the new one
+ * starts at the start of its cycle: no swing phase is cut short at the seam (one may be
+ * lengthened). */
+#define MPCQ_GAIT_MAX 8
+#define MPCQ_GAIT_MANUAL 0     /* want is what mpcq_session_set_gait last wrote */
+#define MPCQ_GAIT_BY_SPEED 1   /* the kernel picks want from the commanded speed */
+typedef struct mpcq_gait_params {        /* 128 bytes */
+  int32_t n_gaits;                      /* 1..MPCQ_GAIT_MAX: the library's entries */
+  int32_t select;                       /* MPCQ_GAIT_MANUAL or MPCQ_GAIT_BY_SPEED */
+  int32_t align;                        /* 1: switch only at a phase boundary; 0: at once */
+  int32_t reserved0;                    /* zero */
+  double thresholds[7];                 /* speed bands: the first n_gaits - 1, non-decreasing, +inf allowed */
+  double hysteresis;                    /* >= 0 */
+  double yaw_weight;                    /* >= 0, metres per rad/s */
+  double reserved[5];                   /* zero */
+} mpcq_gait_params;
+#ifdef __cplusplus
+static_assert(sizeof(mpcq_gait_params) == 128, "mpcq_gait_params is 128 bytes");
+#else
+_Static_assert(sizeof(mpcq_gait_params) == 128, "mpcq_gait_params is 128 bytes");
+#endif
+/* n_gaits 0 (to be set), MPCQ_GAIT_MANUAL, align 1, thresholds all +inf, hysteresis 0,
+ * yaw_weight 0.2421053541332781 = sqrt(0.19^2 + 0.15005^2): the distance of the default
+ * planner's shoulders from the centre, the speed of a foot under a pure turn of 1 rad/s. */
+void mpcq_default_gait_params(mpcq_gait_params* gp);
+/* The gait kernel on its own: one call of the rules above for every robot of a batch.
+ *   gp      the parameters (host, required);  cycles [n_gaits][20][5] doubles (host, required)
+ *   v_ref   [B][6], read with MPCQ_GAIT_BY_SPEED only (may be NULL with MPCQ_GAIT_MANUAL)
+ *   gait    [B][20][5] in/out;  gstate [B][4] int32 in/out
+ * v_ref, gait and gstate are host pointers, or device pointers with MPCQ_FLAG_DEVICE_PTRS (then
+ * MPCQ_FLAG_ASYNC does not wait for the stream).  MPCQ_E_INVALID, nothing launched, the message
+ * naming the field: n_gaits outside 1..8; select or align not 0 or 1; one of the first
+ * n_gaits - 1 thresholds NaN or below its predecessor; hysteresis or yaw_weight negative or not
+ * finite; a reserved field not zero; a cycle that breaks the library rules (the message names
+ * the gait, the row and the field).  The parameters and cycles are checked before anything else. */
+int mpcq_gait_roll_batch(mpcq_ctx* ctx, const mpcq_gait_params* gp, const double* cycles, int64_t batch,
+                         const double* v_ref, double* gait, int32_t* gstate, uint32_t flags);
+/* Opt-in (invalid parameters or cycles: MPCQ_E_INVALID, nothing is launched and the settings in
+ * force stay).  While enabled a tick runs the gait stage between its first tick's
+ * footsteps-only planner pass and its main planner pass, on MPCQ_SV_GAIT, MPCQ_GV_STATE and the
+ * v_ref the planner reads (the scenario's or the staged command), and launches the main pass
+ * without its own roll (MPCQ_PLAN_FOOTSTEPS | MPCQ_PLAN_REFSTATES).  A reset or an auto-reset
+ * puts the robot's row back to (-1, -1, 0, 0).  The first call makes MPCQ_GV_STATE, every row
+ * (-1, -1, 0, 0); calling it again replaces library and parameters, and the rows stay (under
+ * the defensive reads above).  A session that never enables it launches exactly what it did
+ * before.  One difference to the planner's own roll shows with the stage enabled: a roll that
+ * fills row 19 without a shift is written (the planner discards it), and the planner's test
+ * then ends that tick as MPCQ_STATUS_BAD_GAIT, as it would end the next one. */
+int mpcq_session_enable_gait(mpcq_session* s, const mpcq_gait_params* gp, const double* cycles);
+/* The ticks after it run the planner's own roll again; the array stays. */
+int mpcq_session_disable_gait(mpcq_session* s);
+/* Requests: want[b] = ids[b], ids [B] int32, each in [-1, n_gaits); host, or device with
+ * MPCQ_FLAG_DEVICE_PTRS (| MPCQ_FLAG_ASYNC: not blocking).  A host array is validated (the
+ * message names the first offending index); a device array is copied on the stream and covered
+ * by the kernel's defensive read.  Only want is written: -1 withdraws a request that has not
+ * been taken yet, a gait that is already active stays active.  MPCQ_E_INVALID under
+ * MPCQ_GAIT_BY_SPEED (the kernel owns want) and before mpcq_session_enable_gait. */
+int mpcq_session_set_gait(mpcq_session* s, const int32_t* ids, uint32_t flags);
+/* The gait array; it exists from the first mpcq_session_enable_gait on (before: MPCQ_E_INVALID). */
+#define MPCQ_GV_STATE 0     /* [B][4] int32     want, active, phase, switches */
+#define MPCQ_GV_COUNT 1
+/* Copy array `what` to dst (host, or device with MPCQ_FLAG_DEVICE_PTRS); blocking. */
+int mpcq_session_gait_read(mpcq_session* s, int what, void* dst, uint32_t flags);
+/* Device address of array `what` (valid until mpcq_session_destroy). */
+int mpcq_session_gait_device_ptr(mpcq_session* s, int what, void** out);
+
 /* ---- snapshots: save, restore and branch robots on the device ---------------
  * A snapshot is a device-resident copy of everything per-robot that a session holds, plus the
  * few host flags that decide what the next tick launches.  Every call below runs on the
@@ -1171,7 +1283,9 @@ int mpcq_session_estimator_device_ptr(mpcq_session* s, int what, void** out);
  * _enable_estimator; the row is self-describing, so a restore into a session with another lag is
  * legal and re-initialises by the filter's rule 1; MPCQ_EV_EST is derived, rewritten by every
  * tick before anything reads it, and left out: after a restore it shows the session's last tick
- * until the next one), and the tables of mpcq_session_set_robots / _set_plant_robots where in force -- and its shape: N,
+ * until the next one), MPCQ_GV_STATE (after _enable_gait; the gait library and parameters are the controller's
+ * configuration and are not held, so a restore needs a session whose library has as many
+ * cycles), and the tables of mpcq_session_set_robots / _set_plant_robots where in force -- and its shape: N,
  * B, which of these exist, the swing k_mpc, the channel's delay and latency in force at the
  * save (the rings mean nothing under others: a restore into a session whose values differ is
  * MPCQ_E_INVALID); and whether a tick has run since create and whether a reset was ever called.  Not held: the staging of host inputs and the plant's copy of q_w (every
@@ -1210,7 +1324,8 @@ int mpcq_session_snapshot_save(mpcq_session* s, mpcq_snapshot* snap, uint32_t fl
  * (with | MPCQ_FLAG_ASYNC the call enqueues and returns, as mpcq_session_reset).  A device
  * map cannot be validated: an entry outside [0, B_snapshot) acts as -1.
  * A restored robot gets its row of every array the snapshot holds, in ONE launch
- * (gather_rows_kernel).  After it, where the session or the snapshot has a dispatch order in
+ * (gather_rows_kernel) up to 48 arrays, in two beyond (a session with every group enabled has
+ * 49), each on the stream.  After it, where the session or the snapshot has a dispatch order in
  * use, MPCQ_SV_ORDER is rebuilt from the restored iteration counts and pending resets.  A
  * reset recorded in the snapshot stays recorded in the session.
  * A snapshot saved before any tick holds creation state, which only a first tick may consume:
@@ -1232,7 +1347,7 @@ int mpcq_session_snapshot_restore(mpcq_session* s, const mpcq_snapshot* snap, co
 int mpcq_session_fork(mpcq_session* s, const int32_t* map, uint32_t flags);
 /* Checkpoint to the host.  One blob = a 128-byte header, then the groups' arrays unpadded, in
  * the order main, swing, plant, monitor, scenario, robots table, plant robots table, channel,
- * estimator, inside a group by array id (the private main arrays behind the named ones).  The
+ * estimator, gait, inside a group by array id (the private main arrays behind the named ones).  The
  * header, little endian: char magic[8] "MPCQSNP1"; uint32 version (3 with an estimator part, else
  * 2 with a channel part, else 1: a session without either writes the version-1 blob byte for
  * byte, one with a channel and no estimator the version-2 blob; import reads all three); int32
@@ -1241,6 +1356,8 @@ int mpcq_session_fork(mpcq_session* s, const int32_t* map, uint32_t flags);
  * 8 channel, 9 estimator); int64 group_bytes[7]; int64 total (header included); int64 user (0; for the
  * caller, ignored by import); at offset 104 int64 bytes of the channel part; at 112 int32
  * delay, latency in force at the save; at 120 int64 bytes of the estimator part (MPCQ_EV_ROW).
+ * Format version 4 (a session with MPCQ_GV_STATE; flags bit 10) has a 144-byte header: at 128
+ * int64 bytes of the gait part, at 136 int32 n_gaits, at 140 int32 zero.
  * _bytes: the size of snap's blob (snap saved).  _export: dst is a host buffer of exactly
  * that many bytes; blocking.  _import: makes snap the snapshot the blob describes, for s's
  * context; before it touches the device it checks the magic, the version, N against the

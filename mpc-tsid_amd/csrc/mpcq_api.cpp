@@ -376,6 +376,61 @@ int mpcq::estimator_params(const mpcq_estimator_params* ep, mpcq_estimator_param
   return MPCQ_OK;
 }
 
+int mpcq::gait_params(const mpcq_gait_params* gp, const double* cycles, mpcq_gait_params* out, mpcq::GaitArgs* lib) {
+  if (!gp) return fail(MPCQ_E_INVALID, "the gait parameters are NULL (n_gaits has no default)");
+  if (!cycles) return fail(MPCQ_E_INVALID, "the gait cycles are NULL");
+  const mpcq_gait_params& p = *gp;
+  if (p.n_gaits < 1 || p.n_gaits > MPCQ_GAIT_MAX)
+    return fail(MPCQ_E_INVALID, "the gait library needs n_gaits in 1..%d (got %d)", MPCQ_GAIT_MAX, p.n_gaits);
+  if (p.select != MPCQ_GAIT_MANUAL && p.select != MPCQ_GAIT_BY_SPEED)
+    return fail(MPCQ_E_INVALID, "the gait stage's select must be MPCQ_GAIT_MANUAL or MPCQ_GAIT_BY_SPEED (got %d)", p.select);
+  if (p.align != 0 && p.align != 1) return fail(MPCQ_E_INVALID, "the gait stage's align must be 0 or 1 (got %d)", p.align);
+  for (int i = 0; i < p.n_gaits - 1; ++i) {
+    if (isnan(p.thresholds[i])) return fail(MPCQ_E_INVALID, "the gait stage's thresholds[%d] is NaN", i);
+    if (i > 0 && p.thresholds[i] < p.thresholds[i - 1])
+      return fail(MPCQ_E_INVALID, "the gait stage's thresholds[%d] is below thresholds[%d]", i, i - 1);
+  }
+  if (!(isfinite(p.hysteresis) && p.hysteresis >= 0)) return fail(MPCQ_E_INVALID, "the gait stage needs a finite hysteresis >= 0");
+  if (!(isfinite(p.yaw_weight) && p.yaw_weight >= 0)) return fail(MPCQ_E_INVALID, "the gait stage needs a finite yaw_weight >= 0");
+  if (p.reserved0) return fail(MPCQ_E_INVALID, "the gait stage's reserved fields must be zero");
+  for (int i = 0; i < 5; ++i)
+    if (p.reserved[i]) return fail(MPCQ_E_INVALID, "the gait stage's reserved fields must be zero");
+  mpcq::GaitArgs packed{};
+  for (int g = 0; g < MPCQ_GAIT_MAX; ++g) packed.period[g] = 1;
+  for (int g = 0; g < p.n_gaits; ++g) {
+    const double* cy = cycles + (size_t)g * 100;
+    int rows = 0, period = 0;
+    while (rows < 20 && cy[5 * rows] != 0.0) {
+      const double cnt = cy[5 * rows];
+      if (!(cnt >= 1 && cnt <= 64) || cnt != (double)(int)cnt)
+        return fail(MPCQ_E_INVALID, "gait %d, row %d: the count %g is not an integer in 1..64", g, rows, cnt);
+      int bits = 0;
+      for (int q = 0; q < 4; ++q) {
+        const double v = cy[5 * rows + 1 + q];
+        if (v != 0.0 && v != 1.0)
+          return fail(MPCQ_E_INVALID, "gait %d, row %d: the contact %d is %g, neither 0 nor 1", g, rows, q, v);
+        if (v == 1.0) bits |= 1 << q;
+      }
+      packed.lib[g * 20 + rows] = mpcq::gait_pack((int)cnt, bits);
+      period += (int)cnt;
+      ++rows;
+    }
+    if (rows < 1) return fail(MPCQ_E_INVALID, "gait %d, row 0: the count is 0 (a cycle has 1 to 19 rows)", g);
+    if (rows > 19) return fail(MPCQ_E_INVALID, "gait %d, row 19: the count is not 0 (a cycle has 1 to 19 rows)", g);
+    for (int e = 5 * rows; e < 100; ++e) {  // the terminator row too (bitwise: a NaN or a -0.0 is not zero)
+      uint64_t bits;
+      memcpy(&bits, cy + e, 8);
+      if (bits != 0)
+        return fail(MPCQ_E_INVALID, "gait %d, row %d: the %s in or after the terminator row is not zero", g, e / 5,
+                    e % 5 ? "contact" : "count");
+    }
+    packed.period[g] = period;
+  }
+  *out = p;
+  *lib = packed;
+  return MPCQ_OK;
+}
+
 int mpcq::check_ctx(mpcq_ctx* c, int64_t batch) {
   if (!c) return fail(MPCQ_E_INVALID, "ctx is NULL");
   if (batch < 0 || batch > (int64_t)0x7fffffff) return fail(MPCQ_E_INVALID, "bad batch %lld", (long long)batch);
@@ -1293,6 +1348,47 @@ int mpcq_estimator_step_batch(mpcq_ctx* c, const mpcq_estimator_params* ep, int6
     a.robots = robots; a.row = row; a.est = est;
   }
   HIP_TRY(mpcq::launch_estimate(P, a, c->stream));
+  if (!dev) return unstage(c, xs, NX);
+  if (!(flags & MPCQ_FLAG_ASYNC)) HIP_TRY(hipStreamSynchronize(c->stream));
+  return MPCQ_OK;
+}
+
+// Gait stage: requests by hand, switches at phase boundaries, no speed bands; yaw_weight = the
+// distance of the default planner's shoulders (0.19, 0.15005) from the centre.
+void mpcq_default_gait_params(mpcq_gait_params* gp) {
+  if (!gp) return;
+  memset(gp, 0, sizeof(*gp));
+  gp->select = MPCQ_GAIT_MANUAL;
+  gp->align = 1;
+  for (int i = 0; i < MPCQ_GAIT_MAX - 1; ++i) gp->thresholds[i] = INFINITY;
+  gp->yaw_weight = 0.2421053541332781;
+}
+
+int mpcq_gait_roll_batch(mpcq_ctx* c, const mpcq_gait_params* gp, const double* cycles, int64_t B,
+                         const double* v_ref, double* gait, int32_t* gstate, uint32_t flags) {
+  mpcq_gait_params P;
+  mpcq::GaitArgs a{};
+  int rc = gait_params(gp, cycles, &P, &a);  // first: what is wrong with the parameters needs no context
+  if (rc) return rc;
+  rc = check_ctx(c, B);
+  if (rc) return rc;
+  if (!gait || !gstate) return fail(MPCQ_E_INVALID, "gait and gstate are required");
+  if (!v_ref && P.select == MPCQ_GAIT_BY_SPEED) return fail(MPCQ_E_INVALID, "v_ref is required with MPCQ_GAIT_BY_SPEED");
+  if (B == 0) return MPCQ_OK;
+  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
+  DeviceGuard g(c->device);
+  a.batch = B;
+  const size_t b = (size_t)B;
+  enum { VR, GA, GS, NX };
+  Xfer xs[NX] = {{v_ref, nullptr, b * 48, nullptr}, {gait, gait, b * 800, nullptr}, {gstate, gstate, b * 16, nullptr}};
+  if (!dev) {
+    rc = stage(c, xs, NX);
+    if (rc) return rc;
+    a.v_ref = (const double*)xs[VR].dev; a.gait = (double*)xs[GA].dev; a.gstate = (int32_t*)xs[GS].dev;
+  } else {
+    a.v_ref = v_ref; a.gait = gait; a.gstate = gstate;
+  }
+  HIP_TRY(mpcq::launch_gait(P, a, c->stream));
   if (!dev) return unstage(c, xs, NX);
   if (!(flags & MPCQ_FLAG_ASYNC)) HIP_TRY(hipStreamSynchronize(c->stream));
   return MPCQ_OK;

@@ -107,4 +107,7 @@ int monitor_params(const mpcq_monitor_params* mp, mpcq_monitor_params* out);
 int scenario_params(const mpcq_scenario_params* sc, mpcq_scenario_params* out);
 int channel_params(const mpcq_channel_params* ch, mpcq_channel_params* out);
 int estimator_params(const mpcq_estimator_params* ep, mpcq_estimator_params* out);
+// The gait stage's parameters (no defaults: n_gaits is the caller's) and its library, validated:
+// *out, and the cycles packed into lib->lib / lib->period (the other fields of *lib zero).
+int gait_params(const mpcq_gait_params* gp, const double* cycles, mpcq_gait_params* out, GaitArgs* lib);
 }  // namespace mpcq

@@ -186,6 +186,8 @@ struct ResetArgs {
   // the monitor's running episode, or null on a session without a monitor: discarded
   double* ep;            // [B][8]
   int32_t* ep_ticks;     // [B]
+  // the gait stage's rows, or null on a session that never enabled it: back to (-1, -1, 0, 0)
+  int32_t* gstate;       // [B][4]
 };
 hipError_t launch_reset(const ResetArgs& a, hipStream_t s);
 
@@ -344,6 +346,21 @@ struct EstimateArgs {
   double* est;             // [B][12] out
 };
 hipError_t launch_estimate(const mpcq_estimator_params& ep, const EstimateArgs& a, hipStream_t s);
+
+// Gait stage (mpcq_gait.hip); semantics and layouts in include/mpcq.h (mpcq_gait_roll_batch,
+// mpcq_session_enable_gait).  Thirty-two lanes per robot, lane r < 20 owns row r of its table.
+// The library travels in the kernel arguments: one word per cycle row (gait_pack), the
+// periods beside it (1 for the entries past n_gaits: never a divisor of zero).
+constexpr int32_t gait_pack(int count, int contacts) { return count | (contacts << 8); }  // count 1..64, 4 bits
+struct GaitArgs {
+  int64_t batch;
+  const double* v_ref;   // [B][6], or null with MPCQ_GAIT_MANUAL
+  double* gait;          // [B][20][5] in/out
+  int32_t* gstate;       // [B][4] in/out
+  int32_t period[MPCQ_GAIT_MAX];
+  int32_t lib[MPCQ_GAIT_MAX * 20];
+};
+hipError_t launch_gait(const mpcq_gait_params& gp, const GaitArgs& a, hipStream_t s);
 
 // Row gather of a snapshot restore (mpcq_snapshot.hip; semantics in include/mpcq.h,
 // mpcq_session_snapshot_restore / mpcq_debug_gather_rows): row b of every dst array <- row

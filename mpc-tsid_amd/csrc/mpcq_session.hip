@@ -193,6 +193,7 @@ __global__ __launch_bounds__(64) void reset_kernel(ResetArgs a) {
     if (lane < 8) a.ep[b * 8 + lane] = lane == 4 ? INFINITY : 0.0;
     if (lane == 0) a.ep_ticks[b] = 0;
   }
+  if (a.gstate && lane < 4) a.gstate[b * 4 + lane] = lane < 2 ? -1 : 0;  // no request, the table's own roll
 }
 
 }  // namespace

@@ -2,10 +2,11 @@
 // sessions, per-robot state resident in HBM.
 //
 // A session's device arrays come in groups (alloc_group): the main one made by
-// mpcq_session_create, and one each for swing, plant, monitor, scenario, channel and estimator, made when
+// mpcq_session_create, and one each for swing, plant, monitor, scenario, channel, estimator and gait, made when
 // they are first enabled.  A tick (session_tick) is a list of stages, each filling the argument struct of
 // its launch from the groups' arrays.  All numerics run in the HIP kernels.
 #include <math.h>
+#include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -25,7 +26,7 @@ enum { SP_WARM_X = MPCQ_SV_COUNT, SP_PLAN_STATUS, SP_INFO, SP_IN_STATE, SP_IN_LF
 enum { PP_QW_PREV = MPCQ_PV_COUNT, PP_COUNT };
 
 // The arrays of one kind of id: MPCQ_SV_* (the swing slots are null until
-// mpcq_session_enable_swing), MPCQ_PV_*, MPCQ_MV_*, MPCQ_CV_*, MPCQ_HV_*, MPCQ_EV_*.
+// mpcq_session_enable_swing), MPCQ_PV_*, MPCQ_MV_*, MPCQ_CV_*, MPCQ_HV_*, MPCQ_EV_*, MPCQ_GV_*.
 struct Group {
   const char *kind, *enable;  // "<kind> array %d needs mpcq_session_enable_<enable>"
   int named;                  // the ids the _read / _write / _device_ptr entry points reach
@@ -48,11 +49,15 @@ struct mpcq_session {
   Group cv{"scenario", "scenario", MPCQ_CV_COUNT};  // made by the first enable_scenario
   Group hv{"channel", "channel", MPCQ_HV_COUNT};    // made by the first enable_channel
   Group ev{"estimator", "estimator", MPCQ_EV_COUNT};  // made by the first enable_estimator
+  Group gv{"gait", "gait", MPCQ_GV_COUNT};            // made by the first enable_gait
   void* swing_mem = nullptr;                      // MPCQ_SV_SWING_REF, _SWING_STATE, _FRAME
   bool have_order = false;  // MPCQ_SV_ORDER holds the next solve's order (longest previous first)
   bool use_order = true;    // MPCQ_DISPATCH_ORDER=0 turns it off (A/B timing only; results are identical)
   bool resets = false;      // mpcq_session_reset was called: from then on the ticks consult MPCQ_SV_FIRST
   bool swing = false, plant = false, monitor = false, scenario = false, channel = false, estimator = false;
+  bool gait = false;
+  mpcq_gait_params gp{};
+  mpcq::GaitArgs gait_lib{};  // the library in force, packed (period, lib; the launch fills the rest)
   mpcq_swing_params sp{};
   mpcq_plant_params pl{};
   mpcq_monitor_params mp{};
@@ -206,6 +211,7 @@ hipError_t enqueue_reset(mpcq_session* s, const int32_t* mask, const double* gai
   if (s->mv.mem) {  // a reset robot's running episode is discarded
     ra.ep = s->mv.d(MPCQ_MV_EP); ra.ep_ticks = s->mv.i(MPCQ_MV_EP_TICKS);
   }
+  if (s->gv.mem) ra.gstate = s->gv.i(MPCQ_GV_STATE);  // no request, the table's own roll
   hipError_t e = mpcq::launch_reset(ra, c->stream);
   // the robots with a pending reset to the front of the next solve's dispatch (a session that
   // has not ticked yet has no order in use: it keeps the identity)
@@ -338,6 +344,7 @@ int mpcq_session_destroy(mpcq_session* s) {
     if (s->cv.mem) (void)hipFree(s->cv.mem);
     if (s->hv.mem) (void)hipFree(s->hv.mem);
     if (s->ev.mem) (void)hipFree(s->ev.mem);
+    if (s->gv.mem) (void)hipFree(s->gv.mem);
     (void)mpcq_session_snapshot_destroy(s->fork_snap);
   }
   delete s;
@@ -607,6 +614,66 @@ int mpcq_session_disable_estimator(mpcq_session* s) {
   return MPCQ_OK;
 }
 
+int mpcq_session_enable_gait(mpcq_session* s, const mpcq_gait_params* gp, const double* cycles) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  mpcq_gait_params P;
+  mpcq::GaitArgs lib{};
+  int rc = gait_params(gp, cycles, &P, &lib);
+  if (rc) return rc;
+  if (!s->gv.mem) {  // the rows, every one (-1, -1, 0, 0)
+    mpcq_ctx* c = s->ctx;
+    DeviceGuard g(c->device);
+    const size_t nb[MPCQ_GV_COUNT] = {(size_t)s->B * 16};
+    int32_t* h = (int32_t*)malloc(nb[0]);
+    if (!h) return fail(MPCQ_E_NOMEM, "host malloc failed");
+    for (size_t e = 0; e < (size_t)s->B * 4; ++e) h[e] = e % 4 < 2 ? -1 : 0;
+    Group gv = s->gv;
+    rc = alloc_group(c, "the gait array", MPCQ_GV_COUNT, nb, &gv.mem, gv.ptr, gv.bytes);
+    hipError_t e = hipSuccess;
+    if (!rc) e = hipMemcpyAsync(gv.ptr[MPCQ_GV_STATE], h, nb[0], hipMemcpyHostToDevice, c->stream);
+    if (!rc && e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    free(h);
+    if (rc) return rc;
+    if (e != hipSuccess) {
+      (void)hipFree(gv.mem);
+      return fail(MPCQ_E_DEVICE, "initialising the gait array failed: %s", hipGetErrorString(e));
+    }
+    s->gv = gv;
+  }
+  // (by value into every later launch's arguments: a queued tick keeps the library it was launched with)
+  s->gp = P;
+  s->gait_lib = lib;
+  s->gait = true;
+  return MPCQ_OK;
+}
+
+int mpcq_session_disable_gait(mpcq_session* s) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  s->gait = false;
+  return MPCQ_OK;
+}
+
+int mpcq_session_set_gait(mpcq_session* s, const int32_t* ids, uint32_t flags) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  if (!ids) return fail(MPCQ_E_INVALID, "ids is NULL");
+  if (!s->gait) return fail(MPCQ_E_INVALID, "mpcq_session_set_gait needs mpcq_session_enable_gait");
+  if (s->gp.select != MPCQ_GAIT_MANUAL)
+    return fail(MPCQ_E_INVALID, "mpcq_session_set_gait is refused under MPCQ_GAIT_BY_SPEED: the kernel owns want");
+  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
+  if (!dev)
+    for (int64_t b = 0; b < s->B; ++b)
+      if (ids[b] < -1 || ids[b] >= s->gp.n_gaits)
+        return fail(MPCQ_E_INVALID, "ids[%lld] = %d is neither -1 nor a gait of the library (0..%d)", (long long)b,
+                    ids[b], s->gp.n_gaits - 1);
+  mpcq_ctx* c = s->ctx;
+  DeviceGuard g(c->device);
+  // want alone: element 0 of every 16-byte row, on the context's stream (behind the queued ticks)
+  HIP_TRY(hipMemcpy2DAsync(s->gv.ptr[MPCQ_GV_STATE], 16, ids, 4, 4, (size_t)s->B,
+                           dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+  if (!(flags & MPCQ_FLAG_ASYNC) || !dev) HIP_TRY(hipStreamSynchronize(c->stream));
+  return MPCQ_OK;
+}
+
 }  // extern "C"
 
 namespace {
@@ -717,6 +784,12 @@ int tick_plan(mpcq_session* s, const Tick& t) {
     HIP_TRY(mpcq::launch_plan(s->pp, a, c->stream));
   }
   a.ops = MPCQ_PLAN_TICK;
+  if (s->gait) {  // the gait stage rolls in the planner's place, on the command the planner reads
+    mpcq::GaitArgs ga = s->gait_lib;
+    ga.batch = s->B; ga.v_ref = t.v_ref; ga.gait = v.d(MPCQ_SV_GAIT); ga.gstate = s->gv.i(MPCQ_GV_STATE);
+    HIP_TRY(mpcq::launch_gait(s->gp, ga, c->stream));
+    a.ops = MPCQ_PLAN_FOOTSTEPS | MPCQ_PLAN_REFSTATES;
+  }
   HIP_TRY(mpcq::launch_plan(s->pp, a, c->stream));
   HIP_TRY(hipEventRecord(c->ev[1], c->stream));
   c->have_form = true;
@@ -838,7 +911,8 @@ int tick_swing(mpcq_session* s) {
   return MPCQ_OK;
 }
 
-// One tick: its stages in stream order ([scenario] -> inputs -> [observe] -> [estimate] -> planner -> solve ->
+// One tick: its stages in stream order ([scenario] -> inputs -> [observe] -> [estimate] -> planner (with [gait]
+// between its first tick's footsteps-only pass and its main pass) -> solve ->
 // retrieve -> [actuate -> plant] -> [monitor] -> order -> [swing] -> [auto-reset]).
 int session_tick(mpcq_session* s, int k, const double* state, const double* l_feet, const double* v_ref,
                  const int32_t* reduced, uint32_t flags, double* trace) {
@@ -957,6 +1031,10 @@ int mpcq_session_estimator_read(mpcq_session* s, int what, void* dst, uint32_t f
   return group_read(s, &mpcq_session::ev, what, dst, flags);
 }
 
+int mpcq_session_gait_read(mpcq_session* s, int what, void* dst, uint32_t flags) {
+  return group_read(s, &mpcq_session::gv, what, dst, flags);
+}
+
 int mpcq_session_device_ptr(mpcq_session* s, int what, void** out) {
   return group_device_ptr(s, &mpcq_session::sv, what, out);
 }
@@ -979,6 +1057,10 @@ int mpcq_session_channel_device_ptr(mpcq_session* s, int what, void** out) {
 
 int mpcq_session_estimator_device_ptr(mpcq_session* s, int what, void** out) {
   return group_device_ptr(s, &mpcq_session::ev, what, out);
+}
+
+int mpcq_session_gait_device_ptr(mpcq_session* s, int what, void** out) {
+  return group_device_ptr(s, &mpcq_session::gv, what, out);
 }
 
 int mpcq_session_write(mpcq_session* s, int what, const void* src, uint32_t flags) {
@@ -1006,12 +1088,12 @@ namespace {
 
 // The parts of a snapshot, in the blob's order; each is one allocation (alloc_group).
 enum { G_MAIN, G_SWING, G_PLANT, G_MONITOR, G_SCENARIO, G_ROBOTS, G_PLANT_ROBOTS, G_CHANNEL, G_ESTIMATOR,
-       G_COUNT };
+       G_GAIT, G_COUNT };
 const char* const kPartName[G_COUNT] = {"the snapshot's session arrays", "the snapshot's swing arrays",
                                         "the snapshot's plant arrays", "the snapshot's monitor arrays",
                                         "the snapshot's scenario arrays", "the snapshot's robots table",
                                         "the snapshot's plant robots table", "the snapshot's channel arrays",
-                                        "the snapshot's estimator row"};
+                                        "the snapshot's estimator row", "the snapshot's gait rows"};
 
 // What a snapshot's allocations follow from, with the context's N.
 struct SnapShape {
@@ -1021,6 +1103,8 @@ struct SnapShape {
   bool hv = false;              // the channel arrays, primed under
   int delay = 0, latency = 0;   // these depths
   bool ev = false;              // the estimator's row (self-describing: no parameter travels)
+  bool gv = false;              // the gait stage's rows, indices into a library of
+  int n_gaits = 0;              // this many cycles (the library itself is configuration: not held)
 };
 
 }  // namespace
@@ -1045,6 +1129,8 @@ SnapShape shape_of(const mpcq_session* s) {
   sh.hv = s->hv.mem;
   if (sh.hv) { sh.delay = s->ch.delay; sh.latency = s->ch.latency; }
   sh.ev = s->ev.mem;
+  sh.gv = s->gv.mem;
+  if (sh.gv) sh.n_gaits = s->gp.n_gaits;
   return sh;
 }
 
@@ -1076,6 +1162,7 @@ void snap_sizes(const SnapShape& sh, int N, size_t nb[G_COUNT][SP_COUNT]) {
     estimator_bytes(B, nb[G_ESTIMATOR]);
     nb[G_ESTIMATOR][MPCQ_EV_EST] = 0;  // (derived: every tick rewrites it before anything reads it)
   }
+  if (sh.gv) nb[G_GAIT][MPCQ_GV_STATE] = B * 16;
 }
 
 // The session's arrays seen as a snapshot's parts (the arrays a snapshot does not hold: null).
@@ -1098,6 +1185,7 @@ void session_parts(const mpcq_session* s, Group out[G_COUNT]) {
   if (s->hv.mem)
     for (int w = 0; w < MPCQ_HV_COUNT; ++w) { out[G_CHANNEL].ptr[w] = s->hv.ptr[w]; out[G_CHANNEL].bytes[w] = s->hv.bytes[w]; }
   if (s->ev.mem) { out[G_ESTIMATOR].ptr[MPCQ_EV_ROW] = s->ev.ptr[MPCQ_EV_ROW]; out[G_ESTIMATOR].bytes[MPCQ_EV_ROW] = s->ev.bytes[MPCQ_EV_ROW]; }
+  if (s->gv.mem) { out[G_GAIT].ptr[MPCQ_GV_STATE] = s->gv.ptr[MPCQ_GV_STATE]; out[G_GAIT].bytes[MPCQ_GV_STATE] = s->gv.bytes[MPCQ_GV_STATE]; }
 }
 
 // One array of a snapshot (a) next to its counterpart (b; null without one), in the blob's order.
@@ -1107,9 +1195,11 @@ struct SnapItem {
   bool rows;  // per-robot rows (all but MPCQ_MV_TOTALS)
 };
 
-// The listing's bound: what one gather launch takes, and MPCQ_MV_TOTALS, which is listed and
-// never gathered.
-constexpr int kListMax = kGatherMax + 1;
+// The listing's bound, a constant of its own: every array of every part (50 with every group
+// enabled, MPCQ_MV_TOTALS among them, which is listed and never gathered).  A restore gathers
+// them kGatherMax to a launch.
+constexpr int kListMax = 64;
+constexpr int kGatherChunks = (kListMax + mpcq::kGatherMax - 1) / mpcq::kGatherMax;
 
 // The table save, restore, fork, export and import all walk: every array parts `a` hold, with
 // the same array of parts `b` (null: none).  An array `a` holds and `b` lacks is an error (-1).
@@ -1166,6 +1256,8 @@ const char* shape_difference(const SnapShape& a, const SnapShape& b, bool batch_
   if (a.delay != b.delay) return "the channel's delay differs (the rings were filled under another)";
   if (a.latency != b.latency) return "the channel's latency differs (the rings were filled under another)";
   if (a.ev != b.ev) return "the estimator arrays exist on one side only";
+  if (a.gv != b.gv) return "the gait arrays exist on one side only";
+  if (a.n_gaits != b.n_gaits) return "the gait library sizes differ (the rows index another library)";
   return nullptr;
 }
 
@@ -1264,15 +1356,27 @@ int snapshot_restore(mpcq_session* s, const mpcq_snapshot* p, const int32_t* map
   SnapItem it[kListMax];
   const int n = list_arrays(p->g, live, it);
   if (n < 0) return fail(MPCQ_E_INVALID, "the snapshot's arrays do not match the session's");
-  mpcq::GatherArgs a{};
-  int rc = gather_table(it, n, p->sh.B, s->B, &a);
-  if (rc) return rc;
+  // the per-robot arrays, kGatherMax to a launch (one launch up to 48 arrays); every launch's
+  // table is made before the first is enqueued
+  int nr = 0;
+  for (int i = 0; i < n; ++i)
+    if (it[i].rows) it[nr++] = it[i];
+  const int chunks = (nr + mpcq::kGatherMax - 1) / mpcq::kGatherMax;
+  mpcq::GatherArgs ga[kGatherChunks] = {};
+  for (int ch = 0; ch < chunks; ++ch) {
+    const int lo = ch * mpcq::kGatherMax, cnt = nr - lo < mpcq::kGatherMax ? nr - lo : mpcq::kGatherMax;
+    const int rc = gather_table(it + lo, cnt, p->sh.B, s->B, &ga[ch]);
+    if (rc) return rc;
+  }
   DeviceGuard dg(c->device);
   hipError_t e = hipSuccess;
-  a.map = staged(s, dev, map, SP_IN_REDUCED, &e);
-  // creation state, which only a first tick may consume: the rows come with a pending reset
-  a.first = p->have_order ? nullptr : s->sv.i(MPCQ_SV_FIRST);
-  if (e == hipSuccess) e = mpcq::launch_gather_rows(a, c->stream);
+  const int32_t* dmap = staged(s, dev, map, SP_IN_REDUCED, &e);
+  for (int ch = 0; ch < chunks && e == hipSuccess; ++ch) {
+    ga[ch].map = dmap;
+    // creation state, which only a first tick may consume: the rows come with a pending reset
+    ga[ch].first = p->have_order ? nullptr : s->sv.i(MPCQ_SV_FIRST);
+    e = mpcq::launch_gather_rows(ga[ch], c->stream);
+  }
   if (e == hipSuccess && !map && p->sh.mv)  // the batch-wide totals go with the whole batch only
     e = hipMemcpyAsync(s->mv.ptr[MPCQ_MV_TOTALS], p->g[G_MONITOR].ptr[MPCQ_MV_TOTALS], s->mv.bytes[MPCQ_MV_TOTALS],
                        hipMemcpyDeviceToDevice, c->stream);
@@ -1306,13 +1410,20 @@ struct BlobHeader {
   int64_t channel_bytes;   // format version 2: the eighth part,
   int32_t delay, latency;  // and the depths its rings were filled under
   int64_t estimator_bytes; // format version 3: the ninth part
+  // format version 4 only, behind the 128 bytes of versions 1 to 3: the tenth part and the size
+  // of the library its rows index
+  int64_t gait_bytes;
+  int32_t n_gaits, pad;
 };
-static_assert(sizeof(BlobHeader) == 128 && G_CHANNEL == 7 && G_ESTIMATOR == 8 && G_COUNT == 9,
-              "the blob's header is 128 bytes");
+static_assert(sizeof(BlobHeader) == 144 && offsetof(BlobHeader, gait_bytes) == 128 && G_CHANNEL == 7 &&
+                  G_ESTIMATOR == 8 && G_GAIT == 9 && G_COUNT == 10,
+              "the blob's header is 128 bytes, 144 from format version 4 on");
+size_t header_bytes(uint32_t version) { return version >= 4 ? sizeof(BlobHeader) : offsetof(BlobHeader, gait_bytes); }
 
 // The header's byte count of part gi.
 int64_t& part_bytes(BlobHeader& h, int gi) {
-  return gi == G_ESTIMATOR ? h.estimator_bytes : gi == G_CHANNEL ? h.channel_bytes : h.group_bytes[gi];
+  return gi == G_GAIT ? h.gait_bytes : gi == G_ESTIMATOR ? h.estimator_bytes : gi == G_CHANNEL ? h.channel_bytes
+                                                                                                : h.group_bytes[gi];
 }
 const char kMagic[8] = {'M', 'P', 'C', 'Q', 'S', 'N', 'P', '1'};
 
@@ -1321,12 +1432,13 @@ void blob_header(const SnapShape& sh, int N, bool have_order, bool resets, BlobH
   snap_sizes(sh, N, nb);
   memset(h, 0, sizeof(*h));
   memcpy(h->magic, kMagic, 8);
-  h->version = sh.ev ? 3 : sh.hv ? 2 : 1; h->N = N; h->B = sh.B; h->k_mpc = sh.k_mpc;
+  h->version = sh.gv ? 4 : sh.ev ? 3 : sh.hv ? 2 : 1; h->N = N; h->B = sh.B; h->k_mpc = sh.k_mpc;
   h->flags = (have_order ? 1u : 0u) | (resets ? 2u : 0u) | (sh.k_mpc > 0 ? 4u : 0u) | (sh.pv ? 8u : 0u) |
              (sh.mv ? 16u : 0u) | (sh.cv ? 32u : 0u) | (sh.robots ? 64u : 0u) | (sh.plant_robots ? 128u : 0u) |
-             (sh.hv ? 256u : 0u) | (sh.ev ? 512u : 0u);
+             (sh.hv ? 256u : 0u) | (sh.ev ? 512u : 0u) | (sh.gv ? 1024u : 0u);
   h->delay = sh.delay; h->latency = sh.latency;
-  h->total = sizeof(*h);
+  h->n_gaits = sh.n_gaits;
+  h->total = (int64_t)header_bytes(h->version);
   for (int gi = 0; gi < G_COUNT; ++gi) {
     int64_t& gb = part_bytes(*h, gi);
     for (int w = 0; w < SP_COUNT; ++w) gb += (int64_t)nb[gi][w];
@@ -1407,8 +1519,8 @@ int mpcq_session_snapshot_export(const mpcq_snapshot* p, void* dst, int64_t byte
   if (n < 0) return fail(MPCQ_E_DEVICE, "the snapshot holds more than %d arrays", kListMax);
   mpcq_ctx* c = p->ctx;
   DeviceGuard dg(c->device);
-  memcpy(dst, &h, sizeof(h));
-  size_t off = sizeof(h);
+  memcpy(dst, &h, header_bytes(h.version));
+  size_t off = header_bytes(h.version);
   hipError_t e = hipSuccess;
   for (int i = 0; i < n && e == hipSuccess; ++i) {
     e = hipMemcpyAsync((char*)dst + off, it[i].a, it[i].bytes_a, hipMemcpyDeviceToHost, c->stream);
@@ -1427,16 +1539,20 @@ int mpcq_session_snapshot_import(mpcq_session* s, mpcq_snapshot* p, const void* 
   mpcq_ctx* c = s->ctx;
   if (p->ctx != c) return fail(MPCQ_E_INVALID, "the snapshot belongs to another context");
   BlobHeader h;
-  if (bytes < (int64_t)sizeof(h)) return fail(MPCQ_E_INVALID, "%lld bytes are less than a header", (long long)bytes);
-  memcpy(&h, src, sizeof(h));
+  memset(&h, 0, sizeof(h));
+  if (bytes < (int64_t)header_bytes(1)) return fail(MPCQ_E_INVALID, "%lld bytes are less than a header", (long long)bytes);
+  memcpy(&h, src, header_bytes(1));
   if (memcmp(h.magic, kMagic, 8) != 0) return fail(MPCQ_E_INVALID, "not a snapshot blob (magic)");
-  if (h.version < 1 || h.version > 3)
-    return fail(MPCQ_E_INVALID, "blob format version %u, this library reads 1 to 3", h.version);
+  if (h.version < 1 || h.version > 4)
+    return fail(MPCQ_E_INVALID, "blob format version %u, this library reads 1 to 4", h.version);
+  if (bytes < (int64_t)header_bytes(h.version))
+    return fail(MPCQ_E_INVALID, "%lld bytes are less than a version-%u header", (long long)bytes, h.version);
+  memcpy(&h, src, header_bytes(h.version));
   if (h.N != c->N) return fail(MPCQ_E_INVALID, "the blob is of a context with N = %d, this one has N = %d", h.N, c->N);
-  const bool chan = h.flags & 256u, est = h.flags & 512u;
-  if (h.B < 1 || h.B > (int64_t)0x7fffffff || h.k_mpc < 0 || h.k_mpc > 65536 || (h.flags >> 10) ||
-      ((h.flags & 4u) != 0) != (h.k_mpc > 0) || h.version != (est ? 3u : chan ? 2u : 1u) ||
-      (!est && h.estimator_bytes != 0) ||
+  const bool chan = h.flags & 256u, est = h.flags & 512u, gait = h.flags & 1024u;
+  if (h.B < 1 || h.B > (int64_t)0x7fffffff || h.k_mpc < 0 || h.k_mpc > 65536 || (h.flags >> 11) ||
+      ((h.flags & 4u) != 0) != (h.k_mpc > 0) || h.version != (gait ? 4u : est ? 3u : chan ? 2u : 1u) ||
+      (!est && h.estimator_bytes != 0) || (gait && (h.n_gaits < 1 || h.n_gaits > MPCQ_GAIT_MAX || h.pad != 0)) ||
       (chan ? h.delay < 0 || h.delay > MPCQ_CHANNEL_MAX_DELAY || h.latency < 0 || h.latency > MPCQ_CHANNEL_MAX_LATENCY
             : h.delay != 0 || h.latency != 0 || h.channel_bytes != 0))
     return fail(MPCQ_E_INVALID, "the blob's header is inconsistent (B %lld, k_mpc %d, flags %#x)", (long long)h.B,
@@ -1447,6 +1563,7 @@ int mpcq_session_snapshot_import(mpcq_session* s, mpcq_snapshot* p, const void* 
   sh.robots = h.flags & 64u; sh.plant_robots = h.flags & 128u;
   sh.hv = chan; sh.delay = h.delay; sh.latency = h.latency;
   sh.ev = est;
+  sh.gv = gait; sh.n_gaits = gait ? h.n_gaits : 0;
   BlobHeader want;
   blob_header(sh, c->N, h.flags & 1u, h.flags & 2u, &want);
   for (int gi = 0; gi < G_COUNT; ++gi) {
@@ -1464,7 +1581,7 @@ int mpcq_session_snapshot_import(mpcq_session* s, mpcq_snapshot* p, const void* 
   if (rc) return rc;
   SnapItem it[kListMax];
   const int n = list_arrays(fresh.g, nullptr, it);
-  size_t off = sizeof(h);
+  size_t off = header_bytes(h.version);
   hipError_t e = n < 0 ? hipErrorInvalidValue : hipSuccess;
   for (int i = 0; i < n && e == hipSuccess; ++i) {
     e = hipMemcpyAsync(it[i].a, (const char*)src + off, it[i].bytes_a, hipMemcpyHostToDevice, c->stream);

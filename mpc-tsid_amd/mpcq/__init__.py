@@ -28,6 +28,10 @@ Public surface:
   Estimator         the controller's side of the channel, on the device: a per-robot Kalman filter
                     on the MPC's own model that compensates the measurement's delay through the
                     recorded forces and footholds (Session.enable_estimator)
+  Gait              gait transitions on the device: per-robot target gaits from a small library of
+                    gait cycles, switched at phase boundaries by request or by the commanded
+                    speed; the step that enters the horizon comes from the desired cycle
+                    (Session.enable_gait, Session.set_gait); mpcq.gait.cycle builds the cycles
   Snapshot          a session's robots saved on the device (Session.snapshot): restore them, seed
                     another session from them, branch one robot into many (Session.restore,
                     Session.fork), checkpoint them to the host (Snapshot.tobytes,
@@ -54,11 +58,14 @@ from ._lib import (FLAG_ASYNC, FLAG_DEVICE_PTRS, FLAG_ORDER_BY_CLASS, MODE_SETUP
                    HV_CLOCK, HV_DRAW, HV_F_CMD, HV_F_RING, HV_OBS, HV_S_RING, CHANNEL_MAX_DELAY,
                    CHANNEL_MAX_LATENCY, ChannelParams, default_channel_params,
                    EV_EST, EV_ROW, EST_CLOCK, EST_P, EST_POST, EST_PREV, EST_RING, EST_ROW, EST_SLOTS,
-                   ESTIMATOR_MAX_F_LAG, ESTIMATOR_MAX_LAG, EstimatorParams, default_estimator_params)
+                   ESTIMATOR_MAX_F_LAG, ESTIMATOR_MAX_LAG, EstimatorParams, default_estimator_params,
+                   GV_STATE, GAIT_MAX, GAIT_MANUAL, GAIT_BY_SPEED, GaitParams, default_gait_params)
 from . import channel  # noqa: F401
 from .channel import Channel  # noqa: F401
 from . import estimator  # noqa: F401
 from .estimator import Estimator  # noqa: F401
+from . import gait  # noqa: F401
+from .gait import Gait  # noqa: F401
 from .engine import ROBOT_DTYPE, WEIGHTS_DTYPE, Engine, dims, pattern, robots, weights  # noqa: F401
 from .monitor import Monitor  # noqa: F401
 from .plant import Plant  # noqa: F401

@@ -83,6 +83,10 @@ CHANNEL_MAX_DELAY, CHANNEL_MAX_LATENCY = 8, 4
 EV_EST, EV_ROW = range(2)
 EST_POST, EST_PREV, EST_P, EST_CLOCK, EST_RING, EST_SLOTS, EST_ROW = 0, 12, 24, 42, 44, 12, 332
 ESTIMATOR_MAX_LAG, ESTIMATOR_MAX_F_LAG = 8, 4
+# the gait stage: a session's gait array (MPCQ_GV_*), the library's bound, the selection modes
+GV_STATE = 0
+GAIT_MAX = 8
+GAIT_MANUAL, GAIT_BY_SPEED = 0, 1
 SNAPSHOT_USER_OFFSET = 96  # a snapshot blob's header: the int64 left to the caller (include/mpcq.h)
 
 EXPORTS = ("mpcq_abi_version", "mpcq_default_params", "mpcq_dims", "mpcq_pattern",
@@ -113,6 +117,9 @@ EXPORTS = ("mpcq_abi_version", "mpcq_default_params", "mpcq_dims", "mpcq_pattern
            "mpcq_session_channel_device_ptr",
            "mpcq_default_estimator_params", "mpcq_estimator_step_batch", "mpcq_session_enable_estimator",
            "mpcq_session_disable_estimator", "mpcq_session_estimator_read", "mpcq_session_estimator_device_ptr",
+           "mpcq_default_gait_params", "mpcq_gait_roll_batch", "mpcq_session_enable_gait",
+           "mpcq_session_disable_gait", "mpcq_session_set_gait", "mpcq_session_gait_read",
+           "mpcq_session_gait_device_ptr",
            "mpcq_session_snapshot_create", "mpcq_session_snapshot_destroy", "mpcq_session_snapshot_save",
            "mpcq_session_snapshot_restore", "mpcq_session_fork", "mpcq_session_snapshot_bytes",
            "mpcq_session_snapshot_export", "mpcq_session_snapshot_import", "mpcq_debug_gather_rows")
@@ -278,6 +285,21 @@ class EstimatorParams(C.Structure):
         ("q", C.c_double * 12),
         ("r", C.c_double * 12),
         ("p0", C.c_double * 12),
+    ]
+
+
+class GaitParams(C.Structure):
+    """struct mpcq_gait_params (include/mpcq.h)."""
+
+    _fields_ = [
+        ("n_gaits", C.c_int32),
+        ("select", C.c_int32),
+        ("align", C.c_int32),
+        ("reserved0", C.c_int32),
+        ("thresholds", C.c_double * 7),
+        ("hysteresis", C.c_double),
+        ("yaw_weight", C.c_double),
+        ("reserved", C.c_double * 5),
     ]
 
 
@@ -471,6 +493,18 @@ def lib():
     for name in ("mpcq_estimator_step_batch", "mpcq_session_enable_estimator", "mpcq_session_disable_estimator",
                  "mpcq_session_estimator_read", "mpcq_session_estimator_device_ptr"):
         getattr(L, name).restype = C.c_int
+    GP = C.POINTER(GaitParams)
+    L.mpcq_default_gait_params.argtypes = [GP]
+    L.mpcq_default_gait_params.restype = None
+    L.mpcq_gait_roll_batch.argtypes = [vp, GP, vp, C.c_int64, vp, vp, vp, C.c_uint32]
+    L.mpcq_session_enable_gait.argtypes = [vp, GP, vp]
+    L.mpcq_session_disable_gait.argtypes = [vp]
+    L.mpcq_session_set_gait.argtypes = [vp, vp, C.c_uint32]
+    L.mpcq_session_gait_read.argtypes = [vp, C.c_int, vp, C.c_uint32]
+    L.mpcq_session_gait_device_ptr.argtypes = [vp, C.c_int, C.POINTER(vp)]
+    for name in ("mpcq_gait_roll_batch", "mpcq_session_enable_gait", "mpcq_session_disable_gait",
+                 "mpcq_session_set_gait", "mpcq_session_gait_read", "mpcq_session_gait_device_ptr"):
+        getattr(L, name).restype = C.c_int
     L.mpcq_session_snapshot_create.argtypes = [vp, C.POINTER(vp)]
     L.mpcq_session_snapshot_destroy.argtypes = [vp]
     L.mpcq_session_snapshot_save.argtypes = [vp, vp, C.c_uint32]
@@ -644,6 +678,27 @@ def default_estimator_params(**overrides) -> EstimatorParams:
             v = [v] * len(cur) if not hasattr(v, "__len__") else list(v)
             if len(v) != len(cur):
                 raise ValueError(f"estimator parameter {k} takes {len(cur)} values")
+            v = type(cur)(*v)
+        setattr(p, k, v)
+    return p
+
+
+def default_gait_params(**overrides) -> GaitParams:
+    """mpcq_default_gait_params (n_gaits 0: to be set; GAIT_MANUAL, align 1, thresholds all +inf,
+    hysteresis 0, yaw_weight = the default shoulders' distance from the centre); ``thresholds``
+    takes up to 7 values (the rest stay +inf), ``reserved`` a sequence of its length."""
+    p = GaitParams()
+    lib().mpcq_default_gait_params(C.byref(p))
+    for k, v in overrides.items():
+        if not hasattr(p, k):
+            raise AttributeError(f"unknown gait parameter {k}")
+        cur = getattr(p, k)
+        if hasattr(cur, "__len__"):
+            v = [v] * len(cur) if not hasattr(v, "__len__") else list(v)
+            if k == "thresholds" and len(v) < len(cur):
+                v = v + [float("inf")] * (len(cur) - len(v))
+            if len(v) != len(cur):
+                raise ValueError(f"gait parameter {k} takes {len(cur)} values")
             v = type(cur)(*v)
         setattr(p, k, v)
     return p

@@ -121,6 +121,8 @@ class Session:
         self.scenario_params = None
         self.channel_params = None
         self.estimator_params = None
+        self.gait_params = None
+        self.gait_cycles = None
 
     def enable_swing(self, params: L.SwingParams | None = None):
         """Opt in to the swing-foot references: every later tick appends one swing launch over
@@ -384,6 +386,50 @@ class Session:
     def estimator_device_ptr(self, what: int) -> int:
         out = C.c_void_p()
         self.engine._call("mpcq_session_estimator_device_ptr", self._h, what, C.byref(out))
+        return int(out.value or 0)
+
+    # ------------------------------------------------------------------ gait transitions
+    def enable_gait(self, cycles, params: L.GaitParams | None = None, **overrides):
+        """Opt in to gait transitions: every later tick rolls each robot's gait table with the
+        step that enters the horizon taken from a desired gait cycle (include/mpcq.h has the
+        rules).  ``cycles``: 1 to GAIT_MAX library entries, names for ``mpcq.gait.cycle`` or
+        (20, 5) arrays.  ``overrides``: ``select`` (GAIT_MANUAL: ``set_gait`` requests;
+        GAIT_BY_SPEED: the kernel picks from the commanded speed by ``thresholds``, ``hysteresis``
+        and ``yaw_weight``) and ``align`` (1: switch only at a phase boundary).  Calling it again
+        replaces library and parameters; the robots' rows (GV_STATE) stay.  A refusal of the
+        library leaves the settings in force."""
+        from . import gait as G
+        cy = G.library(cycles)
+        gp = G.params_for(cy, params, **overrides)
+        self.engine._call("mpcq_session_enable_gait", self._h, C.byref(gp), C.c_void_p(cy.ctypes.data))
+        self.gait_params, self.gait_cycles = gp, cy
+
+    def disable_gait(self):
+        """The ticks after it run the planner's own roll again; GV_STATE stays."""
+        self.engine._call("mpcq_session_disable_gait", self._h)
+        self.gait_params = None
+
+    def set_gait(self, ids):
+        """Request library entry ``ids`` (a scalar broadcasts to (B,); -1 withdraws a request that
+        has not been taken yet) under GAIT_MANUAL; each robot switches at its next phase
+        boundary (``align`` 1) or at its next tick."""
+        ids = np.ascontiguousarray(np.broadcast_to(np.asarray(ids, np.int32), (self.batch,)))
+        self.engine._call("mpcq_session_set_gait", self._h, C.c_void_p(ids.ctypes.data), 0)
+
+    def set_gait_device(self, ptr: int, asynchronous: bool = True):
+        """``set_gait`` from a device-resident int32 [B], enqueued on the engine's stream."""
+        flags = L.FLAG_DEVICE_PTRS | (L.FLAG_ASYNC if asynchronous else 0)
+        self.engine._call("mpcq_session_set_gait", self._h, C.c_void_p(ptr) if ptr else None, flags)
+
+    def gait_state(self):
+        """GV_STATE (B, 4) int32: (want, active, phase, switches) per robot."""
+        out = np.empty((self.batch, 4), np.int32)
+        self.engine._call("mpcq_session_gait_read", self._h, L.GV_STATE, C.c_void_p(out.ctypes.data), 0)
+        return out
+
+    def gait_device_ptr(self, what: int = L.GV_STATE) -> int:
+        out = C.c_void_p()
+        self.engine._call("mpcq_session_gait_device_ptr", self._h, what, C.byref(out))
         return int(out.value or 0)
 
     # ------------------------------------------------------------------ rollouts
