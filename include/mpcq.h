@@ -80,7 +80,16 @@ extern "C" {
  *      (per-robot target gaits: the step that enters the horizon comes from a desired gait
  *      cycle); its array has an id of its own, MPCQ_GV_STATE: MPCQ_SV_COUNT stays 21.  A
  *      snapshot of a session with the gait array writes blob format version 4 (a 144-byte
- *      header, one more part); one without writes what it wrote before, and import reads all */
+ *      header, one more part); one without writes what it wrote before, and import reads all
+ *   3 (additions, no bump): mpcq_disturbance, mpcq_set_disturbance,
+ *      mpcq_session_set_disturbance, mpcq_session_get_disturbance (a per-instance constant
+ *      disturbance acceleration in the model's dynamics)
+ *   3 (additions, no bump): mpcq_disturb_params, mpcq_default_disturb_params,
+ *      mpcq_disturb_step_batch, mpcq_session_enable_disturb / _disable_disturb / _disturb_read /
+ *      _disturb_device_ptr (a disturbance observer in front of the solve); its arrays have ids
+ *      of their own, MPCQ_DV_*: MPCQ_SV_COUNT stays 21.  A snapshot of a session with those
+ *      arrays writes blob format version 5 (a 160-byte header, one more part); one without
+ *      writes what it wrote before, and import reads all */
 #define MPCQ_ABI_VERSION 3
 
 /* error codes (return values) */
@@ -286,6 +295,42 @@ void mpcq_default_weights(const mpcq_params* p, mpcq_weights* w);
  * from the context's mpcq_params. */
 int mpcq_set_weights(mpcq_ctx* ctx, int64_t count, const mpcq_weights* weights, uint32_t flags);
 
+/* ---- per-instance disturbance -------------------------------------------------
+ * No reference counterpart (the reference's model knows gravity only): a constant acceleration
+ * that the model of instance b carries through every stage of its horizon, beside gravity --
+ * an unmodelled payload's sag, a steady push, a bias the caller has estimated.  The frame is
+ * the instance's xref frame (in a session: the tick's local frame).  With it
+ *   X_{k+1}[6+i] = (the model as it was) + dt * a[i],   i = 0..5, every stage k,
+ * in MPC.py's terms g[6+i] += dt * a[i]: the constant of dynamics row 6+i becomes
+ * v + (-(dt * a[i])) (v: gravity * dt on row 8, -0.0 elsewhere), added before the xref terms,
+ * so a row of +0.0 changes no bit of l, u, x or f0.  Ax and P do not move. */
+typedef struct mpcq_disturbance {   /* 8 doubles = 64 bytes */
+  double a[6];        /* linear acceleration [m/s^2], then angular acceleration [rad/s^2] */
+  double reserved[2];            /* zero */
+} mpcq_disturbance;
+#ifdef __cplusplus
+static_assert(sizeof(mpcq_disturbance) == 64, "mpcq_disturbance is 8 doubles");
+#else
+_Static_assert(sizeof(mpcq_disturbance) == 64, "mpcq_disturbance is 8 doubles");
+#endif
+/* Copies table [count] into memory the context owns, with mpcq_set_robots' and
+ * mpcq_set_weights' rules word for word: from a host pointer the call blocks; with
+ * MPCQ_FLAG_DEVICE_PTRS the copy is device to device on ctx's stream.  In every later
+ * mpcq_formulate_batch and mpcq_solve_batch of ctx (both formulation modes, polish, sliced and
+ * class-ordered solves included; a sliced solve's resumed launch re-formulates from the same
+ * row) instance b takes its disturbance from table[b] -- b is the instance index, whatever
+ * order the workgroups are dispatched in.  The three tables are independent.  count == 0 or
+ * table == NULL clears the table (no disturbance: a context that never sets one launches
+ * exactly what it did before).  While a table is set, a launch with batch > count returns
+ * MPCQ_E_INVALID and launches nothing.
+ * A host table is validated: every a[i] finite, reserved zero; otherwise MPCQ_E_INVALID (the
+ * message names the first offending index and field) and the table in force stays, as it does
+ * when the memory for a larger table cannot be allocated (MPCQ_E_NOMEM).  A device table is
+ * not validated: a NaN or Inf among the six values of a row ends as MPCQ_STATUS_NONFINITE on
+ * that instance alone (in mpcq_formulate_batch it reaches l and u as it is).
+ * mpcq_qp_solve_batch does not look at the table: its caller's l and u hold what they hold. */
+int mpcq_set_disturbance(mpcq_ctx* ctx, int64_t count, const mpcq_disturbance* table, uint32_t flags);
+
 /* ---- formulation -----------------------------------------------------------
  * Replaces MPC.construct_gait + update_matrices (MPC.py:635-652, 290-378) in
  * MODE_UPDATE, and construct_gait + create_matrices (MPC.py:84-234) in
@@ -480,6 +525,17 @@ int mpcq_session_set_weights(mpcq_session* s, const mpcq_weights* weights, uint3
 /* The table in force, weights [B] (host, or device with MPCQ_FLAG_DEVICE_PTRS); blocking.
  * Without a table: mpcq_default_weights(the context's params) for every robot. */
 int mpcq_session_get_weights(mpcq_session* s, mpcq_weights* weights, uint32_t flags);
+/* The session's own table of disturbances, table [B] (mpcq_set_disturbance: the same copy,
+ * validation and flags); independent of the context's table.  The ticks after the call solve
+ * robot b with table[b] in its model, in the tick's local frame.  NULL clears it.  The table
+ * persists across mpcq_session_reset and the monitor's auto-reset.  Like the weights it is the
+ * controller's, not the robot's state: snapshots do not carry it (the blob of a session with a
+ * table is byte for byte the blob without one), and restore, restore_map and fork leave the
+ * table in force untouched. */
+int mpcq_session_set_disturbance(mpcq_session* s, const mpcq_disturbance* table, uint32_t flags);
+/* The table in force, table [B] (host, or device with MPCQ_FLAG_DEVICE_PTRS); blocking.
+ * Without a table: zeros for every robot. */
+int mpcq_session_get_disturbance(mpcq_session* s, mpcq_disturbance* table, uint32_t flags);
 /* Restart a subset of the robots between two ticks; the others are not written at all.
  *   mask  [B] int32, nonzero = reset this robot; NULL = every robot
  *   gait0 [B][20][5] or NULL (the table the session was created with, of which it keeps a
@@ -1269,6 +1325,125 @@ int mpcq_session_gait_read(mpcq_session* s, int what, void* dst, uint32_t flags)
 /* Device address of array `what` (valid until mpcq_session_destroy). */
 int mpcq_session_gait_device_ptr(mpcq_session* s, int what, void** out);
 
+/* ---- disturb: a disturbance observer in front of the solve ---------------------
+ * The one piece of a session that did not react to a payload the controller does not know or
+ * to a steady push was the controller's own model.  This stage estimates, on the device, the
+ * constant acceleration the model lacks from consecutive states and the model itself, and hands
+ * it to the solve as each robot's mpcq_disturbance row (mpcq_disturb.hip).  (`observe` is the
+ * channel's stage; this one is `disturb`.)  No reference counterpart; tests/disturb_model.py
+ * restates every rule below on the host.
+ *
+ * Row, MPCQ_DIST_ROW doubles per robot (nothing in it depends on a parameter: no launch arms
+ * it, a snapshot needs no depth fields):
+ *   [MPCQ_DIST_D     .. +6)   d, the estimate, in the frame of the last tick that ran
+ *   [MPCQ_DIST_PREV  .. +12)  the previous tick's measurement
+ *   [MPCQ_DIST_CLOCK .. +2)   four int32: valid, tau_next, zero, zero
+ *   [MPCQ_DIST_RING  .. +60)  5 slots of 12 doubles: slot j % 5 holds tick j's f0
+ * tau is the stage's own count of ticks since its last first tick.
+ *
+ * One robot-tick (meas [12] what the planner is about to take as its state; f_prev, feet_prev
+ * the PREVIOUS tick's f0 and stance feet; M the estimator's model step above, with the robot
+ * the CONTROLLER believes, never the plant's):
+ *  1. First tick, when the robot is first, valid == 0, or the stored tau_next < 1.  Then d = 0,
+ *     prev = meas, tau_next = 1, valid = 1, the output row is zero, the ring is neither read nor
+ *     written (a new episode may have drawn a new payload).
+ *  2. Otherwise tau = tau_next, and in this order:
+ *     record: slot (tau - 1) % 5 <- f_prev.
+ *     acting force: the f0 recorded for tick tau - 1 - f_lag, and before tick 0 the reference's
+ *       [0, 0, 8] * 4 (MPC_Wrapper.py:78): the estimator's rule.
+ *     frame change: psi = prev[5] + dt * prev[11] (the bits of M's yaw at the end of the tick);
+ *       with c = cos psi, s = sin psi, (d0, d1) and (d3, d4) become (c d0 + s d1, -s d0 + c d1);
+ *       d2 and d5 stay.  A psi that is not finite leaves d as it is.
+ *     sample, unless: the previous tick failed (the plant's rule, as in the estimator); meas or
+ *       prev has a non-finite component; with skip_repeats, meas equals prev bit for bit (the
+ *       channel's hold).  pred = M(prev, feet_prev, acting force); r[i] = (meas[6+i] -
+ *       pred[6+i]) / dt.  The plant's physics do not care what the MPC believed, so r samples
+ *       the whole lumped disturbance whether or not the last solve compensated: the update
+ *       carries no "previously applied" term.
+ *     update: with a sample whose six r are finite, d[i] = d[i] + alpha[i] * (r[i] - d[i]).
+ *     clip: d[i] to [-d_max[i], d_max[i]].
+ *  3. prev = meas and tau_next = tau + 1 are stored; the output row's a = d, reserved zero; the
+ *     diagnostic row = r (NaN where no sample was taken).
+ * With alpha = 0 the estimate stays zero exactly; with alpha = 1 it follows the last sample.
+ * Known limit: the estimator's forecast model does not include the disturbance, so behind a
+ * channel with lag > 0 its estimate carries a near-constant rate offset, which largely cancels
+ * in the difference of consecutive estimates that this stage samples. */
+#define MPCQ_DISTURB_MAX_F_LAG 4
+#define MPCQ_DIST_D 0
+#define MPCQ_DIST_PREV 6
+#define MPCQ_DIST_CLOCK 18
+#define MPCQ_DIST_RING 20
+#define MPCQ_DIST_SLOTS 5   /* MPCQ_DISTURB_MAX_F_LAG + 1 */
+#define MPCQ_DIST_ROW 80    /* doubles: 640 bytes, a multiple of 16 */
+typedef struct mpcq_disturb_params {     /* 128 bytes */
+  double alpha[6];                      /* the filter's gain per component, each in [0, 1] */
+  double d_max[6];                      /* > 0: the estimate is clipped to +-d_max[i] */
+  int32_t f_lag;                        /* 0..4: ticks between a solve and its forces (the channel's latency) */
+  int32_t compensate;                   /* nonzero: a session's solve takes MPCQ_DV_DIST as its disturbance table */
+  int32_t skip_repeats;                 /* nonzero: a repeated measurement row yields no sample */
+  int32_t reserved[5];                  /* zero */
+} mpcq_disturb_params;
+#ifdef __cplusplus
+static_assert(sizeof(mpcq_disturb_params) == 128, "mpcq_disturb_params is 128 bytes");
+#else
+_Static_assert(sizeof(mpcq_disturb_params) == 128, "mpcq_disturb_params is 128 bytes");
+#endif
+/* alpha = 0.2, d_max = 5 m/s^2 (linear) and 30 rad/s^2 (angular), f_lag 0, compensate 1,
+ * skip_repeats 1: starting values, not tuned. */
+void mpcq_default_disturb_params(mpcq_disturb_params* dp);
+/* One tick of the stage for a batch, on its own.
+ *   first       [B] int32 or NULL: nonzero = a first tick for this robot; all_first != 0: all
+ *   meas        [B][12]
+ *   f_prev      [B][12], feet_prev [B][3][4]: the previous tick's f0 and feet (not read by a
+ *               robot that runs a first tick)
+ *   failed_prev [B] int32 or NULL: nonzero = the previous tick failed
+ *   robots      [B] mpcq_robot or NULL (the context's params); a host table is validated as in
+ *               mpcq_set_robots
+ *   row         [B][MPCQ_DIST_ROW] in/out (all zero: a new stage)
+ *   dist        [B] mpcq_disturbance out;  resid [B][6] out or NULL
+ * dp NULL = the defaults.  Host pointers, or device pointers with MPCQ_FLAG_DEVICE_PTRS (then
+ * MPCQ_FLAG_ASYNC does not wait for the stream).  MPCQ_E_INVALID, nothing launched, the message
+ * naming the field: an alpha[i] outside [0, 1], a d_max[i] <= 0, f_lag outside 0..4, any NaN or
+ * infinity, reserved not zero; a NULL meas, f_prev, feet_prev, row or dist.  The parameters are
+ * checked before anything else. */
+int mpcq_disturb_step_batch(mpcq_ctx* ctx, const mpcq_disturb_params* dp, int64_t batch,
+                            const int32_t* first, int all_first, const double* meas,
+                            const double* f_prev, const double* feet_prev,
+                            const int32_t* failed_prev, const mpcq_robot* robots, double* row,
+                            mpcq_disturbance* dist, double* resid, uint32_t flags);
+/* Opt-in (dp NULL = the defaults; invalid parameters: MPCQ_E_INVALID naming the field, nothing
+ * is launched and the parameters in force stay).  While enabled a tick runs the stage after its
+ * estimate stage and before the planner ([scenario] -> inputs -> [observe] -> [estimate] ->
+ * [disturb] -> planner -> solve -> ...): meas = what the planner is about to take as its state
+ * (MPCQ_EV_EST, MPCQ_HV_OBS, or the staged state; the stage does not change it); f_prev =
+ * MPCQ_SV_F0 and feet_prev = row 0 of MPCQ_SV_FSTEPS as they stand before this tick's planner;
+ * failed and first as in the estimator; the robot is the session's mpcq_session_set_robots
+ * table, else the context's params.  With compensate the tick's solve takes MPCQ_DV_DIST as its
+ * disturbance table: it then takes precedence over the table of mpcq_session_set_disturbance.
+ * With compensate == 0 the stage only estimates, and the solve takes the user's table if there
+ * is one.  One more small launch per tick, nothing on the host.  It works without plant,
+ * channel or estimator.  A reset or an auto-reset needs nothing of its own: the first flags
+ * carry it.
+ * The first call makes the MPCQ_DV_* arrays, zero (valid = 0).  Enabling while not enabled
+ * zeroes the rows again (a ring that missed ticks is stale).  Calling it while enabled only
+ * replaces the parameters.  A session that never enables it launches exactly what it did
+ * before. */
+int mpcq_session_enable_disturb(mpcq_session* s, const mpcq_disturb_params* dp);
+/* The ticks after it run without the launch (and the solve takes the user's table again); the
+ * arrays stay. */
+int mpcq_session_disable_disturb(mpcq_session* s);
+/* The stage's arrays; they exist from the first mpcq_session_enable_disturb on (before:
+ * MPCQ_E_INVALID). */
+#define MPCQ_DV_DIST 0      /* [B] mpcq_disturbance   what the solve reads (derived: not in snapshots) */
+#define MPCQ_DV_ROW 1       /* [B][MPCQ_DIST_ROW]     the stage's state */
+#define MPCQ_DV_RESID 2     /* [B][6]                 the last tick's raw sample, NaN where none was taken
+                                                      (derived, for diagnostics: not in snapshots) */
+#define MPCQ_DV_COUNT 3
+/* Copy array `what` to dst (host, or device with MPCQ_FLAG_DEVICE_PTRS); blocking. */
+int mpcq_session_disturb_read(mpcq_session* s, int what, void* dst, uint32_t flags);
+/* Device address of array `what` (valid until mpcq_session_destroy). */
+int mpcq_session_disturb_device_ptr(mpcq_session* s, int what, void** out);
+
 /* ---- snapshots: save, restore and branch robots on the device ---------------
  * A snapshot is a device-resident copy of everything per-robot that a session holds, plus the
  * few host flags that decide what the next tick launches.  Every call below runs on the
@@ -1285,7 +1460,9 @@ int mpcq_session_gait_device_ptr(mpcq_session* s, int what, void** out);
  * tick before anything reads it, and left out: after a restore it shows the session's last tick
  * until the next one), MPCQ_GV_STATE (after _enable_gait; the gait library and parameters are the controller's
  * configuration and are not held, so a restore needs a session whose library has as many
- * cycles), and the tables of mpcq_session_set_robots / _set_plant_robots where in force -- and its shape: N,
+ * cycles), MPCQ_DV_ROW (after _enable_disturb; self-describing like the estimator's row;
+ * MPCQ_DV_DIST and MPCQ_DV_RESID are derived, rewritten by every tick of the stage before
+ * anything reads them, and left out), and the tables of mpcq_session_set_robots / _set_plant_robots where in force -- and its shape: N,
  * B, which of these exist, the swing k_mpc, the channel's delay and latency in force at the
  * save (the rings mean nothing under others: a restore into a session whose values differ is
  * MPCQ_E_INVALID); and whether a tick has run since create and whether a reset was ever called.  Not held: the staging of host inputs and the plant's copy of q_w (every
@@ -1293,8 +1470,9 @@ int mpcq_session_gait_device_ptr(mpcq_session* s, int what, void** out);
  * the restore rebuilds it, and results do not depend on it).  Parameters and enable flags
  * (swing, plant, monitor, scenario parameters; _enable_* / _disable_*) are configuration, not
  * robots' state: the session's own, never touched.  So is the table of
- * mpcq_session_set_weights, the controller's tuning: a snapshot does not hold it (the blob of
- * a session with a table is byte for byte the blob without one) and no restore touches it.
+ * mpcq_session_set_weights, the controller's tuning, and the table of
+ * mpcq_session_set_disturbance: a snapshot holds neither (the blob of a session with a table is
+ * byte for byte the blob without one) and no restore touches them.
  *
  * create: no device memory until the first save.  The snapshot belongs to s's context (hence
  * its N and stream) and may be restored into any session of that context.  A snapshot may be
@@ -1325,7 +1503,7 @@ int mpcq_session_snapshot_save(mpcq_session* s, mpcq_snapshot* snap, uint32_t fl
  * map cannot be validated: an entry outside [0, B_snapshot) acts as -1.
  * A restored robot gets its row of every array the snapshot holds, in ONE launch
  * (gather_rows_kernel) up to 48 arrays, in two beyond (a session with every group enabled has
- * 49), each on the stream.  After it, where the session or the snapshot has a dispatch order in
+ * 50), each on the stream.  After it, where the session or the snapshot has a dispatch order in
  * use, MPCQ_SV_ORDER is rebuilt from the restored iteration counts and pending resets.  A
  * reset recorded in the snapshot stays recorded in the session.
  * A snapshot saved before any tick holds creation state, which only a first tick may consume:
@@ -1347,7 +1525,7 @@ int mpcq_session_snapshot_restore(mpcq_session* s, const mpcq_snapshot* snap, co
 int mpcq_session_fork(mpcq_session* s, const int32_t* map, uint32_t flags);
 /* Checkpoint to the host.  One blob = a 128-byte header, then the groups' arrays unpadded, in
  * the order main, swing, plant, monitor, scenario, robots table, plant robots table, channel,
- * estimator, gait, inside a group by array id (the private main arrays behind the named ones).  The
+ * estimator, gait, disturb, inside a group by array id (the private main arrays behind the named ones).  The
  * header, little endian: char magic[8] "MPCQSNP1"; uint32 version (3 with an estimator part, else
  * 2 with a channel part, else 1: a session without either writes the version-1 blob byte for
  * byte, one with a channel and no estimator the version-2 blob; import reads all three); int32
@@ -1358,6 +1536,9 @@ int mpcq_session_fork(mpcq_session* s, const int32_t* map, uint32_t flags);
  * delay, latency in force at the save; at 120 int64 bytes of the estimator part (MPCQ_EV_ROW).
  * Format version 4 (a session with MPCQ_GV_STATE; flags bit 10) has a 144-byte header: at 128
  * int64 bytes of the gait part, at 136 int32 n_gaits, at 140 int32 zero.
+ * Format version 5 (a session with MPCQ_DV_ROW; flags bit 11) has a 160-byte header: the
+ * version-4 header (its gait fields zero without a gait part), at 144 int64 bytes of the disturb
+ * part (MPCQ_DV_ROW), at 152 int64 zero.
  * _bytes: the size of snap's blob (snap saved).  _export: dst is a host buffer of exactly
  * that many bytes; blocking.  _import: makes snap the snapshot the blob describes, for s's
  * context; before it touches the device it checks the magic, the version, N against the

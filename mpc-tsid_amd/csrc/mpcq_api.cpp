@@ -207,6 +207,19 @@ int check_weights(const mpcq_weights* w, int64_t count) {
   return MPCQ_OK;
 }
 
+// The first entry of a host table that mpcq_set_disturbance rejects, named in the message.
+int check_disturbance(const mpcq_disturbance* d, int64_t count) {
+  for (int64_t i = 0; i < count; ++i) {
+    for (int j = 0; j < 6; ++j)
+      if (!isfinite(d[i].a[j]))
+        return fail(MPCQ_E_INVALID, "disturbance[%lld]: a[%d] must be finite", (long long)i, j);
+    for (int j = 0; j < 2; ++j)
+      if (!(d[i].reserved[j] == 0.0))
+        return fail(MPCQ_E_INVALID, "disturbance[%lld]: reserved must be zero", (long long)i);
+  }
+  return MPCQ_OK;
+}
+
 // The table a launch of `batch` instances reads: null without one, an error if it is too short.
 template <class R>
 int launch_table(const Table<R>& t, const char* what, int64_t batch, const R** out) {
@@ -218,7 +231,7 @@ int launch_table(const Table<R>& t, const char* what, int64_t batch, const R** o
   return MPCQ_OK;
 }
 
-// set_table over either record type (both 128 bytes); check: the host table's validation.
+// set_table over any record type; check: the host table's validation.
 template <class R>
 int set_table_t(mpcq_ctx* c, Table<R>& t, int64_t count, const R* rows, uint32_t flags, const char* what,
                 int (*check)(const R*, int64_t)) {
@@ -376,6 +389,23 @@ int mpcq::estimator_params(const mpcq_estimator_params* ep, mpcq_estimator_param
   return MPCQ_OK;
 }
 
+int mpcq::disturb_params(const mpcq_disturb_params* dp, mpcq_disturb_params* out) {
+  if (dp) *out = *dp;
+  else mpcq_default_disturb_params(out);
+  const mpcq_disturb_params& p = *out;
+  for (int i = 0; i < 6; ++i)
+    if (!(p.alpha[i] >= 0 && p.alpha[i] <= 1))
+      return fail(MPCQ_E_INVALID, "the disturbance stage needs alpha[%d] in [0, 1]", i);
+  for (int i = 0; i < 6; ++i)
+    if (!(isfinite(p.d_max[i]) && p.d_max[i] > 0))
+      return fail(MPCQ_E_INVALID, "the disturbance stage needs a finite d_max[%d] > 0", i);
+  if (p.f_lag < 0 || p.f_lag > MPCQ_DISTURB_MAX_F_LAG)
+    return fail(MPCQ_E_INVALID, "the disturbance stage needs f_lag in 0..%d (got %d)", MPCQ_DISTURB_MAX_F_LAG, p.f_lag);
+  for (int i = 0; i < 5; ++i)
+    if (p.reserved[i]) return fail(MPCQ_E_INVALID, "the disturbance stage's reserved fields must be zero");
+  return MPCQ_OK;
+}
+
 int mpcq::gait_params(const mpcq_gait_params* gp, const double* cycles, mpcq_gait_params* out, mpcq::GaitArgs* lib) {
   if (!gp) return fail(MPCQ_E_INVALID, "the gait parameters are NULL (n_gaits has no default)");
   if (!cycles) return fail(MPCQ_E_INVALID, "the gait cycles are NULL");
@@ -470,31 +500,56 @@ int mpcq::set_table(mpcq_ctx* c, WeightsTable& t, int64_t count, const mpcq_weig
   return set_table_t(c, t, count, weights, flags, "weights", check_weights);
 }
 
-int mpcq::launch_tables(mpcq_ctx* c, const RobotTable& robots, const WeightsTable& weights, FillTables& fill,
-                        int64_t batch, const mpcq_robot** r, const mpcq_weights** w) {
-  *r = nullptr;
-  *w = nullptr;
-  int rc = launch_table(robots, "robot", batch, r);
+int mpcq::set_table(mpcq_ctx* c, DisturbTable& t, int64_t count, const mpcq_disturbance* rows, uint32_t flags) {
+  return set_table_t(c, t, count, rows, flags, "disturbance", check_disturbance);
+}
+
+int mpcq::launch_tables(mpcq_ctx* c, const RobotTable& robots, const WeightsTable* weights,
+                        const DisturbTable& disturb, FillTables& fill, int64_t batch, LaunchArgs* a) {
+  const mpcq_robot* r = nullptr;
+  const mpcq_weights* w = nullptr;
+  const mpcq_disturbance* d = nullptr;
+  a->robots = nullptr;
+  a->weights = nullptr;
+  a->disturb = nullptr;
+  int rc = launch_table(robots, "robot", batch, &r);
   if (rc) return rc;
-  rc = launch_table(weights, "weights", batch, w);
+  if (weights) rc = launch_table(*weights, "weights", batch, &w);
   if (rc) return rc;
-  if (*r && !*w) {
-    mpcq_weights d;
-    mpcq_default_weights(&c->p, &d);
-    rc = ensure_fill(c, fill.weights, batch, d);
-    *w = fill.weights.dev;
-  } else if (*w && !*r) {
-    mpcq_robot d;
-    mpcq_default_robot(&c->p, &d);
-    rc = ensure_fill(c, fill.robots, batch, d);
-    *r = fill.robots.dev;
+  rc = launch_table(disturb, "disturbance", batch, &d);
+  if (rc) return rc;
+  if (!r && !w && !d) return MPCQ_OK;
+  if (!r) {
+    mpcq_robot rec;
+    mpcq_default_robot(&c->p, &rec);
+    rc = ensure_fill(c, fill.robots, batch, rec);
+    if (rc) return rc;
+    r = fill.robots.dev;
   }
-  return rc;
+  if (!w && weights) {
+    mpcq_weights rec;
+    mpcq_default_weights(&c->p, &rec);
+    rc = ensure_fill(c, fill.weights, batch, rec);
+    if (rc) return rc;
+    w = fill.weights.dev;
+  }
+  if (!d) {
+    mpcq_disturbance rec;
+    memset(&rec, 0, sizeof(rec));
+    rc = ensure_fill(c, fill.disturb, batch, rec);
+    if (rc) return rc;
+    d = fill.disturb.dev;
+  }
+  a->robots = r;
+  a->weights = w;
+  a->disturb = d;
+  return MPCQ_OK;
 }
 
 void mpcq::free_tables(FillTables& fill) {
   if (fill.robots.dev) (void)hipFree(fill.robots.dev);
   if (fill.weights.dev) (void)hipFree(fill.weights.dev);
+  if (fill.disturb.dev) (void)hipFree(fill.disturb.dev);
   fill = FillTables{};
 }
 
@@ -659,6 +714,7 @@ int mpcq_destroy(mpcq_ctx* c) {
   if (c->sl_count) (void)hipFree(c->sl_count);
   if (c->robots.dev) (void)hipFree(c->robots.dev);
   if (c->weights.dev) (void)hipFree(c->weights.dev);
+  if (c->disturb.dev) (void)hipFree(c->disturb.dev);
   mpcq::free_tables(c->fill);
   for (auto& e : c->ev)
     if (e) (void)hipEventDestroy(e);
@@ -688,6 +744,11 @@ int mpcq_set_robots(mpcq_ctx* c, int64_t count, const mpcq_robot* robots, uint32
 int mpcq_set_weights(mpcq_ctx* c, int64_t count, const mpcq_weights* weights, uint32_t flags) {
   if (!c) return fail(MPCQ_E_INVALID, "ctx is NULL");
   return set_table(c, c->weights, count, weights, flags);
+}
+
+int mpcq_set_disturbance(mpcq_ctx* c, int64_t count, const mpcq_disturbance* table, uint32_t flags) {
+  if (!c) return fail(MPCQ_E_INVALID, "ctx is NULL");
+  return set_table(c, c->disturb, count, table, flags);
 }
 
 int mpcq_last_kernel_ms(mpcq_ctx* c, double* fms, double* sms) {
@@ -726,7 +787,8 @@ int mpcq_formulate_batch(mpcq_ctx* c, int64_t B, const double* xref, const doubl
   mpcq::LaunchArgs a{};
   a.batch = B;
   a.mode = mode;
-  rc = launch_table(c->robots, "robot", B, &a.robots);  // (no P here: the weights table is not looked at)
+  // (no P here: the weights table is not looked at)
+  rc = mpcq::launch_tables(c, c->robots, nullptr, c->disturb, c->fill, B, &a);
   if (rc) return rc;
   const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
   Xfer xs[6] = {{xref, nullptr, B * n12 * 8, nullptr}, {fsteps, nullptr, (size_t)B * 260 * 8, nullptr},
@@ -765,7 +827,7 @@ static int solve_common(mpcq_ctx* c, int64_t B, bool fused, const double* xref, 
   a.batch = B;
   a.mode = mode;
   if (fused) {  // (the qp path has formulated already)
-    rc = mpcq::launch_tables(c, c->robots, c->weights, c->fill, B, &a.robots, &a.weights);
+    rc = mpcq::launch_tables(c, c->robots, &c->weights, c->disturb, c->fill, B, &a);
     if (rc) return rc;
   }
   const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
@@ -1348,6 +1410,70 @@ int mpcq_estimator_step_batch(mpcq_ctx* c, const mpcq_estimator_params* ep, int6
     a.robots = robots; a.row = row; a.est = est;
   }
   HIP_TRY(mpcq::launch_estimate(P, a, c->stream));
+  if (!dev) return unstage(c, xs, NX);
+  if (!(flags & MPCQ_FLAG_ASYNC)) HIP_TRY(hipStreamSynchronize(c->stream));
+  return MPCQ_OK;
+}
+
+// Disturbance stage: starting values, not tuned (include/mpcq.h).
+void mpcq_default_disturb_params(mpcq_disturb_params* dp) {
+  if (!dp) return;
+  memset(dp, 0, sizeof(*dp));
+  for (int i = 0; i < 6; ++i) {
+    dp->alpha[i] = 0.2;
+    dp->d_max[i] = i < 3 ? 5.0 : 30.0;
+  }
+  dp->compensate = 1;
+  dp->skip_repeats = 1;
+}
+
+int mpcq_disturb_step_batch(mpcq_ctx* c, const mpcq_disturb_params* dp, int64_t B, const int32_t* first,
+                            int all_first, const double* meas, const double* f_prev, const double* feet_prev,
+                            const int32_t* failed_prev, const mpcq_robot* robots, double* row,
+                            mpcq_disturbance* dist, double* resid, uint32_t flags) {
+  mpcq_disturb_params P;
+  int rc = disturb_params(dp, &P);  // first: what is wrong with the parameters needs no context
+  if (rc) return rc;
+  rc = check_ctx(c, B);
+  if (rc) return rc;
+  if (!meas || !f_prev || !feet_prev || !row || !dist)
+    return fail(MPCQ_E_INVALID, "meas, f_prev, feet_prev, row and dist are required");
+  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
+  if (robots && !dev) {
+    rc = check_robots(robots, B);
+    if (rc) return rc;
+  }
+  if (B == 0) return MPCQ_OK;
+  DeviceGuard g(c->device);
+  mpcq::DisturbArgs a{};
+  a.batch = B;
+  a.all_first = all_first != 0;
+  a.dt = c->p.dt;
+  a.gravity = c->p.gravity;
+  mpcq_default_robot(&c->p, &a.dflt);
+  const size_t b = (size_t)B;
+  enum { FI, ME, FP, FT, FA, RB, RO, DI, RE, NX };
+  Xfer xs[NX] = {{first, nullptr, b * 4, nullptr},
+                 {meas, nullptr, b * 96, nullptr},
+                 {f_prev, nullptr, b * 96, nullptr},
+                 {feet_prev, nullptr, b * 96, nullptr},
+                 {failed_prev, nullptr, b * 4, nullptr},
+                 {robots, nullptr, b * sizeof(mpcq_robot), nullptr},
+                 {row, row, b * MPCQ_DIST_ROW * 8, nullptr},
+                 {nullptr, dist, b * sizeof(mpcq_disturbance), nullptr},
+                 {nullptr, resid, resid ? b * 48 : 0, nullptr}};
+  if (!dev) {
+    rc = stage(c, xs, NX);
+    if (rc) return rc;
+    a.first = (const int32_t*)xs[FI].dev; a.meas = (const double*)xs[ME].dev; a.f_prev = (const double*)xs[FP].dev;
+    a.feet_prev = (const double*)xs[FT].dev; a.failed = (const int32_t*)xs[FA].dev;
+    a.robots = (const mpcq_robot*)xs[RB].dev; a.row = (double*)xs[RO].dev;
+    a.dist = (mpcq_disturbance*)xs[DI].dev; a.resid = resid ? (double*)xs[RE].dev : nullptr;
+  } else {
+    a.first = first; a.meas = meas; a.f_prev = f_prev; a.feet_prev = feet_prev; a.failed = failed_prev;
+    a.robots = robots; a.row = row; a.dist = dist; a.resid = resid;
+  }
+  HIP_TRY(mpcq::launch_disturb(P, a, c->stream));
   if (!dev) return unstage(c, xs, NX);
   if (!(flags & MPCQ_FLAG_ASYNC)) HIP_TRY(hipStreamSynchronize(c->stream));
   return MPCQ_OK;

@@ -655,11 +655,27 @@ __device__ __forceinline__ void form_foot(const mpcq_params& p, double mass, con
   }
 }
 
+// The lane's own component of the instance's constant disturbance acceleration (ROB kernels:
+// LaunchArgs::disturb[b], mpcq_set_disturbance; the others have none): dynamics row r >= 6 takes
+// a[r - 6], one global load per lane like weight_x's, not through uni() -- the solve kernels sit
+// at the SGPR ceiling.  Rows r < 6 load a[0] (in bounds) and do not use it.
+template <bool TABLE>
+__device__ __forceinline__ double disturb_a(const LaunchArgs& a, int64_t b, int r) {
+  if constexpr (TABLE) return a.disturb[b].a[r >= 6 ? r - 6 : 0];
+  else return 0.0;
+}
+
 // Bounds of dynamics row (k, r) (MPC.py:197-221, 366-378, 410); xr = xref staged in LDS.
-template <int N>
-__device__ __forceinline__ double dyn_bound(const mpcq_params& p, const double* xr, int k, int r) {
+// TABLE: da = the row's disturbance acceleration (disturb_a), in MPC.py's terms g[r] += dt * da
+// on rows r >= 6; a da of +0.0 adds -0.0 and changes no bit.
+template <int N, bool TABLE = false>
+__device__ __forceinline__ double dyn_bound(const mpcq_params& p, const double* xr, int k, int r,
+                                            [[maybe_unused]] double da = 0.0) {
   constexpr int NP1 = N + 1;
   double v = (r == 8) ? -(-p.gravity * p.dt) : -0.0;
+  if constexpr (TABLE) {
+    if (r >= 6) v = v + (-(p.dt * da));
+  }
   if (k == 0) {
     double ax0 = -xr[r * NP1];
     if (r < 6) ax0 = ax0 + p.dt * (-xr[(r + 6) * NP1]);
@@ -845,9 +861,10 @@ struct Prologue {
 // The engine kernel.  FUSED: formulate from (xref, fsteps) then solve.
 // !FUSED: solve the given (Ax, l, u).  SOLVE=false: formulation only.
 
-// ROB: the per-instance tables, both not null: LaunchArgs::robots in place of p.mass / gI / mu /
+// ROB: the per-instance tables, all not null: LaunchArgs::robots in place of p.mass / gI / mu /
 // fz_max, LaunchArgs::weights in place of p.state_weights / force_weight (the solving kernels
-// only; the host fills a table that is not set with the context's values).
+// only), LaunchArgs::disturb beside gravity in the dynamics rows' constants (the host fills a
+// table that is not set with the context's values, the disturbance's with zeros).
 // An instantiation of its own, so that the kernels of a launch without a table are instruction
 // for instruction what they were before the table existed (the formulation's kernels only: the
 // qp path takes Ax, l, u as given).
@@ -1000,6 +1017,7 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
   // rows are 0 = 0; friction rows u = 0, l = -inf (-OSQP_INFTY) or -fz_max.
   // !FUSED: the caller's l / u for every own row.
   double bnd = 0.0;
+  [[maybe_unused]] double dacc = 0.0;  // (ROB && FUSED: the lane's disturbance acceleration)
   double lo_g[FUSED ? 1 : 3], hi_g[FUSED ? 1 : 3];
   if (t == 0) { sh.flag[0] = 0; sh.flag[1] = 0; sh.flag[2] = 0; sh.flag[3] = 0; }
   for (int e = t; e < 72; e += T) sh.zero[e] = 0.0;  // N = 4: one wave of 64 lanes
@@ -1078,7 +1096,13 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
           form_foot(p, p.mass, p.gI, p.mu, xr[5 * (N + 1) + kk], lv[0], lv[1], lv[2],
                     1.0 - (double)con_[4 * j + q], AbW + FO<N>(kk, q, 0));
       }
-      bnd = dyn_bound<N>(p, xr, k, ph);
+      // ROB: row b of the disturbance table, the lane's own component, loaded here once
+      if constexpr (ROB) {
+        dacc = disturb_a<true>(a, b, ph);
+        bnd = dyn_bound<N, true>(p, xr, k, ph, dacc);
+      } else {
+        bnd = dyn_bound<N>(p, xr, k, ph);
+      }
     }
     if (!SOLVE) {
       sync_all();
@@ -1127,6 +1151,8 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
       // (a device weights table is not validated on the way in, unlike mpcq_params' P)
       if constexpr (ROB) {
         if (!(isfinite(P0X) && isfinite(P0f))) bad = 1;
+        // (nor a device disturbance table: an Inf would leave bnd infinite, not NaN)
+        if (ph >= 6 && !isfinite(dacc)) bad = 1;
       }
       int lgu = 0;  // l > u on an own row (osqp rejects the data)
       if constexpr (FUSED) {
@@ -3259,7 +3285,8 @@ hipError_t launch_t(bool fused, bool solve, const mpcq_params& p, const LaunchAr
   const bool rob = a.robots != nullptr && (fused || !solve);
   // the solving ROB kernels read both tables (mpcq_api.cpp launch_tables passes both or neither)
   if (rob && solve && !a.weights) return hipErrorInvalidValue;
-  if (!rob && a.weights) return hipErrorInvalidValue;
+  if (rob && !a.disturb) return hipErrorInvalidValue;
+  if (!rob && (a.weights || a.disturb)) return hipErrorInvalidValue;
   if (rob && !solve) hipLaunchKernelGGL((engine_kernel<N, true, false, false, true>), grid, block, 0, s, p, a);
   else if (rob && pol) hipLaunchKernelGGL((engine_kernel<N, true, true, true, true>), grid, block, 0, s, p, a);
   else if (rob) hipLaunchKernelGGL((engine_kernel<N, true, true, false, true>), grid, block, 0, s, p, a);

@@ -5,23 +5,27 @@
 #include "mpcq_internal.h"
 
 // A table of per-instance records on the device -- the robots' constants (mpcq_set_robots,
-// mpcq_session_set_robots) or the cost weights (mpcq_set_weights, mpcq_session_set_weights):
+// mpcq_session_set_robots), the cost weights (mpcq_set_weights, mpcq_session_set_weights) or the
+// disturbance accelerations (mpcq_set_disturbance, mpcq_session_set_disturbance):
 // count > 0 = in force.
 template <class R>
 struct Table {
-  static_assert(sizeof(R) == 128, "a table record is 16 doubles");
+  static_assert(sizeof(R) % 64 == 0, "a table record is 8 or 16 doubles");
   R* dev = nullptr;
   int64_t cap = 0;
   int64_t count = 0;
 };
 using RobotTable = Table<mpcq_robot>;
 using WeightsTable = Table<mpcq_weights>;
-// The engine's ROB kernels read both tables.  Where only one is set, the other is one of these:
-// a device table of the context's own values, made at the first launch that needs it and grown
-// with the batch (the context's mpcq_params never change after mpcq_create).
+using DisturbTable = Table<mpcq_disturbance>;
+// The engine's ROB kernels read all three tables.  Where a table is not set beside one that is,
+// it is one of these: a device table of the context's own values (the disturbance's: zeros),
+// made at the first launch that needs it and grown with the batch (the context's mpcq_params
+// never change after mpcq_create).
 struct FillTables {
   RobotTable robots;
   WeightsTable weights;
+  DisturbTable disturb;
 };
 
 struct mpcq_ctx {
@@ -61,6 +65,7 @@ struct mpcq_ctx {
   int32_t* sl_count = nullptr;
   RobotTable robots;  // mpcq_set_robots
   WeightsTable weights;  // mpcq_set_weights
+  DisturbTable disturb;  // mpcq_set_disturbance
   FillTables fill;
 };
 
@@ -94,11 +99,14 @@ int ensure_work(mpcq_ctx* c, int64_t B, double** out);
 // queued launch that still reads the old values; from a host pointer the call then blocks.
 int set_table(mpcq_ctx* c, RobotTable& t, int64_t count, const mpcq_robot* robots, uint32_t flags);
 int set_table(mpcq_ctx* c, WeightsTable& t, int64_t count, const mpcq_weights* weights, uint32_t flags);
-// The tables a fused launch of `batch` instances reads: both null where neither is set (the
-// kernels of a launch without a table), else both not null, the missing one from `fill`.
-// MPCQ_E_INVALID, and nothing to launch, where a table in force is shorter than the batch.
-int launch_tables(mpcq_ctx* c, const RobotTable& robots, const WeightsTable& weights, FillTables& fill, int64_t batch,
-                  const mpcq_robot** r, const mpcq_weights** w);
+int set_table(mpcq_ctx* c, DisturbTable& t, int64_t count, const mpcq_disturbance* rows, uint32_t flags);
+// The tables a formulating launch of `batch` instances reads, into a->robots / weights /
+// disturb: all null where none is set (the kernels of a launch without a table), else all not
+// null, the missing ones from `fill`.  MPCQ_E_INVALID, and nothing to launch, where a table in
+// force is shorter than the batch.  weights null: a formulation-only launch, which has no P --
+// a->weights stays null, and a weights table in force is not looked at.
+int launch_tables(mpcq_ctx* c, const RobotTable& robots, const WeightsTable* weights, const DisturbTable& disturb,
+                  FillTables& fill, int64_t batch, LaunchArgs* a);
 void free_tables(FillTables& fill);
 // The caller's parameters (null: the defaults) into *out, or MPCQ_E_INVALID.
 int swing_params(const mpcq_swing_params* sp, mpcq_swing_params* out);
@@ -107,6 +115,7 @@ int monitor_params(const mpcq_monitor_params* mp, mpcq_monitor_params* out);
 int scenario_params(const mpcq_scenario_params* sc, mpcq_scenario_params* out);
 int channel_params(const mpcq_channel_params* ch, mpcq_channel_params* out);
 int estimator_params(const mpcq_estimator_params* ep, mpcq_estimator_params* out);
+int disturb_params(const mpcq_disturb_params* dp, mpcq_disturb_params* out);
 // The gait stage's parameters (no defaults: n_gaits is the caller's) and its library, validated:
 // *out, and the cycles packed into lib->lib / lib->period (the other fields of *lib zero).
 int gait_params(const mpcq_gait_params* gp, const double* cycles, mpcq_gait_params* out, GaitArgs* lib);

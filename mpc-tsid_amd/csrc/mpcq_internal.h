@@ -62,8 +62,13 @@ struct LaunchArgs {
   // instance like robots.  The ROB instantiations read both tables, so the host passes both or
   // neither: where one table is set and the other is not, the missing one is a device table of
   // the context's values (mpcq_api.cpp launch_tables).  Null with robots null.
-  // (Last, so that the other arguments keep their offsets.)
   const mpcq_weights* weights;
+  // [B] per-instance constant disturbance acceleration (mpcq_set_disturbance,
+  // mpcq_session_set_disturbance), indexed by the instance like robots; read by the formulation
+  // (dyn_bound) of the ROB instantiations, the formulation-only one included.  Passed with the
+  // other two tables or not at all; a table that is not set is one of zeros.
+  // (Last, so that the other arguments keep their offsets.)
+  const mpcq_disturbance* disturb;
 };
 constexpr int32_t kStatusSuspended = 100;  // (internal: the host loop resumes these)
 constexpr int64_t res_lanes(int N) { return 16 * (int64_t)((N + 3) & ~3); }
@@ -346,6 +351,29 @@ struct EstimateArgs {
   double* est;             // [B][12] out
 };
 hipError_t launch_estimate(const mpcq_estimator_params& ep, const EstimateArgs& a, hipStream_t s);
+
+// Disturbance stage (mpcq_disturb.hip); semantics and layouts in include/mpcq.h
+// (mpcq_disturb_step_batch, mpcq_session_enable_disturb).  Sixteen lanes per robot.
+struct DisturbArgs {
+  int64_t batch;
+  const int32_t* first;    // [B] or null: nonzero = a first tick
+  int all_first;           // every robot runs a first tick
+  const double* meas;      // [B][12]
+  const double* f_prev;    // [B][12]
+  const double* feet_prev; // [B][3][4], or null with fsteps
+  const double* fsteps;    // [B][20][13] (a session's tick): the feet are row 0's
+  const int32_t* failed;   // [B] or null: nonzero = the previous tick failed
+  // a session's tick: the previous tick's statuses, failed by the plant's rule (failed null)
+  const int32_t* status;      // [B] or null
+  const int32_t* plan_status; // [B]
+  const mpcq_robot* robots;// [B] or null: dflt
+  mpcq_robot dflt;
+  double dt, gravity;      // the context's
+  double* row;             // [B][MPCQ_DIST_ROW] in/out
+  mpcq_disturbance* dist;  // [B] out
+  double* resid;           // [B][6] out, or null
+};
+hipError_t launch_disturb(const mpcq_disturb_params& dp, const DisturbArgs& a, hipStream_t s);
 
 // Gait stage (mpcq_gait.hip); semantics and layouts in include/mpcq.h (mpcq_gait_roll_batch,
 // mpcq_session_enable_gait).  Thirty-two lanes per robot, lane r < 20 owns row r of its table.

@@ -1,6 +1,7 @@
 // mpcq_model.h — the MPC's own discrete step of the single rigid body, shared by the plant
-// (mpcq_plant.hip: solve3, under its MPCQ_PLANT_MODEL and MPCQ_PLANT_RIGID branches) and the
-// estimator (mpcq_estimator.hip: model_step, the filter's every propagation).
+// (mpcq_plant.hip: solve3, under its MPCQ_PLANT_MODEL and MPCQ_PLANT_RIGID branches), the
+// estimator (mpcq_estimator.hip: model_step, the filter's every propagation) and the disturbance
+// stage (mpcq_disturb.hip: model_step, the prediction its sample is taken against).
 //
 // Include after `#pragma clang fp contract(off)`: no contraction, every sum left to right in
 // the order written here (tests/plant_model.py restates it in numpy).

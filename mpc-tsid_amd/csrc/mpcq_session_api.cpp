@@ -26,7 +26,7 @@ enum { SP_WARM_X = MPCQ_SV_COUNT, SP_PLAN_STATUS, SP_INFO, SP_IN_STATE, SP_IN_LF
 enum { PP_QW_PREV = MPCQ_PV_COUNT, PP_COUNT };
 
 // The arrays of one kind of id: MPCQ_SV_* (the swing slots are null until
-// mpcq_session_enable_swing), MPCQ_PV_*, MPCQ_MV_*, MPCQ_CV_*, MPCQ_HV_*, MPCQ_EV_*, MPCQ_GV_*.
+// mpcq_session_enable_swing), MPCQ_PV_*, MPCQ_MV_*, MPCQ_CV_*, MPCQ_HV_*, MPCQ_EV_*, MPCQ_GV_*, MPCQ_DV_*.
 struct Group {
   const char *kind, *enable;  // "<kind> array %d needs mpcq_session_enable_<enable>"
   int named;                  // the ids the _read / _write / _device_ptr entry points reach
@@ -50,12 +50,15 @@ struct mpcq_session {
   Group hv{"channel", "channel", MPCQ_HV_COUNT};    // made by the first enable_channel
   Group ev{"estimator", "estimator", MPCQ_EV_COUNT};  // made by the first enable_estimator
   Group gv{"gait", "gait", MPCQ_GV_COUNT};            // made by the first enable_gait
+  Group dv{"disturb", "disturb", MPCQ_DV_COUNT};      // made by the first enable_disturb
   void* swing_mem = nullptr;                      // MPCQ_SV_SWING_REF, _SWING_STATE, _FRAME
   bool have_order = false;  // MPCQ_SV_ORDER holds the next solve's order (longest previous first)
   bool use_order = true;    // MPCQ_DISPATCH_ORDER=0 turns it off (A/B timing only; results are identical)
   bool resets = false;      // mpcq_session_reset was called: from then on the ticks consult MPCQ_SV_FIRST
   bool swing = false, plant = false, monitor = false, scenario = false, channel = false, estimator = false;
   bool gait = false;
+  bool disturb_on = false;  // the disturbance stage runs (mpcq_session_enable_disturb)
+  mpcq_disturb_params dp{};
   mpcq_gait_params gp{};
   mpcq::GaitArgs gait_lib{};  // the library in force, packed (period, lib; the launch fills the rest)
   mpcq_swing_params sp{};
@@ -67,6 +70,7 @@ struct mpcq_session {
   RobotTable robots;        // mpcq_session_set_robots (the session's own, not the context's)
   RobotTable plant_robots;  // mpcq_session_set_plant_robots
   WeightsTable weights;     // mpcq_session_set_weights (the controller's tuning: no snapshot holds it)
+  DisturbTable disturb;     // mpcq_session_set_disturbance (the controller's model: no snapshot holds it)
   FillTables fill;          // the table a ROB launch reads in place of the one that is not set
   mpcq_snapshot* fork_snap = nullptr;  // mpcq_session_fork's own, made on first use
 };
@@ -119,6 +123,10 @@ void channel_bytes(size_t B, size_t nb[MPCQ_HV_COUNT]) {  // CLOCK, OBS, F_CMD, 
 
 void estimator_bytes(size_t B, size_t nb[MPCQ_EV_COUNT]) {  // EST, ROW
   nb[MPCQ_EV_EST] = B * 96; nb[MPCQ_EV_ROW] = B * MPCQ_EST_ROW * 8;
+}
+
+void disturb_bytes(size_t B, size_t nb[MPCQ_DV_COUNT]) {  // DIST, ROW, RESID
+  nb[MPCQ_DV_DIST] = B * sizeof(mpcq_disturbance); nb[MPCQ_DV_ROW] = B * MPCQ_DIST_ROW * 8; nb[MPCQ_DV_RESID] = B * 48;
 }
 
 // n arrays of nb[i] bytes, each 256-B aligned, in one allocation zeroed on the context's
@@ -339,12 +347,14 @@ int mpcq_session_destroy(mpcq_session* s) {
     if (s->pv.mem) (void)hipFree(s->pv.mem);
     if (s->plant_robots.dev) (void)hipFree(s->plant_robots.dev);
     if (s->weights.dev) (void)hipFree(s->weights.dev);
+    if (s->disturb.dev) (void)hipFree(s->disturb.dev);
     mpcq::free_tables(s->fill);
     if (s->mv.mem) (void)hipFree(s->mv.mem);
     if (s->cv.mem) (void)hipFree(s->cv.mem);
     if (s->hv.mem) (void)hipFree(s->hv.mem);
     if (s->ev.mem) (void)hipFree(s->ev.mem);
     if (s->gv.mem) (void)hipFree(s->gv.mem);
+    if (s->dv.mem) (void)hipFree(s->dv.mem);
     (void)mpcq_session_snapshot_destroy(s->fork_snap);
   }
   delete s;
@@ -414,6 +424,32 @@ int mpcq_session_get_weights(mpcq_session* s, mpcq_weights* weights, uint32_t fl
   const hipError_t e = hipMemcpy(weights, h, nb, hipMemcpyHostToDevice);
   free(h);
   HIP_TRY(e);
+  return MPCQ_OK;
+}
+
+int mpcq_session_set_disturbance(mpcq_session* s, const mpcq_disturbance* table, uint32_t flags) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  return set_table(s->ctx, s->disturb, table ? s->B : 0, table, flags);
+}
+
+int mpcq_session_get_disturbance(mpcq_session* s, mpcq_disturbance* table, uint32_t flags) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  if (!table) return fail(MPCQ_E_INVALID, "table is NULL");
+  mpcq_ctx* c = s->ctx;
+  DeviceGuard g(c->device);
+  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
+  const size_t nb = (size_t)s->B * sizeof(mpcq_disturbance);
+  if (s->disturb.count) {
+    HIP_TRY(hipMemcpyAsync(table, s->disturb.dev, nb, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
+                           c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MPCQ_OK;
+  }
+  if (!dev) {  // (without a table: no disturbance)
+    memset(table, 0, nb);
+    return MPCQ_OK;
+  }
+  HIP_TRY(hipMemset(table, 0, nb));
   return MPCQ_OK;
 }
 
@@ -614,6 +650,34 @@ int mpcq_session_disable_estimator(mpcq_session* s) {
   return MPCQ_OK;
 }
 
+int mpcq_session_enable_disturb(mpcq_session* s, const mpcq_disturb_params* dp) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  mpcq_disturb_params P;
+  int rc = disturb_params(dp, &P);
+  if (rc) return rc;
+  DeviceGuard g(s->ctx->device);
+  if (!s->dv.mem) {  // the arrays, zero: every row invalid, no disturbance
+    size_t nb[MPCQ_DV_COUNT];
+    disturb_bytes((size_t)s->B, nb);
+    Group dv = s->dv;
+    rc = alloc_group(s->ctx, "the disturb arrays", MPCQ_DV_COUNT, nb, &dv.mem, dv.ptr, dv.bytes);
+    if (rc) return rc;
+    s->dv = dv;
+  } else if (!s->disturb_on) {  // the rings missed the ticks since the disable: every row invalid again
+    for (int w = 0; w < MPCQ_DV_COUNT; ++w)
+      HIP_TRY(hipMemsetAsync(s->dv.ptr[w], 0, s->dv.bytes[w], s->ctx->stream));
+  }
+  s->dp = P;
+  s->disturb_on = true;
+  return MPCQ_OK;
+}
+
+int mpcq_session_disable_disturb(mpcq_session* s) {
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  s->disturb_on = false;
+  return MPCQ_OK;
+}
+
 int mpcq_session_enable_gait(mpcq_session* s, const mpcq_gait_params* gp, const double* cycles) {
   if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
   mpcq_gait_params P;
@@ -759,6 +823,24 @@ int tick_estimate(mpcq_session* s, Tick& t) {
   return MPCQ_OK;
 }
 
+// The disturbance stage: MPCQ_DV_DIST from what the planner is about to take as its state
+// (t.plan_state, which stays), the previous tick's f0, feet and statuses as they stand before
+// this tick's planner, and the model's robots; it takes the first flags as the planner will.
+int tick_disturb(mpcq_session* s, const Tick& t) {
+  mpcq_ctx* c = s->ctx;
+  const Group &v = s->sv, &d = s->dv;
+  mpcq::DisturbArgs a{};
+  a.batch = s->B; a.first = t.first_k; a.all_first = t.k == 0; a.meas = t.plan_state;
+  a.f_prev = v.d(MPCQ_SV_F0); a.fsteps = v.d(MPCQ_SV_FSTEPS);
+  a.status = v.i(MPCQ_SV_STATUS); a.plan_status = v.i(SP_PLAN_STATUS);
+  a.robots = s->robots.count ? s->robots.dev : nullptr;
+  mpcq_default_robot(&c->p, &a.dflt);
+  a.dt = c->p.dt; a.gravity = c->p.gravity;
+  a.row = d.d(MPCQ_DV_ROW); a.dist = (mpcq_disturbance*)d.ptr[MPCQ_DV_DIST]; a.resid = d.d(MPCQ_DV_RESID);
+  HIP_TRY(mpcq::launch_disturb(s->dp, a, c->stream));
+  return MPCQ_OK;
+}
+
 // The channel's actuation model: MPCQ_HV_F_CMD from this tick's (and earlier) MPCQ_SV_F0.
 int tick_actuate(mpcq_session* s) {
   const Group& h = s->hv;
@@ -814,7 +896,12 @@ int tick_solve(mpcq_session* s, const Tick& t) {
   // longest-first by the previous tick's iteration counts (a tick k == 0 restarts cold)
   if (t.k == 0) s->have_order = false;
   a.order = s->have_order && s->use_order ? v.i(MPCQ_SV_ORDER) : nullptr;
-  int rc = mpcq::launch_tables(c, s->robots, s->weights, s->fill, s->B, &a.robots, &a.weights);
+  // a compensating disturbance stage: its estimate, ahead of the user's table
+  DisturbTable est;
+  est.dev = (mpcq_disturbance*)s->dv.ptr[MPCQ_DV_DIST];
+  est.cap = est.count = s->B;
+  const bool comp = s->disturb_on && s->dp.compensate != 0;
+  int rc = mpcq::launch_tables(c, s->robots, &s->weights, comp ? est : s->disturb, s->fill, s->B, &a);
   if (rc) return rc;
   a.first = t.first_k;
   rc = ensure_work(c, s->B, &a.work);
@@ -911,7 +998,7 @@ int tick_swing(mpcq_session* s) {
   return MPCQ_OK;
 }
 
-// One tick: its stages in stream order ([scenario] -> inputs -> [observe] -> [estimate] -> planner (with [gait]
+// One tick: its stages in stream order ([scenario] -> inputs -> [observe] -> [estimate] -> [disturb] -> planner (with [gait]
 // between its first tick's footsteps-only pass and its main pass) -> solve ->
 // retrieve -> [actuate -> plant] -> [monitor] -> order -> [swing] -> [auto-reset]).
 int session_tick(mpcq_session* s, int k, const double* state, const double* l_feet, const double* v_ref,
@@ -931,6 +1018,7 @@ int session_tick(mpcq_session* s, int k, const double* state, const double* l_fe
   if (!rc && !v_ref) t.v_ref = s->cv.d(MPCQ_CV_V_REF);
   if (!rc && s->channel) rc = tick_observe(s, t);
   if (!rc && s->estimator) rc = tick_estimate(s, t);
+  if (!rc && s->disturb_on) rc = tick_disturb(s, t);
   if (!rc) rc = tick_plan(s, t);
   if (!rc) rc = tick_solve(s, t);
   if (!rc) rc = tick_retrieve(s, t);
@@ -1031,6 +1119,10 @@ int mpcq_session_estimator_read(mpcq_session* s, int what, void* dst, uint32_t f
   return group_read(s, &mpcq_session::ev, what, dst, flags);
 }
 
+int mpcq_session_disturb_read(mpcq_session* s, int what, void* dst, uint32_t flags) {
+  return group_read(s, &mpcq_session::dv, what, dst, flags);
+}
+
 int mpcq_session_gait_read(mpcq_session* s, int what, void* dst, uint32_t flags) {
   return group_read(s, &mpcq_session::gv, what, dst, flags);
 }
@@ -1057,6 +1149,10 @@ int mpcq_session_channel_device_ptr(mpcq_session* s, int what, void** out) {
 
 int mpcq_session_estimator_device_ptr(mpcq_session* s, int what, void** out) {
   return group_device_ptr(s, &mpcq_session::ev, what, out);
+}
+
+int mpcq_session_disturb_device_ptr(mpcq_session* s, int what, void** out) {
+  return group_device_ptr(s, &mpcq_session::dv, what, out);
 }
 
 int mpcq_session_gait_device_ptr(mpcq_session* s, int what, void** out) {
@@ -1088,12 +1184,13 @@ namespace {
 
 // The parts of a snapshot, in the blob's order; each is one allocation (alloc_group).
 enum { G_MAIN, G_SWING, G_PLANT, G_MONITOR, G_SCENARIO, G_ROBOTS, G_PLANT_ROBOTS, G_CHANNEL, G_ESTIMATOR,
-       G_GAIT, G_COUNT };
+       G_GAIT, G_DISTURB, G_COUNT };
 const char* const kPartName[G_COUNT] = {"the snapshot's session arrays", "the snapshot's swing arrays",
                                         "the snapshot's plant arrays", "the snapshot's monitor arrays",
                                         "the snapshot's scenario arrays", "the snapshot's robots table",
                                         "the snapshot's plant robots table", "the snapshot's channel arrays",
-                                        "the snapshot's estimator row", "the snapshot's gait rows"};
+                                        "the snapshot's estimator row", "the snapshot's gait rows",
+                                        "the snapshot's disturb rows"};
 
 // What a snapshot's allocations follow from, with the context's N.
 struct SnapShape {
@@ -1105,6 +1202,7 @@ struct SnapShape {
   bool ev = false;              // the estimator's row (self-describing: no parameter travels)
   bool gv = false;              // the gait stage's rows, indices into a library of
   int n_gaits = 0;              // this many cycles (the library itself is configuration: not held)
+  bool dv = false;              // the disturbance stage's row (self-describing, as the estimator's)
 };
 
 }  // namespace
@@ -1131,6 +1229,7 @@ SnapShape shape_of(const mpcq_session* s) {
   sh.ev = s->ev.mem;
   sh.gv = s->gv.mem;
   if (sh.gv) sh.n_gaits = s->gp.n_gaits;
+  sh.dv = s->dv.mem;
   return sh;
 }
 
@@ -1163,6 +1262,7 @@ void snap_sizes(const SnapShape& sh, int N, size_t nb[G_COUNT][SP_COUNT]) {
     nb[G_ESTIMATOR][MPCQ_EV_EST] = 0;  // (derived: every tick rewrites it before anything reads it)
   }
   if (sh.gv) nb[G_GAIT][MPCQ_GV_STATE] = B * 16;
+  if (sh.dv) nb[G_DISTURB][MPCQ_DV_ROW] = B * MPCQ_DIST_ROW * 8;  // (MPCQ_DV_DIST, _RESID: derived)
 }
 
 // The session's arrays seen as a snapshot's parts (the arrays a snapshot does not hold: null).
@@ -1186,6 +1286,7 @@ void session_parts(const mpcq_session* s, Group out[G_COUNT]) {
     for (int w = 0; w < MPCQ_HV_COUNT; ++w) { out[G_CHANNEL].ptr[w] = s->hv.ptr[w]; out[G_CHANNEL].bytes[w] = s->hv.bytes[w]; }
   if (s->ev.mem) { out[G_ESTIMATOR].ptr[MPCQ_EV_ROW] = s->ev.ptr[MPCQ_EV_ROW]; out[G_ESTIMATOR].bytes[MPCQ_EV_ROW] = s->ev.bytes[MPCQ_EV_ROW]; }
   if (s->gv.mem) { out[G_GAIT].ptr[MPCQ_GV_STATE] = s->gv.ptr[MPCQ_GV_STATE]; out[G_GAIT].bytes[MPCQ_GV_STATE] = s->gv.bytes[MPCQ_GV_STATE]; }
+  if (s->dv.mem) { out[G_DISTURB].ptr[MPCQ_DV_ROW] = s->dv.ptr[MPCQ_DV_ROW]; out[G_DISTURB].bytes[MPCQ_DV_ROW] = s->dv.bytes[MPCQ_DV_ROW]; }
 }
 
 // One array of a snapshot (a) next to its counterpart (b; null without one), in the blob's order.
@@ -1195,7 +1296,7 @@ struct SnapItem {
   bool rows;  // per-robot rows (all but MPCQ_MV_TOTALS)
 };
 
-// The listing's bound, a constant of its own: every array of every part (50 with every group
+// The listing's bound, a constant of its own: every array of every part (51 with every group
 // enabled, MPCQ_MV_TOTALS among them, which is listed and never gathered).  A restore gathers
 // them kGatherMax to a launch.
 constexpr int kListMax = 64;
@@ -1258,6 +1359,7 @@ const char* shape_difference(const SnapShape& a, const SnapShape& b, bool batch_
   if (a.ev != b.ev) return "the estimator arrays exist on one side only";
   if (a.gv != b.gv) return "the gait arrays exist on one side only";
   if (a.n_gaits != b.n_gaits) return "the gait library sizes differ (the rows index another library)";
+  if (a.dv != b.dv) return "the disturb arrays exist on one side only";
   return nullptr;
 }
 
@@ -1414,15 +1516,22 @@ struct BlobHeader {
   // of the library its rows index
   int64_t gait_bytes;
   int32_t n_gaits, pad;
+  // format version 5 only, behind the 144 bytes of version 4: the eleventh part
+  int64_t disturb_bytes;
+  int64_t pad5;
 };
-static_assert(sizeof(BlobHeader) == 144 && offsetof(BlobHeader, gait_bytes) == 128 && G_CHANNEL == 7 &&
-                  G_ESTIMATOR == 8 && G_GAIT == 9 && G_COUNT == 10,
-              "the blob's header is 128 bytes, 144 from format version 4 on");
-size_t header_bytes(uint32_t version) { return version >= 4 ? sizeof(BlobHeader) : offsetof(BlobHeader, gait_bytes); }
+static_assert(sizeof(BlobHeader) == 160 && offsetof(BlobHeader, gait_bytes) == 128 &&
+                  offsetof(BlobHeader, disturb_bytes) == 144 && G_CHANNEL == 7 && G_ESTIMATOR == 8 && G_GAIT == 9 &&
+                  G_DISTURB == 10 && G_COUNT == 11,
+              "the blob's header is 128 bytes, 144 in format version 4, 160 from version 5 on");
+size_t header_bytes(uint32_t version) {
+  return version >= 5 ? sizeof(BlobHeader) : version == 4 ? offsetof(BlobHeader, disturb_bytes)
+                                                          : offsetof(BlobHeader, gait_bytes);
+}
 
 // The header's byte count of part gi.
 int64_t& part_bytes(BlobHeader& h, int gi) {
-  return gi == G_GAIT ? h.gait_bytes : gi == G_ESTIMATOR ? h.estimator_bytes : gi == G_CHANNEL ? h.channel_bytes
+  return gi == G_DISTURB ? h.disturb_bytes : gi == G_GAIT ? h.gait_bytes : gi == G_ESTIMATOR ? h.estimator_bytes : gi == G_CHANNEL ? h.channel_bytes
                                                                                                 : h.group_bytes[gi];
 }
 const char kMagic[8] = {'M', 'P', 'C', 'Q', 'S', 'N', 'P', '1'};
@@ -1432,10 +1541,10 @@ void blob_header(const SnapShape& sh, int N, bool have_order, bool resets, BlobH
   snap_sizes(sh, N, nb);
   memset(h, 0, sizeof(*h));
   memcpy(h->magic, kMagic, 8);
-  h->version = sh.gv ? 4 : sh.ev ? 3 : sh.hv ? 2 : 1; h->N = N; h->B = sh.B; h->k_mpc = sh.k_mpc;
+  h->version = sh.dv ? 5 : sh.gv ? 4 : sh.ev ? 3 : sh.hv ? 2 : 1; h->N = N; h->B = sh.B; h->k_mpc = sh.k_mpc;
   h->flags = (have_order ? 1u : 0u) | (resets ? 2u : 0u) | (sh.k_mpc > 0 ? 4u : 0u) | (sh.pv ? 8u : 0u) |
              (sh.mv ? 16u : 0u) | (sh.cv ? 32u : 0u) | (sh.robots ? 64u : 0u) | (sh.plant_robots ? 128u : 0u) |
-             (sh.hv ? 256u : 0u) | (sh.ev ? 512u : 0u) | (sh.gv ? 1024u : 0u);
+             (sh.hv ? 256u : 0u) | (sh.ev ? 512u : 0u) | (sh.gv ? 1024u : 0u) | (sh.dv ? 2048u : 0u);
   h->delay = sh.delay; h->latency = sh.latency;
   h->n_gaits = sh.n_gaits;
   h->total = (int64_t)header_bytes(h->version);
@@ -1543,16 +1652,17 @@ int mpcq_session_snapshot_import(mpcq_session* s, mpcq_snapshot* p, const void* 
   if (bytes < (int64_t)header_bytes(1)) return fail(MPCQ_E_INVALID, "%lld bytes are less than a header", (long long)bytes);
   memcpy(&h, src, header_bytes(1));
   if (memcmp(h.magic, kMagic, 8) != 0) return fail(MPCQ_E_INVALID, "not a snapshot blob (magic)");
-  if (h.version < 1 || h.version > 4)
-    return fail(MPCQ_E_INVALID, "blob format version %u, this library reads 1 to 4", h.version);
+  if (h.version < 1 || h.version > 5)
+    return fail(MPCQ_E_INVALID, "blob format version %u, this library reads 1 to 5", h.version);
   if (bytes < (int64_t)header_bytes(h.version))
     return fail(MPCQ_E_INVALID, "%lld bytes are less than a version-%u header", (long long)bytes, h.version);
   memcpy(&h, src, header_bytes(h.version));
   if (h.N != c->N) return fail(MPCQ_E_INVALID, "the blob is of a context with N = %d, this one has N = %d", h.N, c->N);
-  const bool chan = h.flags & 256u, est = h.flags & 512u, gait = h.flags & 1024u;
-  if (h.B < 1 || h.B > (int64_t)0x7fffffff || h.k_mpc < 0 || h.k_mpc > 65536 || (h.flags >> 11) ||
-      ((h.flags & 4u) != 0) != (h.k_mpc > 0) || h.version != (gait ? 4u : est ? 3u : chan ? 2u : 1u) ||
+  const bool chan = h.flags & 256u, est = h.flags & 512u, gait = h.flags & 1024u, dist = h.flags & 2048u;
+  if (h.B < 1 || h.B > (int64_t)0x7fffffff || h.k_mpc < 0 || h.k_mpc > 65536 || (h.flags >> 12) ||
+      ((h.flags & 4u) != 0) != (h.k_mpc > 0) || h.version != (dist ? 5u : gait ? 4u : est ? 3u : chan ? 2u : 1u) ||
       (!est && h.estimator_bytes != 0) || (gait && (h.n_gaits < 1 || h.n_gaits > MPCQ_GAIT_MAX || h.pad != 0)) ||
+      (!gait && (h.n_gaits != 0 || h.pad != 0)) || h.pad5 != 0 ||
       (chan ? h.delay < 0 || h.delay > MPCQ_CHANNEL_MAX_DELAY || h.latency < 0 || h.latency > MPCQ_CHANNEL_MAX_LATENCY
             : h.delay != 0 || h.latency != 0 || h.channel_bytes != 0))
     return fail(MPCQ_E_INVALID, "the blob's header is inconsistent (B %lld, k_mpc %d, flags %#x)", (long long)h.B,
@@ -1564,6 +1674,7 @@ int mpcq_session_snapshot_import(mpcq_session* s, mpcq_snapshot* p, const void* 
   sh.hv = chan; sh.delay = h.delay; sh.latency = h.latency;
   sh.ev = est;
   sh.gv = gait; sh.n_gaits = gait ? h.n_gaits : 0;
+  sh.dv = dist;
   BlobHeader want;
   blob_header(sh, c->N, h.flags & 1u, h.flags & 2u, &want);
   for (int gi = 0; gi < G_COUNT; ++gi) {

@@ -12,6 +12,9 @@ Public surface:
                     (Engine.set_robots, Session.set_robots)
   weights           per-instance cost weights, the diagonal of P (Engine.set_weights,
                     Session.set_weights): a tuning sweep in one launch
+  disturbances      per-instance constant disturbance accelerations in the model's dynamics
+                    (Engine.set_disturbance, Session.set_disturbance): pushes sampled over one
+                    state in one launch, a known payload or bias compensated
   Swing             batched swing-foot trajectories between two ticks (Session.enable_swing)
   Plant             batched rigid-body plant under the stance feet's forces: true robots that
                     differ from the model, external pushes (Session.enable_plant)
@@ -25,6 +28,9 @@ Public surface:
                     state feedback with dropped frames in front of the planner, delayed, scaled,
                     noisy forces in front of the plant (Session.enable_channel); mpcq.channel
                     restates the draws on the host, bit for bit
+  Disturb           a per-robot disturbance observer in front of the solve: the acceleration the
+                    controller's model lacks (an unknown payload, a steady push), estimated from
+                    consecutive states and handed to the solve (Session.enable_disturb)
   Estimator         the controller's side of the channel, on the device: a per-robot Kalman filter
                     on the MPC's own model that compensates the measurement's delay through the
                     recorded forces and footholds (Session.enable_estimator)
@@ -49,7 +55,7 @@ from ._lib import (FLAG_ASYNC, FLAG_DEVICE_PTRS, FLAG_ORDER_BY_CLASS, MODE_SETUP
                    STATUS_DUAL_INFEASIBLE_INACCURATE, STATUS_BAD_BOUNDS, MpcqError,
                    Params, build, build_info, default_params, lib, source_sha, supported_horizons,
                    SV_FRAME, SV_SWING_REF, SV_SWING_STATE, SWING_STATE, SwingParams, default_swing_params,
-                   Robot, default_robot, Weights, default_weights,
+                   Robot, default_robot, Weights, default_weights, Disturbance,
                    PLANT_MODEL, PLANT_RIGID, PV_F_EFF, PV_STATE_END, PV_WRENCH, PlantParams, default_plant_params,
                    DONE_HEIGHT, DONE_NONFINITE, DONE_SOLVER, DONE_TILT, DONE_TIMEOUT, MV_DONE, MV_EP, MV_EP_TICKS,
                    MV_EPISODES, MV_LAST, MV_TOTALS, TRACE, MonitorParams, default_monitor_params,
@@ -59,14 +65,19 @@ from ._lib import (FLAG_ASYNC, FLAG_DEVICE_PTRS, FLAG_ORDER_BY_CLASS, MODE_SETUP
                    CHANNEL_MAX_LATENCY, ChannelParams, default_channel_params,
                    EV_EST, EV_ROW, EST_CLOCK, EST_P, EST_POST, EST_PREV, EST_RING, EST_ROW, EST_SLOTS,
                    ESTIMATOR_MAX_F_LAG, ESTIMATOR_MAX_LAG, EstimatorParams, default_estimator_params,
+                   DV_DIST, DV_ROW, DV_RESID, DIST_D, DIST_PREV, DIST_CLOCK, DIST_RING, DIST_SLOTS, DIST_ROW,
+                   DISTURB_MAX_F_LAG, DisturbParams, default_disturb_params,
                    GV_STATE, GAIT_MAX, GAIT_MANUAL, GAIT_BY_SPEED, GaitParams, default_gait_params)
 from . import channel  # noqa: F401
 from .channel import Channel  # noqa: F401
 from . import estimator  # noqa: F401
 from .estimator import Estimator  # noqa: F401
+from . import disturb  # noqa: F401
+from .disturb import Disturb  # noqa: F401
 from . import gait  # noqa: F401
 from .gait import Gait  # noqa: F401
-from .engine import ROBOT_DTYPE, WEIGHTS_DTYPE, Engine, dims, pattern, robots, weights  # noqa: F401
+from .engine import (DISTURBANCE_DTYPE, ROBOT_DTYPE, WEIGHTS_DTYPE, Engine, dims, disturbances, pattern,  # noqa: F401
+                     robots, weights)
 from .monitor import Monitor  # noqa: F401
 from .plant import Plant  # noqa: F401
 from . import scenario  # noqa: F401

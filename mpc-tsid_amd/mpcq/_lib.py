@@ -82,6 +82,11 @@ CHANNEL_MAX_DELAY, CHANNEL_MAX_LATENCY = 8, 4
 # (MPCQ_EST_*), the greatest lags
 EV_EST, EV_ROW = range(2)
 EST_POST, EST_PREV, EST_P, EST_CLOCK, EST_RING, EST_SLOTS, EST_ROW = 0, 12, 24, 42, 44, 12, 332
+# the disturbance stage: a session's disturb arrays (MPCQ_DV_*), its row's offsets in doubles
+# (MPCQ_DIST_*), the greatest force lag
+DV_DIST, DV_ROW, DV_RESID = range(3)
+DIST_D, DIST_PREV, DIST_CLOCK, DIST_RING, DIST_SLOTS, DIST_ROW = 0, 6, 18, 20, 5, 80
+DISTURB_MAX_F_LAG = 4
 ESTIMATOR_MAX_LAG, ESTIMATOR_MAX_F_LAG = 8, 4
 # the gait stage: a session's gait array (MPCQ_GV_*), the library's bound, the selection modes
 GV_STATE = 0
@@ -103,6 +108,9 @@ EXPORTS = ("mpcq_abi_version", "mpcq_default_params", "mpcq_dims", "mpcq_pattern
            "mpcq_session_enable_swing",
            "mpcq_default_robot", "mpcq_set_robots", "mpcq_session_set_robots", "mpcq_session_get_robots",
            "mpcq_default_weights", "mpcq_set_weights", "mpcq_session_set_weights", "mpcq_session_get_weights",
+           "mpcq_set_disturbance", "mpcq_session_set_disturbance", "mpcq_session_get_disturbance",
+           "mpcq_default_disturb_params", "mpcq_disturb_step_batch", "mpcq_session_enable_disturb",
+           "mpcq_session_disable_disturb", "mpcq_session_disturb_read", "mpcq_session_disturb_device_ptr",
            "mpcq_session_reset",
            "mpcq_default_plant_params", "mpcq_plant_step_batch", "mpcq_session_enable_plant",
            "mpcq_session_disable_plant", "mpcq_session_set_plant_robots", "mpcq_session_set_wrench",
@@ -288,6 +296,19 @@ class EstimatorParams(C.Structure):
     ]
 
 
+class DisturbParams(C.Structure):
+    """struct mpcq_disturb_params (include/mpcq.h)."""
+
+    _fields_ = [
+        ("alpha", C.c_double * 6),
+        ("d_max", C.c_double * 6),
+        ("f_lag", C.c_int32),
+        ("compensate", C.c_int32),
+        ("skip_repeats", C.c_int32),
+        ("reserved", C.c_int32 * 5),
+    ]
+
+
 class GaitParams(C.Structure):
     """struct mpcq_gait_params (include/mpcq.h)."""
 
@@ -322,6 +343,15 @@ class Weights(C.Structure):
         ("state", C.c_double * 12),
         ("force", C.c_double),
         ("reserved", C.c_double * 3),
+    ]
+
+
+class Disturbance(C.Structure):
+    """struct mpcq_disturbance (include/mpcq.h): the per-instance constant disturbance acceleration."""
+
+    _fields_ = [
+        ("a", C.c_double * 6),
+        ("reserved", C.c_double * 2),
     ]
 
 
@@ -438,6 +468,22 @@ def lib():
     L.mpcq_session_set_weights.argtypes = [vp, vp, C.c_uint32]
     L.mpcq_session_get_weights.argtypes = [vp, vp, C.c_uint32]
     for name in ("mpcq_set_weights", "mpcq_session_set_weights", "mpcq_session_get_weights"):
+        getattr(L, name).restype = C.c_int
+    L.mpcq_set_disturbance.argtypes = [vp, C.c_int64, vp, C.c_uint32]
+    L.mpcq_session_set_disturbance.argtypes = [vp, vp, C.c_uint32]
+    L.mpcq_session_get_disturbance.argtypes = [vp, vp, C.c_uint32]
+    for name in ("mpcq_set_disturbance", "mpcq_session_set_disturbance", "mpcq_session_get_disturbance"):
+        getattr(L, name).restype = C.c_int
+    DP = C.POINTER(DisturbParams)
+    L.mpcq_default_disturb_params.argtypes = [DP]
+    L.mpcq_default_disturb_params.restype = None
+    L.mpcq_disturb_step_batch.argtypes = [vp, DP, C.c_int64, vp, C.c_int] + [vp] * 8 + [C.c_uint32]
+    L.mpcq_session_enable_disturb.argtypes = [vp, DP]
+    L.mpcq_session_disable_disturb.argtypes = [vp]
+    L.mpcq_session_disturb_read.argtypes = [vp, C.c_int, vp, C.c_uint32]
+    L.mpcq_session_disturb_device_ptr.argtypes = [vp, C.c_int, C.POINTER(vp)]
+    for name in ("mpcq_disturb_step_batch", "mpcq_session_enable_disturb", "mpcq_session_disable_disturb",
+                 "mpcq_session_disturb_read", "mpcq_session_disturb_device_ptr"):
         getattr(L, name).restype = C.c_int
     L.mpcq_session_set_plant_robots.argtypes = [vp, vp, C.c_uint32]
     L.mpcq_session_set_wrench.argtypes = [vp, vp, C.c_uint32]
@@ -678,6 +724,25 @@ def default_estimator_params(**overrides) -> EstimatorParams:
             v = [v] * len(cur) if not hasattr(v, "__len__") else list(v)
             if len(v) != len(cur):
                 raise ValueError(f"estimator parameter {k} takes {len(cur)} values")
+            v = type(cur)(*v)
+        setattr(p, k, v)
+    return p
+
+
+def default_disturb_params(**overrides) -> DisturbParams:
+    """mpcq_default_disturb_params (alpha 0.2, d_max 5 m/s^2 and 30 rad/s^2, f_lag 0, compensate 1,
+    skip_repeats 1: starting values, not tuned); an array field takes a sequence of its length,
+    or one number for every entry."""
+    p = DisturbParams()
+    lib().mpcq_default_disturb_params(C.byref(p))
+    for k, v in overrides.items():
+        if not hasattr(p, k):
+            raise AttributeError(f"unknown disturb parameter {k}")
+        cur = getattr(p, k)
+        if hasattr(cur, "__len__"):
+            v = [v] * len(cur) if not hasattr(v, "__len__") else list(v)
+            if len(v) != len(cur):
+                raise ValueError(f"disturb parameter {k} takes {len(cur)} values")
             v = type(cur)(*v)
         setattr(p, k, v)
     return p

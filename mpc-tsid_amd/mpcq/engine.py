@@ -108,6 +108,32 @@ def _weights_table(table, count=None):
     return np.ascontiguousarray(table)
 
 
+# numpy mirror of struct mpcq_disturbance (L.Disturbance)
+DISTURBANCE_DTYPE = np.dtype([("a", np.float64, (6,)), ("reserved", np.float64, (2,))])
+
+
+def disturbances(B: int, lin=None, ang=None):
+    """A table of per-instance constant disturbance accelerations for ``Engine.set_disturbance`` /
+    ``Session.set_disturbance``: a contiguous (B,) array of DISTURBANCE_DTYPE.  lin [m/s^2] and
+    ang [rad/s^2]: a scalar, (3,) or (B,3), in the instance's xref frame; None: zero."""
+    B = int(B)
+    out = np.zeros(B, DISTURBANCE_DTYPE)
+    out["a"][:, :3] = np.broadcast_to(np.asarray(0.0 if lin is None else lin, np.float64), (B, 3))
+    out["a"][:, 3:] = np.broadcast_to(np.asarray(0.0 if ang is None else ang, np.float64), (B, 3))
+    return out
+
+
+def _disturbance_table(table, count=None):
+    """(B,) DISTURBANCE_DTYPE, contiguous, from such an array or a ctypes array of L.Disturbance."""
+    if not isinstance(table, np.ndarray):
+        table = np.frombuffer(bytes(table), DISTURBANCE_DTYPE)
+    if table.dtype != DISTURBANCE_DTYPE or table.ndim != 1:
+        raise ValueError("a disturbance table is a (B,) array of mpcq.DISTURBANCE_DTYPE (mpcq.disturbances())")
+    if count is not None and table.shape[0] != count:
+        raise ValueError(f"expected {count} disturbance rows, got {table.shape[0]}")
+    return np.ascontiguousarray(table)
+
+
 class Engine:
     """One HIP context (device, horizon N, parameters)."""
 
@@ -121,6 +147,7 @@ class Engine:
         self.lock = threading.RLock()
         self.has_robots = False  # whether a per-robot table is in force (set_robots / set_robots_device)
         self.has_weights = False  # whether a weights table is in force (set_weights / set_weights_device)
+        self.has_disturbance = False  # the same for set_disturbance / set_disturbance_device
         h = C.c_void_p()
         L.check(L.lib().mpcq_create(self.device, self.n_steps, C.byref(self.params), C.byref(h)))
         self._h = h
@@ -302,6 +329,24 @@ class Engine:
         stream, not validated).  ``count`` 0 or a null ``ptr`` clears the table."""
         self._call("mpcq_set_weights", self._h, int(count), C.c_void_p(ptr) if ptr else None, L.FLAG_DEVICE_PTRS)
         self.has_weights = bool(ptr) and int(count) > 0
+
+    def set_disturbance(self, table):
+        """Per-instance constant disturbance acceleration (mpcq_set_disturbance): the model of
+        instance b of every later formulate / solve carries ``table[b]`` (``mpcq.disturbances()``)
+        beside gravity through its whole horizon, in the instance's xref frame.  None clears it."""
+        if table is None:
+            self._call("mpcq_set_disturbance", self._h, 0, None, 0)
+            self.has_disturbance = False
+            return
+        t = _disturbance_table(table)
+        self._call("mpcq_set_disturbance", self._h, t.shape[0], _p(t), 0)
+        self.has_disturbance = t.shape[0] > 0
+
+    def set_disturbance_device(self, ptr: int, count: int):
+        """The same from ``count`` mpcq_disturbance records in device memory (copied on the
+        engine's stream, not validated).  ``count`` 0 or a null ``ptr`` clears the table."""
+        self._call("mpcq_set_disturbance", self._h, int(count), C.c_void_p(ptr) if ptr else None, L.FLAG_DEVICE_PTRS)
+        self.has_disturbance = bool(ptr) and int(count) > 0
 
     def set_robots_device(self, ptr: int, count: int):
         """The same from ``count`` mpcq_robot records in device memory (copied on the engine's

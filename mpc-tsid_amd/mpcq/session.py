@@ -22,7 +22,8 @@ import struct
 import numpy as np
 
 from . import _lib as L
-from .engine import ROBOT_DTYPE, WEIGHTS_DTYPE, Engine, _robot_table, _weights_table
+from .engine import (DISTURBANCE_DTYPE, ROBOT_DTYPE, WEIGHTS_DTYPE, Engine, _disturbance_table, _robot_table,
+                     _weights_table)
 
 
 def _shapes(B, N):
@@ -121,6 +122,7 @@ class Session:
         self.scenario_params = None
         self.channel_params = None
         self.estimator_params = None
+        self.disturb_params = None
         self.gait_params = None
         self.gait_cycles = None
 
@@ -155,6 +157,20 @@ class Session:
         """The weights table in force, (B,) WEIGHTS_DTYPE (without one: the engine's parameters)."""
         out = np.zeros(self.batch, WEIGHTS_DTYPE)
         self.engine._call("mpcq_session_get_weights", self._h, C.c_void_p(out.ctypes.data), 0)
+        return out
+
+    def set_disturbance(self, table):
+        """The session's own per-robot constant disturbance accelerations
+        (``mpcq.disturbances(B, ...)``), in each tick's local frame, carried by the model of every
+        solve from the next tick on; None clears them.  Like the weights the table is the
+        controller's: it persists across ``reset``, and no snapshot, ``restore`` or ``fork`` touches it."""
+        t = None if table is None else _disturbance_table(table, self.batch)
+        self.engine._call("mpcq_session_set_disturbance", self._h, None if t is None else C.c_void_p(t.ctypes.data), 0)
+
+    def get_disturbance(self):
+        """The disturbance table in force, (B,) DISTURBANCE_DTYPE (without one: zeros)."""
+        out = np.zeros(self.batch, DISTURBANCE_DTYPE)
+        self.engine._call("mpcq_session_get_disturbance", self._h, C.c_void_p(out.ctypes.data), 0)
         return out
 
     def get_robots(self):
@@ -386,6 +402,46 @@ class Session:
     def estimator_device_ptr(self, what: int) -> int:
         out = C.c_void_p()
         self.engine._call("mpcq_session_estimator_device_ptr", self._h, what, C.byref(out))
+        return int(out.value or 0)
+
+    # ------------------------------------------------------------------ disturbance stage
+    def enable_disturb(self, params: L.DisturbParams | None = None, **overrides):
+        """Opt in to the disturbance stage: every later tick runs, after the estimator and before
+        the planner, a per-robot observer that samples the acceleration the controller's model
+        lacks -- (what the planner is about to read - the model's step from the previous tick's
+        reading under the recorded SV_F0, acting ``f_lag`` ticks late) / dt --, filters it with
+        gain ``alpha``, clips it to ``d_max`` and writes DV_DIST.  With ``compensate`` (the
+        default) the solve takes DV_DIST as its disturbance table, ahead of ``set_disturbance``'s;
+        with ``compensate=0`` the stage only estimates.  Set ``f_lag`` to the channel's
+        ``latency``.  ``params`` None: the defaults, with ``overrides``.  Calling it while
+        enabled only replaces the parameters; enabling after a disable starts every row anew."""
+        if params is not None and overrides:
+            raise ValueError("pass params or overrides, not both")
+        dp = params or L.default_disturb_params(**overrides)
+        self.engine._call("mpcq_session_enable_disturb", self._h, C.byref(dp))
+        self.disturb_params = dp
+
+    def disable_disturb(self):
+        """The ticks after it run without the stage's launch; the arrays stay."""
+        self.engine._call("mpcq_session_disable_disturb", self._h)
+        self.disturb_params = None
+
+    def disturb_read(self, what: int):
+        """DV_DIST (B,) DISTURBANCE_DTYPE what the solve reads, DV_ROW (B, DIST_ROW) the stage's
+        state (``mpcq.disturb.unpack`` names its parts), or DV_RESID (B, 6) the last tick's raw
+        sample (NaN where none was taken)."""
+        B = self.batch
+        shapes = {L.DV_DIST: ((B,), DISTURBANCE_DTYPE), L.DV_ROW: ((B, L.DIST_ROW), np.float64),
+                  L.DV_RESID: ((B, 6), np.float64)}
+        if what not in shapes:
+            raise L.MpcqError(L.E_INVALID, f"unknown disturb array {what}")
+        out = np.empty(*shapes[what])
+        self.engine._call("mpcq_session_disturb_read", self._h, what, C.c_void_p(out.ctypes.data), 0)
+        return out
+
+    def disturb_device_ptr(self, what: int) -> int:
+        out = C.c_void_p()
+        self.engine._call("mpcq_session_disturb_device_ptr", self._h, what, C.byref(out))
         return int(out.value or 0)
 
     # ------------------------------------------------------------------ gait transitions
