@@ -53,13 +53,17 @@ int check_params(const mpcq_params* p) {
   return MPCQ_OK;
 }
 
-// Stage the listed host arrays into the context arena.  Each entry: host
-// pointer, byte count, direction (1 = in, 2 = out).  Returns device pointers.
+// One array argument of a batch entry point: the caller's pointer as an input (host_in), as an
+// output (host_out), or both (an in/out array), its byte count, and where the kernel reaches it
+// (dev, from stage(); it converts to the argument struct's pointer type).  Every entry point
+// names each argument once, here, and fills its argument struct from dev in both pointer modes.
 struct Xfer {
   const void* host_in;
   void* host_out;
   size_t bytes;
   void* dev;
+  template <class T>
+  operator T*() const { return (T*)dev; }
 };
 
 int ensure_arena(mpcq_ctx* c, size_t bytes) {
@@ -110,7 +114,14 @@ int ensure_order(mpcq_ctx* c, int64_t B) {
   return MPCQ_OK;
 }
 
-int stage(mpcq_ctx* c, Xfer* xs, int nx) {
+// Host pointers: the listed arrays into the context's arena, the inputs copied on its stream.
+// Device pointers (dev): nothing is allocated or copied, the kernel reads the caller's arrays.
+// An entry without a pointer has dev null in both.
+int stage(mpcq_ctx* c, Xfer* xs, int nx, bool dev = false) {
+  if (dev) {
+    for (int i = 0; i < nx; ++i) xs[i].dev = xs[i].host_out ? xs[i].host_out : const_cast<void*>(xs[i].host_in);
+    return MPCQ_OK;
+  }
   size_t tot = 0;
   for (int i = 0; i < nx; ++i)
     if (xs[i].host_in || xs[i].host_out) tot += (xs[i].bytes + 255) & ~size_t(255);
@@ -133,6 +144,14 @@ int unstage(mpcq_ctx* c, Xfer* xs, int nx) {
     if (xs[i].host_out)
       HIP_TRY(hipMemcpyAsync(xs[i].host_out, xs[i].dev, xs[i].bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  return MPCQ_OK;
+}
+
+// The end of a batch entry point: host pointers get their outputs back (blocking); with device
+// pointers the call waits for the stream unless MPCQ_FLAG_ASYNC.
+int finish(mpcq_ctx* c, Xfer* xs, int nx, uint32_t flags) {
+  if (!(flags & MPCQ_FLAG_DEVICE_PTRS)) return unstage(c, xs, nx);
+  if (!(flags & MPCQ_FLAG_ASYNC)) HIP_TRY(hipStreamSynchronize(c->stream));
   return MPCQ_OK;
 }
 
@@ -794,22 +813,14 @@ int mpcq_formulate_batch(mpcq_ctx* c, int64_t B, const double* xref, const doubl
   Xfer xs[6] = {{xref, nullptr, B * n12 * 8, nullptr}, {fsteps, nullptr, (size_t)B * 260 * 8, nullptr},
                 {nullptr, Ax, B * nnz * 8, nullptr},   {nullptr, l, B * m * 8, nullptr},
                 {nullptr, u, B * m * 8, nullptr},      {nullptr, status, (size_t)B * 4, nullptr}};
-  if (!dev) {
-    rc = stage(c, xs, 6);
-    if (rc) return rc;
-    a.xref = (const double*)xs[0].dev; a.fsteps = (const double*)xs[1].dev;
-    a.Ax_out = (double*)xs[2].dev; a.l_out = (double*)xs[3].dev; a.u_out = (double*)xs[4].dev;
-    a.status = (int32_t*)xs[5].dev;
-  } else {
-    a.xref = xref; a.fsteps = fsteps; a.Ax_out = Ax; a.l_out = l; a.u_out = u; a.status = status;
-  }
+  rc = stage(c, xs, 6, dev);
+  if (rc) return rc;
+  a.xref = xs[0]; a.fsteps = xs[1]; a.Ax_out = xs[2]; a.l_out = xs[3]; a.u_out = xs[4]; a.status = xs[5];
   HIP_TRY(hipEventRecord(c->ev[0], c->stream));
   HIP_TRY(mpcq::launch_formulate(N, c->p, a, c->stream));
   HIP_TRY(hipEventRecord(c->ev[1], c->stream));
   c->have_form = true;
-  if (!dev) return unstage(c, xs, 6);
-  if (!(flags & MPCQ_FLAG_ASYNC)) HIP_TRY(hipStreamSynchronize(c->stream));
-  return MPCQ_OK;
+  return finish(c, xs, 6, flags);
 }
 
 static int solve_common(mpcq_ctx* c, int64_t B, bool fused, const double* xref, const double* fsteps,
@@ -841,22 +852,11 @@ static int solve_common(mpcq_ctx* c, int64_t B, bool fused, const double* xref, 
       {nullptr, y, B * m * 8, nullptr},           {nullptr, status, (size_t)B * 4, nullptr},
       {nullptr, iters, (size_t)B * 4, nullptr},   {nullptr, rho_out, (size_t)B * 8, nullptr},
       {nullptr, info, (size_t)B * 16, nullptr}};
-  if (!dev) {
-    rc = stage(c, xs, NX);
-    if (rc) return rc;
-    a.xref = (const double*)xs[XR].dev; a.fsteps = (const double*)xs[FS].dev;
-    a.Ax = (const double*)xs[AX].dev; a.l = (const double*)xs[L].dev; a.u = (const double*)xs[U].dev;
-    a.warm_x = (const double*)xs[WX].dev; a.warm_y = (const double*)xs[WY].dev;
-    a.rho_in = (const double*)xs[RI].dev;
-    a.f0 = (double*)xs[F0].dev; a.x = (double*)xs[X].dev; a.y = (double*)xs[Y].dev;
-    a.status = (int32_t*)xs[ST].dev; a.iters = (int32_t*)xs[IT].dev; a.rho_out = (double*)xs[RO].dev;
-    a.info = (int32_t*)xs[IN].dev;
-  } else {
-    a.xref = xref; a.fsteps = fsteps; a.Ax = Ax; a.l = l; a.u = u;
-    a.warm_x = warm_x; a.warm_y = warm_y; a.rho_in = rho_in;
-    a.f0 = f0; a.x = x; a.y = y; a.status = status; a.iters = iters; a.rho_out = rho_out;
-    a.info = info;
-  }
+  rc = stage(c, xs, NX, dev);
+  if (rc) return rc;
+  a.xref = xs[XR]; a.fsteps = xs[FS]; a.Ax = xs[AX]; a.l = xs[L]; a.u = xs[U]; a.warm_x = xs[WX]; a.warm_y = xs[WY];
+  a.rho_in = xs[RI]; a.f0 = xs[F0]; a.x = xs[X]; a.y = xs[Y]; a.status = xs[ST]; a.iters = xs[IT];
+  a.rho_out = xs[RO]; a.info = xs[IN];
   a.stamps = c->stamps;
   rc = ensure_work(c, B, &a.work);
   if (rc) return rc;
@@ -911,9 +911,7 @@ static int solve_common(mpcq_ctx* c, int64_t B, bool fused, const double* xref, 
   HIP_TRY(hipEventRecord(c->ev[3], c->stream));
   if (by_class) HIP_TRY(mpcq::launch_class_learn(cls, its, B, c->cls_sum, c->cls_cnt, c->stream));
   c->have_solve = true;
-  if (!dev) return unstage(c, xs, NX);
-  if (!(flags & MPCQ_FLAG_ASYNC)) HIP_TRY(hipStreamSynchronize(c->stream));
-  return MPCQ_OK;
+  return finish(c, xs, NX, flags);
 }
 
 int mpcq_qp_solve_batch(mpcq_ctx* c, int64_t B, const double* Ax, const double* l, const double* u,
@@ -981,7 +979,10 @@ int mpcq_plan_batch(mpcq_ctx* c, const mpcq_planner_params* pp, int64_t B, uint3
   const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
   const bool fo = ops & MPCQ_PLAN_FOOTSTEPS, rs = ops & MPCQ_PLAN_REFSTATES;
   enum { ST, VC, H, LF, VR, RD, GA, RF, HR, XR, FS, SS, NX };
-  // in/out buffers are staged both ways (host_in and host_out both set)
+  // in/out buffers are staged both ways (host_in and host_out both set).  The arrays of a pass
+  // that `ops` leaves out are null in both pointer modes: planner_kernel reads l_feet and writes
+  // fsteps under MPCQ_PLAN_FOOTSTEPS only, reads and writes rot_flag, h_rot and xref under
+  // MPCQ_PLAN_REFSTATES only (do_fs / do_ref guard every access).
   Xfer xs[NX] = {{state, nullptr, (size_t)B * 96, nullptr},
                  {v_cur, nullptr, (size_t)B * 48, nullptr},
                  {h, nullptr, (size_t)B * 8, nullptr},
@@ -995,22 +996,12 @@ int mpcq_plan_batch(mpcq_ctx* c, const mpcq_planner_params* pp, int64_t B, uint3
                  // fsteps: staged in as well so a BAD_GAIT instance keeps the caller's values
                  {fo ? fsteps : nullptr, fo ? fsteps : nullptr, (size_t)B * 260 * 8, nullptr},
                  {nullptr, status, (size_t)B * 4, nullptr}};
-  if (!dev) {
-    rc = stage(c, xs, NX);
-    if (rc) return rc;
-    a.state = (const double*)xs[ST].dev; a.v_cur = (const double*)xs[VC].dev; a.h = (const double*)xs[H].dev;
-    a.l_feet = (const double*)xs[LF].dev; a.v_ref = (const double*)xs[VR].dev;
-    a.reduced = (const int32_t*)xs[RD].dev; a.gait = (double*)xs[GA].dev; a.rot_flag = (int32_t*)xs[RF].dev;
-    a.h_rot = (double*)xs[HR].dev; a.xref = (double*)xs[XR].dev; a.fsteps = (double*)xs[FS].dev;
-    a.status = (int32_t*)xs[SS].dev;
-  } else {
-    a.state = state; a.v_cur = v_cur; a.h = h; a.l_feet = l_feet; a.v_ref = v_ref; a.reduced = reduced;
-    a.gait = gait; a.rot_flag = rot_flag; a.h_rot = h_rot; a.xref = xref; a.fsteps = fsteps; a.status = status;
-  }
+  rc = stage(c, xs, NX, dev);
+  if (rc) return rc;
+  a.state = xs[ST]; a.v_cur = xs[VC]; a.h = xs[H]; a.l_feet = xs[LF]; a.v_ref = xs[VR]; a.reduced = xs[RD];
+  a.gait = xs[GA]; a.rot_flag = xs[RF]; a.h_rot = xs[HR]; a.xref = xs[XR]; a.fsteps = xs[FS]; a.status = xs[SS];
   HIP_TRY(mpcq::launch_plan(P, a, c->stream));
-  if (!dev) return unstage(c, xs, NX);
-  if (!(flags & MPCQ_FLAG_ASYNC)) HIP_TRY(hipStreamSynchronize(c->stream));
-  return MPCQ_OK;
+  return finish(c, xs, NX, flags);
 }
 
 // Swing-foot constants (TSID_Debug_controller_four_legs_fb_vel.py:96-97, 107; Interface.py:91;
@@ -1040,16 +1031,10 @@ int mpcq_swing_step_batch(mpcq_ctx* c, const mpcq_swing_params* sp, int64_t B, c
   Xfer xs[NX] = {{in, nullptr, (size_t)B * 40 * 8, nullptr},
                  {state, state, (size_t)B * 4 * MPCQ_SWING_STATE * 8, nullptr},
                  {nullptr, out, (size_t)B * 44 * 8, nullptr}};
-  if (!dev) {
-    rc = stage(c, xs, NX);
-    if (rc) return rc;
-    HIP_TRY(mpcq::launch_swing_step(P, B, (const double*)xs[IN].dev, (double*)xs[ST].dev, (double*)xs[OUT].dev,
-                                    c->stream));
-    return unstage(c, xs, NX);
-  }
-  HIP_TRY(mpcq::launch_swing_step(P, B, in, state, out, c->stream));
-  if (!(flags & MPCQ_FLAG_ASYNC)) HIP_TRY(hipStreamSynchronize(c->stream));
-  return MPCQ_OK;
+  rc = stage(c, xs, NX, dev);
+  if (rc) return rc;
+  HIP_TRY(mpcq::launch_swing_step(P, B, xs[IN], xs[ST], xs[OUT], c->stream));
+  return finish(c, xs, NX, flags);
 }
 
 int mpcq_swing_batch(mpcq_ctx* c, const mpcq_swing_params* sp, int64_t B, int k_sub0, int n_sub,
@@ -1080,20 +1065,12 @@ int mpcq_swing_batch(mpcq_ctx* c, const mpcq_swing_params* sp, int64_t B, int k_
                  {nullptr, ref, (size_t)B * n_sub * 36 * 8, nullptr},
                  {nullptr, t0_out, (size_t)B * n_sub * 4 * 8, nullptr},
                  {nullptr, status, (size_t)B * 4, nullptr}};
-  if (!dev) {
-    rc = stage(c, xs, NX);
-    if (rc) return rc;
-    a.gait = (const double*)xs[GA].dev; a.fsteps = (const double*)xs[FS].dev; a.frame = (const double*)xs[FR].dev;
-    a.feet0 = (const double*)xs[F0].dev; a.state = (double*)xs[ST].dev; a.ref = (double*)xs[RF].dev;
-    a.t0_out = (double*)xs[T0].dev; a.status = (int32_t*)xs[SS].dev;
-  } else {
-    a.gait = gait; a.fsteps = fsteps; a.frame = frame; a.feet0 = feet0; a.state = state; a.ref = ref;
-    a.t0_out = t0_out; a.status = status;
-  }
+  rc = stage(c, xs, NX, dev);
+  if (rc) return rc;
+  a.gait = xs[GA]; a.fsteps = xs[FS]; a.frame = xs[FR]; a.feet0 = xs[F0]; a.state = xs[ST]; a.ref = xs[RF];
+  a.t0_out = xs[T0]; a.status = xs[SS];
   HIP_TRY(mpcq::launch_swing(P, a, c->stream));
-  if (!dev) return unstage(c, xs, NX);
-  if (!(flags & MPCQ_FLAG_ASYNC)) HIP_TRY(hipStreamSynchronize(c->stream));
-  return MPCQ_OK;
+  return finish(c, xs, NX, flags);
 }
 
 // Rigid-body plant: one MPC tick of dt, k_mpc substeps (main.py:21), the Coulomb clamp on.
@@ -1134,20 +1111,12 @@ int mpcq_plant_step_batch(mpcq_ctx* c, const mpcq_plant_params* pl, int64_t B, c
                  {robots, nullptr, (size_t)B * sizeof(mpcq_robot), nullptr},
                  {nullptr, state_out, (size_t)B * 96, nullptr},
                  {nullptr, f_eff, (size_t)B * 96, nullptr}};
-  if (!dev) {
-    rc = stage(c, xs, NX);
-    if (rc) return rc;
-    a.state = (const double*)xs[ST].dev; a.feet = (const double*)xs[FT].dev; a.f = (const double*)xs[FF].dev;
-    a.wrench = (const double*)xs[WR].dev; a.robots = (const mpcq_robot*)xs[RB].dev;
-    a.state_out = (double*)xs[SO].dev; a.f_eff = (double*)xs[FE].dev;
-  } else {
-    a.state = state; a.feet = feet; a.f = f; a.wrench = wrench; a.robots = robots;
-    a.state_out = state_out; a.f_eff = f_eff;
-  }
+  rc = stage(c, xs, NX, dev);
+  if (rc) return rc;
+  a.state = xs[ST]; a.feet = xs[FT]; a.f = xs[FF]; a.wrench = xs[WR]; a.robots = xs[RB]; a.state_out = xs[SO];
+  a.f_eff = xs[FE];
   HIP_TRY(mpcq::launch_plant(P, a, c->stream));
-  if (!dev) return unstage(c, xs, NX);
-  if (!(flags & MPCQ_FLAG_ASYNC)) HIP_TRY(hipStreamSynchronize(c->stream));
-  return MPCQ_OK;
+  return finish(c, xs, NX, flags);
 }
 
 // Episode monitor: tilt beyond 0.5 rad or the base below half of h_ref ends an episode.
@@ -1186,23 +1155,13 @@ int mpcq_monitor_step_batch(mpcq_ctx* c, const mpcq_monitor_params* mp, int64_t 
                  {ep_ticks, ep_ticks, b * 4, nullptr}, {episodes, episodes, b * 4, nullptr},
                  {last, last, b * 128, nullptr},       {nullptr, done, b * 4, nullptr},
                  {totals, totals, 64, nullptr},        {trace, trace, b * MPCQ_TRACE * 8, nullptr}};
-  if (!dev) {
-    rc = stage(c, xs, NX);
-    if (rc) return rc;
-    a.q_w = (const double*)xs[QW].dev; a.status = (const int32_t*)xs[ST].dev; a.iters = (const int32_t*)xs[IT].dev;
-    a.f0 = (const double*)xs[F0].dev; a.cost = (const double*)xs[CO].dev; a.state = (const double*)xs[SA].dev;
-    a.v_ref = (const double*)xs[VR].dev; a.ep = (double*)xs[EP].dev; a.ep_ticks = (int32_t*)xs[ET].dev;
-    a.episodes = (int32_t*)xs[ES].dev; a.last = (double*)xs[LA].dev; a.done = (int32_t*)xs[DO].dev;
-    a.totals = (unsigned long long*)xs[TO].dev; a.trace = (double*)xs[TR].dev;
-  } else {
-    a.q_w = q_w; a.status = status; a.iters = iters; a.f0 = f0; a.cost = cost; a.state = state; a.v_ref = v_ref;
-    a.ep = ep; a.ep_ticks = ep_ticks; a.episodes = episodes; a.last = last; a.done = done;
-    a.totals = (unsigned long long*)totals; a.trace = trace;
-  }
+  rc = stage(c, xs, NX, dev);
+  if (rc) return rc;
+  a.q_w = xs[QW]; a.status = xs[ST]; a.iters = xs[IT]; a.f0 = xs[F0]; a.cost = xs[CO]; a.state = xs[SA];
+  a.v_ref = xs[VR]; a.ep = xs[EP]; a.ep_ticks = xs[ET]; a.episodes = xs[ES]; a.last = xs[LA]; a.done = xs[DO];
+  a.totals = xs[TO]; a.trace = xs[TR];
   HIP_TRY(mpcq::launch_monitor(P, a, c->stream));
-  if (!dev) return unstage(c, xs, NX);
-  if (!(flags & MPCQ_FLAG_ASYNC)) HIP_TRY(hipStreamSynchronize(c->stream));
-  return MPCQ_OK;
+  return finish(c, xs, NX, flags);
 }
 
 // Scenario: the reference's predefined joystick at MPC ticks (Joystick.py:82-83), no pushes,
@@ -1254,21 +1213,12 @@ int mpcq_scenario_step_batch(mpcq_ctx* c, const mpcq_scenario_params* sc, int64_
                  {nullptr, wrench_out, b * 48, nullptr},
                  {robots_out, robots_out, b * sizeof(mpcq_robot), nullptr},
                  {draw, draw, b * 64, nullptr}};
-  if (!dev) {
-    rc = stage(c, xs, NX);
-    if (rc) return rc;
-    a.first = (const int32_t*)xs[FI].dev; a.epoch = (int32_t*)xs[EP].dev; a.tick = (int32_t*)xs[TI].dev;
-    a.base = (const mpcq_robot*)xs[BA].dev; a.wrench_in = (const double*)xs[WI].dev;
-    a.v_ref = (double*)xs[VR].dev; a.push = (double*)xs[PU].dev; a.wrench_out = (double*)xs[WO].dev;
-    a.robots_out = (mpcq_robot*)xs[RO].dev; a.draw = (double*)xs[DR].dev;
-  } else {
-    a.first = first; a.epoch = epoch; a.tick = tick; a.base = base; a.wrench_in = wrench_in;
-    a.v_ref = v_ref; a.push = push; a.wrench_out = wrench_out; a.robots_out = robots_out; a.draw = draw;
-  }
+  rc = stage(c, xs, NX, dev);
+  if (rc) return rc;
+  a.first = xs[FI]; a.epoch = xs[EP]; a.tick = xs[TI]; a.base = xs[BA]; a.wrench_in = xs[WI]; a.v_ref = xs[VR];
+  a.push = xs[PU]; a.wrench_out = xs[WO]; a.robots_out = xs[RO]; a.draw = xs[DR];
   HIP_TRY(mpcq::launch_scenario(P, a, c->stream));
-  if (!dev) return unstage(c, xs, NX);
-  if (!(flags & MPCQ_FLAG_ASYNC)) HIP_TRY(hipStreamSynchronize(c->stream));
-  return MPCQ_OK;
+  return finish(c, xs, NX, flags);
 }
 
 // Channel: everything zero, a channel that changes nothing.
@@ -1302,20 +1252,12 @@ int mpcq_channel_observe_batch(mpcq_ctx* c, const mpcq_channel_params* ch, int64
                  {draw, draw, b * 128, nullptr},
                  {s_ring, s_ring, b * MPCQ_CHANNEL_MAX_DELAY * 96, nullptr},
                  {f_ring, f_ring, b * MPCQ_CHANNEL_MAX_LATENCY * 96, nullptr}};
-  if (!dev) {
-    rc = stage(c, xs, NX);
-    if (rc) return rc;
-    a.first = (const int32_t*)xs[FI].dev; a.truth = (const double*)xs[TR].dev; a.clock = (int32_t*)xs[CL].dev;
-    a.obs = (double*)xs[OB].dev; a.draw = (double*)xs[DR].dev; a.s_ring = (double*)xs[SR].dev;
-    a.f_ring = (double*)xs[FR].dev;
-  } else {
-    a.first = first; a.truth = truth; a.clock = clock; a.obs = obs; a.draw = draw; a.s_ring = s_ring;
-    a.f_ring = f_ring;
-  }
+  rc = stage(c, xs, NX, dev);
+  if (rc) return rc;
+  a.first = xs[FI]; a.truth = xs[TR]; a.clock = xs[CL]; a.obs = xs[OB]; a.draw = xs[DR]; a.s_ring = xs[SR];
+  a.f_ring = xs[FR];
   HIP_TRY(mpcq::launch_observe(P, a, c->stream));
-  if (!dev) return unstage(c, xs, NX);
-  if (!(flags & MPCQ_FLAG_ASYNC)) HIP_TRY(hipStreamSynchronize(c->stream));
-  return MPCQ_OK;
+  return finish(c, xs, NX, flags);
 }
 
 int mpcq_channel_actuate_batch(mpcq_ctx* c, const mpcq_channel_params* ch, int64_t B, const double* f0,
@@ -1339,18 +1281,11 @@ int mpcq_channel_actuate_batch(mpcq_ctx* c, const mpcq_channel_params* ch, int64
                  {draw, draw, b * 128, nullptr},
                  {f_ring, f_ring, b * MPCQ_CHANNEL_MAX_LATENCY * 96, nullptr},
                  {nullptr, f_cmd, b * 96, nullptr}};
-  if (!dev) {
-    rc = stage(c, xs, NX);
-    if (rc) return rc;
-    a.f0 = (const double*)xs[F0].dev; a.clock = (const int32_t*)xs[CL].dev; a.draw = (double*)xs[DR].dev;
-    a.f_ring = (double*)xs[FR].dev; a.f_cmd = (double*)xs[FC].dev;
-  } else {
-    a.f0 = f0; a.clock = clock; a.draw = draw; a.f_ring = f_ring; a.f_cmd = f_cmd;
-  }
+  rc = stage(c, xs, NX, dev);
+  if (rc) return rc;
+  a.f0 = xs[F0]; a.clock = xs[CL]; a.draw = xs[DR]; a.f_ring = xs[FR]; a.f_cmd = xs[FC];
   HIP_TRY(mpcq::launch_actuate(P, a, c->stream));
-  if (!dev) return unstage(c, xs, NX);
-  if (!(flags & MPCQ_FLAG_ASYNC)) HIP_TRY(hipStreamSynchronize(c->stream));
-  return MPCQ_OK;
+  return finish(c, xs, NX, flags);
 }
 
 // Estimator: starting values, not tuned (include/mpcq.h).
@@ -1399,20 +1334,12 @@ int mpcq_estimator_step_batch(mpcq_ctx* c, const mpcq_estimator_params* ep, int6
                  {robots, nullptr, b * sizeof(mpcq_robot), nullptr},
                  {row, row, b * MPCQ_EST_ROW * 8, nullptr},
                  {nullptr, est, b * 96, nullptr}};
-  if (!dev) {
-    rc = stage(c, xs, NX);
-    if (rc) return rc;
-    a.first = (const int32_t*)xs[FI].dev; a.obs = (const double*)xs[OB].dev; a.f_prev = (const double*)xs[FP].dev;
-    a.feet_prev = (const double*)xs[FT].dev; a.failed = (const int32_t*)xs[FA].dev;
-    a.robots = (const mpcq_robot*)xs[RB].dev; a.row = (double*)xs[RO].dev; a.est = (double*)xs[ES].dev;
-  } else {
-    a.first = first; a.obs = obs; a.f_prev = f_prev; a.feet_prev = feet_prev; a.failed = failed_prev;
-    a.robots = robots; a.row = row; a.est = est;
-  }
+  rc = stage(c, xs, NX, dev);
+  if (rc) return rc;
+  a.first = xs[FI]; a.obs = xs[OB]; a.f_prev = xs[FP]; a.feet_prev = xs[FT]; a.failed = xs[FA]; a.robots = xs[RB];
+  a.row = xs[RO]; a.est = xs[ES];
   HIP_TRY(mpcq::launch_estimate(P, a, c->stream));
-  if (!dev) return unstage(c, xs, NX);
-  if (!(flags & MPCQ_FLAG_ASYNC)) HIP_TRY(hipStreamSynchronize(c->stream));
-  return MPCQ_OK;
+  return finish(c, xs, NX, flags);
 }
 
 // Disturbance stage: starting values, not tuned (include/mpcq.h).
@@ -1461,22 +1388,13 @@ int mpcq_disturb_step_batch(mpcq_ctx* c, const mpcq_disturb_params* dp, int64_t 
                  {robots, nullptr, b * sizeof(mpcq_robot), nullptr},
                  {row, row, b * MPCQ_DIST_ROW * 8, nullptr},
                  {nullptr, dist, b * sizeof(mpcq_disturbance), nullptr},
-                 {nullptr, resid, resid ? b * 48 : 0, nullptr}};
-  if (!dev) {
-    rc = stage(c, xs, NX);
-    if (rc) return rc;
-    a.first = (const int32_t*)xs[FI].dev; a.meas = (const double*)xs[ME].dev; a.f_prev = (const double*)xs[FP].dev;
-    a.feet_prev = (const double*)xs[FT].dev; a.failed = (const int32_t*)xs[FA].dev;
-    a.robots = (const mpcq_robot*)xs[RB].dev; a.row = (double*)xs[RO].dev;
-    a.dist = (mpcq_disturbance*)xs[DI].dev; a.resid = resid ? (double*)xs[RE].dev : nullptr;
-  } else {
-    a.first = first; a.meas = meas; a.f_prev = f_prev; a.feet_prev = feet_prev; a.failed = failed_prev;
-    a.robots = robots; a.row = row; a.dist = dist; a.resid = resid;
-  }
+                 {nullptr, resid, b * 48, nullptr}};  // (optional: null stays null)
+  rc = stage(c, xs, NX, dev);
+  if (rc) return rc;
+  a.first = xs[FI]; a.meas = xs[ME]; a.f_prev = xs[FP]; a.feet_prev = xs[FT]; a.failed = xs[FA]; a.robots = xs[RB];
+  a.row = xs[RO]; a.dist = xs[DI]; a.resid = xs[RE];
   HIP_TRY(mpcq::launch_disturb(P, a, c->stream));
-  if (!dev) return unstage(c, xs, NX);
-  if (!(flags & MPCQ_FLAG_ASYNC)) HIP_TRY(hipStreamSynchronize(c->stream));
-  return MPCQ_OK;
+  return finish(c, xs, NX, flags);
 }
 
 // Gait stage: requests by hand, switches at phase boundaries, no speed bands; yaw_weight = the
@@ -1507,17 +1425,11 @@ int mpcq_gait_roll_batch(mpcq_ctx* c, const mpcq_gait_params* gp, const double* 
   const size_t b = (size_t)B;
   enum { VR, GA, GS, NX };
   Xfer xs[NX] = {{v_ref, nullptr, b * 48, nullptr}, {gait, gait, b * 800, nullptr}, {gstate, gstate, b * 16, nullptr}};
-  if (!dev) {
-    rc = stage(c, xs, NX);
-    if (rc) return rc;
-    a.v_ref = (const double*)xs[VR].dev; a.gait = (double*)xs[GA].dev; a.gstate = (int32_t*)xs[GS].dev;
-  } else {
-    a.v_ref = v_ref; a.gait = gait; a.gstate = gstate;
-  }
+  rc = stage(c, xs, NX, dev);
+  if (rc) return rc;
+  a.v_ref = xs[VR]; a.gait = xs[GA]; a.gstate = xs[GS];
   HIP_TRY(mpcq::launch_gait(P, a, c->stream));
-  if (!dev) return unstage(c, xs, NX);
-  if (!(flags & MPCQ_FLAG_ASYNC)) HIP_TRY(hipStreamSynchronize(c->stream));
-  return MPCQ_OK;
+  return finish(c, xs, NX, flags);
 }
 
 int mpcq_debug_set_stamps(mpcq_ctx* c, void* buf) {

@@ -1,38 +1,30 @@
 // mpcq_session_api.cpp — the mpcq_session_* entry points of include/mpcq.h: closed-loop
 // sessions, per-robot state resident in HBM.
 //
-// A session's device arrays come in groups (alloc_group): the main one made by
-// mpcq_session_create, and one each for swing, plant, monitor, scenario, channel, estimator and gait, made when
-// they are first enabled.  A tick (session_tick) is a list of stages, each filling the argument struct of
-// its launch from the groups' arrays.  All numerics run in the HIP kernels.
+// A session's device arrays come in parts (grp[], one allocation each): the main one made by
+// mpcq_session_create, the others when their stage is first enabled.  What a part is -- its arrays,
+// their sizes, what a snapshot holds of it, its place in a blob -- is one row of kParts
+// (mpcq_session_layout.h); enables, reads, snapshots and blobs walk that table.  A tick
+// (session_tick) is a list of stages, each filling the argument struct of its launch from the
+// parts' arrays.  All numerics run in the HIP kernels.
 #include <math.h>
 #include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include "mpcq_host.h"
+#include "mpcq_session_layout.h"
 
 using namespace mpcq;
 
 namespace {
 
-// Private arrays, behind the named ones of their group: the warm start, the planner's
-// status, the engine's info, the staging of host inputs (tick: state, l_feet, v_ref,
-// reduced; reset: mask in IN_REDUCED, q_w0 in IN_VREF, gait0 in IN_GAIT), the gait table
-// every robot was created with; the copy of q_w a tick with the plant takes before its
-// retrieve.
-enum { SP_WARM_X = MPCQ_SV_COUNT, SP_PLAN_STATUS, SP_INFO, SP_IN_STATE, SP_IN_LFEET, SP_IN_VREF, SP_IN_REDUCED,
-       SP_GAIT_INIT, SP_IN_GAIT, SP_COUNT };
-enum { PP_QW_PREV = MPCQ_PV_COUNT, PP_COUNT };
-
-// The arrays of one kind of id: MPCQ_SV_* (the swing slots are null until
-// mpcq_session_enable_swing), MPCQ_PV_*, MPCQ_MV_*, MPCQ_CV_*, MPCQ_HV_*, MPCQ_EV_*, MPCQ_GV_*, MPCQ_DV_*.
+// The arrays of one part, by the part's own ids (null: not there, or not held).
 struct Group {
-  const char *kind, *enable;  // "<kind> array %d needs mpcq_session_enable_<enable>"
-  int named;                  // the ids the _read / _write / _device_ptr entry points reach
-  void* mem = nullptr;
-  void* ptr[SP_COUNT] = {};
-  size_t bytes[SP_COUNT] = {};
+  void* mem = nullptr;  // the allocation (null: the part is absent, or a table's, which its Table<> owns)
+  void* ptr[kPartArrays] = {};
+  size_t bytes[kPartArrays] = {};
+  bool there() const { return mem || ptr[0]; }
   double* d(int w) const { return (double*)ptr[w]; }
   int32_t* i(int w) const { return (int32_t*)ptr[w]; }
 };
@@ -43,21 +35,11 @@ struct mpcq_session {
   mpcq_ctx* ctx = nullptr;
   int64_t B = 0;
   mpcq_planner_params pp{};
-  Group sv{"session", "swing", MPCQ_SV_COUNT};
-  Group pv{"plant", "plant", MPCQ_PV_COUNT};      // made by the first enable_plant / set_wrench
-  Group mv{"monitor", "monitor", MPCQ_MV_COUNT};  // made by the first enable_monitor
-  Group cv{"scenario", "scenario", MPCQ_CV_COUNT};  // made by the first enable_scenario
-  Group hv{"channel", "channel", MPCQ_HV_COUNT};    // made by the first enable_channel
-  Group ev{"estimator", "estimator", MPCQ_EV_COUNT};  // made by the first enable_estimator
-  Group gv{"gait", "gait", MPCQ_GV_COUNT};            // made by the first enable_gait
-  Group dv{"disturb", "disturb", MPCQ_DV_COUNT};      // made by the first enable_disturb
-  void* swing_mem = nullptr;                      // MPCQ_SV_SWING_REF, _SWING_STATE, _FRAME
+  Group grp[G_COUNT];       // the parts' arrays (made by mpcq_session_create and the first enable of each)
+  bool on[G_COUNT] = {};    // the part's stage runs (mpcq_session_enable_* / _disable_*)
   bool have_order = false;  // MPCQ_SV_ORDER holds the next solve's order (longest previous first)
   bool use_order = true;    // MPCQ_DISPATCH_ORDER=0 turns it off (A/B timing only; results are identical)
   bool resets = false;      // mpcq_session_reset was called: from then on the ticks consult MPCQ_SV_FIRST
-  bool swing = false, plant = false, monitor = false, scenario = false, channel = false, estimator = false;
-  bool gait = false;
-  bool disturb_on = false;  // the disturbance stage runs (mpcq_session_enable_disturb)
   mpcq_disturb_params dp{};
   mpcq_gait_params gp{};
   mpcq::GaitArgs gait_lib{};  // the library in force, packed (period, lib; the launch fills the rest)
@@ -65,7 +47,7 @@ struct mpcq_session {
   mpcq_plant_params pl{};
   mpcq_monitor_params mp{};
   mpcq_scenario_params sc{};
-  mpcq_channel_params ch{};  // (delay and latency: what the rings in hv were primed under)
+  mpcq_channel_params ch{};  // (delay and latency: what the channel's rings were primed under)
   mpcq_estimator_params ep{};
   RobotTable robots;        // mpcq_session_set_robots (the session's own, not the context's)
   RobotTable plant_robots;  // mpcq_session_set_plant_robots
@@ -77,65 +59,13 @@ struct mpcq_session {
 
 namespace {
 
-// Bytes of an array of the main group (layouts: include/mpcq.h).
-size_t sv_bytes(int what, int64_t B, int N) {
-  const size_t b = (size_t)B;
-  switch (what) {
-    case MPCQ_SV_F0: case MPCQ_SV_STATE: case MPCQ_SV_L_FEET: case SP_IN_STATE: case SP_IN_LFEET: return b * 12 * 8;
-    case MPCQ_SV_X: case SP_WARM_X: return b * 24 * N * 8;
-    case MPCQ_SV_X_ROBOT: return b * 12 * N * 8;
-    case MPCQ_SV_Q_W: case SP_IN_VREF: return b * 6 * 8;
-    case MPCQ_SV_COST: return b * 13 * 8;
-    case MPCQ_SV_XREF: return b * 12 * (N + 1) * 8;
-    case MPCQ_SV_FSTEPS: return b * 260 * 8;
-    case MPCQ_SV_GAIT: case SP_GAIT_INIT: case SP_IN_GAIT: return b * 100 * 8;
-    case MPCQ_SV_Y: return b * 44 * N * 8;
-    case MPCQ_SV_RHO: case MPCQ_SV_H_ROT: return b * 8;
-    case MPCQ_SV_STATUS: case MPCQ_SV_ITERS: case MPCQ_SV_ROT_FLAG: case MPCQ_SV_ORDER: case MPCQ_SV_FIRST:
-    case SP_PLAN_STATUS: case SP_IN_REDUCED: return b * 4;
-    case SP_INFO: return b * 16;
-  }
-  return 0;  // (the swing arrays exist from mpcq_session_enable_swing on)
-}
-
-// Bytes of the arrays of the other groups: the one statement, for the enables that allocate them
-// and for the snapshots that mirror them.
-void swing_bytes(size_t B, int k_mpc, size_t nb[3]) {  // MPCQ_SV_SWING_REF, _SWING_STATE, _FRAME
-  nb[0] = B * k_mpc * 36 * 8; nb[1] = B * 4 * MPCQ_SWING_STATE * 8; nb[2] = B * 24;
-}
-void plant_bytes(size_t B, size_t nb[PP_COUNT]) {  // STATE_END, F_EFF, WRENCH, qw_prev
-  nb[MPCQ_PV_STATE_END] = B * 96; nb[MPCQ_PV_F_EFF] = B * 96; nb[MPCQ_PV_WRENCH] = B * 48; nb[PP_QW_PREV] = B * 48;
-}
-void monitor_bytes(size_t B, size_t nb[MPCQ_MV_COUNT]) {  // DONE, EP, EP_TICKS, EPISODES, LAST, TOTALS
-  const size_t m[MPCQ_MV_COUNT] = {B * 4, B * 64, B * 4, B * 4, B * 128, 64};
-  for (int w = 0; w < MPCQ_MV_COUNT; ++w) nb[w] = m[w];
-}
-void scenario_bytes(size_t B, size_t nb[MPCQ_CV_COUNT]) {  // EPOCH, TICK, V_REF, PUSH, WRENCH, ROBOTS, DRAW
-  const size_t c[MPCQ_CV_COUNT] = {B * 4, B * 4, B * 48, B * 48, B * 48, B * sizeof(mpcq_robot), B * 64};
-  for (int w = 0; w < MPCQ_CV_COUNT; ++w) nb[w] = c[w];
-}
-
-void channel_bytes(size_t B, size_t nb[MPCQ_HV_COUNT]) {  // CLOCK, OBS, F_CMD, DRAW, S_RING, F_RING
-  const size_t h[MPCQ_HV_COUNT] = {B * 8, B * 96, B * 96, B * 128, B * MPCQ_CHANNEL_MAX_DELAY * 96,
-                                   B * MPCQ_CHANNEL_MAX_LATENCY * 96};
-  for (int w = 0; w < MPCQ_HV_COUNT; ++w) nb[w] = h[w];
-}
-
-void estimator_bytes(size_t B, size_t nb[MPCQ_EV_COUNT]) {  // EST, ROW
-  nb[MPCQ_EV_EST] = B * 96; nb[MPCQ_EV_ROW] = B * MPCQ_EST_ROW * 8;
-}
-
-void disturb_bytes(size_t B, size_t nb[MPCQ_DV_COUNT]) {  // DIST, ROW, RESID
-  nb[MPCQ_DV_DIST] = B * sizeof(mpcq_disturbance); nb[MPCQ_DV_ROW] = B * MPCQ_DIST_ROW * 8; nb[MPCQ_DV_RESID] = B * 48;
-}
-
-// n arrays of nb[i] bytes, each 256-B aligned, in one allocation zeroed on the context's
-// stream (the call blocks): *mem, ptr[i] (null where nb[i] is 0) and bytes[i].  On a failure
+// The arrays of nb[w] bytes, each 256-B aligned, in one allocation zeroed on the context's
+// stream (the call blocks): g->mem, ptr[w] (null where nb[w] is 0) and bytes[w].  On a failure
 // nothing stays allocated and nothing is written.
-int alloc_group(mpcq_ctx* c, const char* what, int n, const size_t* nb, void** mem, void** ptr, size_t* bytes) {
+int alloc_group(mpcq_ctx* c, const char* what, const size_t nb[kPartArrays], Group* g) {
   auto padded = [](size_t b) { return (b + 255) & ~size_t(255); };
   size_t tot = 0;
-  for (int i = 0; i < n; ++i) tot += padded(nb[i]);
+  for (int w = 0; w < kPartArrays; ++w) tot += padded(nb[w]);
   void* m = nullptr;
   if (hipMalloc(&m, tot) != hipSuccess) return fail(MPCQ_E_NOMEM, "hipMalloc(%zu) for %s failed", tot, what);
   hipError_t e = hipMemsetAsync(m, 0, tot, c->stream);
@@ -145,27 +75,93 @@ int alloc_group(mpcq_ctx* c, const char* what, int n, const size_t* nb, void** m
     return fail(MPCQ_E_DEVICE, "zeroing %s failed: %s", what, hipGetErrorString(e));
   }
   size_t off = 0;
-  for (int i = 0; i < n; ++i) {
-    ptr[i] = nb[i] ? (char*)m + off : nullptr;
-    bytes[i] = nb[i];
-    off += padded(nb[i]);
+  for (int w = 0; w < kPartArrays; ++w) {
+    g->ptr[w] = nb[w] ? (char*)m + off : nullptr;
+    g->bytes[w] = nb[w];
+    off += padded(nb[w]);
   }
-  *mem = m;
+  g->mem = m;
   return MPCQ_OK;
 }
 
-// The array behind an id of group g, for the _read / _write / _device_ptr entry points.
-int find(const Group& g, int what) {
-  if (what < 0 || what >= g.named) return fail(MPCQ_E_INVALID, "unknown %s array %d", g.kind, what);
-  if (!g.ptr[what]) return fail(MPCQ_E_INVALID, "%s array %d needs mpcq_session_enable_%s", g.kind, what, g.enable);
-  return MPCQ_OK;
+// Part gi of the session as g (an empty Group takes it away); a part whose arrays are ids of
+// another part too shows there as well.
+void install_part(mpcq_session* s, int gi, const Group& g) {
+  const Part& p = kParts[gi];
+  s->grp[gi] = g;
+  for (int w = 0; p.alias >= 0 && w < p.count; ++w) {
+    s->grp[p.alias].ptr[p.alias_at + w] = g.ptr[w];
+    s->grp[p.alias].bytes[p.alias_at + w] = g.bytes[w];
+  }
 }
 
-int group_read(mpcq_session* s, Group mpcq_session::*group, int what, void* dst, uint32_t flags) {
-  if (!s || !dst) return fail(MPCQ_E_INVALID, "NULL argument");
-  const Group& g = s->*group;
-  const int rc = find(g, what);
+// Nothing to fill: the arrays stay zero.
+int no_fill(const Group&) { return MPCQ_OK; }
+
+// Part gi of the session where it does not exist yet: allocated from its row of kParts, zero, then
+// fill(g) (enqueues on the context's stream; an mpcq code).  All or nothing: on a failure the
+// session is as it was.
+template <class Fill>
+int ensure_part(mpcq_session* s, int gi, Fill fill, int k_mpc = 0) {
+  if (s->grp[gi].mem) return MPCQ_OK;
+  mpcq_ctx* c = s->ctx;
+  size_t nb[kPartArrays];
+  part_sizes(gi, (size_t)s->B, c->N, k_mpc, false, nb);
+  Group g;
+  int rc = alloc_group(c, kParts[gi].live, nb, &g);
   if (rc) return rc;
+  install_part(s, gi, g);
+  rc = fill(s->grp[gi]);
+  if (rc) {
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(g.mem);
+    install_part(s, gi, Group{});
+  }
+  return rc;
+}
+
+int init_failed(int gi, hipError_t e) {
+  return fail(MPCQ_E_DEVICE, "initialising %s failed: %s", kParts[gi].live, hipGetErrorString(e));
+}
+
+// Array w of a fresh part from one row of row_bytes bytes, the same for every robot (blocking).
+int fill_rows(mpcq_session* s, int gi, const Group& g, int w, const void* row, size_t row_bytes) {
+  char* h = (char*)malloc(g.bytes[w]);
+  if (!h) return fail(MPCQ_E_NOMEM, "host malloc failed");
+  for (size_t off = 0; off < g.bytes[w]; off += row_bytes) memcpy(h + off, row, row_bytes);
+  hipError_t e = hipMemcpyAsync(g.ptr[w], h, g.bytes[w], hipMemcpyHostToDevice, s->ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(s->ctx->stream);
+  free(h);
+  return e == hipSuccess ? MPCQ_OK : init_failed(gi, e);
+}
+
+// A part whose rows missed the ticks since its stage was disabled: arrays [w0, w1) zero again.
+int rezero(mpcq_session* s, int gi, int w0, int w1) {
+  const Group& g = s->grp[gi];
+  for (int w = w0; w < w1; ++w) HIP_TRY(hipMemsetAsync(g.ptr[w], 0, g.bytes[w], s->ctx->stream));
+  return MPCQ_OK;
+}
+
+int disable_part(mpcq_session* s, int gi) {  // (the arrays stay)
+  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
+  s->on[gi] = false;
+  return MPCQ_OK;
+}
+
+// The array behind an id of part gi, for the _read / _write / _device_ptr entry points.
+int find(const mpcq_session* s, int gi, int what) {
+  const Part& p = kParts[gi];
+  if (what < 0 || what >= p.named) return fail(MPCQ_E_INVALID, "unknown %s array %d", p.kind, what);
+  if (!s->grp[gi].ptr[what])
+    return fail(MPCQ_E_INVALID, "%s array %d needs mpcq_session_enable_%s", p.kind, what, p.enable);
+  return MPCQ_OK;
+}
+
+int group_read(mpcq_session* s, int gi, int what, void* dst, uint32_t flags) {
+  if (!s || !dst) return fail(MPCQ_E_INVALID, "NULL argument");
+  const int rc = find(s, gi, what);
+  if (rc) return rc;
+  const Group& g = s->grp[gi];
   DeviceGuard dg(s->ctx->device);
   const hipMemcpyKind kind = (flags & MPCQ_FLAG_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
   HIP_TRY(hipMemcpyAsync(dst, g.ptr[what], g.bytes[what], kind, s->ctx->stream));
@@ -173,11 +169,48 @@ int group_read(mpcq_session* s, Group mpcq_session::*group, int what, void* dst,
   return MPCQ_OK;
 }
 
-int group_device_ptr(mpcq_session* s, Group mpcq_session::*group, int what, void** out) {
+int group_device_ptr(mpcq_session* s, int gi, int what, void** out) {
   if (!s || !out) return fail(MPCQ_E_INVALID, "NULL argument");
-  const int rc = find(s->*group, what);
+  const int rc = find(s, gi, what);
   if (rc) return rc;
-  *out = (s->*group).ptr[what];
+  *out = s->grp[gi].ptr[what];
+  return MPCQ_OK;
+}
+
+// A table of robots seen as its part: one array, there while the table is in force (the Table<>
+// owns the memory).
+void table_part(mpcq_session* s, int gi, const RobotTable& t) {
+  Group g;
+  if (t.count > 0) {
+    g.ptr[0] = t.dev;
+    g.bytes[0] = kParts[gi].bytes(0, (size_t)s->B, s->ctx->N, 0);
+  }
+  s->grp[gi] = g;
+}
+
+// The session's own table (robots, weights or disturbance) into `out`, or without one B records
+// of `dflt`; the bytes the caller receives are the table's, to a host or a device pointer.
+template <class R>
+int get_table_t(mpcq_session* s, const Table<R>& t, const R& dflt, R* out, uint32_t flags) {
+  mpcq_ctx* c = s->ctx;
+  DeviceGuard g(c->device);
+  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
+  const size_t nb = (size_t)s->B * sizeof(R);
+  if (t.count) {
+    HIP_TRY(hipMemcpyAsync(out, t.dev, nb, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MPCQ_OK;
+  }
+  if (!dev) {
+    for (int64_t b = 0; b < s->B; ++b) out[b] = dflt;
+    return MPCQ_OK;
+  }
+  R* h = (R*)malloc(nb);
+  if (!h) return fail(MPCQ_E_NOMEM, "host malloc failed");
+  for (int64_t b = 0; b < s->B; ++b) h[b] = dflt;
+  const hipError_t e = hipMemcpy(out, h, nb, hipMemcpyHostToDevice);
+  free(h);
+  HIP_TRY(e);
   return MPCQ_OK;
 }
 
@@ -189,8 +222,8 @@ template <class T>
 const T* staged(mpcq_session* s, bool dev, const T* src, int buf, hipError_t* e) {
   if (!src || dev) return src;
   if (*e == hipSuccess)
-    *e = hipMemcpyAsync(s->sv.ptr[buf], src, s->sv.bytes[buf], hipMemcpyHostToDevice, s->ctx->stream);
-  return (const T*)s->sv.ptr[buf];
+    *e = hipMemcpyAsync(s->grp[G_MAIN].ptr[buf], src, s->grp[G_MAIN].bytes[buf], hipMemcpyHostToDevice, s->ctx->stream);
+  return (const T*)s->grp[G_MAIN].ptr[buf];
 }
 
 // What mpcq_session_reset enqueues on the context's stream, from device pointers: the reset
@@ -199,7 +232,7 @@ const T* staged(mpcq_session* s, bool dev, const T* src, int buf, hipError_t* e)
 // mpcq_session_create: the creation state is what reset_kernel writes, and nothing else.
 hipError_t enqueue_reset(mpcq_session* s, const int32_t* mask, const double* gait0, const double* q_w0, bool mark) {
   mpcq_ctx* c = s->ctx;
-  const Group& v = s->sv;
+  const Group& v = s->grp[G_MAIN];
   mpcq::ResetArgs ra{};
   ra.batch = s->B; ra.N = c->N; ra.mask = mask; ra.q_w0 = q_w0;
   ra.gait_src = gait0 ? gait0 : v.d(SP_GAIT_INIT);
@@ -212,14 +245,14 @@ hipError_t enqueue_reset(mpcq_session* s, const int32_t* mask, const double* gai
   ra.x_robot = v.d(MPCQ_SV_X_ROBOT); ra.cost = v.d(MPCQ_SV_COST);
   ra.status = v.i(MPCQ_SV_STATUS); ra.iters = v.i(MPCQ_SV_ITERS);
   ra.first = mark ? v.i(MPCQ_SV_FIRST) : nullptr;
-  if (s->swing) {
+  if (s->on[G_SWING]) {
     ra.swing_ref = v.d(MPCQ_SV_SWING_REF); ra.swing_ref_doubles = (int64_t)s->sp.k_mpc * 36;
     ra.swing_state = v.d(MPCQ_SV_SWING_STATE); ra.frame = v.d(MPCQ_SV_FRAME);
   }
-  if (s->mv.mem) {  // a reset robot's running episode is discarded
-    ra.ep = s->mv.d(MPCQ_MV_EP); ra.ep_ticks = s->mv.i(MPCQ_MV_EP_TICKS);
+  if (s->grp[G_MONITOR].mem) {  // a reset robot's running episode is discarded
+    ra.ep = s->grp[G_MONITOR].d(MPCQ_MV_EP); ra.ep_ticks = s->grp[G_MONITOR].i(MPCQ_MV_EP_TICKS);
   }
-  if (s->gv.mem) ra.gstate = s->gv.i(MPCQ_GV_STATE);  // no request, the table's own roll
+  if (s->grp[G_GAIT].mem) ra.gstate = s->grp[G_GAIT].i(MPCQ_GV_STATE);  // no request, the table's own roll
   hipError_t e = mpcq::launch_reset(ra, c->stream);
   // the robots with a pending reset to the front of the next solve's dispatch (a session that
   // has not ticked yet has no order in use: it keeps the identity)
@@ -227,14 +260,6 @@ hipError_t enqueue_reset(mpcq_session* s, const int32_t* mask, const double* gai
     e = mpcq::launch_order(v.i(MPCQ_SV_ITERS), ra.first, s->B, v.i(MPCQ_SV_ORDER), c->stream);
   if (mark) s->resets = true;
   return e;
-}
-
-// The plant's arrays, all zero: made by the first mpcq_session_enable_plant / _set_wrench.
-int ensure_plant_mem(mpcq_session* s) {
-  if (s->pv.mem) return MPCQ_OK;
-  size_t nb[PP_COUNT];
-  plant_bytes((size_t)s->B, nb);
-  return alloc_group(s->ctx, "the plant arrays", PP_COUNT, nb, &s->pv.mem, s->pv.ptr, s->pv.bytes);
 }
 
 // The table of the robots the plant moves, or null (the context's params): the plant's own,
@@ -247,13 +272,13 @@ const mpcq_robot* plant_table(const mpcq_session* s) {
 // init the one mpcq_session_enable_scenario enqueues.
 hipError_t enqueue_scenario(mpcq_session* s, const mpcq_scenario_params& sc, const int32_t* first, bool all_first,
                             bool init) {
-  const Group& v = s->cv;
+  const Group& v = s->grp[G_SCENARIO];
   mpcq::ScenarioArgs a{};
   a.batch = s->B; a.first = first; a.all_first = all_first; a.init = init;
   a.epoch = v.i(MPCQ_CV_EPOCH); a.tick = v.i(MPCQ_CV_TICK);
   a.base = plant_table(s);
   mpcq_default_robot(&s->ctx->p, &a.dflt);
-  a.wrench_in = s->pv.mem ? s->pv.d(MPCQ_PV_WRENCH) : nullptr;
+  a.wrench_in = s->grp[G_PLANT].mem ? s->grp[G_PLANT].d(MPCQ_PV_WRENCH) : nullptr;
   a.v_ref = v.d(MPCQ_CV_V_REF); a.push = v.d(MPCQ_CV_PUSH); a.wrench_out = v.d(MPCQ_CV_WRENCH);
   a.robots_out = (mpcq_robot*)v.ptr[MPCQ_CV_ROBOTS]; a.draw = v.d(MPCQ_CV_DRAW);
   return mpcq::launch_scenario(sc, a, s->ctx->stream);
@@ -309,10 +334,8 @@ int mpcq_session_create(mpcq_ctx* c, int64_t B, const mpcq_planner_params* pp, c
     const char* e = getenv("MPCQ_DISPATCH_ORDER");
     s->use_order = !(e && e[0] == '0');
   }
-  size_t nb[SP_COUNT];
-  for (int w = 0; w < SP_COUNT; ++w) nb[w] = sv_bytes(w, B, N);
   DeviceGuard g(c->device);
-  rc = alloc_group(c, "the session", SP_COUNT, nb, &s->sv.mem, s->sv.ptr, s->sv.bytes);
+  rc = ensure_part(s, G_MAIN, no_fill);
   if (rc) {
     free(h);
     delete s;
@@ -321,7 +344,7 @@ int mpcq_session_create(mpcq_ctx* c, int64_t B, const mpcq_planner_params* pp, c
   // every array defined before the first tick: the table a reset without gait0 goes back to,
   // the order, and what a reset of every robot writes (the gait table from gait_init) -- but
   // with no reset pending: MPCQ_SV_FIRST stays zero
-  const Group& v = s->sv;
+  const Group& v = s->grp[G_MAIN];
   hipError_t e = hipMemcpyAsync(v.ptr[SP_GAIT_INIT], gait0, v.bytes[SP_GAIT_INIT], hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess)
     e = hipMemcpyAsync(v.ptr[MPCQ_SV_ORDER], ident, v.bytes[MPCQ_SV_ORDER], hipMemcpyHostToDevice, c->stream);
@@ -338,23 +361,16 @@ int mpcq_session_create(mpcq_ctx* c, int64_t B, const mpcq_planner_params* pp, c
 
 int mpcq_session_destroy(mpcq_session* s) {
   if (!s) return MPCQ_OK;
-  if (s->sv.mem) {
+  if (s->grp[G_MAIN].mem) {
     DeviceGuard g(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);
-    (void)hipFree(s->sv.mem);
-    if (s->swing_mem) (void)hipFree(s->swing_mem);
+    for (int gi = 0; gi < G_COUNT; ++gi)
+      if (s->grp[gi].mem) (void)hipFree(s->grp[gi].mem);
     if (s->robots.dev) (void)hipFree(s->robots.dev);
-    if (s->pv.mem) (void)hipFree(s->pv.mem);
     if (s->plant_robots.dev) (void)hipFree(s->plant_robots.dev);
     if (s->weights.dev) (void)hipFree(s->weights.dev);
     if (s->disturb.dev) (void)hipFree(s->disturb.dev);
     mpcq::free_tables(s->fill);
-    if (s->mv.mem) (void)hipFree(s->mv.mem);
-    if (s->cv.mem) (void)hipFree(s->cv.mem);
-    if (s->hv.mem) (void)hipFree(s->hv.mem);
-    if (s->ev.mem) (void)hipFree(s->ev.mem);
-    if (s->gv.mem) (void)hipFree(s->gv.mem);
-    if (s->dv.mem) (void)hipFree(s->dv.mem);
     (void)mpcq_session_snapshot_destroy(s->fork_snap);
   }
   delete s;
@@ -363,35 +379,17 @@ int mpcq_session_destroy(mpcq_session* s) {
 
 int mpcq_session_set_robots(mpcq_session* s, const mpcq_robot* robots, uint32_t flags) {
   if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
-  return set_table(s->ctx, s->robots, robots ? s->B : 0, robots, flags);
+  const int rc = set_table(s->ctx, s->robots, robots ? s->B : 0, robots, flags);
+  table_part(s, G_ROBOTS, s->robots);
+  return rc;
 }
 
 int mpcq_session_get_robots(mpcq_session* s, mpcq_robot* robots, uint32_t flags) {
   if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
   if (!robots) return fail(MPCQ_E_INVALID, "robots is NULL");
-  mpcq_ctx* c = s->ctx;
-  DeviceGuard g(c->device);
-  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
-  const size_t nb = (size_t)s->B * sizeof(mpcq_robot);
-  if (s->robots.count) {
-    HIP_TRY(hipMemcpyAsync(robots, s->robots.dev, nb, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
-                           c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return MPCQ_OK;
-  }
   mpcq_robot d;
-  mpcq_default_robot(&c->p, &d);
-  if (!dev) {
-    for (int64_t b = 0; b < s->B; ++b) robots[b] = d;
-    return MPCQ_OK;
-  }
-  mpcq_robot* h = (mpcq_robot*)malloc(nb);
-  if (!h) return fail(MPCQ_E_NOMEM, "host malloc failed");
-  for (int64_t b = 0; b < s->B; ++b) h[b] = d;
-  const hipError_t e = hipMemcpy(robots, h, nb, hipMemcpyHostToDevice);
-  free(h);
-  HIP_TRY(e);
-  return MPCQ_OK;
+  mpcq_default_robot(&s->ctx->p, &d);
+  return get_table_t(s, s->robots, d, robots, flags);
 }
 
 int mpcq_session_set_weights(mpcq_session* s, const mpcq_weights* weights, uint32_t flags) {
@@ -402,29 +400,9 @@ int mpcq_session_set_weights(mpcq_session* s, const mpcq_weights* weights, uint3
 int mpcq_session_get_weights(mpcq_session* s, mpcq_weights* weights, uint32_t flags) {
   if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
   if (!weights) return fail(MPCQ_E_INVALID, "weights is NULL");
-  mpcq_ctx* c = s->ctx;
-  DeviceGuard g(c->device);
-  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
-  const size_t nb = (size_t)s->B * sizeof(mpcq_weights);
-  if (s->weights.count) {
-    HIP_TRY(hipMemcpyAsync(weights, s->weights.dev, nb, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
-                           c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return MPCQ_OK;
-  }
   mpcq_weights d;
-  mpcq_default_weights(&c->p, &d);
-  if (!dev) {
-    for (int64_t b = 0; b < s->B; ++b) weights[b] = d;
-    return MPCQ_OK;
-  }
-  mpcq_weights* h = (mpcq_weights*)malloc(nb);
-  if (!h) return fail(MPCQ_E_NOMEM, "host malloc failed");
-  for (int64_t b = 0; b < s->B; ++b) h[b] = d;
-  const hipError_t e = hipMemcpy(weights, h, nb, hipMemcpyHostToDevice);
-  free(h);
-  HIP_TRY(e);
-  return MPCQ_OK;
+  mpcq_default_weights(&s->ctx->p, &d);
+  return get_table_t(s, s->weights, d, weights, flags);
 }
 
 int mpcq_session_set_disturbance(mpcq_session* s, const mpcq_disturbance* table, uint32_t flags) {
@@ -435,22 +413,7 @@ int mpcq_session_set_disturbance(mpcq_session* s, const mpcq_disturbance* table,
 int mpcq_session_get_disturbance(mpcq_session* s, mpcq_disturbance* table, uint32_t flags) {
   if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
   if (!table) return fail(MPCQ_E_INVALID, "table is NULL");
-  mpcq_ctx* c = s->ctx;
-  DeviceGuard g(c->device);
-  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
-  const size_t nb = (size_t)s->B * sizeof(mpcq_disturbance);
-  if (s->disturb.count) {
-    HIP_TRY(hipMemcpyAsync(table, s->disturb.dev, nb, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
-                           c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return MPCQ_OK;
-  }
-  if (!dev) {  // (without a table: no disturbance)
-    memset(table, 0, nb);
-    return MPCQ_OK;
-  }
-  HIP_TRY(hipMemset(table, 0, nb));
-  return MPCQ_OK;
+  return get_table_t(s, s->disturb, mpcq_disturbance{}, table, flags);  // (without a table: no disturbance)
 }
 
 int mpcq_session_enable_swing(mpcq_session* s, const mpcq_swing_params* sp) {
@@ -458,19 +421,13 @@ int mpcq_session_enable_swing(mpcq_session* s, const mpcq_swing_params* sp) {
   mpcq_swing_params P;
   int rc = swing_params(sp, &P);
   if (rc) return rc;
-  if (s->swing) {
-    if (P.k_mpc != s->sp.k_mpc) return fail(MPCQ_E_INVALID, "swing is enabled with k_mpc = %d", s->sp.k_mpc);
-    s->sp = P;
-    return MPCQ_OK;
-  }
-  size_t nb[3];  // all-zero state = new generators
-  swing_bytes((size_t)s->B, P.k_mpc, nb);
+  if (s->on[G_SWING] && P.k_mpc != s->sp.k_mpc)
+    return fail(MPCQ_E_INVALID, "swing is enabled with k_mpc = %d", s->sp.k_mpc);
   DeviceGuard g(s->ctx->device);
-  rc = alloc_group(s->ctx, "the swing arrays", 3, nb, &s->swing_mem, s->sv.ptr + MPCQ_SV_SWING_REF,
-                   s->sv.bytes + MPCQ_SV_SWING_REF);
+  rc = ensure_part(s, G_SWING, no_fill, P.k_mpc);  // all-zero state = new generators
   if (rc) return rc;
   s->sp = P;
-  s->swing = true;
+  s->on[G_SWING] = true;
   return MPCQ_OK;
 }
 
@@ -482,33 +439,31 @@ int mpcq_session_enable_plant(mpcq_session* s, const mpcq_plant_params* pl) {
   if (P.dt != s->ctx->p.dt)
     return fail(MPCQ_E_INVALID, "the plant's dt %g is not the context's %g", P.dt, s->ctx->p.dt);
   DeviceGuard g(s->ctx->device);
-  rc = ensure_plant_mem(s);
+  rc = ensure_part(s, G_PLANT, no_fill);
   if (rc) return rc;
   s->pl = P;
-  s->plant = true;
+  s->on[G_PLANT] = true;
   return MPCQ_OK;
 }
 
-int mpcq_session_disable_plant(mpcq_session* s) {
-  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
-  s->plant = false;
-  return MPCQ_OK;
-}
+int mpcq_session_disable_plant(mpcq_session* s) { return disable_part(s, G_PLANT); }
 
 int mpcq_session_set_plant_robots(mpcq_session* s, const mpcq_robot* robots, uint32_t flags) {
   if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
-  return set_table(s->ctx, s->plant_robots, robots ? s->B : 0, robots, flags);
+  const int rc = set_table(s->ctx, s->plant_robots, robots ? s->B : 0, robots, flags);
+  table_part(s, G_PLANT_ROBOTS, s->plant_robots);
+  return rc;
 }
 
 int mpcq_session_set_wrench(mpcq_session* s, const double* wrench, uint32_t flags) {
   if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
   mpcq_ctx* c = s->ctx;
   DeviceGuard g(c->device);
-  const int rc = ensure_plant_mem(s);
+  const int rc = ensure_part(s, G_PLANT, no_fill);  // (the first of this and mpcq_session_enable_plant makes it)
   if (rc) return rc;
   const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
-  void* dst = s->pv.ptr[MPCQ_PV_WRENCH];
-  const size_t nb = s->pv.bytes[MPCQ_PV_WRENCH];
+  void* dst = s->grp[G_PLANT].ptr[MPCQ_PV_WRENCH];
+  const size_t nb = s->grp[G_PLANT].bytes[MPCQ_PV_WRENCH];
   // on the context's stream: behind every queued tick that still reads the old wrench
   if (!wrench) HIP_TRY(hipMemsetAsync(dst, 0, nb, c->stream));
   else HIP_TRY(hipMemcpyAsync(dst, wrench, nb, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
@@ -521,70 +476,36 @@ int mpcq_session_enable_monitor(mpcq_session* s, const mpcq_monitor_params* mp) 
   mpcq_monitor_params P;
   int rc = monitor_params(mp, &P);
   if (rc) return rc;
-  if (!s->mv.mem) {  // the arrays, zero but for ep[4] = +inf
-    mpcq_ctx* c = s->ctx;
-    DeviceGuard g(c->device);
-    const size_t B = (size_t)s->B;
-    size_t nb[MPCQ_MV_COUNT];
-    monitor_bytes(B, nb);
-    double* h = (double*)malloc(nb[MPCQ_MV_EP]);
-    if (!h) return fail(MPCQ_E_NOMEM, "host malloc failed");
-    for (size_t e = 0; e < B * 8; ++e) h[e] = e % 8 == 4 ? INFINITY : 0.0;
-    Group mv = s->mv;
-    rc = alloc_group(c, "the monitor arrays", MPCQ_MV_COUNT, nb, &mv.mem, mv.ptr, mv.bytes);
-    hipError_t e = hipSuccess;
-    if (!rc) e = hipMemcpyAsync(mv.ptr[MPCQ_MV_EP], h, nb[MPCQ_MV_EP], hipMemcpyHostToDevice, c->stream);
-    if (!rc && e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    free(h);
-    if (rc) return rc;
-    if (e != hipSuccess) {
-      (void)hipFree(mv.mem);
-      return fail(MPCQ_E_DEVICE, "initialising the monitor arrays failed: %s", hipGetErrorString(e));
-    }
-    s->mv = mv;
-  }
+  DeviceGuard g(s->ctx->device);
+  const double ep0[8] = {0.0, 0.0, 0.0, 0.0, INFINITY, 0.0, 0.0, 0.0};  // the arrays, zero but for ep[4] = +inf
+  rc = ensure_part(s, G_MONITOR,
+                   [&](const Group& m) { return fill_rows(s, G_MONITOR, m, MPCQ_MV_EP, ep0, sizeof(ep0)); });
+  if (rc) return rc;
   s->mp = P;
-  s->monitor = true;
+  s->on[G_MONITOR] = true;
   return MPCQ_OK;
 }
 
-int mpcq_session_disable_monitor(mpcq_session* s) {
-  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
-  s->monitor = false;
-  return MPCQ_OK;
-}
+int mpcq_session_disable_monitor(mpcq_session* s) { return disable_part(s, G_MONITOR); }
 
 int mpcq_session_enable_scenario(mpcq_session* s, const mpcq_scenario_params* sc) {
   if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
   mpcq_scenario_params P;
   int rc = scenario_params(sc, &P);
   if (rc) return rc;
-  if (!s->cv.mem) {  // the arrays, zero; the launch gives every robot the draw of epoch 0
-    size_t nb[MPCQ_CV_COUNT];
-    scenario_bytes((size_t)s->B, nb);
-    DeviceGuard g(s->ctx->device);
-    Group cv = s->cv;
-    rc = alloc_group(s->ctx, "the scenario arrays", MPCQ_CV_COUNT, nb, &cv.mem, cv.ptr, cv.bytes);
-    if (rc) return rc;
-    s->cv = cv;
+  DeviceGuard g(s->ctx->device);
+  // the arrays, zero; the launch gives every robot the draw of epoch 0
+  rc = ensure_part(s, G_SCENARIO, [&](const Group&) {
     const hipError_t e = enqueue_scenario(s, P, nullptr, false, true);
-    if (e != hipSuccess) {
-      (void)hipStreamSynchronize(s->ctx->stream);
-      (void)hipFree(cv.mem);
-      s->cv = Group{"scenario", "scenario", MPCQ_CV_COUNT};
-      return fail(MPCQ_E_DEVICE, "initialising the scenario arrays failed: %s", hipGetErrorString(e));
-    }
-  }
+    return e == hipSuccess ? MPCQ_OK : init_failed(G_SCENARIO, e);
+  });
+  if (rc) return rc;
   s->sc = P;
-  s->scenario = true;
+  s->on[G_SCENARIO] = true;
   return MPCQ_OK;
 }
 
-int mpcq_session_disable_scenario(mpcq_session* s) {
-  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
-  s->scenario = false;
-  return MPCQ_OK;
-}
+int mpcq_session_disable_scenario(mpcq_session* s) { return disable_part(s, G_SCENARIO); }
 
 int mpcq_session_enable_channel(mpcq_session* s, const mpcq_channel_params* ch) {
   if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
@@ -592,36 +513,21 @@ int mpcq_session_enable_channel(mpcq_session* s, const mpcq_channel_params* ch) 
   int rc = channel_params(ch, &P);
   if (rc) return rc;
   DeviceGuard g(s->ctx->device);
-  const bool fresh = !s->hv.mem;
-  Group hv = s->hv;
-  if (fresh) {  // the arrays, zero
-    size_t nb[MPCQ_HV_COUNT];
-    channel_bytes((size_t)s->B, nb);
-    rc = alloc_group(s->ctx, "the channel arrays", MPCQ_HV_COUNT, nb, &hv.mem, hv.ptr, hv.bytes);
-    if (rc) return rc;
-  }
   // the rings hold nothing the coming ticks may read: every robot primes at its next observe
-  if (!s->channel || P.delay != s->ch.delay || P.latency != s->ch.latency) {
-    const hipError_t e = mpcq::launch_channel_arm(hv.i(MPCQ_HV_CLOCK), s->B, s->ctx->stream);
-    if (e != hipSuccess) {
-      if (fresh) {
-        (void)hipStreamSynchronize(s->ctx->stream);
-        (void)hipFree(hv.mem);
-      }
-      return fail(MPCQ_E_DEVICE, "arming the channel's clock failed: %s", hipGetErrorString(e));
-    }
-  }
-  s->hv = hv;
+  auto arm = [&](const Group& h) {
+    const hipError_t e = mpcq::launch_channel_arm(h.i(MPCQ_HV_CLOCK), s->B, s->ctx->stream);
+    return e == hipSuccess ? MPCQ_OK
+                           : fail(MPCQ_E_DEVICE, "arming the channel's clock failed: %s", hipGetErrorString(e));
+  };
+  if (!s->grp[G_CHANNEL].mem) rc = ensure_part(s, G_CHANNEL, arm);  // the arrays, zero
+  else if (!s->on[G_CHANNEL] || P.delay != s->ch.delay || P.latency != s->ch.latency) rc = arm(s->grp[G_CHANNEL]);
+  if (rc) return rc;
   s->ch = P;
-  s->channel = true;
+  s->on[G_CHANNEL] = true;
   return MPCQ_OK;
 }
 
-int mpcq_session_disable_channel(mpcq_session* s) {
-  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
-  s->channel = false;
-  return MPCQ_OK;
-}
+int mpcq_session_disable_channel(mpcq_session* s) { return disable_part(s, G_CHANNEL); }
 
 int mpcq_session_enable_estimator(mpcq_session* s, const mpcq_estimator_params* ep) {
   if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
@@ -629,26 +535,16 @@ int mpcq_session_enable_estimator(mpcq_session* s, const mpcq_estimator_params* 
   int rc = estimator_params(ep, &P);
   if (rc) return rc;
   DeviceGuard g(s->ctx->device);
-  if (!s->ev.mem) {  // the arrays, zero: every filter invalid
-    size_t nb[MPCQ_EV_COUNT];
-    estimator_bytes((size_t)s->B, nb);
-    Group ev = s->ev;
-    rc = alloc_group(s->ctx, "the estimator arrays", MPCQ_EV_COUNT, nb, &ev.mem, ev.ptr, ev.bytes);
-    if (rc) return rc;
-    s->ev = ev;
-  } else if (!s->estimator) {  // the rings missed the ticks since the disable: every filter invalid again
-    HIP_TRY(hipMemsetAsync(s->ev.ptr[MPCQ_EV_ROW], 0, s->ev.bytes[MPCQ_EV_ROW], s->ctx->stream));
-  }
+  // the arrays, zero: every filter invalid (again, where the rings missed the ticks since a disable)
+  if (s->grp[G_ESTIMATOR].mem && !s->on[G_ESTIMATOR]) rc = rezero(s, G_ESTIMATOR, MPCQ_EV_ROW, MPCQ_EV_ROW + 1);
+  else rc = ensure_part(s, G_ESTIMATOR, no_fill);
+  if (rc) return rc;
   s->ep = P;
-  s->estimator = true;
+  s->on[G_ESTIMATOR] = true;
   return MPCQ_OK;
 }
 
-int mpcq_session_disable_estimator(mpcq_session* s) {
-  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
-  s->estimator = false;
-  return MPCQ_OK;
-}
+int mpcq_session_disable_estimator(mpcq_session* s) { return disable_part(s, G_ESTIMATOR); }
 
 int mpcq_session_enable_disturb(mpcq_session* s, const mpcq_disturb_params* dp) {
   if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
@@ -656,27 +552,16 @@ int mpcq_session_enable_disturb(mpcq_session* s, const mpcq_disturb_params* dp) 
   int rc = disturb_params(dp, &P);
   if (rc) return rc;
   DeviceGuard g(s->ctx->device);
-  if (!s->dv.mem) {  // the arrays, zero: every row invalid, no disturbance
-    size_t nb[MPCQ_DV_COUNT];
-    disturb_bytes((size_t)s->B, nb);
-    Group dv = s->dv;
-    rc = alloc_group(s->ctx, "the disturb arrays", MPCQ_DV_COUNT, nb, &dv.mem, dv.ptr, dv.bytes);
-    if (rc) return rc;
-    s->dv = dv;
-  } else if (!s->disturb_on) {  // the rings missed the ticks since the disable: every row invalid again
-    for (int w = 0; w < MPCQ_DV_COUNT; ++w)
-      HIP_TRY(hipMemsetAsync(s->dv.ptr[w], 0, s->dv.bytes[w], s->ctx->stream));
-  }
+  // the arrays, zero: every row invalid, no disturbance (again, after a disable)
+  if (s->grp[G_DISTURB].mem && !s->on[G_DISTURB]) rc = rezero(s, G_DISTURB, 0, MPCQ_DV_COUNT);
+  else rc = ensure_part(s, G_DISTURB, no_fill);
+  if (rc) return rc;
   s->dp = P;
-  s->disturb_on = true;
+  s->on[G_DISTURB] = true;
   return MPCQ_OK;
 }
 
-int mpcq_session_disable_disturb(mpcq_session* s) {
-  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
-  s->disturb_on = false;
-  return MPCQ_OK;
-}
+int mpcq_session_disable_disturb(mpcq_session* s) { return disable_part(s, G_DISTURB); }
 
 int mpcq_session_enable_gait(mpcq_session* s, const mpcq_gait_params* gp, const double* cycles) {
   if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
@@ -684,43 +569,24 @@ int mpcq_session_enable_gait(mpcq_session* s, const mpcq_gait_params* gp, const 
   mpcq::GaitArgs lib{};
   int rc = gait_params(gp, cycles, &P, &lib);
   if (rc) return rc;
-  if (!s->gv.mem) {  // the rows, every one (-1, -1, 0, 0)
-    mpcq_ctx* c = s->ctx;
-    DeviceGuard g(c->device);
-    const size_t nb[MPCQ_GV_COUNT] = {(size_t)s->B * 16};
-    int32_t* h = (int32_t*)malloc(nb[0]);
-    if (!h) return fail(MPCQ_E_NOMEM, "host malloc failed");
-    for (size_t e = 0; e < (size_t)s->B * 4; ++e) h[e] = e % 4 < 2 ? -1 : 0;
-    Group gv = s->gv;
-    rc = alloc_group(c, "the gait array", MPCQ_GV_COUNT, nb, &gv.mem, gv.ptr, gv.bytes);
-    hipError_t e = hipSuccess;
-    if (!rc) e = hipMemcpyAsync(gv.ptr[MPCQ_GV_STATE], h, nb[0], hipMemcpyHostToDevice, c->stream);
-    if (!rc && e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    free(h);
-    if (rc) return rc;
-    if (e != hipSuccess) {
-      (void)hipFree(gv.mem);
-      return fail(MPCQ_E_DEVICE, "initialising the gait array failed: %s", hipGetErrorString(e));
-    }
-    s->gv = gv;
-  }
+  DeviceGuard g(s->ctx->device);
+  const int32_t row0[4] = {-1, -1, 0, 0};  // the rows, every one (want, active, phase, switches) = (-1, -1, 0, 0)
+  rc = ensure_part(s, G_GAIT,
+                   [&](const Group& v) { return fill_rows(s, G_GAIT, v, MPCQ_GV_STATE, row0, sizeof(row0)); });
+  if (rc) return rc;
   // (by value into every later launch's arguments: a queued tick keeps the library it was launched with)
   s->gp = P;
   s->gait_lib = lib;
-  s->gait = true;
+  s->on[G_GAIT] = true;
   return MPCQ_OK;
 }
 
-int mpcq_session_disable_gait(mpcq_session* s) {
-  if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
-  s->gait = false;
-  return MPCQ_OK;
-}
+int mpcq_session_disable_gait(mpcq_session* s) { return disable_part(s, G_GAIT); }
 
 int mpcq_session_set_gait(mpcq_session* s, const int32_t* ids, uint32_t flags) {
   if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
   if (!ids) return fail(MPCQ_E_INVALID, "ids is NULL");
-  if (!s->gait) return fail(MPCQ_E_INVALID, "mpcq_session_set_gait needs mpcq_session_enable_gait");
+  if (!s->on[G_GAIT]) return fail(MPCQ_E_INVALID, "mpcq_session_set_gait needs mpcq_session_enable_gait");
   if (s->gp.select != MPCQ_GAIT_MANUAL)
     return fail(MPCQ_E_INVALID, "mpcq_session_set_gait is refused under MPCQ_GAIT_BY_SPEED: the kernel owns want");
   const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
@@ -732,7 +598,7 @@ int mpcq_session_set_gait(mpcq_session* s, const int32_t* ids, uint32_t flags) {
   mpcq_ctx* c = s->ctx;
   DeviceGuard g(c->device);
   // want alone: element 0 of every 16-byte row, on the context's stream (behind the queued ticks)
-  HIP_TRY(hipMemcpy2DAsync(s->gv.ptr[MPCQ_GV_STATE], 16, ids, 4, 4, (size_t)s->B,
+  HIP_TRY(hipMemcpy2DAsync(s->grp[G_GAIT].ptr[MPCQ_GV_STATE], 16, ids, 4, 4, (size_t)s->B,
                            dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
   if (!(flags & MPCQ_FLAG_ASYNC) || !dev) HIP_TRY(hipStreamSynchronize(c->stream));
   return MPCQ_OK;
@@ -761,7 +627,7 @@ struct Tick {
 // lives in arrays the retrieve kernel rewrites: this tick reads a copy.
 int tick_inputs(mpcq_session* s, const double* state, const double* l_feet, const double* v_ref,
                 const int32_t* reduced, bool dev, Tick& t) {
-  const Group& v = s->sv;
+  const Group& v = s->grp[G_MAIN];
   hipStream_t st = s->ctx->stream;
   hipError_t e = hipSuccess;
   t.state = staged(s, dev, state, SP_IN_STATE, &e);
@@ -786,7 +652,7 @@ int tick_inputs(mpcq_session* s, const double* state, const double* l_feet, cons
 // This tick's command, push and (on a first tick) true robots; it takes the first flags as
 // the planner will.
 int tick_scenario(mpcq_session* s, int k) {
-  const int32_t* first = s->resets && k != 0 ? s->sv.i(MPCQ_SV_FIRST) : nullptr;
+  const int32_t* first = s->resets && k != 0 ? s->grp[G_MAIN].i(MPCQ_SV_FIRST) : nullptr;
   HIP_TRY(enqueue_scenario(s, s->sc, first, k == 0, false));
   return MPCQ_OK;
 }
@@ -794,7 +660,7 @@ int tick_scenario(mpcq_session* s, int k) {
 // The channel's measurement model: the planner's state becomes the observation of the truth
 // (t.state, which the plant keeps); it takes the first flags as the planner will.
 int tick_observe(mpcq_session* s, Tick& t) {
-  const Group& h = s->hv;
+  const Group& h = s->grp[G_CHANNEL];
   mpcq::ObserveArgs a{};
   a.batch = s->B; a.first = t.first_k; a.all_first = t.k == 0; a.truth = t.state;
   a.clock = h.i(MPCQ_HV_CLOCK); a.obs = h.d(MPCQ_HV_OBS); a.draw = h.d(MPCQ_HV_DRAW);
@@ -809,7 +675,7 @@ int tick_observe(mpcq_session* s, Tick& t) {
 // tick's planner, and the model's robots; it takes the first flags as the planner will.
 int tick_estimate(mpcq_session* s, Tick& t) {
   mpcq_ctx* c = s->ctx;
-  const Group &v = s->sv, &e = s->ev;
+  const Group &v = s->grp[G_MAIN], &e = s->grp[G_ESTIMATOR];
   mpcq::EstimateArgs a{};
   a.batch = s->B; a.first = t.first_k; a.all_first = t.k == 0; a.obs = t.plan_state;
   a.f_prev = v.d(MPCQ_SV_F0); a.fsteps = v.d(MPCQ_SV_FSTEPS);
@@ -828,7 +694,7 @@ int tick_estimate(mpcq_session* s, Tick& t) {
 // this tick's planner, and the model's robots; it takes the first flags as the planner will.
 int tick_disturb(mpcq_session* s, const Tick& t) {
   mpcq_ctx* c = s->ctx;
-  const Group &v = s->sv, &d = s->dv;
+  const Group &v = s->grp[G_MAIN], &d = s->grp[G_DISTURB];
   mpcq::DisturbArgs a{};
   a.batch = s->B; a.first = t.first_k; a.all_first = t.k == 0; a.meas = t.plan_state;
   a.f_prev = v.d(MPCQ_SV_F0); a.fsteps = v.d(MPCQ_SV_FSTEPS);
@@ -843,9 +709,9 @@ int tick_disturb(mpcq_session* s, const Tick& t) {
 
 // The channel's actuation model: MPCQ_HV_F_CMD from this tick's (and earlier) MPCQ_SV_F0.
 int tick_actuate(mpcq_session* s) {
-  const Group& h = s->hv;
+  const Group& h = s->grp[G_CHANNEL];
   mpcq::ActuateArgs a{};
-  a.batch = s->B; a.f0 = s->sv.d(MPCQ_SV_F0); a.clock = h.i(MPCQ_HV_CLOCK); a.draw = h.d(MPCQ_HV_DRAW);
+  a.batch = s->B; a.f0 = s->grp[G_MAIN].d(MPCQ_SV_F0); a.clock = h.i(MPCQ_HV_CLOCK); a.draw = h.d(MPCQ_HV_DRAW);
   a.f_ring = h.d(MPCQ_HV_F_RING); a.f_cmd = h.d(MPCQ_HV_F_CMD);
   HIP_TRY(mpcq::launch_actuate(s->ch, a, s->ctx->stream));
   return MPCQ_OK;
@@ -854,7 +720,7 @@ int tick_actuate(mpcq_session* s) {
 // The planner (processing.py:80-89, 131), between ev[0] and ev[1].
 int tick_plan(mpcq_session* s, const Tick& t) {
   mpcq_ctx* c = s->ctx;
-  const Group& v = s->sv;
+  const Group& v = s->grp[G_MAIN];
   mpcq::PlanArgs a{};
   a.batch = s->B; a.N = c->N; a.k = t.k; a.first = t.first_k;
   a.state = t.plan_state; a.l_feet = t.l_feet; a.v_ref = t.v_ref; a.reduced = t.reduced;
@@ -866,9 +732,9 @@ int tick_plan(mpcq_session* s, const Tick& t) {
     HIP_TRY(mpcq::launch_plan(s->pp, a, c->stream));
   }
   a.ops = MPCQ_PLAN_TICK;
-  if (s->gait) {  // the gait stage rolls in the planner's place, on the command the planner reads
+  if (s->on[G_GAIT]) {  // the gait stage rolls in the planner's place, on the command the planner reads
     mpcq::GaitArgs ga = s->gait_lib;
-    ga.batch = s->B; ga.v_ref = t.v_ref; ga.gait = v.d(MPCQ_SV_GAIT); ga.gstate = s->gv.i(MPCQ_GV_STATE);
+    ga.batch = s->B; ga.v_ref = t.v_ref; ga.gait = v.d(MPCQ_SV_GAIT); ga.gstate = s->grp[G_GAIT].i(MPCQ_GV_STATE);
     HIP_TRY(mpcq::launch_gait(s->gp, ga, c->stream));
     a.ops = MPCQ_PLAN_FOOTSTEPS | MPCQ_PLAN_REFSTATES;
   }
@@ -882,7 +748,7 @@ int tick_plan(mpcq_session* s, const Tick& t) {
 // and ev[3].
 int tick_solve(mpcq_session* s, const Tick& t) {
   mpcq_ctx* c = s->ctx;
-  const Group& v = s->sv;
+  const Group& v = s->grp[G_MAIN];
   mpcq::LaunchArgs a{};
   a.batch = s->B;
   a.mode = t.k == 0 ? MPCQ_MODE_SETUP : MPCQ_MODE_UPDATE;
@@ -898,9 +764,9 @@ int tick_solve(mpcq_session* s, const Tick& t) {
   a.order = s->have_order && s->use_order ? v.i(MPCQ_SV_ORDER) : nullptr;
   // a compensating disturbance stage: its estimate, ahead of the user's table
   DisturbTable est;
-  est.dev = (mpcq_disturbance*)s->dv.ptr[MPCQ_DV_DIST];
+  est.dev = (mpcq_disturbance*)s->grp[G_DISTURB].ptr[MPCQ_DV_DIST];
   est.cap = est.count = s->B;
-  const bool comp = s->disturb_on && s->dp.compensate != 0;
+  const bool comp = s->on[G_DISTURB] && s->dp.compensate != 0;
   int rc = mpcq::launch_tables(c, s->robots, &s->weights, comp ? est : s->disturb, s->fill, s->B, &a);
   if (rc) return rc;
   a.first = t.first_k;
@@ -917,7 +783,7 @@ int tick_solve(mpcq_session* s, const Tick& t) {
 // q_w that swing and plant need as it stands before the retrieve moves it.
 int tick_retrieve(mpcq_session* s, const Tick& t) {
   mpcq_ctx* c = s->ctx;
-  const Group& v = s->sv;
+  const Group& v = s->grp[G_MAIN];
   const size_t B = (size_t)s->B;
   mpcq::SessionArgs a{};
   a.batch = s->B;
@@ -931,13 +797,13 @@ int tick_retrieve(mpcq_session* s, const Tick& t) {
   a.weights = s->weights.count ? s->weights.dev : nullptr;
   for (int i = 0; i < 8; ++i) a.shoulders[i] = s->pp.shoulders[i];
   a.first = t.first;
-  if (s->swing) {  // the frame of this tick's fsteps: q_w's x, y, yaw
+  if (s->on[G_SWING]) {  // the frame of this tick's fsteps: q_w's x, y, yaw
     double* fr = v.d(MPCQ_SV_FRAME);
     HIP_TRY(hipMemcpy2DAsync(fr, 24, a.q_w, 48, 16, B, hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(hipMemcpy2DAsync(fr + 2, 24, a.q_w + 5, 48, 8, B, hipMemcpyDeviceToDevice, c->stream));
   }
-  if (s->plant)  // the world pose the plant starts from
-    HIP_TRY(hipMemcpyAsync(s->pv.ptr[PP_QW_PREV], a.q_w, B * 48, hipMemcpyDeviceToDevice, c->stream));
+  if (s->on[G_PLANT])  // the world pose the plant starts from
+    HIP_TRY(hipMemcpyAsync(s->grp[G_PLANT].ptr[PP_QW_PREV], a.q_w, B * 48, hipMemcpyDeviceToDevice, c->stream));
   HIP_TRY(mpcq::launch_retrieve(c->N, a, c->stream));
   return MPCQ_OK;
 }
@@ -945,19 +811,19 @@ int tick_retrieve(mpcq_session* s, const Tick& t) {
 // The rigid body under this tick's forces takes the place of the prediction.
 int tick_plant(mpcq_session* s, const Tick& t) {
   mpcq_ctx* c = s->ctx;
-  const Group& v = s->sv;
+  const Group& v = s->grp[G_MAIN];
   mpcq::PlantArgs a{};
   a.batch = s->B;
   a.state = t.state; a.fsteps = v.d(MPCQ_SV_FSTEPS);
-  a.f = s->channel ? s->hv.d(MPCQ_HV_F_CMD) : v.d(MPCQ_SV_F0);  // (tick_actuate has run)
+  a.f = s->on[G_CHANNEL] ? s->grp[G_CHANNEL].d(MPCQ_HV_F_CMD) : v.d(MPCQ_SV_F0);  // (tick_actuate has run)
   // a scenario's pushes ride on the user's wrench, its robots replace the table
-  a.wrench = s->scenario && s->sc.pushes ? s->cv.d(MPCQ_CV_WRENCH) : s->pv.d(MPCQ_PV_WRENCH);
-  a.robots = s->scenario && s->sc.robots ? (const mpcq_robot*)s->cv.ptr[MPCQ_CV_ROBOTS] : plant_table(s);
+  a.wrench = s->on[G_SCENARIO] && s->sc.pushes ? s->grp[G_SCENARIO].d(MPCQ_CV_WRENCH) : s->grp[G_PLANT].d(MPCQ_PV_WRENCH);
+  a.robots = s->on[G_SCENARIO] && s->sc.robots ? (const mpcq_robot*)s->grp[G_SCENARIO].ptr[MPCQ_CV_ROBOTS] : plant_table(s);
   mpcq_default_robot(&c->p, &a.dflt);
-  a.state_out = s->pv.d(MPCQ_PV_STATE_END); a.f_eff = s->pv.d(MPCQ_PV_F_EFF);
+  a.state_out = s->grp[G_PLANT].d(MPCQ_PV_STATE_END); a.f_eff = s->grp[G_PLANT].d(MPCQ_PV_F_EFF);
   a.tail = 1;
   a.status = v.i(MPCQ_SV_STATUS); a.plan_status = v.i(SP_PLAN_STATUS); a.gait = v.d(MPCQ_SV_GAIT);
-  a.q_w_prev = s->pv.d(PP_QW_PREV); a.q_w = v.d(MPCQ_SV_Q_W);
+  a.q_w_prev = s->grp[G_PLANT].d(PP_QW_PREV); a.q_w = v.d(MPCQ_SV_Q_W);
   a.next_state = v.d(MPCQ_SV_STATE); a.next_l_feet = v.d(MPCQ_SV_L_FEET);
   for (int i = 0; i < 8; ++i) a.shoulders[i] = s->pp.shoulders[i];
   HIP_TRY(mpcq::launch_plant(s->pl, a, c->stream));
@@ -966,7 +832,7 @@ int tick_plant(mpcq_session* s, const Tick& t) {
 
 // Whose episode ended with this tick, and the episodes' statistics.
 int tick_monitor(mpcq_session* s, const Tick& t) {
-  const Group &v = s->sv, &m = s->mv;
+  const Group &v = s->grp[G_MAIN], &m = s->grp[G_MONITOR];
   mpcq::MonitorArgs a{};
   a.batch = s->B;
   a.q_w = v.d(MPCQ_SV_Q_W); a.status = v.i(MPCQ_SV_STATUS); a.iters = v.i(MPCQ_SV_ITERS); a.f0 = v.d(MPCQ_SV_F0);
@@ -981,7 +847,7 @@ int tick_monitor(mpcq_session* s, const Tick& t) {
 // The next solve's dispatch order (the retrieve has cleared every pending reset: by
 // iteration counts alone).
 int tick_order(mpcq_session* s) {
-  const Group& v = s->sv;
+  const Group& v = s->grp[G_MAIN];
   HIP_TRY(mpcq::launch_order(v.i(MPCQ_SV_ITERS), nullptr, s->B, v.i(MPCQ_SV_ORDER), s->ctx->stream));
   s->have_order = true;
   return MPCQ_OK;
@@ -989,7 +855,7 @@ int tick_order(mpcq_session* s) {
 
 // The tick's swing-foot references, substeps 0..k_mpc-1 (virtual-robot lift-off).
 int tick_swing(mpcq_session* s) {
-  const Group& v = s->sv;
+  const Group& v = s->grp[G_MAIN];
   mpcq::SwingArgs a{};
   a.batch = s->B; a.k_sub0 = 0; a.n_sub = s->sp.k_mpc;
   a.gait = v.d(MPCQ_SV_GAIT); a.fsteps = v.d(MPCQ_SV_FSTEPS); a.frame = v.d(MPCQ_SV_FRAME);
@@ -1004,7 +870,7 @@ int tick_swing(mpcq_session* s) {
 int session_tick(mpcq_session* s, int k, const double* state, const double* l_feet, const double* v_ref,
                  const int32_t* reduced, uint32_t flags, double* trace) {
   if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
-  if (!v_ref && !(s->scenario && s->sc.commands))
+  if (!v_ref && !(s->on[G_SCENARIO] && s->sc.commands))
     return fail(MPCQ_E_INVALID, "v_ref is required (without a scenario that commands)");
   if (k < 0) return fail(MPCQ_E_INVALID, "k must be >= 0");
   mpcq_ctx* c = s->ctx;
@@ -1013,23 +879,23 @@ int session_tick(mpcq_session* s, int k, const double* state, const double* l_fe
   Tick t{};
   t.k = k;
   t.trace = trace;
-  int rc = s->scenario ? tick_scenario(s, k) : MPCQ_OK;
+  int rc = s->on[G_SCENARIO] ? tick_scenario(s, k) : MPCQ_OK;
   if (!rc) rc = tick_inputs(s, state, l_feet, v_ref, reduced, dev, t);
-  if (!rc && !v_ref) t.v_ref = s->cv.d(MPCQ_CV_V_REF);
-  if (!rc && s->channel) rc = tick_observe(s, t);
-  if (!rc && s->estimator) rc = tick_estimate(s, t);
-  if (!rc && s->disturb_on) rc = tick_disturb(s, t);
+  if (!rc && !v_ref) t.v_ref = s->grp[G_SCENARIO].d(MPCQ_CV_V_REF);
+  if (!rc && s->on[G_CHANNEL]) rc = tick_observe(s, t);
+  if (!rc && s->on[G_ESTIMATOR]) rc = tick_estimate(s, t);
+  if (!rc && s->on[G_DISTURB]) rc = tick_disturb(s, t);
   if (!rc) rc = tick_plan(s, t);
   if (!rc) rc = tick_solve(s, t);
   if (!rc) rc = tick_retrieve(s, t);
-  if (!rc && s->plant && s->channel) rc = tick_actuate(s);
-  if (!rc && s->plant) rc = tick_plant(s, t);
-  if (!rc && s->monitor) rc = tick_monitor(s, t);
+  if (!rc && s->on[G_PLANT] && s->on[G_CHANNEL]) rc = tick_actuate(s);
+  if (!rc && s->on[G_PLANT]) rc = tick_plant(s, t);
+  if (!rc && s->on[G_MONITOR]) rc = tick_monitor(s, t);
   if (!rc) rc = tick_order(s);
-  if (!rc && s->swing) rc = tick_swing(s);
+  if (!rc && s->on[G_SWING]) rc = tick_swing(s);
   if (rc) return rc;
   // auto-reset, last: the swing launch above has read the tick's gait and fsteps
-  if (s->monitor && s->mp.auto_reset) HIP_TRY(enqueue_reset(s, s->mv.i(MPCQ_MV_DONE), nullptr, nullptr, true));
+  if (s->on[G_MONITOR] && s->mp.auto_reset) HIP_TRY(enqueue_reset(s, s->grp[G_MONITOR].i(MPCQ_MV_DONE), nullptr, nullptr, true));
   // host inputs are staged in buffers the next tick reuses: host calls block
   if (!(flags & MPCQ_FLAG_ASYNC) || !dev) HIP_TRY(hipStreamSynchronize(c->stream));
   return MPCQ_OK;
@@ -1048,12 +914,12 @@ int mpcq_session_run(mpcq_session* s, int k0, int n_ticks, const double* v_ref, 
                      uint32_t flags) {
   if (!s) return fail(MPCQ_E_INVALID, "session is NULL");
   if (!(flags & MPCQ_FLAG_DEVICE_PTRS)) return fail(MPCQ_E_INVALID, "mpcq_session_run needs MPCQ_FLAG_DEVICE_PTRS");
-  if (!v_ref && !(s->scenario && s->sc.commands))
+  if (!v_ref && !(s->on[G_SCENARIO] && s->sc.commands))
     return fail(MPCQ_E_INVALID, "v_ref is required (without a scenario that commands)");
   if (v_ref && v_ref_ticks < 1) return fail(MPCQ_E_INVALID, "v_ref [v_ref_ticks][B][6] needs v_ref_ticks >= 1");
   if (k0 < 0 || n_ticks < 1) return fail(MPCQ_E_INVALID, "need k0 >= 0 and n_ticks >= 1");
   if (k0 > INT32_MAX - n_ticks) return fail(MPCQ_E_INVALID, "k0 + n_ticks overflows");
-  if (trace && !s->monitor) return fail(MPCQ_E_INVALID, "a trace needs mpcq_session_enable_monitor");
+  if (trace && !s->on[G_MONITOR]) return fail(MPCQ_E_INVALID, "a trace needs mpcq_session_enable_monitor");
   const size_t B = (size_t)s->B;
   for (int t = 0; t < n_ticks; ++t) {
     const int row = t < v_ref_ticks ? t : v_ref_ticks - 1;
@@ -1096,72 +962,72 @@ int mpcq_session_reset(mpcq_session* s, const int32_t* mask, const double* gait0
 }
 
 int mpcq_session_read(mpcq_session* s, int what, void* dst, uint32_t flags) {
-  return group_read(s, &mpcq_session::sv, what, dst, flags);
+  return group_read(s, G_MAIN, what, dst, flags);
 }
 
 int mpcq_session_plant_read(mpcq_session* s, int what, void* dst, uint32_t flags) {
-  return group_read(s, &mpcq_session::pv, what, dst, flags);
+  return group_read(s, G_PLANT, what, dst, flags);
 }
 
 int mpcq_session_monitor_read(mpcq_session* s, int what, void* dst, uint32_t flags) {
-  return group_read(s, &mpcq_session::mv, what, dst, flags);
+  return group_read(s, G_MONITOR, what, dst, flags);
 }
 
 int mpcq_session_scenario_read(mpcq_session* s, int what, void* dst, uint32_t flags) {
-  return group_read(s, &mpcq_session::cv, what, dst, flags);
+  return group_read(s, G_SCENARIO, what, dst, flags);
 }
 
 int mpcq_session_channel_read(mpcq_session* s, int what, void* dst, uint32_t flags) {
-  return group_read(s, &mpcq_session::hv, what, dst, flags);
+  return group_read(s, G_CHANNEL, what, dst, flags);
 }
 
 int mpcq_session_estimator_read(mpcq_session* s, int what, void* dst, uint32_t flags) {
-  return group_read(s, &mpcq_session::ev, what, dst, flags);
+  return group_read(s, G_ESTIMATOR, what, dst, flags);
 }
 
 int mpcq_session_disturb_read(mpcq_session* s, int what, void* dst, uint32_t flags) {
-  return group_read(s, &mpcq_session::dv, what, dst, flags);
+  return group_read(s, G_DISTURB, what, dst, flags);
 }
 
 int mpcq_session_gait_read(mpcq_session* s, int what, void* dst, uint32_t flags) {
-  return group_read(s, &mpcq_session::gv, what, dst, flags);
+  return group_read(s, G_GAIT, what, dst, flags);
 }
 
 int mpcq_session_device_ptr(mpcq_session* s, int what, void** out) {
-  return group_device_ptr(s, &mpcq_session::sv, what, out);
+  return group_device_ptr(s, G_MAIN, what, out);
 }
 
 int mpcq_session_plant_device_ptr(mpcq_session* s, int what, void** out) {
-  return group_device_ptr(s, &mpcq_session::pv, what, out);
+  return group_device_ptr(s, G_PLANT, what, out);
 }
 
 int mpcq_session_monitor_device_ptr(mpcq_session* s, int what, void** out) {
-  return group_device_ptr(s, &mpcq_session::mv, what, out);
+  return group_device_ptr(s, G_MONITOR, what, out);
 }
 
 int mpcq_session_scenario_device_ptr(mpcq_session* s, int what, void** out) {
-  return group_device_ptr(s, &mpcq_session::cv, what, out);
+  return group_device_ptr(s, G_SCENARIO, what, out);
 }
 
 int mpcq_session_channel_device_ptr(mpcq_session* s, int what, void** out) {
-  return group_device_ptr(s, &mpcq_session::hv, what, out);
+  return group_device_ptr(s, G_CHANNEL, what, out);
 }
 
 int mpcq_session_estimator_device_ptr(mpcq_session* s, int what, void** out) {
-  return group_device_ptr(s, &mpcq_session::ev, what, out);
+  return group_device_ptr(s, G_ESTIMATOR, what, out);
 }
 
 int mpcq_session_disturb_device_ptr(mpcq_session* s, int what, void** out) {
-  return group_device_ptr(s, &mpcq_session::dv, what, out);
+  return group_device_ptr(s, G_DISTURB, what, out);
 }
 
 int mpcq_session_gait_device_ptr(mpcq_session* s, int what, void** out) {
-  return group_device_ptr(s, &mpcq_session::gv, what, out);
+  return group_device_ptr(s, G_GAIT, what, out);
 }
 
 int mpcq_session_write(mpcq_session* s, int what, const void* src, uint32_t flags) {
   if (!s || !src) return fail(MPCQ_E_INVALID, "NULL argument");
-  const int rc = find(s->sv, what);
+  const int rc = find(s, G_MAIN, what);
   if (rc) return rc;
   // the engine indexes robots through the order: only order_kernel writes it
   if (what == MPCQ_SV_ORDER) return fail(MPCQ_E_INVALID, "MPCQ_SV_ORDER is read-only");
@@ -1171,7 +1037,7 @@ int mpcq_session_write(mpcq_session* s, int what, const void* src, uint32_t flag
     return fail(MPCQ_E_INVALID, "MPCQ_SV_SWING_REF and MPCQ_SV_FRAME are read-only");
   DeviceGuard g(s->ctx->device);
   const hipMemcpyKind kind = (flags & MPCQ_FLAG_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  HIP_TRY(hipMemcpyAsync(s->sv.ptr[what], src, s->sv.bytes[what], kind, s->ctx->stream));
+  HIP_TRY(hipMemcpyAsync(s->grp[G_MAIN].ptr[what], src, s->grp[G_MAIN].bytes[what], kind, s->ctx->stream));
   HIP_TRY(hipStreamSynchronize(s->ctx->stream));
   return MPCQ_OK;
 }
@@ -1179,33 +1045,6 @@ int mpcq_session_write(mpcq_session* s, int what, const void* src, uint32_t flag
 }  // extern "C"
 
 // ---- snapshots: save, restore and branch robots on the device (include/mpcq.h) ------------
-
-namespace {
-
-// The parts of a snapshot, in the blob's order; each is one allocation (alloc_group).
-enum { G_MAIN, G_SWING, G_PLANT, G_MONITOR, G_SCENARIO, G_ROBOTS, G_PLANT_ROBOTS, G_CHANNEL, G_ESTIMATOR,
-       G_GAIT, G_DISTURB, G_COUNT };
-const char* const kPartName[G_COUNT] = {"the snapshot's session arrays", "the snapshot's swing arrays",
-                                        "the snapshot's plant arrays", "the snapshot's monitor arrays",
-                                        "the snapshot's scenario arrays", "the snapshot's robots table",
-                                        "the snapshot's plant robots table", "the snapshot's channel arrays",
-                                        "the snapshot's estimator row", "the snapshot's gait rows",
-                                        "the snapshot's disturb rows"};
-
-// What a snapshot's allocations follow from, with the context's N.
-struct SnapShape {
-  int64_t B = 0;
-  int k_mpc = 0;  // 0: no swing arrays
-  bool pv = false, mv = false, cv = false, robots = false, plant_robots = false;
-  bool hv = false;              // the channel arrays, primed under
-  int delay = 0, latency = 0;   // these depths
-  bool ev = false;              // the estimator's row (self-describing: no parameter travels)
-  bool gv = false;              // the gait stage's rows, indices into a library of
-  int n_gaits = 0;              // this many cycles (the library itself is configuration: not held)
-  bool dv = false;              // the disturbance stage's row (self-describing, as the estimator's)
-};
-
-}  // namespace
 
 struct mpcq_snapshot {
   mpcq_ctx* ctx = nullptr;
@@ -1221,72 +1060,19 @@ namespace {
 SnapShape shape_of(const mpcq_session* s) {
   SnapShape sh;
   sh.B = s->B;
-  sh.k_mpc = s->swing ? s->sp.k_mpc : 0;
-  sh.pv = s->pv.mem; sh.mv = s->mv.mem; sh.cv = s->cv.mem;
-  sh.robots = s->robots.count > 0; sh.plant_robots = s->plant_robots.count > 0;
-  sh.hv = s->hv.mem;
-  if (sh.hv) { sh.delay = s->ch.delay; sh.latency = s->ch.latency; }
-  sh.ev = s->ev.mem;
-  sh.gv = s->gv.mem;
-  if (sh.gv) sh.n_gaits = s->gp.n_gaits;
-  sh.dv = s->dv.mem;
+  for (int gi = 0; gi < G_COUNT; ++gi) sh.has[gi] = s->grp[gi].there();
+  // the parameters the parts' arrays were filled under
+  if (sh.has[G_SWING]) sh.k_mpc = s->sp.k_mpc;
+  if (sh.has[G_CHANNEL]) { sh.delay = s->ch.delay; sh.latency = s->ch.latency; }
+  if (sh.has[G_GAIT]) sh.n_gaits = s->gp.n_gaits;
   return sh;
-}
-
-// The main group's arrays a snapshot holds: not the staging of host inputs (every tick
-// rewrites it before reading), not MPCQ_SV_ORDER (a permutation: rebuilt, never copied by
-// rows), not the swing slots (a part of their own).
-bool main_held(int w) {
-  return w != MPCQ_SV_ORDER && w != MPCQ_SV_SWING_REF && w != MPCQ_SV_SWING_STATE && w != MPCQ_SV_FRAME &&
-         w != SP_IN_STATE && w != SP_IN_LFEET && w != SP_IN_VREF && w != SP_IN_REDUCED && w != SP_IN_GAIT;
-}
-
-// Bytes of every array of every part of a snapshot of this shape (0: not held).
-void snap_sizes(const SnapShape& sh, int N, size_t nb[G_COUNT][SP_COUNT]) {
-  const size_t B = (size_t)sh.B;
-  memset(nb, 0, sizeof(size_t) * G_COUNT * SP_COUNT);
-  for (int w = 0; w < SP_COUNT; ++w)
-    if (main_held(w)) nb[G_MAIN][w] = sv_bytes(w, sh.B, N);
-  if (sh.k_mpc > 0) swing_bytes(B, sh.k_mpc, nb[G_SWING]);
-  if (sh.pv) {
-    plant_bytes(B, nb[G_PLANT]);
-    nb[G_PLANT][PP_QW_PREV] = 0;  // (a tick with the plant takes it before its retrieve)
-  }
-  if (sh.mv) monitor_bytes(B, nb[G_MONITOR]);
-  if (sh.cv) scenario_bytes(B, nb[G_SCENARIO]);
-  if (sh.robots) nb[G_ROBOTS][0] = B * sizeof(mpcq_robot);
-  if (sh.plant_robots) nb[G_PLANT_ROBOTS][0] = B * sizeof(mpcq_robot);
-  if (sh.hv) channel_bytes(B, nb[G_CHANNEL]);
-  if (sh.ev) {
-    estimator_bytes(B, nb[G_ESTIMATOR]);
-    nb[G_ESTIMATOR][MPCQ_EV_EST] = 0;  // (derived: every tick rewrites it before anything reads it)
-  }
-  if (sh.gv) nb[G_GAIT][MPCQ_GV_STATE] = B * 16;
-  if (sh.dv) nb[G_DISTURB][MPCQ_DV_ROW] = B * MPCQ_DIST_ROW * 8;  // (MPCQ_DV_DIST, _RESID: derived)
 }
 
 // The session's arrays seen as a snapshot's parts (the arrays a snapshot does not hold: null).
 void session_parts(const mpcq_session* s, Group out[G_COUNT]) {
-  for (int w = 0; w < SP_COUNT; ++w)
-    if (main_held(w)) { out[G_MAIN].ptr[w] = s->sv.ptr[w]; out[G_MAIN].bytes[w] = s->sv.bytes[w]; }
-  if (s->swing)
-    for (int i = 0; i < 3; ++i) {
-      out[G_SWING].ptr[i] = s->sv.ptr[MPCQ_SV_SWING_REF + i]; out[G_SWING].bytes[i] = s->sv.bytes[MPCQ_SV_SWING_REF + i];
-    }
-  if (s->pv.mem)
-    for (int w = 0; w < MPCQ_PV_COUNT; ++w) { out[G_PLANT].ptr[w] = s->pv.ptr[w]; out[G_PLANT].bytes[w] = s->pv.bytes[w]; }
-  if (s->mv.mem)
-    for (int w = 0; w < MPCQ_MV_COUNT; ++w) { out[G_MONITOR].ptr[w] = s->mv.ptr[w]; out[G_MONITOR].bytes[w] = s->mv.bytes[w]; }
-  if (s->cv.mem)
-    for (int w = 0; w < MPCQ_CV_COUNT; ++w) { out[G_SCENARIO].ptr[w] = s->cv.ptr[w]; out[G_SCENARIO].bytes[w] = s->cv.bytes[w]; }
-  const size_t tb = (size_t)s->B * sizeof(mpcq_robot);
-  if (s->robots.count > 0) { out[G_ROBOTS].ptr[0] = s->robots.dev; out[G_ROBOTS].bytes[0] = tb; }
-  if (s->plant_robots.count > 0) { out[G_PLANT_ROBOTS].ptr[0] = s->plant_robots.dev; out[G_PLANT_ROBOTS].bytes[0] = tb; }
-  if (s->hv.mem)
-    for (int w = 0; w < MPCQ_HV_COUNT; ++w) { out[G_CHANNEL].ptr[w] = s->hv.ptr[w]; out[G_CHANNEL].bytes[w] = s->hv.bytes[w]; }
-  if (s->ev.mem) { out[G_ESTIMATOR].ptr[MPCQ_EV_ROW] = s->ev.ptr[MPCQ_EV_ROW]; out[G_ESTIMATOR].bytes[MPCQ_EV_ROW] = s->ev.bytes[MPCQ_EV_ROW]; }
-  if (s->gv.mem) { out[G_GAIT].ptr[MPCQ_GV_STATE] = s->gv.ptr[MPCQ_GV_STATE]; out[G_GAIT].bytes[MPCQ_GV_STATE] = s->gv.bytes[MPCQ_GV_STATE]; }
-  if (s->dv.mem) { out[G_DISTURB].ptr[MPCQ_DV_ROW] = s->dv.ptr[MPCQ_DV_ROW]; out[G_DISTURB].bytes[MPCQ_DV_ROW] = s->dv.bytes[MPCQ_DV_ROW]; }
+  for (int gi = 0; gi < G_COUNT; ++gi)
+    for (int w = 0; w < kParts[gi].count; ++w)
+      if (kParts[gi].held >> w & 1u) { out[gi].ptr[w] = s->grp[gi].ptr[w]; out[gi].bytes[w] = s->grp[gi].bytes[w]; }
 }
 
 // One array of a snapshot (a) next to its counterpart (b; null without one), in the blob's order.
@@ -1307,11 +1093,11 @@ constexpr int kGatherChunks = (kListMax + mpcq::kGatherMax - 1) / mpcq::kGatherM
 int list_arrays(const Group a[G_COUNT], const Group* b, SnapItem out[kListMax]) {
   int n = 0;
   for (int gi = 0; gi < G_COUNT; ++gi)
-    for (int w = 0; w < SP_COUNT; ++w) {
+    for (int w = 0; w < kPartArrays; ++w) {
       if (!a[gi].ptr[w]) continue;
       if (n == kListMax || (b && !b[gi].ptr[w])) return -1;
       out[n++] = SnapItem{a[gi].ptr[w], b ? b[gi].ptr[w] : nullptr, a[gi].bytes[w], b ? b[gi].bytes[w] : 0,
-                          !(gi == G_MONITOR && w == MPCQ_MV_TOTALS)};
+                          (kParts[gi].rows >> w & 1u) != 0};
     }
   return n;
 }
@@ -1326,13 +1112,11 @@ void free_parts(mpcq_snapshot* p) {
 
 // The allocations of a snapshot of this shape into *p (which holds none): all or nothing.
 int alloc_parts(mpcq_ctx* c, const SnapShape& sh, mpcq_snapshot* p) {
-  size_t nb[G_COUNT][SP_COUNT];
+  size_t nb[G_COUNT][kPartArrays];
   snap_sizes(sh, c->N, nb);
   for (int gi = 0; gi < G_COUNT; ++gi) {
-    size_t tot = 0;
-    for (int w = 0; w < SP_COUNT; ++w) tot += nb[gi][w];
-    if (!tot) continue;
-    const int rc = alloc_group(c, kPartName[gi], SP_COUNT, nb[gi], &p->g[gi].mem, p->g[gi].ptr, p->g[gi].bytes);
+    if (!sh.has[gi]) continue;
+    const int rc = alloc_group(c, kParts[gi].snap, nb[gi], &p->g[gi]);
     if (rc) {
       free_parts(p);
       return rc;
@@ -1341,26 +1125,6 @@ int alloc_parts(mpcq_ctx* c, const SnapShape& sh, mpcq_snapshot* p) {
   p->ctx = c;
   p->sh = sh;
   return MPCQ_OK;
-}
-
-// The first difference between a snapshot's shape and a session's, as text; or null.
-const char* shape_difference(const SnapShape& a, const SnapShape& b, bool batch_too) {
-  if (batch_too && a.B != b.B) return "the batch sizes differ (a restore without a map needs the same batch)";
-  if ((a.k_mpc > 0) != (b.k_mpc > 0)) return "the swing arrays exist on one side only";
-  if (a.k_mpc != b.k_mpc) return "the swing k_mpc differs";
-  if (a.pv != b.pv) return "the plant arrays exist on one side only";
-  if (a.mv != b.mv) return "the monitor arrays exist on one side only";
-  if (a.cv != b.cv) return "the scenario arrays exist on one side only";
-  if (a.robots != b.robots) return "the robots table is in force on one side only";
-  if (a.plant_robots != b.plant_robots) return "the plant robots table is in force on one side only";
-  if (a.hv != b.hv) return "the channel arrays exist on one side only";
-  if (a.delay != b.delay) return "the channel's delay differs (the rings were filled under another)";
-  if (a.latency != b.latency) return "the channel's latency differs (the rings were filled under another)";
-  if (a.ev != b.ev) return "the estimator arrays exist on one side only";
-  if (a.gv != b.gv) return "the gait arrays exist on one side only";
-  if (a.n_gaits != b.n_gaits) return "the gait library sizes differ (the rows index another library)";
-  if (a.dv != b.dv) return "the disturb arrays exist on one side only";
-  return nullptr;
 }
 
 // A host map: every entry -1 or in [0, rows_src); with `full`, no -1 either.
@@ -1460,9 +1224,13 @@ int snapshot_restore(mpcq_session* s, const mpcq_snapshot* p, const int32_t* map
   if (n < 0) return fail(MPCQ_E_INVALID, "the snapshot's arrays do not match the session's");
   // the per-robot arrays, kGatherMax to a launch (one launch up to 48 arrays); every launch's
   // table is made before the first is enqueued
-  int nr = 0;
-  for (int i = 0; i < n; ++i)
+  // (the batch-wide ones -- MPCQ_MV_TOTALS -- go with the whole batch only, behind the gathers)
+  SnapItem whole[kListMax];
+  int nr = 0, nw = 0;
+  for (int i = 0; i < n; ++i) {
     if (it[i].rows) it[nr++] = it[i];
+    else whole[nw++] = it[i];
+  }
   const int chunks = (nr + mpcq::kGatherMax - 1) / mpcq::kGatherMax;
   mpcq::GatherArgs ga[kGatherChunks] = {};
   for (int ch = 0; ch < chunks; ++ch) {
@@ -1476,17 +1244,16 @@ int snapshot_restore(mpcq_session* s, const mpcq_snapshot* p, const int32_t* map
   for (int ch = 0; ch < chunks && e == hipSuccess; ++ch) {
     ga[ch].map = dmap;
     // creation state, which only a first tick may consume: the rows come with a pending reset
-    ga[ch].first = p->have_order ? nullptr : s->sv.i(MPCQ_SV_FIRST);
+    ga[ch].first = p->have_order ? nullptr : s->grp[G_MAIN].i(MPCQ_SV_FIRST);
     e = mpcq::launch_gather_rows(ga[ch], c->stream);
   }
-  if (e == hipSuccess && !map && p->sh.mv)  // the batch-wide totals go with the whole batch only
-    e = hipMemcpyAsync(s->mv.ptr[MPCQ_MV_TOTALS], p->g[G_MONITOR].ptr[MPCQ_MV_TOTALS], s->mv.bytes[MPCQ_MV_TOTALS],
-                       hipMemcpyDeviceToDevice, c->stream);
+  for (int i = 0; i < nw && !map && e == hipSuccess; ++i)
+    e = hipMemcpyAsync(whole[i].b, whole[i].a, whole[i].bytes_b, hipMemcpyDeviceToDevice, c->stream);
   if (e == hipSuccess) {
     if (!p->have_order || p->resets) s->resets = true;
     if (s->have_order || p->have_order) {  // as enqueue_reset: the pending resets to the front
-      e = mpcq::launch_order(s->sv.i(MPCQ_SV_ITERS), s->resets ? s->sv.i(MPCQ_SV_FIRST) : nullptr, s->B,
-                             s->sv.i(MPCQ_SV_ORDER), c->stream);
+      e = mpcq::launch_order(s->grp[G_MAIN].i(MPCQ_SV_ITERS), s->resets ? s->grp[G_MAIN].i(MPCQ_SV_FIRST) : nullptr, s->B,
+                             s->grp[G_MAIN].i(MPCQ_SV_ORDER), c->stream);
       s->have_order = true;
     }
   }
@@ -1496,63 +1263,6 @@ int snapshot_restore(mpcq_session* s, const mpcq_snapshot* p, const int32_t* map
   }
   HIP_TRY(e);
   return MPCQ_OK;
-}
-
-// The blob's header (include/mpcq.h, mpcq_session_snapshot_export).
-struct BlobHeader {
-  char magic[8];
-  uint32_t version;
-  int32_t N;
-  int64_t B;
-  int32_t k_mpc;
-  uint32_t flags;
-  int64_t group_bytes[G_CHANNEL];  // the seven parts of format version 1
-  int64_t total;
-  int64_t user;
-  int64_t channel_bytes;   // format version 2: the eighth part,
-  int32_t delay, latency;  // and the depths its rings were filled under
-  int64_t estimator_bytes; // format version 3: the ninth part
-  // format version 4 only, behind the 128 bytes of versions 1 to 3: the tenth part and the size
-  // of the library its rows index
-  int64_t gait_bytes;
-  int32_t n_gaits, pad;
-  // format version 5 only, behind the 144 bytes of version 4: the eleventh part
-  int64_t disturb_bytes;
-  int64_t pad5;
-};
-static_assert(sizeof(BlobHeader) == 160 && offsetof(BlobHeader, gait_bytes) == 128 &&
-                  offsetof(BlobHeader, disturb_bytes) == 144 && G_CHANNEL == 7 && G_ESTIMATOR == 8 && G_GAIT == 9 &&
-                  G_DISTURB == 10 && G_COUNT == 11,
-              "the blob's header is 128 bytes, 144 in format version 4, 160 from version 5 on");
-size_t header_bytes(uint32_t version) {
-  return version >= 5 ? sizeof(BlobHeader) : version == 4 ? offsetof(BlobHeader, disturb_bytes)
-                                                          : offsetof(BlobHeader, gait_bytes);
-}
-
-// The header's byte count of part gi.
-int64_t& part_bytes(BlobHeader& h, int gi) {
-  return gi == G_DISTURB ? h.disturb_bytes : gi == G_GAIT ? h.gait_bytes : gi == G_ESTIMATOR ? h.estimator_bytes : gi == G_CHANNEL ? h.channel_bytes
-                                                                                                : h.group_bytes[gi];
-}
-const char kMagic[8] = {'M', 'P', 'C', 'Q', 'S', 'N', 'P', '1'};
-
-void blob_header(const SnapShape& sh, int N, bool have_order, bool resets, BlobHeader* h) {
-  size_t nb[G_COUNT][SP_COUNT];
-  snap_sizes(sh, N, nb);
-  memset(h, 0, sizeof(*h));
-  memcpy(h->magic, kMagic, 8);
-  h->version = sh.dv ? 5 : sh.gv ? 4 : sh.ev ? 3 : sh.hv ? 2 : 1; h->N = N; h->B = sh.B; h->k_mpc = sh.k_mpc;
-  h->flags = (have_order ? 1u : 0u) | (resets ? 2u : 0u) | (sh.k_mpc > 0 ? 4u : 0u) | (sh.pv ? 8u : 0u) |
-             (sh.mv ? 16u : 0u) | (sh.cv ? 32u : 0u) | (sh.robots ? 64u : 0u) | (sh.plant_robots ? 128u : 0u) |
-             (sh.hv ? 256u : 0u) | (sh.ev ? 512u : 0u) | (sh.gv ? 1024u : 0u) | (sh.dv ? 2048u : 0u);
-  h->delay = sh.delay; h->latency = sh.latency;
-  h->n_gaits = sh.n_gaits;
-  h->total = (int64_t)header_bytes(h->version);
-  for (int gi = 0; gi < G_COUNT; ++gi) {
-    int64_t& gb = part_bytes(*h, gi);
-    for (int w = 0; w < SP_COUNT; ++w) gb += (int64_t)nb[gi][w];
-    h->total += gb;
-  }
 }
 
 }  // namespace
@@ -1647,45 +1357,13 @@ int mpcq_session_snapshot_import(mpcq_session* s, mpcq_snapshot* p, const void* 
   if (!p || !src) return fail(MPCQ_E_INVALID, "NULL argument");
   mpcq_ctx* c = s->ctx;
   if (p->ctx != c) return fail(MPCQ_E_INVALID, "the snapshot belongs to another context");
-  BlobHeader h;
-  memset(&h, 0, sizeof(h));
-  if (bytes < (int64_t)header_bytes(1)) return fail(MPCQ_E_INVALID, "%lld bytes are less than a header", (long long)bytes);
-  memcpy(&h, src, header_bytes(1));
-  if (memcmp(h.magic, kMagic, 8) != 0) return fail(MPCQ_E_INVALID, "not a snapshot blob (magic)");
-  if (h.version < 1 || h.version > 5)
-    return fail(MPCQ_E_INVALID, "blob format version %u, this library reads 1 to 5", h.version);
-  if (bytes < (int64_t)header_bytes(h.version))
-    return fail(MPCQ_E_INVALID, "%lld bytes are less than a version-%u header", (long long)bytes, h.version);
-  memcpy(&h, src, header_bytes(h.version));
-  if (h.N != c->N) return fail(MPCQ_E_INVALID, "the blob is of a context with N = %d, this one has N = %d", h.N, c->N);
-  const bool chan = h.flags & 256u, est = h.flags & 512u, gait = h.flags & 1024u, dist = h.flags & 2048u;
-  if (h.B < 1 || h.B > (int64_t)0x7fffffff || h.k_mpc < 0 || h.k_mpc > 65536 || (h.flags >> 12) ||
-      ((h.flags & 4u) != 0) != (h.k_mpc > 0) || h.version != (dist ? 5u : gait ? 4u : est ? 3u : chan ? 2u : 1u) ||
-      (!est && h.estimator_bytes != 0) || (gait && (h.n_gaits < 1 || h.n_gaits > MPCQ_GAIT_MAX || h.pad != 0)) ||
-      (!gait && (h.n_gaits != 0 || h.pad != 0)) || h.pad5 != 0 ||
-      (chan ? h.delay < 0 || h.delay > MPCQ_CHANNEL_MAX_DELAY || h.latency < 0 || h.latency > MPCQ_CHANNEL_MAX_LATENCY
-            : h.delay != 0 || h.latency != 0 || h.channel_bytes != 0))
-    return fail(MPCQ_E_INVALID, "the blob's header is inconsistent (B %lld, k_mpc %d, flags %#x)", (long long)h.B,
-                h.k_mpc, h.flags);
   SnapShape sh;
-  sh.B = h.B; sh.k_mpc = h.k_mpc;
-  sh.pv = h.flags & 8u; sh.mv = h.flags & 16u; sh.cv = h.flags & 32u;
-  sh.robots = h.flags & 64u; sh.plant_robots = h.flags & 128u;
-  sh.hv = chan; sh.delay = h.delay; sh.latency = h.latency;
-  sh.ev = est;
-  sh.gv = gait; sh.n_gaits = gait ? h.n_gaits : 0;
-  sh.dv = dist;
-  BlobHeader want;
-  blob_header(sh, c->N, h.flags & 1u, h.flags & 2u, &want);
-  for (int gi = 0; gi < G_COUNT; ++gi) {
-    const int64_t have = part_bytes(h, gi), need = part_bytes(want, gi);
-    if (have != need)
-      return fail(MPCQ_E_INVALID, "the blob's part %d has %lld bytes, its shape says %lld", gi, (long long)have,
-                  (long long)need);
-  }
-  if (h.total != want.total || bytes != want.total)
-    return fail(MPCQ_E_INVALID, "the blob says %lld bytes, its shape %lld, the caller %lld (truncated?)",
-                (long long)h.total, (long long)want.total, (long long)bytes);
+  bool have_order = false, resets = false;
+  char msg[256];
+  if (!parse_blob_header(src, bytes, c->N, &sh, &have_order, &resets, msg, sizeof(msg)))
+    return fail(MPCQ_E_INVALID, "%s", msg);
+  BlobHeader h;
+  blob_header(sh, c->N, have_order, resets, &h);
   DeviceGuard dg(c->device);
   mpcq_snapshot fresh;
   int rc = alloc_parts(c, sh, &fresh);
@@ -1706,8 +1384,8 @@ int mpcq_session_snapshot_import(mpcq_session* s, mpcq_snapshot* p, const void* 
   free_parts(p);
   for (int gi = 0; gi < G_COUNT; ++gi) p->g[gi] = fresh.g[gi];
   p->sh = sh;
-  p->have_order = h.flags & 1u;
-  p->resets = h.flags & 2u;
+  p->have_order = have_order;
+  p->resets = resets;
   p->saved = true;
   return MPCQ_OK;
 }

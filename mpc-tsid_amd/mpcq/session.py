@@ -39,6 +39,28 @@ def _shapes(B, N):
     }
 
 
+# The arrays of the opt-in groups: kind -> {array id: (shape from B, dtype)}.
+_GROUPS = {
+    "plant": {L.PV_STATE_END: (lambda B: (B, 12), np.float64), L.PV_F_EFF: (lambda B: (B, 12), np.float64),
+              L.PV_WRENCH: (lambda B: (B, 6), np.float64)},
+    "monitor": {L.MV_DONE: (lambda B: (B,), np.int32), L.MV_EP: (lambda B: (B, 8), np.float64),
+                L.MV_EP_TICKS: (lambda B: (B,), np.int32), L.MV_EPISODES: (lambda B: (B,), np.int32),
+                L.MV_LAST: (lambda B: (B, 16), np.float64), L.MV_TOTALS: (lambda B: (8,), np.uint64)},
+    "scenario": {L.CV_EPOCH: (lambda B: (B,), np.int32), L.CV_TICK: (lambda B: (B,), np.int32),
+                 L.CV_V_REF: (lambda B: (B, 6), np.float64), L.CV_PUSH: (lambda B: (B, 6), np.float64),
+                 L.CV_WRENCH: (lambda B: (B, 6), np.float64), L.CV_ROBOTS: (lambda B: (B,), ROBOT_DTYPE),
+                 L.CV_DRAW: (lambda B: (B, 8), np.float64)},
+    "channel": {L.HV_CLOCK: (lambda B: (B, 2), np.int32), L.HV_OBS: (lambda B: (B, 12), np.float64),
+                L.HV_F_CMD: (lambda B: (B, 12), np.float64), L.HV_DRAW: (lambda B: (B, 16), np.float64),
+                L.HV_S_RING: (lambda B: (B, L.CHANNEL_MAX_DELAY, 12), np.float64),
+                L.HV_F_RING: (lambda B: (B, L.CHANNEL_MAX_LATENCY, 12), np.float64)},
+    "estimator": {L.EV_EST: (lambda B: (B, 12), np.float64), L.EV_ROW: (lambda B: (B, L.EST_ROW), np.float64)},
+    "disturb": {L.DV_DIST: (lambda B: (B,), DISTURBANCE_DTYPE), L.DV_ROW: (lambda B: (B, L.DIST_ROW), np.float64),
+                L.DV_RESID: (lambda B: (B, 6), np.float64)},
+    "gait": {L.GV_STATE: (lambda B: (B, 4), np.int32)},
+}
+
+
 class Snapshot:
     """A device-resident copy of a session's robots (``Session.snapshot``): every per-robot array
     of every group the session holds, and ``Session.k`` at the save.  It belongs to the
@@ -126,6 +148,45 @@ class Session:
         self.gait_params = None
         self.gait_cycles = None
 
+    # ------------------------------------------------------------------ the groups' arrays
+    def _group_shape(self, kind: str, what: int):
+        """(shape, dtype) of array ``what`` of a group; "session": the main group."""
+        if kind == "session":
+            if what not in self._shapes and what in (L.SV_SWING_REF, L.SV_SWING_STATE, L.SV_FRAME):
+                raise L.MpcqError(L.E_INVALID, f"session array {what} needs enable_swing()")
+            return self._shapes[what]
+        if what not in _GROUPS[kind]:
+            raise L.MpcqError(L.E_INVALID, f"unknown {kind} array {what}")
+        shape, dt = _GROUPS[kind][what]
+        return shape(self.batch), dt
+
+    @staticmethod
+    def _entry(kind: str, call: str) -> str:
+        return f"mpcq_session_{call}" if kind == "session" else f"mpcq_session_{kind}_{call}"
+
+    def _group_read(self, kind: str, what: int):
+        out = np.empty(*self._group_shape(kind, what))
+        self.engine._call(self._entry(kind, "read"), self._h, what, C.c_void_p(out.ctypes.data), 0)
+        return out
+
+    def _group_ptr(self, kind: str, what: int) -> int:
+        out = C.c_void_p()
+        self.engine._call(self._entry(kind, "device_ptr"), self._h, what, C.byref(out))
+        return int(out.value or 0)
+
+    def _enable(self, kind: str, params, overrides, *more):
+        """``params``, or the group's defaults with ``overrides``, into mpcq_session_enable_<kind>
+        (``more``: its further arguments) and, once the library has taken them, ``<kind>_params``."""
+        if params is not None and overrides:
+            raise ValueError("pass params or overrides, not both")
+        p = params or getattr(L, f"default_{kind}_params")(**overrides)
+        self.engine._call(f"mpcq_session_enable_{kind}", self._h, C.byref(p), *more)
+        setattr(self, f"{kind}_params", p)
+
+    def _disable(self, kind: str):
+        self.engine._call(f"mpcq_session_disable_{kind}", self._h)
+        setattr(self, f"{kind}_params", None)
+
     def enable_swing(self, params: L.SwingParams | None = None):
         """Opt in to the swing-foot references: every later tick appends one swing launch over
         substeps 0..k_mpc-1 of its gait / fsteps (SV_SWING_REF, SV_SWING_STATE, SV_FRAME)."""
@@ -186,14 +247,11 @@ class Session:
         and SV_Q_W / SV_STATE / SV_L_FEET follow the plant's end state instead of the MPC's
         prediction (``plant_read``: PV_STATE_END, PV_F_EFF, PV_WRENCH).  ``params`` None: the
         defaults with the engine's dt.  Calling it again replaces the parameters."""
-        pl = params or L.default_plant_params(dt=self.engine.params.dt)
-        self.engine._call("mpcq_session_enable_plant", self._h, C.byref(pl))
-        self.plant_params = pl
+        self._enable("plant", params, {} if params else dict(dt=self.engine.params.dt))
 
     def disable_plant(self):
         """The ticks after it run without the plant; the wrench and the plant's table stay."""
-        self.engine._call("mpcq_session_disable_plant", self._h)
-        self.plant_params = None
+        self._disable("plant")
 
     def set_plant_robots(self, table):
         """The true robots the plant moves (``mpcq.robots(B, ...)``, or one entry for every
@@ -221,16 +279,10 @@ class Session:
 
     def plant_read(self, what: int):
         """PV_STATE_END (B, 12), PV_F_EFF (B, 12) or PV_WRENCH (B, 6)."""
-        if what not in (L.PV_STATE_END, L.PV_F_EFF, L.PV_WRENCH):
-            raise L.MpcqError(L.E_INVALID, f"unknown plant array {what}")
-        out = np.empty((self.batch, 6 if what == L.PV_WRENCH else 12))
-        self.engine._call("mpcq_session_plant_read", self._h, what, C.c_void_p(out.ctypes.data), 0)
-        return out
+        return self._group_read("plant", what)
 
     def plant_device_ptr(self, what: int) -> int:
-        out = C.c_void_p()
-        self.engine._call("mpcq_session_plant_device_ptr", self._h, what, C.byref(out))
-        return int(out.value or 0)
+        return self._group_ptr("plant", what)
 
     # ------------------------------------------------------------------ episode monitor
     def enable_monitor(self, params: L.MonitorParams | None = None, **overrides):
@@ -241,37 +293,19 @@ class Session:
         itself restarts the robots whose episode ended.  ``params`` None: the defaults, with
         ``overrides`` (``max_tilt``, ``min_height``, ``max_ticks``, ``auto_reset``).  Calling it
         again replaces the parameters and keeps the arrays."""
-        if params is not None and overrides:
-            raise ValueError("pass params or overrides, not both")
-        mp = params or L.default_monitor_params(**overrides)
-        self.engine._call("mpcq_session_enable_monitor", self._h, C.byref(mp))
-        self.monitor_params = mp
+        self._enable("monitor", params, overrides)
 
     def disable_monitor(self):
         """The ticks after it run without the monitor and its auto-reset; the arrays stay."""
-        self.engine._call("mpcq_session_disable_monitor", self._h)
-        self.monitor_params = None
-
-    def _monitor_shape(self, what: int):
-        B = self.batch
-        shapes = {L.MV_DONE: ((B,), np.int32), L.MV_EP: ((B, 8), np.float64), L.MV_EP_TICKS: ((B,), np.int32),
-                  L.MV_EPISODES: ((B,), np.int32), L.MV_LAST: ((B, 16), np.float64), L.MV_TOTALS: ((8,), np.uint64)}
-        if what not in shapes:
-            raise L.MpcqError(L.E_INVALID, f"unknown monitor array {what}")
-        return shapes[what]
+        self._disable("monitor")
 
     def monitor_read(self, what: int):
         """MV_DONE (B,) int32, MV_EP (B, 8), MV_EP_TICKS (B,) int32, MV_EPISODES (B,) int32,
         MV_LAST (B, 16) or MV_TOTALS (8,) uint64."""
-        shape, dt = self._monitor_shape(what)
-        out = np.empty(shape, dt)
-        self.engine._call("mpcq_session_monitor_read", self._h, what, C.c_void_p(out.ctypes.data), 0)
-        return out
+        return self._group_read("monitor", what)
 
     def monitor_device_ptr(self, what: int) -> int:
-        out = C.c_void_p()
-        self.engine._call("mpcq_session_monitor_device_ptr", self._h, what, C.byref(out))
-        return int(out.value or 0)
+        return self._group_ptr("monitor", what)
 
     # ------------------------------------------------------------------ scenarios
     def enable_scenario(self, params: L.ScenarioParams | None = None, **overrides):
@@ -283,39 +317,20 @@ class Session:
         ``mpcq.scenario``; pushes and robots act through ``enable_plant``.  ``params`` None: the
         defaults (the reference's predefined joystick), with ``overrides``.  Calling it again
         replaces the parameters and keeps the arrays."""
-        if params is not None and overrides:
-            raise ValueError("pass params or overrides, not both")
-        sc = params or L.default_scenario_params(**overrides)
-        self.engine._call("mpcq_session_enable_scenario", self._h, C.byref(sc))
-        self.scenario_params = sc
+        self._enable("scenario", params, overrides)
 
     def disable_scenario(self):
         """The ticks after it run without the scenario launch: the plant is back on the user's
         wrench and tables, ``v_ref=None`` is an error again; the arrays stay."""
-        self.engine._call("mpcq_session_disable_scenario", self._h)
-        self.scenario_params = None
-
-    def _scenario_shape(self, what: int):
-        B = self.batch
-        shapes = {L.CV_EPOCH: ((B,), np.int32), L.CV_TICK: ((B,), np.int32), L.CV_V_REF: ((B, 6), np.float64),
-                  L.CV_PUSH: ((B, 6), np.float64), L.CV_WRENCH: ((B, 6), np.float64), L.CV_ROBOTS: ((B,), ROBOT_DTYPE),
-                  L.CV_DRAW: ((B, 8), np.float64)}
-        if what not in shapes:
-            raise L.MpcqError(L.E_INVALID, f"unknown scenario array {what}")
-        return shapes[what]
+        self._disable("scenario")
 
     def scenario_read(self, what: int):
         """CV_EPOCH (B,) int32, CV_TICK (B,) int32, CV_V_REF / CV_PUSH / CV_WRENCH (B, 6),
         CV_ROBOTS (B,) ROBOT_DTYPE or CV_DRAW (B, 8)."""
-        shape, dt = self._scenario_shape(what)
-        out = np.empty(shape, dt)
-        self.engine._call("mpcq_session_scenario_read", self._h, what, C.c_void_p(out.ctypes.data), 0)
-        return out
+        return self._group_read("scenario", what)
 
     def scenario_device_ptr(self, what: int) -> int:
-        out = C.c_void_p()
-        self.engine._call("mpcq_session_scenario_device_ptr", self._h, what, C.byref(out))
-        return int(out.value or 0)
+        return self._group_ptr("scenario", what)
 
     # ------------------------------------------------------------------ channel
     def enable_channel(self, params: L.ChannelParams | None = None, **overrides):
@@ -329,38 +344,19 @@ class Session:
         ``params`` None: the defaults (all zero: a channel that changes nothing), with
         ``overrides``.  Calling it again with the same delay and latency only replaces the
         amplitudes; other depths refill the rings at the next tick."""
-        if params is not None and overrides:
-            raise ValueError("pass params or overrides, not both")
-        ch = params or L.default_channel_params(**overrides)
-        self.engine._call("mpcq_session_enable_channel", self._h, C.byref(ch))
-        self.channel_params = ch
+        self._enable("channel", params, overrides)
 
     def disable_channel(self):
         """The ticks after it run without the channel's two launches; the arrays stay."""
-        self.engine._call("mpcq_session_disable_channel", self._h)
-        self.channel_params = None
-
-    def _channel_shape(self, what: int):
-        B = self.batch
-        shapes = {L.HV_CLOCK: ((B, 2), np.int32), L.HV_OBS: ((B, 12), np.float64), L.HV_F_CMD: ((B, 12), np.float64),
-                  L.HV_DRAW: ((B, 16), np.float64), L.HV_S_RING: ((B, L.CHANNEL_MAX_DELAY, 12), np.float64),
-                  L.HV_F_RING: ((B, L.CHANNEL_MAX_LATENCY, 12), np.float64)}
-        if what not in shapes:
-            raise L.MpcqError(L.E_INVALID, f"unknown channel array {what}")
-        return shapes[what]
+        self._disable("channel")
 
     def channel_read(self, what: int):
         """HV_CLOCK (B, 2) int32 (epoch, next tau), HV_OBS / HV_F_CMD (B, 12), HV_DRAW (B, 16),
         HV_S_RING (B, 8, 12) or HV_F_RING (B, 4, 12)."""
-        shape, dt = self._channel_shape(what)
-        out = np.empty(shape, dt)
-        self.engine._call("mpcq_session_channel_read", self._h, what, C.c_void_p(out.ctypes.data), 0)
-        return out
+        return self._group_read("channel", what)
 
     def channel_device_ptr(self, what: int) -> int:
-        out = C.c_void_p()
-        self.engine._call("mpcq_session_channel_device_ptr", self._h, what, C.byref(out))
-        return int(out.value or 0)
+        return self._group_ptr("channel", what)
 
     # ------------------------------------------------------------------ estimator
     def enable_estimator(self, params: L.EstimatorParams | None = None, **overrides):
@@ -373,36 +369,19 @@ class Session:
         ``sigma**2``.  ``params`` None: the defaults, with ``overrides``.  Calling it while
         enabled only replaces the parameters (another ``lag`` re-initialises every robot at its
         next tick); enabling after a disable starts every filter anew."""
-        if params is not None and overrides:
-            raise ValueError("pass params or overrides, not both")
-        ep = params or L.default_estimator_params(**overrides)
-        self.engine._call("mpcq_session_enable_estimator", self._h, C.byref(ep))
-        self.estimator_params = ep
+        self._enable("estimator", params, overrides)
 
     def disable_estimator(self):
         """The ticks after it run without the estimator's launch; the arrays stay."""
-        self.engine._call("mpcq_session_disable_estimator", self._h)
-        self.estimator_params = None
-
-    def _estimator_shape(self, what: int):
-        B = self.batch
-        shapes = {L.EV_EST: ((B, 12), np.float64), L.EV_ROW: ((B, L.EST_ROW), np.float64)}
-        if what not in shapes:
-            raise L.MpcqError(L.E_INVALID, f"unknown estimator array {what}")
-        return shapes[what]
+        self._disable("estimator")
 
     def estimator_read(self, what: int):
         """EV_EST (B, 12) the last tick's estimate, or EV_ROW (B, EST_ROW) the filter state
         (``mpcq.estimator.unpack`` names its parts)."""
-        shape, dt = self._estimator_shape(what)
-        out = np.empty(shape, dt)
-        self.engine._call("mpcq_session_estimator_read", self._h, what, C.c_void_p(out.ctypes.data), 0)
-        return out
+        return self._group_read("estimator", what)
 
     def estimator_device_ptr(self, what: int) -> int:
-        out = C.c_void_p()
-        self.engine._call("mpcq_session_estimator_device_ptr", self._h, what, C.byref(out))
-        return int(out.value or 0)
+        return self._group_ptr("estimator", what)
 
     # ------------------------------------------------------------------ disturbance stage
     def enable_disturb(self, params: L.DisturbParams | None = None, **overrides):
@@ -415,34 +394,20 @@ class Session:
         with ``compensate=0`` the stage only estimates.  Set ``f_lag`` to the channel's
         ``latency``.  ``params`` None: the defaults, with ``overrides``.  Calling it while
         enabled only replaces the parameters; enabling after a disable starts every row anew."""
-        if params is not None and overrides:
-            raise ValueError("pass params or overrides, not both")
-        dp = params or L.default_disturb_params(**overrides)
-        self.engine._call("mpcq_session_enable_disturb", self._h, C.byref(dp))
-        self.disturb_params = dp
+        self._enable("disturb", params, overrides)
 
     def disable_disturb(self):
         """The ticks after it run without the stage's launch; the arrays stay."""
-        self.engine._call("mpcq_session_disable_disturb", self._h)
-        self.disturb_params = None
+        self._disable("disturb")
 
     def disturb_read(self, what: int):
         """DV_DIST (B,) DISTURBANCE_DTYPE what the solve reads, DV_ROW (B, DIST_ROW) the stage's
         state (``mpcq.disturb.unpack`` names its parts), or DV_RESID (B, 6) the last tick's raw
         sample (NaN where none was taken)."""
-        B = self.batch
-        shapes = {L.DV_DIST: ((B,), DISTURBANCE_DTYPE), L.DV_ROW: ((B, L.DIST_ROW), np.float64),
-                  L.DV_RESID: ((B, 6), np.float64)}
-        if what not in shapes:
-            raise L.MpcqError(L.E_INVALID, f"unknown disturb array {what}")
-        out = np.empty(*shapes[what])
-        self.engine._call("mpcq_session_disturb_read", self._h, what, C.c_void_p(out.ctypes.data), 0)
-        return out
+        return self._group_read("disturb", what)
 
     def disturb_device_ptr(self, what: int) -> int:
-        out = C.c_void_p()
-        self.engine._call("mpcq_session_disturb_device_ptr", self._h, what, C.byref(out))
-        return int(out.value or 0)
+        return self._group_ptr("disturb", what)
 
     # ------------------------------------------------------------------ gait transitions
     def enable_gait(self, cycles, params: L.GaitParams | None = None, **overrides):
@@ -462,8 +427,7 @@ class Session:
 
     def disable_gait(self):
         """The ticks after it run the planner's own roll again; GV_STATE stays."""
-        self.engine._call("mpcq_session_disable_gait", self._h)
-        self.gait_params = None
+        self._disable("gait")
 
     def set_gait(self, ids):
         """Request library entry ``ids`` (a scalar broadcasts to (B,); -1 withdraws a request that
@@ -479,14 +443,10 @@ class Session:
 
     def gait_state(self):
         """GV_STATE (B, 4) int32: (want, active, phase, switches) per robot."""
-        out = np.empty((self.batch, 4), np.int32)
-        self.engine._call("mpcq_session_gait_read", self._h, L.GV_STATE, C.c_void_p(out.ctypes.data), 0)
-        return out
+        return self._group_read("gait", L.GV_STATE)
 
     def gait_device_ptr(self, what: int = L.GV_STATE) -> int:
-        out = C.c_void_p()
-        self.engine._call("mpcq_session_gait_device_ptr", self._h, what, C.byref(out))
-        return int(out.value or 0)
+        return self._group_ptr("gait", what)
 
     # ------------------------------------------------------------------ rollouts
     def _to_device(self, a):
@@ -664,23 +624,13 @@ class Session:
         flags = L.FLAG_DEVICE_PTRS | (L.FLAG_ASYNC if asynchronous else 0)
         self.engine._call("mpcq_session_fork", self._h, C.c_void_p(map_ptr) if map_ptr else None, flags)
 
-    def _shape(self, what: int):
-        if what not in self._shapes and what in (L.SV_SWING_REF, L.SV_SWING_STATE, L.SV_FRAME):
-            raise L.MpcqError(L.E_INVALID, f"session array {what} needs enable_swing()")
-        return self._shapes[what]
-
     def read(self, what: int):
-        shape, dt = self._shape(what)
-        out = np.empty(shape, dt)
-        self.engine._call("mpcq_session_read", self._h, what, C.c_void_p(out.ctypes.data), 0)
-        return out
+        return self._group_read("session", what)
 
     def write(self, what: int, value):
-        shape, dt = self._shape(what)
+        shape, dt = self._group_shape("session", what)
         a = np.ascontiguousarray(np.broadcast_to(np.asarray(value, dt), shape))
         self.engine._call("mpcq_session_write", self._h, what, C.c_void_p(a.ctypes.data), 0)
 
     def device_ptr(self, what: int) -> int:
-        out = C.c_void_p()
-        self.engine._call("mpcq_session_device_ptr", self._h, what, C.byref(out))
-        return int(out.value or 0)
+        return self._group_ptr("session", what)

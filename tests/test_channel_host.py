@@ -213,5 +213,5 @@ def test_session_enable_channel_overrides_and_refusals():
     s.disable_channel()
     assert s.engine.calls[-1][0] == "mpcq_session_disable_channel" and s.channel_params is None
     with pytest.raises(L.MpcqError):
-        s._channel_shape(6)
-    assert s._channel_shape(L.HV_S_RING) == ((5, 8, 12), np.float64) and s._channel_shape(L.HV_CLOCK) == ((5, 2), np.int32)
+        s._group_shape("channel", 6)
+    assert s._group_shape("channel", L.HV_S_RING) == ((5, 8, 12), np.float64) and s._group_shape("channel", L.HV_CLOCK) == ((5, 2), np.int32)

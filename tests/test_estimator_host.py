@@ -207,5 +207,5 @@ def test_session_enable_estimator_overrides_and_refusals():
     s.disable_estimator()
     assert s.engine.calls[-1][0] == "mpcq_session_disable_estimator" and s.estimator_params is None
     with pytest.raises(L.MpcqError):
-        s._estimator_shape(2)
-    assert s._estimator_shape(L.EV_ROW) == ((5, 332), np.float64) and s._estimator_shape(L.EV_EST) == ((5, 12), np.float64)
+        s._group_shape("estimator", 2)
+    assert s._group_shape("estimator", L.EV_ROW) == ((5, 332), np.float64) and s._group_shape("estimator", L.EV_EST) == ((5, 12), np.float64)
