@@ -211,6 +211,45 @@ int check_robots(const mpcq_robot* r, int64_t count) {
   return MPCQ_OK;
 }
 
+// What mpcq_estimator_step_batch and mpcq_disturb_step_batch share, after their parameters: the
+// context, the required arrays (the measurement and the first output under the entry point's own
+// names; xs[MI_NX] is its row), a host table's entries, the record's context fields, and the
+// staging of xs[0 .. nx) -- the record's arrays in front, the entry point's own rows behind.
+// B == 0 returns MPCQ_OK with nothing staged.
+enum { MI_FIRST, MI_MEAS, MI_F_PREV, MI_FEET, MI_FAILED, MI_ROBOTS, MI_NX };
+int model_inputs(mpcq_ctx* c, int64_t B, const int32_t* first, int all_first, const char* meas_name, const double* meas,
+                 const double* f_prev, const double* feet_prev, const int32_t* failed_prev, const mpcq_robot* robots,
+                 const char* out_name, uint32_t flags, Xfer* xs, int nx, mpcq::ModelInputs* a) {
+  int rc = mpcq::check_ctx(c, B);
+  if (rc) return rc;
+  if (!meas || !f_prev || !feet_prev || !xs[MI_NX].host_out || !xs[MI_NX + 1].host_out)
+    return fail(MPCQ_E_INVALID, "%s, f_prev, feet_prev, row and %s are required", meas_name, out_name);
+  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
+  if (robots && !dev) {
+    rc = check_robots(robots, B);
+    if (rc) return rc;
+  }
+  if (B == 0) return MPCQ_OK;
+  DeviceGuard g(c->device);
+  a->batch = B;
+  a->all_first = all_first != 0;
+  a->dt = c->p.dt;
+  a->gravity = c->p.gravity;
+  mpcq_default_robot(&c->p, &a->dflt);
+  const size_t b = (size_t)B;
+  xs[MI_FIRST] = {first, nullptr, b * 4, nullptr};
+  xs[MI_MEAS] = {meas, nullptr, b * 96, nullptr};
+  xs[MI_F_PREV] = {f_prev, nullptr, b * 96, nullptr};
+  xs[MI_FEET] = {feet_prev, nullptr, b * 96, nullptr};
+  xs[MI_FAILED] = {failed_prev, nullptr, b * 4, nullptr};
+  xs[MI_ROBOTS] = {robots, nullptr, b * sizeof(mpcq_robot), nullptr};
+  rc = stage(c, xs, nx, dev);
+  if (rc) return rc;
+  a->first = xs[MI_FIRST]; a->meas = xs[MI_MEAS]; a->f_prev = xs[MI_F_PREV]; a->feet_prev = xs[MI_FEET];
+  a->failed = xs[MI_FAILED]; a->robots = xs[MI_ROBOTS];
+  return MPCQ_OK;
+}
+
 // The first entry of a host table that mpcq_set_weights rejects, named in the message.
 int check_weights(const mpcq_weights* w, int64_t count) {
   for (int64_t i = 0; i < count; ++i) {
@@ -1307,39 +1346,18 @@ int mpcq_estimator_step_batch(mpcq_ctx* c, const mpcq_estimator_params* ep, int6
   mpcq_estimator_params P;
   int rc = estimator_params(ep, &P);  // first: what is wrong with the parameters needs no context
   if (rc) return rc;
-  rc = check_ctx(c, B);
-  if (rc) return rc;
-  if (!obs || !f_prev || !feet_prev || !row || !est)
-    return fail(MPCQ_E_INVALID, "obs, f_prev, feet_prev, row and est are required");
-  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
-  if (robots && !dev) {
-    rc = check_robots(robots, B);
-    if (rc) return rc;
-  }
-  if (B == 0) return MPCQ_OK;
-  DeviceGuard g(c->device);
+  const size_t b = B > 0 ? (size_t)B : 0;
+  Xfer xs[MI_NX + 2] = {};
+  xs[MI_NX] = {row, row, b * MPCQ_EST_ROW * 8, nullptr};
+  xs[MI_NX + 1] = {nullptr, est, b * 96, nullptr};
   mpcq::EstimateArgs a{};
-  a.batch = B;
-  a.all_first = all_first != 0;
-  a.dt = c->p.dt;
-  a.gravity = c->p.gravity;
-  mpcq_default_robot(&c->p, &a.dflt);
-  const size_t b = (size_t)B;
-  enum { FI, OB, FP, FT, FA, RB, RO, ES, NX };
-  Xfer xs[NX] = {{first, nullptr, b * 4, nullptr},
-                 {obs, nullptr, b * 96, nullptr},
-                 {f_prev, nullptr, b * 96, nullptr},
-                 {feet_prev, nullptr, b * 96, nullptr},
-                 {failed_prev, nullptr, b * 4, nullptr},
-                 {robots, nullptr, b * sizeof(mpcq_robot), nullptr},
-                 {row, row, b * MPCQ_EST_ROW * 8, nullptr},
-                 {nullptr, est, b * 96, nullptr}};
-  rc = stage(c, xs, NX, dev);
-  if (rc) return rc;
-  a.first = xs[FI]; a.obs = xs[OB]; a.f_prev = xs[FP]; a.feet_prev = xs[FT]; a.failed = xs[FA]; a.robots = xs[RB];
-  a.row = xs[RO]; a.est = xs[ES];
+  rc = model_inputs(c, B, first, all_first, "obs", obs, f_prev, feet_prev, failed_prev, robots, "est", flags, xs,
+                    MI_NX + 2, &a);
+  if (rc || B == 0) return rc;
+  DeviceGuard g(c->device);
+  a.row = xs[MI_NX]; a.est = xs[MI_NX + 1];
   HIP_TRY(mpcq::launch_estimate(P, a, c->stream));
-  return finish(c, xs, NX, flags);
+  return finish(c, xs, MI_NX + 2, flags);
 }
 
 // Disturbance stage: starting values, not tuned (include/mpcq.h).
@@ -1361,40 +1379,19 @@ int mpcq_disturb_step_batch(mpcq_ctx* c, const mpcq_disturb_params* dp, int64_t 
   mpcq_disturb_params P;
   int rc = disturb_params(dp, &P);  // first: what is wrong with the parameters needs no context
   if (rc) return rc;
-  rc = check_ctx(c, B);
-  if (rc) return rc;
-  if (!meas || !f_prev || !feet_prev || !row || !dist)
-    return fail(MPCQ_E_INVALID, "meas, f_prev, feet_prev, row and dist are required");
-  const bool dev = flags & MPCQ_FLAG_DEVICE_PTRS;
-  if (robots && !dev) {
-    rc = check_robots(robots, B);
-    if (rc) return rc;
-  }
-  if (B == 0) return MPCQ_OK;
-  DeviceGuard g(c->device);
+  const size_t b = B > 0 ? (size_t)B : 0;
+  Xfer xs[MI_NX + 3] = {};
+  xs[MI_NX] = {row, row, b * MPCQ_DIST_ROW * 8, nullptr};
+  xs[MI_NX + 1] = {nullptr, dist, b * sizeof(mpcq_disturbance), nullptr};
+  xs[MI_NX + 2] = {nullptr, resid, b * 48, nullptr};  // (optional: null stays null)
   mpcq::DisturbArgs a{};
-  a.batch = B;
-  a.all_first = all_first != 0;
-  a.dt = c->p.dt;
-  a.gravity = c->p.gravity;
-  mpcq_default_robot(&c->p, &a.dflt);
-  const size_t b = (size_t)B;
-  enum { FI, ME, FP, FT, FA, RB, RO, DI, RE, NX };
-  Xfer xs[NX] = {{first, nullptr, b * 4, nullptr},
-                 {meas, nullptr, b * 96, nullptr},
-                 {f_prev, nullptr, b * 96, nullptr},
-                 {feet_prev, nullptr, b * 96, nullptr},
-                 {failed_prev, nullptr, b * 4, nullptr},
-                 {robots, nullptr, b * sizeof(mpcq_robot), nullptr},
-                 {row, row, b * MPCQ_DIST_ROW * 8, nullptr},
-                 {nullptr, dist, b * sizeof(mpcq_disturbance), nullptr},
-                 {nullptr, resid, b * 48, nullptr}};  // (optional: null stays null)
-  rc = stage(c, xs, NX, dev);
-  if (rc) return rc;
-  a.first = xs[FI]; a.meas = xs[ME]; a.f_prev = xs[FP]; a.feet_prev = xs[FT]; a.failed = xs[FA]; a.robots = xs[RB];
-  a.row = xs[RO]; a.dist = xs[DI]; a.resid = xs[RE];
+  rc = model_inputs(c, B, first, all_first, "meas", meas, f_prev, feet_prev, failed_prev, robots, "dist", flags, xs,
+                    MI_NX + 3, &a);
+  if (rc || B == 0) return rc;
+  DeviceGuard g(c->device);
+  a.row = xs[MI_NX]; a.dist = xs[MI_NX + 1]; a.resid = xs[MI_NX + 2];
   HIP_TRY(mpcq::launch_disturb(P, a, c->stream));
-  return finish(c, xs, NX, flags);
+  return finish(c, xs, MI_NX + 3, flags);
 }
 
 // Gait stage: requests by hand, switches at phase boundaries, no speed bands; yaw_weight = the

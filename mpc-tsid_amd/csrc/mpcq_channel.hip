@@ -5,27 +5,24 @@
 // mpcq_session_enable_channel.  One tick of latency is the reference's asynchronous mode
 // (MPC_Wrapper.py:57-78); the rest has no reference counterpart.
 //
-// Sixteen lanes per robot, lane c < 12 owns component c (lanes 12..15 own the four leg gains of
-// the draw row); four robots per wave64, one wave per workgroup.  Every row (state, observation,
-// ring slot, force) is 96 contiguous bytes moved by consecutive lanes, a wave's access 384
-// contiguous bytes; the per-component Philox calls run in parallel, the robot-uniform hold draw
-// is computed by each of the robot's lanes.  A robot's rows are touched by its own 16 lanes of
-// one wave only, which run in lockstep: every load of a row precedes the store that replaces it
-// in program order.  Batch tails are lanes that return at once.  No LDS, no atomics, plain
-// vector loads and stores.  Integer arithmetic for the generator, FP64 without contraction for
-// what is derived, every derived value exact or a single rounding: mpcq/channel.py and
-// tests/channel_model.py restate it on the host, bit for bit.
+// Sixteen lanes per robot (mpcq_stage16.h); lanes 12..15 own the four leg gains of the draw row.
+// Every row (state, observation, ring slot, force) is 96 contiguous bytes moved by consecutive
+// lanes, a wave's access 384 contiguous bytes; the per-component Philox calls run in parallel,
+// the robot-uniform hold draw is computed by each of the robot's lanes.  A robot's lanes run in
+// lockstep: every load of a row precedes the store that replaces it in program order.  Integer
+// arithmetic for the generator, FP64 without contraction for what is derived, every derived
+// value exact or a single rounding: mpcq/channel.py and tests/channel_model.py restate it on the
+// host, bit for bit.
 #include "mpcq_internal.h"
 
 #pragma clang fp contract(off)
 
 #include "mpcq_philox.h"
+#include "mpcq_stage16.h"
 
 namespace mpcq {
 namespace {
 
-constexpr int kLanes = 16;             // per robot
-constexpr int kRobots = 64 / kLanes;   // per wave
 constexpr int kSDepth = MPCQ_CHANNEL_MAX_DELAY, kFDepth = MPCQ_CHANNEL_MAX_LATENCY;
 
 // the centred sum of the four words at unit variance: the sum and the difference are exact
@@ -39,8 +36,9 @@ __device__ inline double normal4(const W4& w) {
 __device__ inline double sym(const W4& w) { return 2.0 * u01(w.w0, w.w1) - 1.0; }
 
 __global__ __launch_bounds__(64) void observe_kernel(mpcq_channel_params ch, ObserveArgs a) {
-  const int c = threadIdx.x & (kLanes - 1);
-  const int64_t b = (int64_t)blockIdx.x * kRobots + (threadIdx.x >> 4);
+  const Lane16 ln = lane16();
+  const int c = ln.c;
+  const int64_t b = ln.b;
   if (b >= a.batch) return;
   const uint32_t k0 = (uint32_t)ch.seed, k1 = (uint32_t)(ch.seed >> 32);
   const bool first = a.all_first || (a.first && a.first[b] != 0);
@@ -75,7 +73,7 @@ __global__ __launch_bounds__(64) void observe_kernel(mpcq_channel_params ch, Obs
     for (int s = 0; s < kSDepth; ++s) ring[s * 12] = truth;
     if (first) {  // the result before any solve (MPC_Wrapper.py:78)
       double* fr = a.f_ring + b * (kFDepth * 12) + c;
-      const double f = c % 3 == 2 ? 8.0 : 0.0;
+      const double f = f_before_first(c);
 #pragma unroll
       for (int s = 0; s < kFDepth; ++s) fr[s * 12] = f;
     }
@@ -100,8 +98,9 @@ __global__ __launch_bounds__(64) void observe_kernel(mpcq_channel_params ch, Obs
 }
 
 __global__ __launch_bounds__(64) void actuate_kernel(mpcq_channel_params ch, ActuateArgs a) {
-  const int c = threadIdx.x & (kLanes - 1);
-  const int64_t b = (int64_t)blockIdx.x * kRobots + (threadIdx.x >> 4);
+  const Lane16 ln = lane16();
+  const int c = ln.c;
+  const int64_t b = ln.b;
   if (b >= a.batch || c >= 12) return;
   const uint32_t k0 = (uint32_t)ch.seed, k1 = (uint32_t)(ch.seed >> 32);
   const int32_t epoch = a.clock[2 * b];
@@ -142,17 +141,11 @@ __global__ __launch_bounds__(64) void arm_kernel(int32_t* clock, int64_t batch) 
 }  // namespace
 
 hipError_t launch_observe(const mpcq_channel_params& ch, const ObserveArgs& a, hipStream_t s) {
-  if (a.batch <= 0) return hipSuccess;
-  if (a.batch > INT32_MAX) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(observe_kernel, dim3((unsigned)((a.batch + kRobots - 1) / kRobots)), dim3(64), 0, s, ch, a);
-  return hipGetLastError();
+  return launch16(observe_kernel, ch, a, s);
 }
 
 hipError_t launch_actuate(const mpcq_channel_params& ch, const ActuateArgs& a, hipStream_t s) {
-  if (a.batch <= 0) return hipSuccess;
-  if (a.batch > INT32_MAX) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(actuate_kernel, dim3((unsigned)((a.batch + kRobots - 1) / kRobots)), dim3(64), 0, s, ch, a);
-  return hipGetLastError();
+  return launch16(actuate_kernel, ch, a, s);
 }
 
 hipError_t launch_channel_arm(int32_t* clock, int64_t batch, hipStream_t s) {

@@ -5,19 +5,14 @@
 // mpcq_disturbance row (include/mpcq.h, mpcq_disturb_step_batch / mpcq_session_enable_disturb).
 // No reference counterpart: the reference's model knows gravity only.
 //
-// The estimator's shape (mpcq_estimator.hip): sixteen lanes per robot, four robots per wave64,
-// one wave per workgroup.  Every row (measurement, previous measurement, ring slot, estimate) is
-// moved by the robot's consecutive lanes, lane c < 12 owning component c.  What a lane loaded is
-// handed to the robot's other lanes by row-local shuffles (width 16), never through LDS; each
-// lane then runs the robot's whole tick, the model step included, so the sums over feet run left
-// to right in foot order on every lane and the bits are the plant's.  Control flow is uniform
-// over a robot's sixteen lanes, so every shuffle reads lanes that are active.  A robot's row is
-// touched by its own 16 lanes only; the one word this launch both stores and may need again (the
-// previous tick's f0, at f_lag 0) travels in registers, and the ring has MAX_F_LAG + 1 slots, so
-// the slot recorded is never the slot read.  Batch tails are lanes that return at once.  No LDS,
-// no atomics, plain vector loads and stores.  One model step per robot: the launch's cost is
-// latency.  FP64 without contraction: tests/disturb_model.py restates it in numpy and differs
-// by the device library's sin / cos.
+// Sixteen lanes per robot (mpcq_stage16.h).  The rows are the measurement, the previous
+// measurement, the ring slots and the estimate.  Each lane runs the robot's whole tick, the model
+// step included, so the sums over feet run left to right in foot order on every lane and the
+// bits are the plant's.  The one word this launch both stores and may need again (the previous
+// tick's f0, at f_lag 0) travels in registers, and the ring has MAX_F_LAG + 1 slots, so the slot
+// recorded is never the slot read.  One model step per robot: the launch's cost is latency.  FP64
+// without contraction: tests/disturb_model.py restates it in numpy and differs by the device
+// library's sin / cos.
 #include <math.h>
 
 #include "mpcq_internal.h"
@@ -25,55 +20,32 @@
 #pragma clang fp contract(off)
 
 #include "mpcq_model.h"
+#include "mpcq_stage16.h"
 
 namespace mpcq {
 namespace {
 
-constexpr int kLanes = 16;             // per robot
-constexpr int kRobots = 64 / kLanes;   // per wave
 constexpr int kSlots = MPCQ_DIST_SLOTS;
 static_assert(kSlots == MPCQ_DISTURB_MAX_F_LAG + 1, "the ring holds f_lag + 1 ticks");
 static_assert(MPCQ_DIST_RING + kSlots * 12 == MPCQ_DIST_ROW && MPCQ_DIST_ROW % 2 == 0, "the stage's row");
 static_assert(MPCQ_DIST_PREV == MPCQ_DIST_D + 6 && MPCQ_DIST_CLOCK == MPCQ_DIST_PREV + 12 &&
                   MPCQ_DIST_RING == MPCQ_DIST_CLOCK + 2, "the stage's row");
 
-// v of the robot's lanes 0..n-1 on every lane of the robot
-template <int n>
-__device__ __forceinline__ void gather(double v, double* out) {
-#pragma unroll
-  for (int i = 0; i < n; ++i) out[i] = __shfl(v, i, kLanes);
-}
-
-// v[c] as a chain of selects.  The empty asm keeps the compiler from folding the chain into
-// v[c]: an array indexed by a lane's number would live in scratch.
-template <int n>
-__device__ __forceinline__ double pick(const double* v, int c) {
-  double r = v[0];
-#pragma unroll
-  for (int i = 1; i < n; ++i) {
-    r = c == i ? v[i] : r;
-    asm("" : "+v"(r));
-  }
-  return r;
-}
-
 __global__ __launch_bounds__(64) void disturb_kernel(mpcq_disturb_params dp, DisturbArgs a) {
-  const int c = threadIdx.x & (kLanes - 1);
-  const int64_t b = (int64_t)blockIdx.x * kRobots + (threadIdx.x >> 4);
+  const Lane16 ln = lane16();
+  const int c = ln.c, cc = ln.cc, c6 = ln.c6;
+  const int64_t b = ln.b;
   if (b >= a.batch) return;
-  const int cc = c < 12 ? c : 11;  // lanes 12..15 load what lane 11 loads and store no component
-  const int c6 = c < 6 ? c : 5;    // the same for the six-component rows
   double* row = a.row + b * MPCQ_DIST_ROW;
   int32_t* clk = (int32_t*)(row + MPCQ_DIST_CLOCK);
   const int32_t valid = clk[0], tau_next = clk[1];
 
   const double y_own = a.meas[b * 12 + cc];
   const double prev_own = row[MPCQ_DIST_PREV + cc];
-  const unsigned shift = threadIdx.x & 48u;
-  const unsigned bad = (unsigned)(__ballot(!isfinite(y_own) || !isfinite(prev_own)) >> shift) & 0xfffu;
-  const unsigned same = (unsigned)(__ballot(__double_as_longlong(y_own) == __double_as_longlong(prev_own)) >> shift) & 0xfffu;
+  const unsigned bad = robot_bits12(!isfinite(y_own) || !isfinite(prev_own), ln.shift);
+  const unsigned same = robot_bits12(__double_as_longlong(y_own) == __double_as_longlong(prev_own), ln.shift);
 
-  const bool first = a.all_first || (a.first && a.first[b] != 0);
+  const bool first = first_tick(a, b);
   // (tau_next < 1 on a valid row is not the stage's own: it initialises too, and every ring
   // index below is then non-negative)
   const bool init = first || valid == 0 || tau_next < 1;
@@ -87,29 +59,16 @@ __global__ __launch_bounds__(64) void disturb_kernel(mpcq_disturb_params dp, Dis
   int tau = 0;
   if (!init) {
     tau = tau_next;
-    bool failed = false;
-    if (a.failed) {
-      failed = a.failed[b] != 0;
-    } else if (a.status) {  // the plant's rule
-      const int st = a.status[b];
-      failed = !(st == MPCQ_STATUS_SOLVED || st == MPCQ_STATUS_SOLVED_INACCURATE || st == MPCQ_STATUS_MAX_ITER_REACHED) ||
-               a.plan_status[b] != 0;
-    }
-    const bool skip = failed || bad != 0u || (dp.skip_repeats != 0 && same == 0xfffu);
-    // the robot the controller believes (scalars: a struct chosen at run time would live in scratch)
-    const mpcq_robot* rp = a.robots ? a.robots + b : nullptr;
-    const double mass = rp ? rp->mass : a.dflt.mass;
-    double gI[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) gI[i] = rp ? rp->gI[i] : a.dflt.gI[i];
+    const bool skip = prev_failed(a, b) || bad != 0u || (dp.skip_repeats != 0 && same == 0xfffu);
+    double mass, gI[9];
+    believed_robot(a, b, mass, gI);
     const double dt = a.dt;
     gather<6>(row[MPCQ_DIST_D + c6], d);
     // the previous tick's inputs: its f0 for the record, its feet and the force that acted
     const double f_last = a.f_prev[b * 12 + cc];
-    const double feet_own = a.feet_prev ? a.feet_prev[b * 12 + cc]
-                                        : a.fsteps[b * 260 + 1 + 3 * (cc & 3) + (cc >> 2)];
+    const double feet_own = prev_feet_own(a.feet_prev, a.fsteps, b, cc);
     const int fj = tau - 1 - dp.f_lag;
-    double f_own = cc % 3 == 2 ? 8.0 : 0.0;  // before tick 0: MPC_Wrapper.py:78
+    double f_own = f_before_first(cc);
     if (fj >= 0) f_own = row[MPCQ_DIST_RING + (fj % kSlots) * 12 + cc];  // (f_lag 0: replaced below)
     if (dp.f_lag == 0) f_own = f_last;
     if (c < 12) row[MPCQ_DIST_RING + ((tau - 1) % kSlots) * 12 + c] = f_last;  // the record
@@ -170,10 +129,7 @@ __global__ __launch_bounds__(64) void disturb_kernel(mpcq_disturb_params dp, Dis
 }  // namespace
 
 hipError_t launch_disturb(const mpcq_disturb_params& dp, const DisturbArgs& a, hipStream_t s) {
-  if (a.batch <= 0) return hipSuccess;
-  if (a.batch > INT32_MAX) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(disturb_kernel, dim3((unsigned)((a.batch + kRobots - 1) / kRobots)), dim3(64), 0, s, dp, a);
-  return hipGetLastError();
+  return launch16(disturb_kernel, dp, a, s);
 }
 
 }  // namespace mpcq

@@ -71,6 +71,13 @@ struct LaunchArgs {
   const mpcq_disturbance* disturb;
 };
 constexpr int32_t kStatusSuspended = 100;  // (internal: the host loop resumes these)
+// The plant's rule, which every stage of a session shares: a robot whose solve ended in none of
+// SOLVED, SOLVED_INACCURATE, MAX_ITER_REACHED, or whose planner failed (where the reference
+// raises), failed its tick.
+__host__ __device__ inline bool solve_failed(int status, int plan_status) {
+  return !(status == MPCQ_STATUS_SOLVED || status == MPCQ_STATUS_SOLVED_INACCURATE ||
+           status == MPCQ_STATUS_MAX_ITER_REACHED) || plan_status != 0;
+}
 constexpr int64_t res_lanes(int N) { return 16 * (int64_t)((N + 3) & ~3); }
 
 // Doubles of engine workspace per instance: 0 up to 32 stages (everything in LDS);
@@ -330,31 +337,10 @@ hipError_t launch_actuate(const mpcq_channel_params& ch, const ActuateArgs& a, h
 // mpcq_session_enable_channel's launch: every non-negative stored tau to its complement
 hipError_t launch_channel_arm(int32_t* clock, int64_t batch, hipStream_t s);
 
-// Estimate stage (mpcq_estimator.hip); semantics and layouts in include/mpcq.h
-// (mpcq_estimator_step_batch, mpcq_session_enable_estimator).  Sixteen lanes per robot.
-struct EstimateArgs {
-  int64_t batch;
-  const int32_t* first;    // [B] or null: nonzero = a first tick
-  int all_first;           // every robot runs a first tick
-  const double* obs;       // [B][12]
-  const double* f_prev;    // [B][12]
-  const double* feet_prev; // [B][3][4], or null with fsteps
-  const double* fsteps;    // [B][20][13] (a session's tick): the feet are row 0's
-  const int32_t* failed;   // [B] or null: nonzero = the previous tick failed
-  // a session's tick: the previous tick's statuses, failed by the plant's rule (failed null)
-  const int32_t* status;      // [B] or null
-  const int32_t* plan_status; // [B]
-  const mpcq_robot* robots;// [B] or null: dflt
-  mpcq_robot dflt;
-  double dt, gravity;      // the context's
-  double* row;             // [B][MPCQ_EST_ROW] in/out
-  double* est;             // [B][12] out
-};
-hipError_t launch_estimate(const mpcq_estimator_params& ep, const EstimateArgs& a, hipStream_t s);
-
-// Disturbance stage (mpcq_disturb.hip); semantics and layouts in include/mpcq.h
-// (mpcq_disturb_step_batch, mpcq_session_enable_disturb).  Sixteen lanes per robot.
-struct DisturbArgs {
+// What the stages that run the controller's model read, alone (mpcq_*_step_batch) or in a
+// session's tick: the measurement, the previous tick's forces, feet and failure, the robot the
+// controller believes.
+struct ModelInputs {
   int64_t batch;
   const int32_t* first;    // [B] or null: nonzero = a first tick
   int all_first;           // every robot runs a first tick
@@ -363,12 +349,25 @@ struct DisturbArgs {
   const double* feet_prev; // [B][3][4], or null with fsteps
   const double* fsteps;    // [B][20][13] (a session's tick): the feet are row 0's
   const int32_t* failed;   // [B] or null: nonzero = the previous tick failed
-  // a session's tick: the previous tick's statuses, failed by the plant's rule (failed null)
+  // a session's tick: the previous tick's statuses, failed by solve_failed (failed null)
   const int32_t* status;      // [B] or null
   const int32_t* plan_status; // [B]
   const mpcq_robot* robots;// [B] or null: dflt
   mpcq_robot dflt;
   double dt, gravity;      // the context's
+};
+
+// Estimate stage (mpcq_estimator.hip); semantics and layouts in include/mpcq.h
+// (mpcq_estimator_step_batch, mpcq_session_enable_estimator).  Sixteen lanes per robot.
+struct EstimateArgs : ModelInputs {
+  double* row;             // [B][MPCQ_EST_ROW] in/out
+  double* est;             // [B][12] out
+};
+hipError_t launch_estimate(const mpcq_estimator_params& ep, const EstimateArgs& a, hipStream_t s);
+
+// Disturbance stage (mpcq_disturb.hip); semantics and layouts in include/mpcq.h
+// (mpcq_disturb_step_batch, mpcq_session_enable_disturb).  Sixteen lanes per robot.
+struct DisturbArgs : ModelInputs {
   double* row;             // [B][MPCQ_DIST_ROW] in/out
   mpcq_disturbance* dist;  // [B] out
   double* resid;           // [B][6] out, or null

@@ -126,10 +126,7 @@ __global__ __launch_bounds__(64) void plant_kernel(mpcq_plant_params pl, PlantAr
   double* so = a.state_out + b * 12;
   double* fe = a.f_eff ? a.f_eff + b * 12 : nullptr;
   if (a.tail) {
-    const int st = a.status[b];
-    const bool failed = !(st == MPCQ_STATUS_SOLVED || st == MPCQ_STATUS_SOLVED_INACCURATE ||
-                          st == MPCQ_STATUS_MAX_ITER_REACHED) || a.plan_status[b] != 0;
-    if (failed) {  // the retrieve kept its pose and virtual state: so does the plant
+    if (solve_failed(a.status[b], a.plan_status[b])) {  // the retrieve kept its pose and virtual state: so does the plant
 #pragma unroll
       for (int e = 0; e < 12; ++e) {
         so[e] = NAN;

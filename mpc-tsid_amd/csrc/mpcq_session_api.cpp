@@ -670,40 +670,40 @@ int tick_observe(mpcq_session* s, Tick& t) {
   return MPCQ_OK;
 }
 
-// The estimator: the planner's state becomes the filter's estimate from what it would have
-// taken (t.plan_state), the previous tick's f0, feet and statuses as they stand before this
-// tick's planner, and the model's robots; it takes the first flags as the planner will.
-int tick_estimate(mpcq_session* s, Tick& t) {
+// What the estimator and the disturbance stage read in a tick: what the planner would take as
+// its state (t.plan_state), the previous tick's f0, feet and statuses as they stand before this
+// tick's planner, and the model's robots; they take the first flags as the planner will.
+void tick_model_inputs(mpcq_session* s, const Tick& t, mpcq::ModelInputs* a) {
   mpcq_ctx* c = s->ctx;
-  const Group &v = s->grp[G_MAIN], &e = s->grp[G_ESTIMATOR];
+  const Group& v = s->grp[G_MAIN];
+  a->batch = s->B; a->first = t.first_k; a->all_first = t.k == 0; a->meas = t.plan_state;
+  a->f_prev = v.d(MPCQ_SV_F0); a->fsteps = v.d(MPCQ_SV_FSTEPS);
+  a->status = v.i(MPCQ_SV_STATUS); a->plan_status = v.i(SP_PLAN_STATUS);
+  a->robots = s->robots.count ? s->robots.dev : nullptr;
+  mpcq_default_robot(&c->p, &a->dflt);
+  a->dt = c->p.dt; a->gravity = c->p.gravity;
+}
+
+// The estimator: the planner's state becomes the filter's estimate from what it would have
+// taken (tick_model_inputs).
+int tick_estimate(mpcq_session* s, Tick& t) {
+  const Group& e = s->grp[G_ESTIMATOR];
   mpcq::EstimateArgs a{};
-  a.batch = s->B; a.first = t.first_k; a.all_first = t.k == 0; a.obs = t.plan_state;
-  a.f_prev = v.d(MPCQ_SV_F0); a.fsteps = v.d(MPCQ_SV_FSTEPS);
-  a.status = v.i(MPCQ_SV_STATUS); a.plan_status = v.i(SP_PLAN_STATUS);
-  a.robots = s->robots.count ? s->robots.dev : nullptr;
-  mpcq_default_robot(&c->p, &a.dflt);
-  a.dt = c->p.dt; a.gravity = c->p.gravity;
+  tick_model_inputs(s, t, &a);
   a.row = e.d(MPCQ_EV_ROW); a.est = e.d(MPCQ_EV_EST);
-  HIP_TRY(mpcq::launch_estimate(s->ep, a, c->stream));
+  HIP_TRY(mpcq::launch_estimate(s->ep, a, s->ctx->stream));
   t.plan_state = e.d(MPCQ_EV_EST);
   return MPCQ_OK;
 }
 
 // The disturbance stage: MPCQ_DV_DIST from what the planner is about to take as its state
-// (t.plan_state, which stays), the previous tick's f0, feet and statuses as they stand before
-// this tick's planner, and the model's robots; it takes the first flags as the planner will.
+// (t.plan_state, which stays; tick_model_inputs).
 int tick_disturb(mpcq_session* s, const Tick& t) {
-  mpcq_ctx* c = s->ctx;
-  const Group &v = s->grp[G_MAIN], &d = s->grp[G_DISTURB];
+  const Group& d = s->grp[G_DISTURB];
   mpcq::DisturbArgs a{};
-  a.batch = s->B; a.first = t.first_k; a.all_first = t.k == 0; a.meas = t.plan_state;
-  a.f_prev = v.d(MPCQ_SV_F0); a.fsteps = v.d(MPCQ_SV_FSTEPS);
-  a.status = v.i(MPCQ_SV_STATUS); a.plan_status = v.i(SP_PLAN_STATUS);
-  a.robots = s->robots.count ? s->robots.dev : nullptr;
-  mpcq_default_robot(&c->p, &a.dflt);
-  a.dt = c->p.dt; a.gravity = c->p.gravity;
+  tick_model_inputs(s, t, &a);
   a.row = d.d(MPCQ_DV_ROW); a.dist = (mpcq_disturbance*)d.ptr[MPCQ_DV_DIST]; a.resid = d.d(MPCQ_DV_RESID);
-  HIP_TRY(mpcq::launch_disturb(s->dp, a, c->stream));
+  HIP_TRY(mpcq::launch_disturb(s->dp, a, s->ctx->stream));
   return MPCQ_OK;
 }
 

@@ -21,6 +21,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from . import _stage as S
 from .engine import Engine, _p
 from .scenario import _key, philox, u01
 
@@ -136,8 +137,7 @@ class Channel:
     def observe_device(self, batch: int, truth_ptr: int, clock_ptr: int, obs_ptr: int, draw_ptr: int, s_ring_ptr: int,
                        f_ring_ptr: int, first_ptr: int = 0, all_first: bool = False, asynchronous: bool = True):
         """observe on device-resident arrays (pointers on the engine's device; 0 = absent)."""
-        flags = L.FLAG_DEVICE_PTRS | (L.FLAG_ASYNC if asynchronous else 0)
-        v = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        v, flags = S.v, S.device_flags(asynchronous)
         self.engine._call("mpcq_channel_observe_batch", self.engine._h, C.byref(self.params), int(batch), v(first_ptr),
                           int(bool(all_first)), v(truth_ptr), v(clock_ptr), v(obs_ptr), v(draw_ptr), v(s_ring_ptr),
                           v(f_ring_ptr), flags)
@@ -145,7 +145,6 @@ class Channel:
     def actuate_device(self, batch: int, f0_ptr: int, clock_ptr: int, draw_ptr: int, f_ring_ptr: int, f_cmd_ptr: int,
                        asynchronous: bool = True):
         """actuate on device-resident arrays."""
-        flags = L.FLAG_DEVICE_PTRS | (L.FLAG_ASYNC if asynchronous else 0)
-        v = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        v, flags = S.v, S.device_flags(asynchronous)
         self.engine._call("mpcq_channel_actuate_batch", self.engine._h, C.byref(self.params), int(batch), v(f0_ptr),
                           v(clock_ptr), v(draw_ptr), v(f_ring_ptr), v(f_cmd_ptr), flags)

@@ -17,7 +17,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from .engine import ROBOT_DTYPE, Engine, _p
+from . import _stage as S
+from .engine import Engine, _p
 
 F_INIT = np.tile([0.0, 0.0, 8.0], 4)  # the result before any solve (MPC_Wrapper.py:78)
 
@@ -54,37 +55,18 @@ class Estimator:
         nonzero = a first tick / the previous tick failed, ``robots`` (B,) ROBOT_DTYPE the
         robots the controller believes (None: the engine's parameters).  Returns (est (B, 12),
         rows)."""
-        obs = np.ascontiguousarray(obs, np.float64)
-        if obs.ndim != 2 or obs.shape[1] != 12:
-            raise ValueError("obs must be (B, 12)")
-        B = obs.shape[0]
-        f_prev = np.ascontiguousarray(np.broadcast_to(np.asarray(f_prev, np.float64), (B, 12)))
-        feet_prev = np.ascontiguousarray(np.broadcast_to(np.asarray(feet_prev, np.float64), (B, 3, 4)))
-        if rows is None:
-            rows = new_rows(B)
-        if not (isinstance(rows, np.ndarray) and rows.shape == (B, L.EST_ROW) and rows.dtype == np.float64
-                and rows.flags.c_contiguous):
-            raise ValueError(f"rows must be a contiguous float64 array of shape ({B}, {L.EST_ROW})")
-        mask = lambda m: None if m is None else np.ascontiguousarray(  # noqa: E731
-            np.broadcast_to(np.asarray(m) != 0, (B,)), np.int32)
-        fi, fa = mask(first), mask(failed_prev)
-        tab = None
-        if robots is not None:
-            tab = np.ascontiguousarray(robots, ROBOT_DTYPE)
-            if tab.shape != (B,):
-                raise ValueError(f"robots must be ({B},)")
+        B, rows, (fi, *ins) = S.model_inputs("obs", obs, f_prev, feet_prev, rows, L.EST_ROW, first, failed_prev,
+                                             robots)
         est = np.empty((B, 12))
         self.engine._call("mpcq_estimator_step_batch", self.engine._h, C.byref(self.params), B, _p(fi),
-                          int(bool(all_first)), _p(obs), _p(f_prev), _p(feet_prev), _p(fa),
-                          None if tab is None else C.c_void_p(tab.ctypes.data), _p(rows), _p(est), 0)
+                          int(bool(all_first)), *map(_p, ins), _p(est), 0)
         return est, rows
 
     def step_device(self, batch: int, obs_ptr: int, f_prev_ptr: int, feet_prev_ptr: int, row_ptr: int, est_ptr: int,
                     first_ptr: int = 0, all_first: bool = False, failed_prev_ptr: int = 0, robots_ptr: int = 0,
                     asynchronous: bool = True):
         """step on device-resident arrays (pointers on the engine's device; 0 = absent)."""
-        flags = L.FLAG_DEVICE_PTRS | (L.FLAG_ASYNC if asynchronous else 0)
-        v = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        v, flags = S.v, S.device_flags(asynchronous)
         self.engine._call("mpcq_estimator_step_batch", self.engine._h, C.byref(self.params), int(batch), v(first_ptr),
                           int(bool(all_first)), v(obs_ptr), v(f_prev_ptr), v(feet_prev_ptr), v(failed_prev_ptr),
                           v(robots_ptr), v(row_ptr), v(est_ptr), flags)

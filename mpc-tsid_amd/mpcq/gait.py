@@ -14,6 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from . import _stage as S
 from .engine import Engine, _f64, _p
 from .planner import _MASKS
 
@@ -93,7 +94,6 @@ class Gait:
     # ------------------------------------------------------------------ device pointers
     def roll_device(self, batch: int, gait_ptr: int, state_ptr: int, v_ref_ptr: int = 0, asynchronous: bool = True):
         """roll on device-resident arrays (pointers on the engine's device; 0 = absent)."""
-        flags = L.FLAG_DEVICE_PTRS | (L.FLAG_ASYNC if asynchronous else 0)
-        v = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        v, flags = S.v, S.device_flags(asynchronous)
         self.engine._call("mpcq_gait_roll_batch", self.engine._h, C.byref(self.params), _p(self.cycles), int(batch),
                           v(v_ref_ptr), v(gait_ptr), v(state_ptr), flags)

@@ -13,6 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from . import _stage as S
 from .engine import Engine, _f64, _p
 
 
@@ -66,8 +67,7 @@ class Monitor:
                     episodes_ptr: int = 0, last_ptr: int = 0, totals_ptr: int = 0, trace_ptr: int = 0,
                     asynchronous: bool = True):
         """step on device-resident arrays (pointers on the engine's device; 0 = absent)."""
-        flags = L.FLAG_DEVICE_PTRS | (L.FLAG_ASYNC if asynchronous else 0)
-        v = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        v, flags = S.v, S.device_flags(asynchronous)
         self.engine._call("mpcq_monitor_step_batch", self.engine._h, C.byref(self.params), int(batch), v(q_w_ptr),
                           v(status_ptr), v(iters_ptr), v(f0_ptr), v(cost_ptr), v(state_ptr), v(v_ref_ptr), v(ep_ptr),
                           v(ep_ticks_ptr), v(episodes_ptr), v(last_ptr), v(done_ptr), v(totals_ptr), v(trace_ptr),

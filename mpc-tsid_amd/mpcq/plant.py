@@ -15,6 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from . import _stage as S
 from .engine import Engine, _f64, _p, _robot_table
 
 
@@ -48,7 +49,6 @@ class Plant:
                     f_eff_ptr: int = 0, wrench_ptr: int = 0, robots_ptr: int = 0, asynchronous: bool = True):
         """step on device-resident arrays (pointers on the engine's device; 0 = absent);
         ``state_out_ptr`` may be ``state_ptr``.  A device robots table is not validated."""
-        flags = L.FLAG_DEVICE_PTRS | (L.FLAG_ASYNC if asynchronous else 0)
-        v = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        v, flags = S.v, S.device_flags(asynchronous)
         self.engine._call("mpcq_plant_step_batch", self.engine._h, C.byref(self.params), int(batch), v(state_ptr),
                           v(feet_ptr), v(f_ptr), v(wrench_ptr), v(robots_ptr), v(state_out_ptr), v(f_eff_ptr), flags)

@@ -22,6 +22,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from . import _stage as S
 from .engine import ROBOT_DTYPE, Engine, _p, _robot_table
 
 _M0, _M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
@@ -187,8 +188,7 @@ class Scenario:
                     wrench_out_ptr: int, first_ptr: int = 0, all_first: bool = False, base_ptr: int = 0,
                     wrench_in_ptr: int = 0, robots_out_ptr: int = 0, draw_ptr: int = 0, asynchronous: bool = True):
         """step on device-resident arrays (pointers on the engine's device; 0 = absent)."""
-        flags = L.FLAG_DEVICE_PTRS | (L.FLAG_ASYNC if asynchronous else 0)
-        v = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        v, flags = S.v, S.device_flags(asynchronous)
         self.engine._call("mpcq_scenario_step_batch", self.engine._h, C.byref(self.params), int(batch), v(first_ptr),
                           int(bool(all_first)), v(epoch_ptr), v(tick_ptr), v(base_ptr), v(wrench_in_ptr), v(v_ref_ptr),
                           v(push_ptr), v(wrench_out_ptr), v(robots_out_ptr), v(draw_ptr), flags)

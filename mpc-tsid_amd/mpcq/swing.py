@@ -20,6 +20,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from . import _stage as S
 from .engine import Engine, _f64, _p
 
 
@@ -68,8 +69,7 @@ class Swing:
 
     # ------------------------------------------------------------------ device pointers
     def step_device(self, in_ptr: int, state_ptr: int, out_ptr: int, asynchronous: bool = True):
-        flags = L.FLAG_DEVICE_PTRS | (L.FLAG_ASYNC if asynchronous else 0)
-        v = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        v, flags = S.v, S.device_flags(asynchronous)
         self.engine._call("mpcq_swing_step_batch", self.engine._h, C.byref(self.params), self.batch, v(in_ptr),
                           v(state_ptr), v(out_ptr), flags)
 
@@ -79,8 +79,7 @@ class Swing:
         """advance on device-resident arrays (pointers on the engine's device); the state is
         the caller's device array, not ``self.state``."""
         n = int(self.params.k_mpc) - int(k_sub0) if n_sub is None else int(n_sub)
-        flags = L.FLAG_DEVICE_PTRS | (L.FLAG_ASYNC if asynchronous else 0)
-        v = lambda q: C.c_void_p(q) if q else None  # noqa: E731
+        v, flags = S.v, S.device_flags(asynchronous)
         self.engine._call("mpcq_swing_batch", self.engine._h, C.byref(self.params), self.batch, int(k_sub0), n,
                           v(gait_ptr), v(fsteps_ptr), v(frame_ptr), v(feet0_ptr), v(state_ptr), v(ref_ptr),
                           v(t0_ptr), v(status_ptr), flags)
