@@ -27,29 +27,24 @@
 // The two sweeps run at once in rows 0 and 1 of wave 0 (one instruction
 // stream), reading G / H from LDS; S^{-1}, U^{-1}, M^{-1} rows stay in the
 // stage lanes' registers.
+//
+// Files: mpcq_engine_layout.h (CSC offsets, slots, per-horizon
+// switches, Smem / Work / Prologue), mpcq_engine_lanes.h (lane primitives),
+// mpcq_engine_gj.h (Gauss-Jordan and Schur steps), mpcq_engine_form.h (formulation
+// pieces); here the kernel, in numbered sections, its launcher and the per-horizon entry.
 #include <math.h>
 
 #include <type_traits>
 #include <utility>
 
 #include "mpcq_internal.h"
+#include "mpcq_engine_layout.h"
+#include "mpcq_engine_lanes.h"
+#include "mpcq_engine_gj.h"
+#include "mpcq_engine_form.h"
 
 namespace mpcq {
 namespace {
-
-// LDS views used by the loops.  Reads of loop-invariant data (the scaled A,
-// the sweep matrices) go through these pointers, which the loops launder with
-// an empty asm so the compiler re-reads LDS instead of hoisting dozens of
-// invariant values into registers.
-typedef __attribute__((address_space(3))) const double lds_cd;
-typedef __attribute__((address_space(3))) double lds_d;
-typedef double dbl2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) const dbl2 lds_cd2;
-// the per-instance workspace (N > 32) in the global address space: generic (flat)
-// loads would also count in lgkmcnt, so every LDS wait behind them would wait for L2
-typedef __attribute__((address_space(1))) const double g_cd;
-typedef __attribute__((address_space(1))) double g_d;
-typedef __attribute__((address_space(1))) const dbl2 g_cd2;
 
 constexpr double kInf = 1e30;  // OSQP_INFTY
 constexpr double kMinScaling = 1e-4, kMaxScaling = 1e4;
@@ -59,6 +54,9 @@ constexpr double kDivTol = 1e-30;
 // constraint classes (OSQP set_rho_vec)
 enum : unsigned { RC_LOOSE = 0, RC_INEQ = 1, RC_EQ = 2 };
 
+#ifndef MPCQ_STAMP_WAVE
+#define MPCQ_STAMP_WAVE 0
+#endif
 #if defined(MPCQ_STAMPS) && defined(MPCQ_STAMPS_LEAN)
 // lean variant: only the uniform points after the loop's barriers (1 prologue, 2 factor,
 // 3 P1-P4, 7 sweeps, 10 P8-P9, 11 checks, 12 epilogue), accumulated in SGPRs without a
@@ -76,38 +74,6 @@ enum : unsigned { RC_LOOSE = 0, RC_INEQ = 1, RC_EQ = 2 };
 #define STAMP(i) do {} while (0)
 #endif
 
-// ---------------------------------------------------------------------------
-// CSC offsets of MPC.create_ML's pattern (see mpcq_pattern in mpcq_api.cpp).
-template <int N>
-__device__ __forceinline__ int XO(int k, int i) {  // state column X_{k+1}[i]
-  return (k < N - 1) ? 30 * k + (i < 6 ? 2 * i : 12 + 3 * (i - 6)) : 30 * (N - 1) + i;
-}
-template <int N>
-__device__ __forceinline__ int FO(int k, int f, int c) {  // force column f_k[3f+c]
-  return 30 * N - 18 + 96 * k + 24 * f + 7 * c;
-}
-// lane (within the stage row) that owns force / state index psi = 3f + c
-__host__ __device__ constexpr int LN(int psi) { return 4 * (psi / 3) + psi % 3; }
-
-// Step-ordered slots of the sweep arrays.  The top chain walks stages 0, 1, ..
-// upwards and the bottom chain N-1, N-2, .. downwards; storing the bottom
-// stages in reverse (stage k > MID at slot N + MID - k) makes both chains walk
-// their slots in the same direction, so every lane of the sweep wave addresses
-// step j as (its own base) + j * (a uniform stride): an immediate offset, no
-// per-step pointer arithmetic.  SIG: G/H, S^-1 and the right-hand sides
-// (stages 0..N-1); SIGX: the state vectors xs[q] = X_q, q = 0..N.
-template <int N>
-__host__ __device__ constexpr int SIG(int k) { return k <= N / 2 ? k : N + N / 2 - k; }
-template <int N>
-__host__ __device__ constexpr int SIGX(int q) { return q <= N / 2 ? q : N + N / 2 + 1 - q; }
-
-// Stage rows of the layout: a wave64 holds four 16-lane rows, so the workgroup
-// has N rounded up to a multiple of 4 rows.  The rows past N ("phantom" rows)
-// run as copies of stage N-1: they read what row N-1 reads and store the same
-// values to the same places (identical stores), are left out of the in-place
-// updates and the sums, and their maxima duplicate row N-1's.
-template <int N>
-constexpr int kRows = (N + 3) & ~3;
 // Sliced solves (LaunchArgs::slice_iters / resume, mpcq_set_slice) beyond 16 stages: one
 // instance per CU there, so a long solve dispatched in a late round ends the launch late
 // (DESIGN.md section 8).  Up to 16 stages two instances share a CU and slicing does not
@@ -118,744 +84,37 @@ constexpr int kRows = (N + 3) & ~3;
 template <int N>
 constexpr bool kSlice = slice_supported(N);
 
-// ---------------------------------------------------------------------------
-// cross-lane helpers
-
-__device__ __forceinline__ void wave_sync() {
-  // LDS is processed in order per wave, so a hand-off inside one wave needs no
-  // hardware barrier; the asm memory clobber stops the compiler from moving
-  // LDS accesses across this point.
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ void sync_all() { __syncthreads(); }
-
-template <int CTRL>
-__device__ __forceinline__ double dppd(double v) {
-  // one v_mov_b64_dpp for row_newbcast (DPP64); other controls split in two.
-  // Every lane of every row is active wherever these run, so no "old" value.
-  return __longlong_as_double(__builtin_amdgcn_mov_dpp(__double_as_longlong(v), CTRL, 0xF, 0xF, false));
-}
-// broadcast lane J of each 16-lane row (DPP row_newbcast, gfx90a+)
-template <int J>
-__device__ __forceinline__ double rbc(double v) { return dppd<0x150 + J>(v); }
-// broadcast lane J of each quad (quad_perm J,J,J,J)
-template <int J>
-__device__ __forceinline__ double qbc(double v) { return dppd<85 * J>(v); }
-// lane i of each quad takes the quad's lane Ji (quad_perm [J0, J1, J2, J3]): a select between
-// quad broadcasts on the lane's place in its quad, as one move
-template <int J0, int J1, int J2, int J3>
-__device__ __forceinline__ double qperm(double v) { return dppd<J0 + 4 * J1 + 16 * J2 + 64 * J3>(v); }
-
-// Every element of a[] in a register at one point: one empty asm reads and redefines them
-// all, so the loads that produce them are all issued ahead of it and waited for once.  Left
-// to itself the compiler put some of the check's LDS reads one behind the other through the
-// same registers, each with its own s_waitcnt lgkmcnt(0) in front of its use (N = 16: twelve
-// round trips in a row in the residuals' primal side).  Values and
-// arithmetic are untouched.
-#define MPCQ_HV(i) "+v"(a[i])
-#define MPCQ_HV4(i) MPCQ_HV(i), MPCQ_HV(i + 1), MPCQ_HV(i + 2), MPCQ_HV(i + 3)
-template <int n>
-__device__ __forceinline__ void hold_all(double (&a)[n]) {
-  static_assert((n >= 1 && n <= 8) || n == 15 || n == 21, "hold_all: spell this count out");
-  if constexpr (n == 1) asm volatile("" : MPCQ_HV(0));
-  if constexpr (n == 2) asm volatile("" : MPCQ_HV(0), MPCQ_HV(1));
-  if constexpr (n == 3) asm volatile("" : MPCQ_HV(0), MPCQ_HV(1), MPCQ_HV(2));
-  if constexpr (n == 4) asm volatile("" : MPCQ_HV4(0));
-  if constexpr (n == 5) asm volatile("" : MPCQ_HV4(0), MPCQ_HV(4));
-  if constexpr (n == 6) asm volatile("" : MPCQ_HV4(0), MPCQ_HV(4), MPCQ_HV(5));
-  if constexpr (n == 7) asm volatile("" : MPCQ_HV4(0), MPCQ_HV(4), MPCQ_HV(5), MPCQ_HV(6));
-  if constexpr (n == 8) asm volatile("" : MPCQ_HV4(0), MPCQ_HV4(4));
-  if constexpr (n == 15) asm volatile("" : MPCQ_HV4(0), MPCQ_HV4(4), MPCQ_HV4(8), MPCQ_HV(12), MPCQ_HV(13), MPCQ_HV(14));
-  if constexpr (n == 21) asm volatile("" : MPCQ_HV4(0), MPCQ_HV4(4), MPCQ_HV4(8), MPCQ_HV4(12), MPCQ_HV4(16), MPCQ_HV(20));
-}
-#undef MPCQ_HV4
-#undef MPCQ_HV
-
-// i0 + sum_{j<12} g_j * v_j, v_j broadcast from lane j of the row (v_fmac_f64_dpp).
-// One dependent chain: the fmac issue interval exceeds its latency.  s_nop 1: a VALU
-// write of v then a DPP read of it needs two wait states.
-__device__ __forceinline__ double bdot12(const double (&g)[12], double v, double i0) {
-  double a0 = i0;
-  asm volatile("s_nop 1\n\t"
-      "v_fmac_f64_dpp %0, %1, %2 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %0, %1, %3 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %0, %1, %4 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %0, %1, %5 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %0, %1, %6 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %0, %1, %7 row_newbcast:5 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %0, %1, %8 row_newbcast:6 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %0, %1, %9 row_newbcast:7 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %0, %1, %10 row_newbcast:8 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %0, %1, %11 row_newbcast:9 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %0, %1, %12 row_newbcast:10 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %0, %1, %13 row_newbcast:11 row_mask:0xf bank_mask:0xf"
-      : "+v"(a0)
-      : "v"(v), "v"(g[0]), "v"(g[1]), "v"(g[2]), "v"(g[3]), "v"(g[4]), "v"(g[5]), "v"(g[6]), "v"(g[7]),
-        "v"(g[8]), "v"(g[9]), "v"(g[10]), "v"(g[11]));
-  return a0;
-}
-// i0 + sum_psi g_psi * v(lane LN(psi)) over a stage's 12 force / state slots, the
-// broadcasts folded into v_fmac_f64_dpp (one chain; s_nop 1 covers the DPP read hazard).
-__device__ __forceinline__ double bdot_ln12(const double (&g)[12], double v, double i0) {
-  double a0 = i0;
-  asm("s_nop 1\n\t"
-      "v_fmac_f64_dpp %0, %1, %2 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %0, %1, %3 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %0, %1, %4 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %0, %1, %5 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %0, %1, %6 row_newbcast:5 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %0, %1, %7 row_newbcast:6 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %0, %1, %8 row_newbcast:8 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %0, %1, %9 row_newbcast:9 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %0, %1, %10 row_newbcast:10 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %0, %1, %11 row_newbcast:12 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %0, %1, %12 row_newbcast:13 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %0, %1, %13 row_newbcast:14 row_mask:0xf bank_mask:0xf"
-      : "+v"(a0)
-      : "v"(v), "v"(g[0]), "v"(g[1]), "v"(g[2]), "v"(g[3]), "v"(g[4]), "v"(g[5]), "v"(g[6]), "v"(g[7]),
-        "v"(g[8]), "v"(g[9]), "v"(g[10]), "v"(g[11]));
-  return a0;
-}
-// i0 + sum_{j<6} g_j * v_j, v_j broadcast from lane j of the row: half of a
-// 12-term row product (the split sweep, ph_sweep)
-__device__ __forceinline__ double bdot6(const double (&g)[6], double v, double i0) {
-  double a0 = i0;
-  asm volatile("s_nop 1\n\t"
-      "v_fmac_f64_dpp %0, %1, %2 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %0, %1, %3 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %0, %1, %4 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %0, %1, %5 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %0, %1, %6 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %0, %1, %7 row_newbcast:5 row_mask:0xf bank_mask:0xf"
-      : "+v"(a0)
-      : "v"(v), "v"(g[0]), "v"(g[1]), "v"(g[2]), "v"(g[3]), "v"(g[4]), "v"(g[5]));
-  return a0;
-}
-// i0 + sum_i g_i * v(lane LN(6 + i)), i < 6: the velocity slots
-__device__ __forceinline__ double bdot_ln6v(const double (&g)[6], double v, double i0) {
-  double a0 = i0;
-  asm("s_nop 1\n\t"
-      "v_fmac_f64_dpp %0, %1, %2 row_newbcast:8 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %0, %1, %3 row_newbcast:9 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %0, %1, %4 row_newbcast:10 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %0, %1, %5 row_newbcast:12 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %0, %1, %6 row_newbcast:13 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %0, %1, %7 row_newbcast:14 row_mask:0xf bank_mask:0xf"
-      : "+v"(a0)
-      : "v"(v), "v"(g[0]), "v"(g[1]), "v"(g[2]), "v"(g[3]), "v"(g[4]), "v"(g[5]));
-  return a0;
-}
-// (a + b) * m, rounded as the two C operations, issued where the statement stands relative
-// to the other volatile asm blocks (the sweeps' chains)
-__device__ __forceinline__ double add_mul_here(double a, double b, double m) {
-  double r;
-  asm volatile("v_add_f64 %0, %1, %2\n\t"
-               "v_mul_f64 %0, %0, %3" : "=&v"(r) : "v"(a), "v"(b), "v"(m));
-  return r;
-}
-// lower half: keep a; upper half: b of lane l - 32 (one permlane32_swap per dword)
-__device__ __forceinline__ double keep_lo_take_lo(double a, double b) {
-  const long long x = __double_as_longlong(a), y = __double_as_longlong(b);
-  const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)x, (unsigned)y, false, false);
-  const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)(x >> 32), (unsigned)(y >> 32), false, false);
-  return __longlong_as_double(((long long)hi[0] << 32) | lo[0]);
-}
-
-template <int... J>
-__device__ __forceinline__ void gather_seq(double v, double (&all)[12], std::integer_sequence<int, J...>) {
-  ((all[J] = rbc<LN(J)>(v)), ...);
-}
-// the stage's 12-vector from the column lanes
-__device__ __forceinline__ void gather12(double v, double (&all)[12]) {
-  gather_seq(v, all, std::make_integer_sequence<int, 12>{});
-}
-template <int... J>
-__device__ __forceinline__ void gatherd_seq(double v, double (&all)[12], std::integer_sequence<int, J...>) {
-  ((all[J] = rbc<J>(v)), ...);
-}
-// lanes 0..11 of the row, in lane order
-__device__ __forceinline__ void gather_direct12(double v, double (&all)[12]) {
-  gatherd_seq(v, all, std::make_integer_sequence<int, 12>{});
-}
-// sum_j a_j b_j over 12 terms in three interleaved chains (shorter dependency path)
-__device__ __forceinline__ double dot12(const double (&a)[12], const double (&b)[12]) {
-  double s0 = a[0] * b[0], s1 = a[1] * b[1], s2 = a[2] * b[2];
-#pragma unroll
-  for (int j = 3; j < 12; j += 3) {
-    s0 += a[j] * b[j];
-    s1 += a[j + 1] * b[j + 1];
-    s2 += a[j + 2] * b[j + 2];
-  }
-  return (s0 + s1) + s2;
-}
-// v(lane l) + v(lane l +- 16): rows 0 + 1 and rows 2 + 3, the same sum order in both rows
-__device__ __forceinline__ double row_pair_sum(double v) {
-  const long long b = __double_as_longlong(v);
-  const auto lo = __builtin_amdgcn_permlane16_swap((unsigned)b, (unsigned)b, false, false);
-  const auto hi = __builtin_amdgcn_permlane16_swap((unsigned)(b >> 32), (unsigned)(b >> 32), false, false);
-  const double a0 = __longlong_as_double(((long long)hi[0] << 32) | lo[0]);
-  const double a1 = __longlong_as_double(((long long)hi[1] << 32) | lo[1]);
-  return a0 + a1;
-}
-// v(lane l) + v(lane l +- 32): rows 0 + 2 and rows 1 + 3 (one add of the same two values
-// in both lanes of a pair: the sum is bit-identical in both)
-__device__ __forceinline__ double pair_sum32(double v) {
-  const long long b = __double_as_longlong(v);
-  const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)b, (unsigned)b, false, false);
-  const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)(b >> 32), (unsigned)(b >> 32), false, false);
-  const double a0 = __longlong_as_double(((long long)hi[0] << 32) | lo[0]);
-  const double a1 = __longlong_as_double(((long long)hi[1] << 32) | lo[1]);
-  return a0 + a1;
-}
-// max(a, b) as the hardware instruction, for operands the compiler cannot prove canonical
-// (DPP / permlane moves, LDS loads): C's fmax would canonicalize each of them first (see
-// clamp_hw); the engine's values are never signalling NaNs
-__device__ __forceinline__ double fmax_hw(double a, double b) {
-  double r;
-  asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-__device__ __forceinline__ double row_pair_max(double v) {
-  const long long b = __double_as_longlong(v);
-  const auto lo = __builtin_amdgcn_permlane16_swap((unsigned)b, (unsigned)b, false, false);
-  const auto hi = __builtin_amdgcn_permlane16_swap((unsigned)(b >> 32), (unsigned)(b >> 32), false, false);
-  return fmax_hw(__longlong_as_double(((long long)hi[0] << 32) | lo[0]),
-                 __longlong_as_double(((long long)hi[1] << 32) | lo[1]));
-}
-__device__ __forceinline__ double pair_max(double v) {
-  const long long b = __double_as_longlong(v);
-  const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)b, (unsigned)b, false, false);
-  const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)(b >> 32), (unsigned)(b >> 32), false, false);
-  return fmax_hw(__longlong_as_double(((long long)hi[0] << 32) | lo[0]),
-                 __longlong_as_double(((long long)hi[1] << 32) | lo[1]));
-}
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-// Launder an LDS base pointer: the pointer round-trips a VGPR through an empty asm
-// (opaque to the optimiser, so loads through it are not hoisted out of loops)
-// and comes back uniform in an SGPR via readfirstlane, costing no VGPR.
-template <typename P>
-__device__ __forceinline__ void lds_uniform(P*& q) {
-  asm volatile("" : "+v"(q));
-  if constexpr (sizeof(P*) == 4) {  // an LDS pointer
-    q = reinterpret_cast<P*>(static_cast<unsigned long>(
-        __builtin_amdgcn_readfirstlane(static_cast<int>(reinterpret_cast<unsigned long>(q)))));
-  } else {  // a global-workspace pointer (horizons beyond 32 stages)
-    const unsigned long long v = reinterpret_cast<unsigned long long>(q);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((int)v), hi = __builtin_amdgcn_readfirstlane((int)(v >> 32));
-    q = reinterpret_cast<P*>(((unsigned long long)hi << 32) | lo);
-  }
-}
-// a wave-uniform double kept in SGPRs
-__device__ __forceinline__ double uni(double v) {
-  const long long bits = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_readfirstlane((int)bits);
-  const int hi = __builtin_amdgcn_readfirstlane((int)(bits >> 32));
-  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-// min(max(v, lo), hi) as the two hardware instructions.  C's fmax / fmin on values the
-// compiler cannot prove canonical (loads, held registers) make it canonicalize each operand
-// first (v_max_f64 x, x: IEEE mode quiets a signalling NaN), one extra FP64 instruction per
-// bound and use; the engine's values are never signalling NaNs, and for every other input
-// (quiet NaNs included: maxNum / minNum) the result is the same.
-__device__ __forceinline__ double clamp_hw(double v, double lo, double hi) {
-  double r;
-  asm("v_max_f64 %0, %1, %2\n\tv_min_f64 %0, %0, %3" : "=&v"(r) : "v"(v), "v"(lo), "v"(hi));
-  return r;
-}
-__device__ __forceinline__ double sel3(int i, double a0, double a1, double a2) {
-  return i == 0 ? a0 : (i == 1 ? a1 : a2);
-}
-
-// f(integral_constant<int, J>) for J in the sequence, in order
-template <typename F, int... J>
-__device__ __forceinline__ void for_each_j(F&& f, std::integer_sequence<int, J...>) {
-  (f(std::integral_constant<int, J>{}), ...);
-}
-// a0 += v(lane J) g0, a1 += v(lane J) g1, a2 += v(lane J) g2, v broadcast from lane J of the
-// row (v_fmac_f64_dpp; s_nop 1 covers a VALU write of v just before)
-template <int J>
-__device__ __forceinline__ void fmac3_bc(double& a0, double& a1, double& a2, double v, double g0, double g1, double g2) {
-  asm("s_nop 1\n\t"
-      "v_fmac_f64_dpp %0, %3, %4 row_newbcast:%7 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %1, %3, %5 row_newbcast:%7 row_mask:0xf bank_mask:0xf\n\t"
-      "v_fmac_f64_dpp %2, %3, %6 row_newbcast:%7 row_mask:0xf bank_mask:0xf"
-      : "+v"(a0), "+v"(a1), "+v"(a2)
-      : "v"(v), "v"(g0), "v"(g1), "v"(g2), "n"(J));
-}
-
-// Gauss-Jordan inverse of a 12x12 SPD matrix held one row per column lane
-// (row psi in lane LN(psi)); pivots broadcast by row_newbcast, no pivoting.
-// gj_fmac<PV>: the pivot's eleven row updates c[j] += a * R[j](lane LN(PV)), j != PV, as
-// v_fmac_f64_dpp (the broadcast folded into the FMA: one instruction per entry instead of
-// a DPP move and an FMA; fma(a, b, c) and c += b a round alike, so the same bits)
-#define MPCQ_GJ11(J)                                                                         \
-  asm("s_nop 1\n\t"                                                                          \
-      "v_fmac_f64_dpp %0, %11, %22 row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n\t"       \
-      "v_fmac_f64_dpp %1, %12, %22 row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n\t"       \
-      "v_fmac_f64_dpp %2, %13, %22 row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n\t"       \
-      "v_fmac_f64_dpp %3, %14, %22 row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n\t"       \
-      "v_fmac_f64_dpp %4, %15, %22 row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n\t"       \
-      "v_fmac_f64_dpp %5, %16, %22 row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n\t"       \
-      "v_fmac_f64_dpp %6, %17, %22 row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n\t"       \
-      "v_fmac_f64_dpp %7, %18, %22 row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n\t"       \
-      "v_fmac_f64_dpp %8, %19, %22 row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n\t"       \
-      "v_fmac_f64_dpp %9, %20, %22 row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n\t"       \
-      "v_fmac_f64_dpp %10, %21, %22 row_newbcast:" #J " row_mask:0xf bank_mask:0xf"          \
-      : "+v"(o[0]), "+v"(o[1]), "+v"(o[2]), "+v"(o[3]), "+v"(o[4]), "+v"(o[5]), "+v"(o[6]),  \
-        "+v"(o[7]), "+v"(o[8]), "+v"(o[9]), "+v"(o[10])                                      \
-      : "v"(r[0]), "v"(r[1]), "v"(r[2]), "v"(r[3]), "v"(r[4]), "v"(r[5]), "v"(r[6]), "v"(r[7]), \
-        "v"(r[8]), "v"(r[9]), "v"(r[10]), "v"(a))
-template <int PV>
-__device__ __forceinline__ void gj_fmac(double (&c)[12], const double (&R)[12], double a) {
-  constexpr int J = LN(PV);
-  double o[11], r[11];  // the entries j != PV in order (register renames, no moves)
-#pragma unroll
-  for (int q = 0; q < 11; ++q) {
-    o[q] = c[q < PV ? q : q + 1];
-    r[q] = R[q < PV ? q : q + 1];
-  }
-  if constexpr (J == 0) MPCQ_GJ11(0);
-  else if constexpr (J == 1) MPCQ_GJ11(1);
-  else if constexpr (J == 2) MPCQ_GJ11(2);
-  else if constexpr (J == 4) MPCQ_GJ11(4);
-  else if constexpr (J == 5) MPCQ_GJ11(5);
-  else if constexpr (J == 6) MPCQ_GJ11(6);
-  else if constexpr (J == 8) MPCQ_GJ11(8);
-  else if constexpr (J == 9) MPCQ_GJ11(9);
-  else if constexpr (J == 10) MPCQ_GJ11(10);
-  else if constexpr (J == 12) MPCQ_GJ11(12);
-  else if constexpr (J == 13) MPCQ_GJ11(13);
-  else if constexpr (J == 14) MPCQ_GJ11(14);
-  else static_assert(J < 0, "a column lane LN(i)");
-#pragma unroll
-  for (int q = 0; q < 11; ++q) c[q < PV ? q : q + 1] = o[q];
-}
-#undef MPCQ_GJ11
-// FOLD = false (beyond 32 stages): the DPP move + FMA form -- the folded blocks hold all
-// their operands at once, which the 168 / 128-VGPR budgets there pay for in spills inside
-// the ADMM loop (N = 48: 6 -> 15 scratch reloads per iteration in the gfx950 assembly)
-// Lazy pivot rows (round 5): the pivot row is not normalised when it is used -- its lane's
-// multiplier is 0, so its row stays p and its diagonal becomes 1 -- and each row is scaled
-// by its own pivot's 1/d once, after the twelfth step.  A row that has been a pivot is then
-// d times the textbook (normalised) row; every later update of it is linear in the row, so
-// it stays d times the textbook row, and the final scaling gives the same inverse.  It saves
-// the selects that gave the pivot lane a zero base (22 v_cndmask_b32 per pivot, about 40 %
-// of the Gauss-Jordan instructions) for 12 multiplies at the end; the rounding differs from
-// the normalised form in the last bits.  Up to 32 stages (FOLD); beyond, the normalised
-// form stays: the lazy one measured 12-14 % fewer factorisation cycles (N = 16 84.8 k ->
-// 74.1 k, N = 32 124 k -> 108 k, profiles/r05h_factime*) with the statuses and iterations
-// of the oracle kept, but at N = 48 its (2-3x larger, ~1e-12) first-solve rounding grew to
-// 2.1e-7 after five warm-started ticks (8.1e-8 normalised; tools/drift.py,
-// profiles/r05j_drift_*).  -DMPCQ_GJ_NORM: the normalised form everywhere.
-#ifdef MPCQ_GJ_NORM
-template <bool FOLD>
-constexpr bool kGjLazy = false;
-#else
-template <bool FOLD>
-constexpr bool kGjLazy = FOLD;
+// Timing experiments only (> 1: the state sweep, or the factorisation, repeated in place)
+#ifndef MPCQ_REP_SWEEP
+#define MPCQ_REP_SWEEP 1
 #endif
-template <int PV, bool FOLD>
-__device__ __forceinline__ void gj_step(double (&R)[12], int me, bool& ok, double& sc) {
-  constexpr bool LAZY = kGjLazy<FOLD>;
-  const double d = rbc<LN(PV)>(R[PV]);
-#ifdef MPCQ_DEBUG_PIVOT
-  if (!(d > 0.0) && me == PV) printf("pivot fail blk %d thr %d PV %d d %g\n", (int)blockIdx.x, (int)threadIdx.x, PV, d);
+#ifndef MPCQ_REP_FACTOR
+#define MPCQ_REP_FACTOR 1
 #endif
-  if (!(d > 0.0)) ok = false;
-  // 1/d: v_rcp_f64 and two Newton steps (the pivots are positive and far from the
-  // denormal / overflow range, so the IEEE division's scaling and fix-up are not needed)
-  double id = __builtin_amdgcn_rcp(d);
-  double e_ = fma(-d, id, 1.0);
-  id = fma(id, e_, id);
-  e_ = fma(-d, id, 1.0);
-  id = fma(id, e_, id);
-  // one multiplier per row: every other row R - (R[PV] / d) p, so each entry is a single
-  // FMA on the broadcast pivot row; the pivot row itself: p / d (normalised form) or p
-  // (lazy: multiplier 0, scaled by sc = 1/d at the end)
-  const bool isp = me == PV;
-  const double a = isp ? (LAZY ? 0.0 : id) : -(R[PV] * id);
-  if constexpr (FOLD) {
-    double c[12];
-#pragma unroll
-    for (int j = 0; j < 12; ++j) c[j] = (isp && !LAZY) ? 0.0 : R[j];
-    gj_fmac<PV>(c, R, a);
-#pragma unroll
-    for (int j = 0; j < 12; ++j)
-      if (j != PV) R[j] = c[j];
-  } else {
-#pragma unroll
-    for (int j = 0; j < 12; ++j) {
-      if (j == PV) continue;
-      const double base = (isp && !LAZY) ? 0.0 : R[j];
-      R[j] = fma(a, rbc<LN(PV)>(R[j]), base);
-    }
-  }
-  if constexpr (LAZY) {
-    R[PV] = isp ? 1.0 : a;
-    if (isp) sc = id;
-  } else {
-    R[PV] = a;
-  }
-}
-template <bool FOLD, int... P>
-__device__ __forceinline__ void gj_seq(double (&R)[12], int me, bool& ok, double& sc, std::integer_sequence<int, P...>) {
-  (gj_step<P, FOLD>(R, me, ok, sc), ...);
-}
-template <bool FOLD>
-__device__ __forceinline__ void gj12(double (&R)[12], int me, bool& ok) {
-  double sc = 1.0;
-  gj_seq<FOLD>(R, me, ok, sc, std::make_integer_sequence<int, 12>{});
-  if constexpr (kGjLazy<FOLD>) {
-#pragma unroll
-    for (int j = 0; j < 12; ++j) R[j] *= sc;
-  }
-}
-
-// Ro -= G C' for one 12x12 coupling block C held one row per column lane in
-// compact form (ca on column CI mod 6, c6 on the velocity columns): column CI of
-// the product takes row CI of C from lane LN(CI) by row broadcast
-// The broadcasts fold into v_fmac_f64_dpp (one instruction per term instead of a DPP
-// move and an FMA); the two chains start from -0 (x + -0 = x for every x, so the first
-// term is the plain product, as a multiply) and keep their order: the same bits.
-#define MPCQ_SCHUR2_LANE(J)                                                                  \
-  asm("s_nop 1\n\t"                                                                          \
-      "v_fmac_f64_dpp %0, %2, %8 row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n\t"        \
-      "v_fmac_f64_dpp %1, %3, %9 row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n\t"        \
-      "v_fmac_f64_dpp %0, %4, %10 row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n\t"       \
-      "v_fmac_f64_dpp %1, %5, %11 row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n\t"       \
-      "v_fmac_f64_dpp %0, %6, %12 row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n\t"       \
-      "v_fmac_f64_dpp %1, %7, %13 row_newbcast:" #J " row_mask:0xf bank_mask:0xf\n\t"       \
-      "v_fmac_f64_dpp %0, %14, %15 row_newbcast:" #J " row_mask:0xf bank_mask:0xf"           \
-      : "+v"(a0), "+v"(a1)                                                                   \
-      : "v"(ca), "v"(c6[0]), "v"(c6[1]), "v"(c6[2]), "v"(c6[3]), "v"(c6[4]), "v"(ga), "v"(G[6]), \
-        "v"(G[7]), "v"(G[8]), "v"(G[9]), "v"(G[10]), "v"(c6[5]), "v"(G[11]))
-template <int CI, bool FOLD>
-__device__ __forceinline__ void schur_col(double (&Ro)[12], const double (&G)[12], double ca,
-                                          const double (&c6)[6]) {
-  constexpr int J = LN(CI);
-  if constexpr (!FOLD) {  // (beyond 32 stages, as gj_step)
-    double a0 = G[CI < 6 ? CI : CI - 6] * rbc<J>(ca), a1 = G[6] * rbc<J>(c6[0]);
-    a0 = fma(G[7], rbc<J>(c6[1]), a0);
-    a1 = fma(G[8], rbc<J>(c6[2]), a1);
-    a0 = fma(G[9], rbc<J>(c6[3]), a0);
-    a1 = fma(G[10], rbc<J>(c6[4]), a1);
-    a0 = fma(G[11], rbc<J>(c6[5]), a0);
-    Ro[CI] -= a0 + a1;
-    return;
-  }
-  const double ga = G[CI < 6 ? CI : CI - 6];
-  // a0 = ga ca + G7 c1 + G9 c3 + G11 c5, a1 = G6 c0 + G8 c2 + G10 c4 (c broadcast from lane J)
-  double a0 = -0.0, a1 = -0.0;
-  if constexpr (J == 0) MPCQ_SCHUR2_LANE(0);
-  else if constexpr (J == 1) MPCQ_SCHUR2_LANE(1);
-  else if constexpr (J == 2) MPCQ_SCHUR2_LANE(2);
-  else if constexpr (J == 4) MPCQ_SCHUR2_LANE(4);
-  else if constexpr (J == 5) MPCQ_SCHUR2_LANE(5);
-  else if constexpr (J == 6) MPCQ_SCHUR2_LANE(6);
-  else if constexpr (J == 8) MPCQ_SCHUR2_LANE(8);
-  else if constexpr (J == 9) MPCQ_SCHUR2_LANE(9);
-  else if constexpr (J == 10) MPCQ_SCHUR2_LANE(10);
-  else if constexpr (J == 12) MPCQ_SCHUR2_LANE(12);
-  else if constexpr (J == 13) MPCQ_SCHUR2_LANE(13);
-  else if constexpr (J == 14) MPCQ_SCHUR2_LANE(14);
-  else static_assert(J < 0, "a column lane LN(i)");
-  Ro[CI] -= a0 + a1;
-}
-#undef MPCQ_SCHUR2_LANE
-template <bool FOLD, int... C>
-__device__ __forceinline__ void schur_cols(double (&Ro)[12], const double (&G)[12], double ca,
-                                           const double (&c6)[6], std::integer_sequence<int, C...>) {
-  (schur_col<C, FOLD>(Ro, G, ca, c6), ...);
-}
-// ---------------------------------------------------------------------------
-// Formulation pieces (restating MPC.py; oracle/mpcq_oracle.c is the CPU twin)
-
-__device__ __forceinline__ void inv3(const double* M, double* R) {
-  const double a = M[0], b = M[1], c = M[2], d = M[3], e = M[4], f = M[5], g = M[6], h = M[7],
-               i = M[8];
-  const double A = e * i - f * h, B = -(d * i - f * g), C = d * h - e * g;
-  const double det = a * A + b * B + c * C;
-  const double id = 1.0 / det;
-  R[0] = A * id; R[1] = -(b * i - c * h) * id; R[2] = (b * f - c * e) * id;
-  R[3] = B * id; R[4] = (a * i - c * g) * id;  R[5] = -(a * f - c * d) * id;
-  R[6] = C * id; R[7] = -(a * h - b * g) * id; R[8] = (a * e - b * d) * id;
-}
-
-// The per-robot constants of the workgroup's instance (ROB kernels: LaunchArgs::robots[b],
-// mpcq_set_robots; the others take the launch's mpcq_params, the code they always had).  b is
-// the instance (after the order[] mapping), the same for every lane, so each value is fetched
-// once and comes back uniform in SGPRs (uni): fz_max at kernel entry (the bounds need it to the
-// end), mass / gI / mu where the formulation starts (their 22 SGPRs are dead again before the
-// solve).
-struct RobotK {
-  double mass, gI[9], mu;
-};
-__device__ __forceinline__ void load_robot(const mpcq_robot* r, RobotK& rb) {
-  rb.mass = uni(r->mass);
-#pragma unroll
-  for (int j = 0; j < 9; ++j) rb.gI[j] = uni(r->gI[j]);
-  rb.mu = uni(r->mu);
-}
-
-// The diagonal of P of the workgroup's instance (ROB solve kernels: LaunchArgs::weights[b],
-// mpcq_set_weights; the others keep the launch's mpcq_params, the code they always had): the force
-// weight uniform in SGPRs, the lane's own state weight (ph = its state index) as one global load.
-template <bool TABLE>
-__device__ __forceinline__ double weight_f(const LaunchArgs& a, int64_t b, double dflt) {
-  if constexpr (TABLE) return uni(a.weights[b].force);
-  else return dflt;
-}
-template <bool TABLE>
-__device__ __forceinline__ double weight_x(const LaunchArgs& a, int64_t b, int ph, double dflt) {
-  if constexpr (TABLE) return a.weights[b].state[ph];
-  else return dflt;
-}
-
-// The 24 CSC values of one foot's three force columns in one stage: dt/m row,
-// B rows 9..11 = dt inv(Rz(yaw) gI) [lever]x (MPC.py:339-345), swing flag S
-// (MPC.py:628), friction-cone coefficients (MPC.py:136-148).
-__device__ __forceinline__ void form_foot(const mpcq_params& p, double mass, const double (&gI)[9], double mu,
-                                          double yaw, double l0, double l1, double l2, double swing, double* out) {
-  const double cy = cos(yaw), sy = sin(yaw);
-  const double R[9] = {cy, -sy, 0.0, sy, cy, 0.0, 0.0, 0.0, 1.0};
-  double M[9], Mi[9];
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
-      M[3 * r + t] = R[3 * r + 0] * gI[0 * 3 + t] + R[3 * r + 1] * gI[1 * 3 + t] +
-                     R[3 * r + 2] * gI[2 * 3 + t];
-  inv3(M, Mi);
-  const double S[9] = {0.0, -l2, l1, l2, 0.0, -l0, -l1, l0, 0.0};
-  const double dtm = p.dt / mass;
-  int pos = 0;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    out[pos++] = dtm;
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-      out[pos++] = p.dt * (Mi[3 * r + 0] * S[0 * 3 + c] + Mi[3 * r + 1] * S[1 * 3 + c] +
-                           Mi[3 * r + 2] * S[2 * 3 + c]);
-    out[pos++] = swing;
-    if (c < 2) {
-      out[pos++] = 1.0;
-      out[pos++] = -1.0;
-    } else {
-#pragma unroll
-      for (int t = 0; t < 4; ++t) out[pos++] = -mu;
-      out[pos++] = -1.0;
-    }
-  }
-}
-
-// The lane's own component of the instance's constant disturbance acceleration (ROB kernels:
-// LaunchArgs::disturb[b], mpcq_set_disturbance; the others have none): dynamics row r >= 6 takes
-// a[r - 6], one global load per lane like weight_x's, not through uni() -- the solve kernels sit
-// at the SGPR ceiling.  Rows r < 6 load a[0] (in bounds) and do not use it.
-template <bool TABLE>
-__device__ __forceinline__ double disturb_a(const LaunchArgs& a, int64_t b, int r) {
-  if constexpr (TABLE) return a.disturb[b].a[r >= 6 ? r - 6 : 0];
-  else return 0.0;
-}
-
-// Bounds of dynamics row (k, r) (MPC.py:197-221, 366-378, 410); xr = xref staged in LDS.
-// TABLE: da = the row's disturbance acceleration (disturb_a), in MPC.py's terms g[r] += dt * da
-// on rows r >= 6; a da of +0.0 adds -0.0 and changes no bit.
-template <int N, bool TABLE = false>
-__device__ __forceinline__ double dyn_bound(const mpcq_params& p, const double* xr, int k, int r,
-                                            [[maybe_unused]] double da = 0.0) {
-  constexpr int NP1 = N + 1;
-  double v = (r == 8) ? -(-p.gravity * p.dt) : -0.0;
-  if constexpr (TABLE) {
-    if (r >= 6) v = v + (-(p.dt * da));
-  }
-  if (k == 0) {
-    double ax0 = -xr[r * NP1];
-    if (r < 6) ax0 = ax0 + p.dt * (-xr[(r + 6) * NP1]);
-    v = v + ax0;
-  }
-  double dv;
-  if (k >= 1) {
-    dv = -xr[r * NP1 + k];
-    if (r < 6) dv = dv + (-p.dt) * xr[(r + 6) * NP1 + k];
-    dv = dv + xr[r * NP1 + k + 1];
-  } else {
-    dv = xr[r * NP1 + 1];
-  }
-  return v + dv;
-}
 
 // ---------------------------------------------------------------------------
-// Shared memory of one instance (N=16: 78.6 KB -> 2 instances per CU; N=32:
-// 156.7 KB -> 1; N=48: 140 KB with S^{-1} / F W / R^{-1} Q in global memory).
+// Function-body macros of engine_kernel: they name its locals, and are #undef-ed after it.
 
-// The sweep matrices (G / H / M^{-1} in GH, S^{-1} in Sm) are 12 x 12, row-major
-// with a row stride of RS = 12 doubles (96 B).  Column reads (the outward sweep:
-// 12 lanes, consecutive doubles) are conflict-free; the inward sweep's b128 row
-// reads (lane r at 96 r) collide 2-3 ways inside a 16-lane group.  A 13-double
-// stride removes that but needs 3 KB more LDS than two instances per CU leave at
-// N = 16.  GS = one stage's slot.
-constexpr int RS = 12, GS = 12 * RS;
-// Offset of slot q in GH / Sm: the slots of the bottom chain (q > N/2) sit two
-// doubles (16 B) further on.  The sweep's b128 row reads put 4 lanes of one chain
-// and 8 of the other in each 16-lane bank group; rows 96 B apart cover only the
-// eight 4-bank slots at multiples of 8 dwords, so without the shift the two
-// chains' rows met in the same banks (2-way conflicts), with it they interleave.
-template <int N>
-constexpr int kSlotPad = 2;
-template <int N>
-__host__ __device__ constexpr int SLOT(int q) { return GS * q + (q > N / 2 ? kSlotPad<N> : 0); }
-
-// Rejected round-4 solve variants (block cyclic reduction of the state system; the
-// termination check deferred into the next iteration) were measured slower and removed
-// in round 5; their code is kept as a patch, tools/attic/engine_cr_dc_round4.patch, and
-// their measurements in DESIGN.md section 8 (round 4) items 3-4.
-// Four more were measured slower and removed later, their code kept as
-// tools/attic/engine_variants_round6.patch: three or four 16-stage instances per CU in the
-// beyond-32-stage layout (round 5: C2 62.0 k / 35.3 k against 127.6 k QP/s; DESIGN.md section
-// 8b item 4), the explicit state-system inverse at 16 stages (round 5: 1.92 against 1.85 us per
-// iteration and one instance per CU, C2 86 k against 126 k QP/s; section 8b item 6), the
-// nested-dissection state solve (round 6: N = 32 2.976 against 2.875 us per iteration; section
-// 8 item 1) and slicing at 16 stages (kSlice above).
-// Horizons beyond 32 stages do not fit a CU's LDS (N = 48: 236 KB): S^{-1}, F W and
-// R^{-1} Q move to a per-instance global workspace (LaunchArgs::work, work_doubles(N)
-// doubles per instance, L2-resident), the rest stays in LDS (N = 48: 140 KB).
-template <int N>
-constexpr bool kBig = N > 32;
-// F W stays in LDS at every N (the ADMM loop reads it every iteration: from L2 at
-// N = 48 it cost the right-hand-side phase ~14 k cycles per iteration, r03d
-// stamps); beyond 49 stages the scaled constraint values (126 N - 18 doubles) leave
-// LDS instead (N = 64: 197 KB with them, 133 KB without); the engine reads them
-// through the same accessors, the stage-parallel phases from L2.
-template <int N>
-constexpr bool kAbG = N > 49;
-// Beyond 48 stages (13-16 waves: 128 VGPRs) the F_k row is read from the workspace in
-// the loop and the z update's constants are batch-loaded from private memory instead
-// of being held; from 33 to 48 stages (168 VGPRs) holding them is faster.  Measured at
-// every horizon 33..64 with both, either and neither (tools/bigsweep.py,
-// profiles/r03o_bigsweep.txt: N = 48 9.05 us per iteration held vs 10.37 not; N = 56
-// 19.27 not held vs 20.06).  -DMPCQ_FR_HELD / -DMPCQ_ZC_HELD: held everywhere (experiments).
-#ifdef MPCQ_FR_HELD
-template <int N> constexpr bool kFrWork = false;
-#else
-template <int N> constexpr bool kFrWork = N > 48;
-#endif
-#ifdef MPCQ_ZC_HELD
-template <int N> constexpr bool kZcMem = false;
-#else
-template <int N> constexpr bool kZcMem = N > 48;
-#endif
-// The outward sweep of ph_sweep_split (33..48 stages) as ph_sweep_lag's: full 12-term
-// column products per lane (the outward sweep needs no S^{-1}, which is what sent the
-// split sweep's inward half to the stage-parallel S^{-1} phase).  Round 4 (r04h, per
-// iteration alone / 256 in flight): N = 40 6.07 -> 5.93 / 6.94 -> 6.73 us, N = 48 6.89 ->
-// 6.79 / 7.69 -> 7.62; beyond 48 stages mixed (N = 64 14.96 -> 14.78 / 18.73 -> 19.55), so
-// the split products stay there.  -DMPCQ_SPLIT_OUT: the split outward products everywhere.
-#ifdef MPCQ_SPLIT_OUT
-template <int N> constexpr bool kLagOut = false;
-#else
-template <int N> constexpr bool kLagOut = N <= 48;
-#endif
-// Stage stride of F W in LDS (doubles).  ph_recover reads row ph of F_k W_k as three
-// ds_read_b128 per lane (16-B units 36 k + 3 ph at a 72-double stride): within each
-// 16-lane bank group of that instruction (two stages' lanes), ph 0/1/2 of one stage met
-// ph 6/7/8 of the next in the same banks (2-way conflicts); at a 96-double stride (256 B
-// x 3, stages 0 mod 16 units apart) the twelve rows of each group land in distinct banks.
-// Up to 32 stages, where the LDS has the 24 N doubles (N = 16: 80,048 B, still two
-// instances per CU).
-template <int N>
-constexpr int kFWS = kBig<N> ? 72 : 96;
-// Up to 16 stages the ADMM loop's exit status goes through LDS (Smem::flag[4]) instead of
-// a register carried across the loop: the N = 16 kernel then spills 27 instead of 43
-// VGPRs (scratch 256 -> 224 B per lane) and its C2 HBM traffic falls 127 -> 88 MB per
-// launch, per-iteration time unchanged (same box, r04u).  At N = 32 the same change made
-// the iteration 1.3 % slower and doubled the traffic through the rho-update path's spills,
-// so the status stays a register there.
-template <int N>
-constexpr bool kXstLds = N <= 16;
-// From 17 to 48 stages (round 5) the exit status is not carried at all: after the loop it is
-// re-derived from what the loop leaves -- a failed factorisation sets sh.flag[2], and an
-// early exit stops with iter <= max_iter after the same tests, in the same order, on the
-// residuals and infeasibility bits that stay live after the loop anyway.  Carried in a
-// register, it was spilled and stored once per check segment at N = 32 (round 4).
-// Beyond 48 stages (128 VGPRs) the re-derivation cost the iteration 8 % (N = 64 15.2 -> 16.5
-// us alone, 19.7 -> 21.2 at 256 in flight, r05v): there the status is carried as in round 4.
-template <int N>
-constexpr bool kXstRe = !kXstLds<N> && N <= 48;
-template <int N>
-struct Work {  // offsets (doubles) inside one instance's workspace
-  // SM starts two slots in (a pad kept from round 2; the sweep no longer reads it)
-  // FR: each lane's row of F_k (12 doubles, lane-interleaved: entry i of thread t at 16 kRows i + t)
-  static constexpr int SM = 2 * GS, FW = SM + N * GS + 2, QL = FW + 72 * N, ZERO = QL + 36 * N, AB = ZERO + 72,
-                       FR = AB + (kAbG<N> ? ((126 * N - 18 + 1) & ~1) : 0), SIZE = FR + (N > 48 ? 12 * 16 * kRows<N> : 0);
-};
-
-template <int N>
-struct Smem {
-  double Ab[kAbG<N> ? 2 : 126 * N - 18];  // scaled constraint values, CSC order (N > 49: Work<N>::AB)
-  // GH[0] = M^{-1}, GH[SIG(k)] = G_k (1 <= k <= m), GH[SIG(k+1)] = H_k (m <= k < N-1),
-  // row-major (the sweeps' step order, see SIG).
-  // During the factorisation slot k holds Q_k [0,36), F_k W_k [36,108) and the
-  // dynamics-row rho of stage k [108,120); during scaling the row factors; in
-  // the prologue xref / fsteps / the gait walk.
-  alignas(16) double GH[N][GS];
-  double GHpad[2];  // the bottom slots' shift (SLOT)
-  // (N > 32: these three live in the global workspace, Work<N>)
-  alignas(16) double Sm[kBig<N> ? 1 : N][GS];  // S_k^{-1} / U_k^{-1} of stage k at SLOT(SIG(k)), row-major (row stride RS)
-  double Smpad[2];
-  // F_k W_k (12x6, row psi at [6 psi]); W_k = B_k' R on rows 6..11: here beyond 32 stages
-  // (stage stride 72), FWs at the end up to 32 stages (stride kFWS = 96)
-  alignas(16) double FWb[kBig<N> ? N : 1][72];
-  double QL[kBig<N> ? 1 : N][36];   // B_k F_k W_k = R^{-1} W_k' F_k W_k (6x6)
-  union {
-    struct {
-      // sweep right-hand side of stage k's states = bo[k] + na[k]: bo from stage k
-      // itself, na from stage k+1's dynamics rows (Hd (w - beta) + H6 w, summed by
-      // ph_rhs); nb is scratch of the checks
-      double bo[N][12];
-      double na[N][12];
-      double nb[N][12];
-      double yv[N][12];      // w = S^{-1} y of the inward sweep (states / duals during the checks)
-      double xs[N + 1][12];  // X_k (xs[k+1] = X_{k+1}, stage k's states)
-    } it;
-    struct {
-      alignas(16) double St[144];  // sweep hand-offs of the factorisation (16-B aligned: the
-      alignas(16) double Sb[144];  // couplings read them as column pairs)
-      // (32 unused bytes, where the nested-dissection variant's two placeholders sat: at N = 4
-      // fa is the union's larger member, so they keep every later array's LDS offset there)
-      alignas(16) double fapad_[4];
-    } fa;
-  } u;
-  // per-wave partial reductions (32 per wave); during the sweeps the sink of lanes
-  // whose store is void (lane (t & 31) + 12 j, j <= N/2 + 1)
-  double red[(8 * kRows<N> + 32 > 12 * (N / 2 + 2) + 32) ? 8 * kRows<N> + 32 : 12 * (N / 2 + 2) + 32];
-  double dump[64];  // sink of predicated stores (never read): lane & 63
-  // (13 unused doubles: where round 4's deferred-check arrays sat; they keep every later
-  // array's LDS offset, and with it the compiler's register allocation, as measured)
-  double pad13_[13];
-  alignas(16) double zero[72];  // zeros: masked coefficient reads point here instead of selecting
-  // flag[4] (kXstLds): the ADMM loop's exit status, written by thread 0 at the (uniform)
-  // exits and read by every thread after the loop
-  int flag[kXstLds<N> ? 5 : 4];
-  // (up to 32 stages) F W at its 96-double stride, last: its round-4 growth leaves every
-  // other array's LDS offset -- and the compiler's register allocation -- as before
-  alignas(16) double FWs[kBig<N> ? 1 : N][kBig<N> ? 2 : kFWS<N>];
-};
-
-// prologue aliases inside GH
-template <int N>
-struct Prologue {
-  static constexpr int XR = 0;             // xref, 12(N+1) doubles
-  static constexpr int FS = 12 * (N + 1);  // fsteps, 260 doubles
-  static constexpr int INTS = FS + 260;    // phase_of_stage[N], contact[20][4] as ints
-};
+// The lane's offsets (LaneOffs) as local names: the held O0, or (RECOMP) re-derived from
+// freshly laundered coordinates.
+#define MPCQ_LANE_OFFS(RECOMP)                                                                              \
+  if constexpr (RECOMP) launder();                                                                         \
+  const LaneOffs O_ = (RECOMP) ? offs() : O0;                                                              \
+  [[maybe_unused]] const int oXd = O_.oXd, oHd = O_.oHd, oH6 = O_.oH6, oF = O_.oF, oFa = O_.oFa,           \
+                             oFb = O_.oFb, oF4 = O_.oF4, oFW = O_.oFW, oQL = O_.oQL, oXSp = O_.oXSp,       \
+                             oXSp6 = O_.oXSp6, rXS = O_.rXS, rXSpm = O_.rXSpm, rXSp6m = O_.rXSp6m,         \
+                             oHdm = O_.oHdm, oH6m = O_.oH6m, oFWcm = O_.oFWcm, oQLm = O_.oQLm, oB0 = O_.oB0; \
+  [[maybe_unused]] const bool ta0 = O_.ta0;                                                                \
+  [[maybe_unused]] double* const Wbo = O_.Wbo;                                                             \
+  [[maybe_unused]] double* const Wna = O_.Wna
+// The check's lane ids, re-derived from a laundered thread index: the red[] addresses
+// built from them would otherwise be hoisted out of the ADMM loop and spilled too.
+#define MPCQ_CHECK_IDS()                                           \
+  int tl_ = t;                                                     \
+  asm volatile("" : "+v"(tl_));                                    \
+  [[maybe_unused]] const int wv = tl_ >> 6, lane = tl_ & 63, s = tl_ & 15
+// the ADMM loop's exit status: LDS (kXstLds; read after the loop's closing barrier) or status
+#define MPCQ_SET_XST(v_) do { if constexpr (kXstLds<N>) { if (t == 0) sh.flag[4] = (v_); } else if constexpr (!kXstRe<N>) { status = (v_); } } while (0)
 
 // ---------------------------------------------------------------------------
 // The engine kernel.  FUSED: formulate from (xref, fsteps) then solve.
@@ -873,16 +132,14 @@ __global__ __launch_bounds__(16 * kRows<N>, 2)
 void engine_kernel(mpcq_params p, LaunchArgs a) {
   constexpr int NR = kRows<N>, NW = NR / 4, T = 16 * NR, n = 24 * N, m = 44 * N, nnz = 126 * N - 18,
                 MID = N / 2;
-#ifndef MPCQ_STAMP_WAVE
-#define MPCQ_STAMP_WAVE 0
-#endif
   [[maybe_unused]] constexpr int kStampT = 64 * (MPCQ_STAMP_WAVE < T / 64 ? MPCQ_STAMP_WAVE : T / 64 - 1);
   // the two chains of the state sweeps: top stages 0..MID-1, bottom N-1..MID+1
   // (BOT stages: MID - 1 for even N, MID for odd N), meeting at stage MID
   constexpr int BOT = N - 1 - MID;
+  // ---- 1. pointers and lane coordinates ---------------------------------------------------------
   __shared__ Smem<N> sh;
   const int t = threadIdx.x, wv = t >> 6, lane = t & 63;
-  // lane coordinates; the loops launder them (see launder()) so that the
+  // lane coordinates; the loops launder them (launder, at the end of this section) so that the
   // compiler recomputes the many LDS offsets derived from them instead of
   // hoisting each one into a register of its own
   const bool phantom = (t >> 4) >= N;  // a row past the horizon: a copy of stage N-1 (kRows)
@@ -955,7 +212,7 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
   // iteration, C3 33.85 -> 33.35 ms, profiles/r04e_*; round 2's +2 % there is not
   // reproduced).  Beyond 32 stages (the split sweep) lane 11's row, unmeasured.
   int rr_ = s < 12 ? s : (N <= 32 ? s - 12 : 11);
-  // store v at q when c holds, else into this lane's sink (branch-free)
+  // the base pointers and the lane coordinates, opaque to the optimiser from here on
   auto launder = [&]() __attribute__((always_inline)) {
     lds_uniform(Ab); lds_uniform(GHr); lds_uniform(SmR); lds_uniform(FWr); lds_uniform(QLr);
     asm volatile("" : "+v"(k), "+v"(f), "+v"(c), "+v"(cc), "+v"(ph), "+v"(fo), "+v"(xo),
@@ -963,7 +220,7 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
   };
   (void)lane;
 
-  // ---- scaled-A accessors ---------------------------------------------------
+  // ---- 2. scaled-A accessors, own rows and columns, bounds --------------------------------------
   auto Xd = [&](int kk, int i) __attribute__((always_inline)) { return Ab[XO<N>(kk, i)]; };
   // dynamics row i of stage kk on X_kk[i] / on X_kk[i+6] (i < 6), kk >= 1
   // (loads stay in bounds for kk == 0 / i >= 6; callers mask those values)
@@ -1030,7 +287,7 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
   for (int e = t; e < (int)(sizeof(sh.u.it) / sizeof(double)); e += T) (&sh.u.it.bo[0][0])[e] = 0.0;
 #endif
 
-  // ---------------------------------------------------------------- prologue
+  // ---- 3. prologue: formulation (FUSED) or the caller's QP --------------------------------------
   if (FUSED || !SOLVE) {
     double* xr = gh0 + Prologue<N>::XR;
     double* fs = gh0 + Prologue<N>::FS;
@@ -1171,6 +428,7 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
       if (status == 0 && sh.flag[1]) status = (sh.flag[1] & 1) ? MPCQ_STATUS_NONFINITE : MPCQ_STATUS_BAD_BOUNDS;
     }
 
+    // ---- 4. the iterate, rho and the bounds -----------------------------------------------------
     // persistent per-lane state (column values of c == 3 lanes are shadows)
     double xf = 0.0, xX = 0.0, Df = 1.0, DX = 1.0;
     double z[3] = {0.0, 0.0, 0.0}, y[3] = {0.0, 0.0, 0.0}, E[3] = {1.0, 1.0, 1.0};
@@ -1252,7 +510,7 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
       }
     };
 
-    // ---- row / column operators --------------------------------------------
+    // ---- 5. row and column operators, lane offsets ----------------------------------------------
     // A v for own rows from own forces vf (column lanes), own states vX and the
     // previous stage's states in xs[k]; also returns the force gather.
     auto row_A = [&](double vf, double vX, double (&out)[3]) __attribute__((always_inline)) {
@@ -1278,8 +536,181 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
     };
     auto Pbf = [&]() __attribute__((always_inline)) { return cscale * (Df * P0f * Df); };
     auto PbX = [&]() __attribute__((always_inline)) { return cscale * (DX * P0X * DX); };
+    // per-lane constants of the ADMM loop and the residuals: LDS offsets, flags
+    const bool hp = k >= 1, isv = ph >= 6;
+    const int zXS = (int)(sh.zero - &sh.u.it.xs[0][0]);  // X_0 is not stored: stage 0 reads zeros
+    const double m2 = cc == 2 ? 1.0 : 0.0;
+    // masked variants for the loop: a lane whose term is structurally absent reads a
+    // zero (stage 0 has no previous stage; H6 only on the position rows; the force Schur
+    // terms beta, (R^-1 Q) g only on the velocity rows), so no selects are needed
+    int zAb;  // offset of a zero block from Ab (masked reads)
+    if constexpr (ABG) zAb = Work<N>::ZERO - Work<N>::AB;
+    else zAb = (int)(sh.zero - sh.Ab);
+    lds_cd* XSr = (lds_cd*)&sh.u.it.xs[0][0];
+    double* const Wdump = &sh.dump[t & 63];
+    // The LDS offsets of the lane's coefficients, derived from its coordinates.  O0
+    // is derived once and held (the loop phases up to 32 stages, where the ADMM loop
+    // has the registers); a phase run between long stretches of other work -- the
+    // termination check at every N, every loop phase beyond 32 stages (168 VGPRs) --
+    // re-derives them from freshly laundered coordinates (MPCQ_LANE_OFFS(true)), a
+    // few integer ops each: held across the ADMM loop, the compiler spills them, and
+    // each use then waits on its own scratch round trip (the reloads sit right in
+    // front of their LDS reads, one after another).
+    struct LaneOffs {
+      int oXd, oHd, oH6, oF, oFa, oFb, oF4, oFW, oQL, oXSp, oXSp6, rXS, rXSpm, rXSp6m, oHdm, oH6m, oFWcm, oQLm,
+          oB0;
+      bool ta0;
+      double* Wbo;
+      double* Wna;
+    };
+    auto offs = [&]() __attribute__((always_inline)) -> LaneOffs {
+      const bool hp_ = k >= 1, isv_ = ph >= 6;
+      LaneOffs o;
+      o.oXd = xo;                                                 // Xd(k, ph)
+      o.oHd = XO<N>(hp_ ? k - 1 : 0, ph) + (ph < 6 ? 1 : 2);      // Hd(k, ph)
+      o.oH6 = XO<N>(hp_ ? k - 1 : 0, ph < 6 ? ph + 6 : 11) + 1;   // H6(k, ph)
+      o.oF = fo;
+      const int ta = c < 3 ? c : 3;  // first own friction row
+      o.ta0 = (ta >> 1) == 0;
+      o.oFa = FO<N>(k, f, ta >> 1) + 5 + (ta & 1);
+      o.oFb = FO<N>(k, f, 2) + 5 + ta;
+      o.oF4 = FO<N>(k, f, 2) + 9;
+      o.oFW = kFWS<N> * k + 6 * ph;
+      const int oFWc = kFWS<N> * k + (isv_ ? ph - 6 : 0);
+      o.oQL = 36 * k + 6 * (isv_ ? ph - 6 : 0);
+      o.oXSp = 12 * k + ph;  // natural order (update_info)
+      o.oXSp6 = 12 * k + (ph < 6 ? ph + 6 : ph);
+      // the sweep's states in its slots (SIGX): own X_{k+1}, the previous stage's X_k
+      auto xsl = [](int kk) __attribute__((always_inline)) -> int { return 12 * SIGX<N>(kk + 1); };
+      o.rXS = xsl(k) + ph;
+      o.rXSpm = hp_ ? xsl(k - 1) + ph : zXS;
+      o.rXSp6m = hp_ ? xsl(k - 1) + (ph < 6 ? ph + 6 : ph) : zXS;
+      o.oHdm = hp_ ? o.oHd : zAb;
+      o.oH6m = hp_ && !isv_ ? o.oH6 : zAb;
+      o.oFWcm = isv_ ? oFWc : zFW;
+      o.oQLm = isv_ ? o.oQL : zQL;
+      o.oB0 = FO<N>(k, 0, 0) + (ph >= 9 ? ph - 8 : 0);  // B row ph on force (fp, cp): + 24 fp + 7 cp
+      o.Wbo = &sh.u.it.bo[SIG<N>(k)][ph];
+      o.Wna = &sh.u.it.na[SIG<N>(hp_ ? k - 1 : N - 1)][ph];
+      return o;
+    };
+    LaneOffs O0 = offs();  // (re-derived at the top of every stretch of iterations up to 32 stages, below)
+    // (MPCQ_LANE_OFFS, above the kernel, gives a phase their names: from O0, or re-derived)
+    // beyond 32 stages the loop phases re-derive them too
+    constexpr bool kRecompLoop = BIG;
+    auto launder_p = [&]() __attribute__((always_inline)) {
+      lds_uniform(Ab); lds_uniform(GHr); lds_uniform(SmR); lds_uniform(FWr); lds_uniform(QLr); lds_uniform(XSr);
+    };
+    // force column of A' v for own-row values v (dynamics rows 6..11 by row broadcast,
+    // swing, friction by quad broadcast)
+    auto colF_c = [&](const double (&A)[10], const double (&v)[3]) __attribute__((always_inline)) -> double {
+      const double w6 = rbc<LN(6)>(v[0]), w7 = rbc<LN(7)>(v[0]), w8 = rbc<LN(8)>(v[0]);
+      const double w9 = rbc<LN(9)>(v[0]), w10 = rbc<LN(10)>(v[0]), w11 = rbc<LN(11)>(v[0]);
+      const double wf0 = qbc<0>(v[2]), wf1 = qbc<1>(v[2]), wf2 = qbc<2>(v[2]);
+      const double wf3 = qbc<3>(v[0]), wf4 = qbc<3>(v[1]);
+      double sA = A[0] * (cc == 0 ? w6 : (cc == 1 ? w7 : w8));
+      double sB = A[1] * w9;
+      sA += A[2] * w10;
+      sB += A[3] * w11;
+      sA += A[4] * v[1];
+      sB += A[5] * (cc == 1 ? wf2 : wf0);
+      sA += A[6] * (cc == 1 ? wf3 : wf1);
+      const double sC = (A[7] * wf2 + A[8] * wf3) + A[9] * wf4;  // friction rows 2..4 (cc == 2)
+      return (sA + sB) + m2 * sC;
+    };
+    // Row maxima of several quantities at once, by a transposing butterfly over the
+    // 16-lane row: each step pairs lane s with a partner that differs in one bit
+    // (row_mirror: s ^ 15, bit 3; row_half_mirror: s ^ 7, bit 2; quad xor 2, bit 1;
+    // quad xor 1, bit 0) and the lanes on either side of that bit keep half of the
+    // quantities, so a step reduces half as many values as the one before instead of
+    // every quantity taking all four steps (12 quantities: 13 maxima and 13 DPP moves
+    // instead of 48 each, for 26 two-way selects instead of 12).  Maxima are exact in
+    // any order: the results are the ones the per-quantity reduction gave.
+    // one step: lanes with the bit clear keep quantity a, the others b
+    auto tstep = [](auto ctrl, double a, double b, bool hi) __attribute__((always_inline)) {
+      constexpr int C = decltype(ctrl)::value;
+      const double mine = hi ? b : a, send = hi ? a : b;
+      return fmax_hw(mine, dppd<C>(send));
+    };
+    auto sstep = [](auto ctrl, double a) __attribute__((always_inline)) {
+      constexpr int C = decltype(ctrl)::value;
+      return fmax_hw(a, dppd<C>(a));
+    };
+    using kMirror = std::integral_constant<int, 0x140>;   // row_mirror (s ^ 15)
+    using kHalfMir = std::integral_constant<int, 0x141>;  // row_half_mirror (s ^ 7)
+    using kXor2 = std::integral_constant<int, 0x4E>;      // quad_perm [2,3,0,1]
+    using kXor1 = std::integral_constant<int, 0xB1>;      // quad_perm [1,0,3,2]
+    // six quantities over bits 3, 2, 1: lane s keeps quantity 3 b3 + (b2 ? 2 : b1),
+    // maximised over the eight lanes s ^ {0, 15, 7, 8, 2, 13, 5, 10}
+    auto tred6 = [&](const double (&v)[6], int s_) __attribute__((always_inline)) {
+      const bool h3 = s_ & 8, h2 = s_ & 4, h1 = s_ & 2;
+      const double a0 = tstep(kMirror{}, v[0], v[3], h3), a1 = tstep(kMirror{}, v[1], v[4], h3),
+                   a2 = tstep(kMirror{}, v[2], v[5], h3);
+      const double c0 = tstep(kHalfMir{}, a0, a2, h2), c1 = tstep(kHalfMir{}, a1, a2, h2);
+      return tstep(kXor2{}, c0, c1, h1);
+    };
+    // three quantities over the whole row: lane s keeps x0 on lanes 0..3, x1 on 4..7,
+    // x2 on 8..15
+    auto tred3 = [&](double x0, double x1, double x2, int s_) __attribute__((always_inline)) {
+      const bool h3 = s_ & 8, h2 = s_ & 4;
+      const double a0 = tstep(kMirror{}, x0, x2, h3), a1 = tstep(kMirror{}, x1, x2, h3);
+      return sstep(kXor1{}, sstep(kXor2{}, tstep(kHalfMir{}, a0, a1, h2)));
+    };
+    // A v on the own rows for own-column values (vf, vX), the previous stage's states in P
+    auto rowA = [&](double vf, double vX, lds_cd* P, double (&ax)[3]) __attribute__((always_inline)) {
+      MPCQ_LANE_OFFS(true);
+      const int zP = (int)((lds_cd*)sh.zero - P);  // stage 0 has no X_0 term: read zeros, not slot -1
+      // every operand of the rows in one batch of loads (up to 32 stages, hold_all): the
+      // twelve B coefficients, then the state terms' and the friction / swing rows'
+      double L[21];
+#pragma unroll
+      for (int psi = 0; psi < 12; ++psi) L[psi] = Ab[oB0 + 24 * (psi / 3) + 7 * (psi % 3)];
+      L[12] = Ab[oXd]; L[13] = Ab[oHd]; L[14] = P[hp ? oXSp - 12 : zP];
+      L[15] = Ab[oH6]; L[16] = P[hp ? oXSp6 - 12 : zP];
+      L[17] = Ab[oFb]; L[18] = Ab[oFa]; L[19] = Ab[oF4]; L[20] = Ab[oF + 4];
+      if constexpr (!BIG) hold_all(L);
+      double bco[12];
+#pragma unroll
+      for (int psi = 0; psi < 12; ++psi) {
+        const int cp = psi % 3;
+        bco[psi] = (ph >= 9 || (isv && cp == ph - 6)) ? L[psi] : 0.0;
+      }
+      const double bfx = bdot_ln12(bco, vf, 0.0);
+      double dyn = L[12] * vX;
+      const double d1 = dyn + L[13] * L[14];
+      const double d2 = d1 + L[15] * L[16];
+      dyn = hp ? (isv ? d1 : d2) : dyn;
+      dyn = isv ? dyn + bfx : dyn;
+      const double q0 = qbc<0>(vf), q1 = qbc<1>(vf), q2 = qbc<2>(vf);
+      const double frA = L[17] * q2 + L[18] * (ta0 ? q0 : q1);
+      const double frB = L[19] * q2;
+      const double swg = L[20] * vf;
+      ax[0] = cl ? dyn : frA;
+      ax[1] = cl ? swg : frB;
+      ax[2] = cl ? frA : 0.0;
+    };
+    // A' w on the own columns for own-row values w, the next stage's dynamics-row w in W
+    auto colAt = [&](const double (&w)[3], const double* W, double& atf, double& atX)
+        __attribute__((always_inline)) {
+      MPCQ_LANE_OFFS(true);
+      const double* wn = W + 12 * (k < N - 1 ? k + 1 : k);
+      // the force column's ten coefficients, then the state column's and the next stage's
+      // duals: one batch of loads (up to 32 stages, hold_all)
+      double L[15];
+#pragma unroll
+      for (int i = 0; i < 10; ++i) L[i] = Ab[fo + i];
+      L[10] = Ab[oXd]; L[11] = Ab[oXd + 1]; L[12] = Ab[oXd + 2];
+      L[13] = wn[isv ? ph - 6 : ph]; L[14] = wn[ph];
+      if constexpr (!BIG) hold_all(L);
+      const double A[10] = {L[0], L[1], L[2], L[3], L[4], L[5], L[6], L[7], L[8], L[9]};
+      atf = colF_c(A, w);
+      const double sXv = L[10] * w[0];
+      const double x1 = sXv + L[11] * L[13];
+      const double x2 = x1 + L[12] * L[14];
+      atX = k < N - 1 ? (isv ? x2 : x1) : sXv;
+    };
 
-    // ---- factorisation --------------------------------------------------------
+    // ---- 6. factorisation -----------------------------------------------------------------------
     // dynamics-row rho of stage kk (published in GH[kk][108..120) at factor time)
     // (stage-keyed scratch: unshifted slots; every read of it precedes the serial
     // steps that overwrite the slots with G / H at SLOT offsets)
@@ -1343,192 +774,6 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
       }
     };
 
-      auto ph_sweep_lag = [&]() __attribute__((always_inline)) {
-          // P5-P7: the state solve on wave 0 alone (no block barrier inside), up to 32
-          // stages (beyond: ph_sweep_split).
-          // Inward step j = 1..MID: top kk(j) = j, bottom kk(j) = N-1-j.  Half 0 (rows
-          // 0 top / 1 bottom) runs the recurrence y_kk = b_kk - G_kk y_kk(j-1) (G_kk of
-          // the top in GH[kk], H_kk of the bottom in GH[kk+1], stored negated), one
-          // full 12-term row per lane.  Half 1 (rows 2 / 3) runs the same instruction
-          // stream on S^{-1} rows two stages behind: w_kk(j-2) = S^{-1} y_kk(j-2), its y
-          // handed over by permlane32_swap.  Step MID+1 is the meeting stage: half 0
-          // solves x_m = M^{-1} (y_m + v_m - b_m) (top and bottom rows joined by
-          // permlane16_swap), half 1 the last top w.  Then the outward sweeps.
-          const int half = (t >> 5) & 1;
-#ifndef MPCQ_REP_SWEEP
-#define MPCQ_REP_SWEEP 1
-#endif
-#pragma nounroll
-          for (int rep_ = 0; rep_ < MPCQ_REP_SWEEP; ++rep_) {  // > 1: timing experiments only
-          double xp = 0.0;
-          // Step-ordered bases (SIG): step j's rows / right-hand sides / w / X are at
-          // base + j * stride for every lane, an immediate offset.  Half 0: G_j (top,
-          // slot j) / H_{N-1-j} (bottom, slot MID+j); half 1: S^{-1} of stage kk(j-2),
-          // top slot j-2 / bottom slot MID-1+j.  Step 1's rows are iteration-invariant:
-          // wave 0 reads them before the barrier that publishes the right-hand sides.
-          // (N > 32: S^{-1} is global, so the row pointer is a generic one)
-          using swp = lds_cd;
-          using swp2 = lds_cd2;
-          swp* const GHs = GHr;
-          // (the bottom chain's slots are past N/2: +2, SLOT)
-          swp* const Mb = half == 0 ? GHs + (GS * (cr == 0 ? 0 : MID) + (cr == 0 ? 0 : kSlotPad<N>) + RS * rr_)
-                                    : (swp*)&sh.Sm[0][0] + (GS * (cr == 0 ? -2 : MID - 1) + (cr == 0 ? 0 : kSlotPad<N>) + RS * rr_);
-          double g[12];
-          auto row12 = [&](swp* q) __attribute__((always_inline)) {  // 16-B aligned row: 6 ds_read_b128
-#pragma unroll
-            for (int i = 0; i < 6; ++i) {
-              const dbl2 v = ((swp2*)q)[i];
-              g[2 * i] = v.x;
-              g[2 * i + 1] = v.y;
-            }
-          };
-          // the rows of step j (j a constant after unrolling): every lane reads a slot the
-          // factorisation wrote -- the steps a chain does not take (half 1's first step,
-          // the bottom chain's steps past its BOT stages at even N) re-read a row of the
-          // chain's own, and their products are discarded by the hand-off select / the sink
-          auto rowp = [&](int j) __attribute__((always_inline)) -> swp* {
-            if (j >= 2 && j <= BOT) return Mb + GS * j;
-            const int jj = half == 0 ? (cr == 0 ? j : (j < BOT ? j : BOT))
-                                     : (cr == 0 ? (j > 2 ? j : 2) : (j < BOT + 1 ? j : BOT + 1));
-            return Mb + GS * jj;
-          };
-          STAMP(15);  // (diagnostic builds: as in ph_sweep_split)
-          if (t < 64) row12(rowp(1));
-          sync_all();
-          STAMP(3);
-          // outward step j reads G_{MID-j+1}' (top, slot MID+1-j) / H_{MID+j-1}'
-          // (bottom, slot N-j) columns: Ob + (MID - j) GS (LDS offsets are unsigned,
-          // so the bases sit at the lowest slot a chain reaches)
-          lds_cd* const Ob = GHr + (GS * (cr == 0 ? 1 : N - MID) + (cr == 0 ? 0 : kSlotPad<N>) + rr_);
-          if (t < 64) {
-            // the sweeps are every wave's critical path (the other waves of the
-            // instance wait at the barrier): issue them ahead of a co-resident
-            // instance's stage-parallel phases
-            __builtin_amdgcn_s_setprio(3);
-            // right-hand side of step j: top stage j (slot j), bottom stage N-1-j (slot
-            // MID+1+j, except the meeting stage MID at the bottom's last step BOT, slot
-            // MID, which the bottom re-reads in the steps it does not take); na at +12N
-            lds_cd* const Bb = (lds_cd*)&sh.u.it.bo[0][0] + (12 * (cr == 0 ? 0 : MID + 1) + rr_);
-            lds_cd* const Bm = (lds_cd*)&sh.u.it.bo[0][0] + (12 * MID + rr_);
-            auto rhs = [&](int j) __attribute__((always_inline)) -> lds_cd* {  // j: a constant
-              return (j >= BOT && cr != 0) ? Bm : Bb + 12 * j;
-            };
-            // w of stage kk(j-2) (half 1): top slot j-2, bottom slot MID-1+j; the other
-            // lanes store into the sink with the same stride
-            lds_d* const sink = (lds_d*)&sh.red[0] + (t & 31);
-            lds_d* const Yb = (half == 1 && s < 12) ? (lds_d*)&sh.u.it.yv[0][0] + (12 * (cr == 0 ? -2 : MID - 1) + rr_)
-                                                    : sink;
-            // step MID+1's store: every lane has one target, so it is one store and no branch
-            lds_d* const Ym = ((N & 1) || cr == 0) ? Yb + 12 * (MID + 1) : sink;
-            lds_d* const Pm = (half == 0 && cr == 0 && s < 12)
-                                  ? (lds_d*)&sh.u.it.xs[0][0] + (12 * SIGX<N>(MID + 1) + rr_) : Ym;
-            // right-hand sides run two steps ahead: step j sums the one of step j+1
-            // (loaded during step j-1) and loads the one of step j+2; half 1 (the w
-            // products) starts its chain from 0.  The first two (y_kk(0) and step 1's)
-            // are loaded together and waited for once: they were published by the
-            // barrier just passed, so this round trip is on the critical path.
-            const double m0 = half == 0 ? 1.0 : 0.0;
-            double s0 = rhs(0)[0], s1 = rhs(0)[12 * N];
-            double c0 = rhs(1)[0], c1 = rhs(1)[12 * N];
-            double src = half == 0 ? s0 + s1 : 0.0;  // y_kk(0) (half 0)
-            double bcn = add_mul_here(c0, c1, m0);
-            double b0 = rhs(2)[0], b1 = rhs(2)[12 * N];
-#pragma unroll
-            for (int j = 1; j <= MID + 1; ++j) {
-              asm volatile("" : : : "memory");
-              double gc[12];
-#pragma unroll
-              for (int i = 0; i < 12; ++i) gc[i] = g[i];
-              const double bc = j <= MID ? bcn : 0.0;
-              if (j < MID) {  // prefetch the next step's rows
-                row12(rowp(j + 1));
-              } else if (j == MID) {  // the meeting step: M^{-1} rows (half 0), the S walk (half 1)
-                row12(half == 0 ? GHs + RS * rr_ : rowp(MID + 1));
-                lds_cd* qb = (lds_cd*)&sh.u.it.bo[0][0] + (12 * MID + rr_);
-                b0 = qb[0]; b1 = qb[12 * N];
-              } else {  // the last step: the first outward step's columns
-#pragma unroll
-                for (int i = 0; i < 12; ++i) g[i] = Ob[RS * i + GS * (MID - 1)];
-              }
-              asm volatile("" : : : "memory");  // the prefetch is issued here, not sunk to its use
-              double s_in = src;
-              if (j == MID + 1) s_in = half == 0 ? row_pair_sum(src) - (b0 + b1) : src;
-              const double acc = bdot12(gc, s_in, bc);
-              // the next right-hand side is summed after the chain: its loads were
-              // issued at the end of the previous step, and summing them ahead of the
-              // chain would put their LDS latency on the critical path
-              // (the sum and its mask as a volatile asm, which keeps its place behind the chain's
-              // block: an empty-asm launder of b0 / b1 did too, but it redefines them, and the
-              // compiler then copied the first pair and put a wait state in front of every sum)
-              if (j < MID) bcn = add_mul_here(b0, b1, m0);
-              if (j + 2 <= MID) {
-                b0 = rhs(j + 2)[0]; b1 = rhs(j + 2)[12 * N];
-              }
-              if (j >= 2 && j <= MID) {  // half 1: w of stage kk(j-2)
-                Yb[12 * j] = acc;
-              } else if (j == MID + 1) {
-                // the last step's one store: x_m from row 0's state lanes, half 1's last w
-                // (even N: the bottom's kk(MID-1) is the meeting stage, no w), else the sink
-                *Pm = acc;
-              }
-              if (j <= MID) {
-                // half 0 continues with y_kk(j) (the bottom chain stops after step BOT), half 1
-                // receives y_kk(j-1) from half 0
-                const bool adv = j <= BOT || cr == 0;
-                src = keep_lo_take_lo(adv ? acc : src, src);
-                // (the hand-off stays ahead of the next step's row reads: with the reads
-                // between it and the chain, the chain's opening s_nop is dropped, nop_elide.py)
-                asm volatile("" : "+v"(src));
-              } else {
-                xp = acc;
-              }
-            }
-            STAMP(6);
-          }
-          if (t < 64) {
-            // Outward step j: top kk = MID-j: X_kk = w_kk - G_{kk+1}' X_{kk+1}; bottom
-            // kk = MID+j: X_kk = w_kk - H_{kk-1}' X_{kk-1} (columns from Ob - j GS).  Lane
-            // rr reads column rr (a full 12-term product per lane; half 1 repeats half 0).
-            // w of stage kk: top slot MID-j, bottom slot N-j (Wb - 12 j); X_kk = xs[kk+1]:
-            // top slot MID+1-j, bottom slot N-j (SIGX; Xb - 12 j).  The bottom row's last
-            // step (kk = N) is idle: its store goes to the sink.
-            // (bases at step MID's slot: step j at base + 12 (MID - j))
-            lds_cd* const Wb = (lds_cd*)&sh.u.it.yv[0][0] + (12 * (cr == 0 ? 0 : N - MID) + rr_);
-            lds_d* const sinkO = (lds_d*)&sh.red[0] + (t & 31);
-            lds_d* const Xb = (half == 0 && s < 12) ? (lds_d*)&sh.u.it.xs[0][0] + (12 * (cr == 0 ? 1 : N - MID) + rr_)
-                                                    : sinkO;
-            wave_sync();  // the w written by half 1
-            double bq = Wb[12 * (MID - 1)];
-#pragma unroll
-            for (int j = 1; j <= MID; ++j) {
-              asm volatile("" : : : "memory");
-              double gc[12];
-#pragma unroll
-              for (int i = 0; i < 12; ++i) gc[i] = g[i];
-              const double bc = bq;
-              if (j < MID) {
-#pragma unroll
-                for (int i = 0; i < 12; ++i) g[i] = Ob[RS * i + GS * (MID - j - 1)];
-                // (even N: the bottom chain has no step MID; it re-reads its last w)
-                if (j + 1 <= BOT) bq = Wb[12 * (MID - j - 1)];
-                else bq = Wb[12 * (MID - (cr == 0 ? j + 1 : BOT))];
-              }
-              asm volatile("" : : : "memory");
-              const double acc = bdot12(gc, xp, bc);  // x = w - G' x_next with -G stored
-              if (j < MID) {
-                xp = acc;
-                Xb[12 * (MID - j)] = acc;
-              } else if constexpr (N & 1) {
-                *Xb = acc;
-              } else {  // even N: the bottom chain has no step MID
-                *(cr == 0 ? Xb : sinkO) = acc;
-              }
-            }
-            __builtin_amdgcn_s_setprio(0);
-          }
-          wave_sync();
-          }  // MPCQ_REP_SWEEP
-      };
     // pr: per-own-row rho override (polish: 1/delta on active rows, 0 elsewhere);
     // nullptr in the ADMM loop, where the class rho applies
     auto factor = [&](double sigma, const double* pr) __attribute__((always_inline)) -> bool {
@@ -1717,207 +962,7 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
       return good;
     };
 
-    // ---- residuals (OSQP update_info), uniform results ---------------------
-    double pri_res = 0.0, dua_res = 0.0, eps_pri = 0.0, eps_dua = 0.0, s_pri = 0.0, s_dua = 0.0;
-  // per-lane constants of the ADMM loop and the residuals: LDS offsets, flags
-    const bool hp = k >= 1, isv = ph >= 6;
-    const int zXS = (int)(sh.zero - &sh.u.it.xs[0][0]);  // X_0 is not stored: stage 0 reads zeros
-    const double m2 = cc == 2 ? 1.0 : 0.0;
-    // masked variants for the loop: a lane whose term is structurally absent reads a
-    // zero (stage 0 has no previous stage; H6 only on the position rows; the force Schur
-    // terms beta, (R^-1 Q) g only on the velocity rows), so no selects are needed
-    int zAb;  // offset of a zero block from Ab (masked reads)
-    if constexpr (ABG) zAb = Work<N>::ZERO - Work<N>::AB;
-    else zAb = (int)(sh.zero - sh.Ab);
-    lds_cd* XSr = (lds_cd*)&sh.u.it.xs[0][0];
-    double* const Wdump = &sh.dump[t & 63];
-    // The LDS offsets of the lane's coefficients, derived from its coordinates.  O0
-    // is derived once and held (the loop phases up to 32 stages, where the ADMM loop
-    // has the registers); a phase run between long stretches of other work -- the
-    // termination check at every N, every loop phase beyond 32 stages (168 VGPRs) --
-    // re-derives them from freshly laundered coordinates (MPCQ_LANE_OFFS(true)), a
-    // few integer ops each: held across the ADMM loop, the compiler spills them, and
-    // each use then waits on its own scratch round trip (the reloads sit right in
-    // front of their LDS reads, one after another).
-    struct LaneOffs {
-      int oXd, oHd, oH6, oF, oFa, oFb, oF4, oFW, oQL, oXSp, oXSp6, rXS, rXSpm, rXSp6m, oHdm, oH6m, oFWcm, oQLm,
-          oB0;
-      bool ta0;
-      double* Wbo;
-      double* Wna;
-    };
-    auto offs = [&]() __attribute__((always_inline)) -> LaneOffs {
-      const bool hp_ = k >= 1, isv_ = ph >= 6;
-      LaneOffs o;
-      o.oXd = xo;                                                 // Xd(k, ph)
-      o.oHd = XO<N>(hp_ ? k - 1 : 0, ph) + (ph < 6 ? 1 : 2);      // Hd(k, ph)
-      o.oH6 = XO<N>(hp_ ? k - 1 : 0, ph < 6 ? ph + 6 : 11) + 1;   // H6(k, ph)
-      o.oF = fo;
-      const int ta = c < 3 ? c : 3;  // first own friction row
-      o.ta0 = (ta >> 1) == 0;
-      o.oFa = FO<N>(k, f, ta >> 1) + 5 + (ta & 1);
-      o.oFb = FO<N>(k, f, 2) + 5 + ta;
-      o.oF4 = FO<N>(k, f, 2) + 9;
-      o.oFW = kFWS<N> * k + 6 * ph;
-      const int oFWc = kFWS<N> * k + (isv_ ? ph - 6 : 0);
-      o.oQL = 36 * k + 6 * (isv_ ? ph - 6 : 0);
-      o.oXSp = 12 * k + ph;  // natural order (update_info)
-      o.oXSp6 = 12 * k + (ph < 6 ? ph + 6 : ph);
-      // the sweep's states in its slots (SIGX): own X_{k+1}, the previous stage's X_k
-      auto xsl = [](int kk) __attribute__((always_inline)) -> int { return 12 * SIGX<N>(kk + 1); };
-      o.rXS = xsl(k) + ph;
-      o.rXSpm = hp_ ? xsl(k - 1) + ph : zXS;
-      o.rXSp6m = hp_ ? xsl(k - 1) + (ph < 6 ? ph + 6 : ph) : zXS;
-      o.oHdm = hp_ ? o.oHd : zAb;
-      o.oH6m = hp_ && !isv_ ? o.oH6 : zAb;
-      o.oFWcm = isv_ ? oFWc : zFW;
-      o.oQLm = isv_ ? o.oQL : zQL;
-      o.oB0 = FO<N>(k, 0, 0) + (ph >= 9 ? ph - 8 : 0);  // B row ph on force (fp, cp): + 24 fp + 7 cp
-      o.Wbo = &sh.u.it.bo[SIG<N>(k)][ph];
-      o.Wna = &sh.u.it.na[SIG<N>(hp_ ? k - 1 : N - 1)][ph];
-      return o;
-    };
-    LaneOffs O0 = offs();  // (re-derived at the top of every stretch of iterations up to 32 stages, below)
-#define MPCQ_LANE_OFFS(RECOMP)                                                                              \
-  if constexpr (RECOMP) launder();                                                                         \
-  const LaneOffs O_ = (RECOMP) ? offs() : O0;                                                              \
-  [[maybe_unused]] const int oXd = O_.oXd, oHd = O_.oHd, oH6 = O_.oH6, oF = O_.oF, oFa = O_.oFa,           \
-                             oFb = O_.oFb, oF4 = O_.oF4, oFW = O_.oFW, oQL = O_.oQL, oXSp = O_.oXSp,       \
-                             oXSp6 = O_.oXSp6, rXS = O_.rXS, rXSpm = O_.rXSpm, rXSp6m = O_.rXSp6m,         \
-                             oHdm = O_.oHdm, oH6m = O_.oH6m, oFWcm = O_.oFWcm, oQLm = O_.oQLm, oB0 = O_.oB0; \
-  [[maybe_unused]] const bool ta0 = O_.ta0;                                                                \
-  [[maybe_unused]] double* const Wbo = O_.Wbo;                                                             \
-  [[maybe_unused]] double* const Wna = O_.Wna
-    // beyond 32 stages the loop phases re-derive them too
-    constexpr bool kRecompLoop = BIG;
-    auto launder_p = [&]() __attribute__((always_inline)) {
-      lds_uniform(Ab); lds_uniform(GHr); lds_uniform(SmR); lds_uniform(FWr); lds_uniform(QLr); lds_uniform(XSr);
-    };
-    // force column of A' v for own-row values v (dynamics rows 6..11 by row broadcast,
-    // swing, friction by quad broadcast)
-    auto colF_c = [&](const double (&A)[10], const double (&v)[3]) __attribute__((always_inline)) -> double {
-      const double w6 = rbc<LN(6)>(v[0]), w7 = rbc<LN(7)>(v[0]), w8 = rbc<LN(8)>(v[0]);
-      const double w9 = rbc<LN(9)>(v[0]), w10 = rbc<LN(10)>(v[0]), w11 = rbc<LN(11)>(v[0]);
-      const double wf0 = qbc<0>(v[2]), wf1 = qbc<1>(v[2]), wf2 = qbc<2>(v[2]);
-      const double wf3 = qbc<3>(v[0]), wf4 = qbc<3>(v[1]);
-      double sA = A[0] * (cc == 0 ? w6 : (cc == 1 ? w7 : w8));
-      double sB = A[1] * w9;
-      sA += A[2] * w10;
-      sB += A[3] * w11;
-      sA += A[4] * v[1];
-      sB += A[5] * (cc == 1 ? wf2 : wf0);
-      sA += A[6] * (cc == 1 ? wf3 : wf1);
-      const double sC = (A[7] * wf2 + A[8] * wf3) + A[9] * wf4;  // friction rows 2..4 (cc == 2)
-      return (sA + sB) + m2 * sC;
-    };
-    // Row maxima of several quantities at once, by a transposing butterfly over the
-    // 16-lane row: each step pairs lane s with a partner that differs in one bit
-    // (row_mirror: s ^ 15, bit 3; row_half_mirror: s ^ 7, bit 2; quad xor 2, bit 1;
-    // quad xor 1, bit 0) and the lanes on either side of that bit keep half of the
-    // quantities, so a step reduces half as many values as the one before instead of
-    // every quantity taking all four steps (12 quantities: 13 maxima and 13 DPP moves
-    // instead of 48 each, for 26 two-way selects instead of 12).  Maxima are exact in
-    // any order: the results are the ones the per-quantity reduction gave.
-    // one step: lanes with the bit clear keep quantity a, the others b
-    auto tstep = [](auto ctrl, double a, double b, bool hi) __attribute__((always_inline)) {
-      constexpr int C = decltype(ctrl)::value;
-      const double mine = hi ? b : a, send = hi ? a : b;
-      return fmax_hw(mine, dppd<C>(send));
-    };
-    auto sstep = [](auto ctrl, double a) __attribute__((always_inline)) {
-      constexpr int C = decltype(ctrl)::value;
-      return fmax_hw(a, dppd<C>(a));
-    };
-    using kMirror = std::integral_constant<int, 0x140>;   // row_mirror (s ^ 15)
-    using kHalfMir = std::integral_constant<int, 0x141>;  // row_half_mirror (s ^ 7)
-    using kXor2 = std::integral_constant<int, 0x4E>;      // quad_perm [2,3,0,1]
-    using kXor1 = std::integral_constant<int, 0xB1>;      // quad_perm [1,0,3,2]
-    // six quantities over bits 3, 2, 1: lane s keeps quantity 3 b3 + (b2 ? 2 : b1),
-    // maximised over the eight lanes s ^ {0, 15, 7, 8, 2, 13, 5, 10}
-    auto tred6 = [&](const double (&v)[6], int s_) __attribute__((always_inline)) {
-      const bool h3 = s_ & 8, h2 = s_ & 4, h1 = s_ & 2;
-      const double a0 = tstep(kMirror{}, v[0], v[3], h3), a1 = tstep(kMirror{}, v[1], v[4], h3),
-                   a2 = tstep(kMirror{}, v[2], v[5], h3);
-      const double c0 = tstep(kHalfMir{}, a0, a2, h2), c1 = tstep(kHalfMir{}, a1, a2, h2);
-      return tstep(kXor2{}, c0, c1, h1);
-    };
-    // three quantities over the whole row: lane s keeps x0 on lanes 0..3, x1 on 4..7,
-    // x2 on 8..15
-    auto tred3 = [&](double x0, double x1, double x2, int s_) __attribute__((always_inline)) {
-      const bool h3 = s_ & 8, h2 = s_ & 4;
-      const double a0 = tstep(kMirror{}, x0, x2, h3), a1 = tstep(kMirror{}, x1, x2, h3);
-      return sstep(kXor1{}, sstep(kXor2{}, tstep(kHalfMir{}, a0, a1, h2)));
-    };
-    // A v on the own rows for own-column values (vf, vX), the previous stage's states in P
-    auto rowA = [&](double vf, double vX, lds_cd* P, double (&ax)[3]) __attribute__((always_inline)) {
-      MPCQ_LANE_OFFS(true);
-      const int zP = (int)((lds_cd*)sh.zero - P);  // stage 0 has no X_0 term: read zeros, not slot -1
-      // every operand of the rows in one batch of loads (up to 32 stages, hold_all): the
-      // twelve B coefficients, then the state terms' and the friction / swing rows'
-      double L[21];
-#pragma unroll
-      for (int psi = 0; psi < 12; ++psi) L[psi] = Ab[oB0 + 24 * (psi / 3) + 7 * (psi % 3)];
-      L[12] = Ab[oXd]; L[13] = Ab[oHd]; L[14] = P[hp ? oXSp - 12 : zP];
-      L[15] = Ab[oH6]; L[16] = P[hp ? oXSp6 - 12 : zP];
-      L[17] = Ab[oFb]; L[18] = Ab[oFa]; L[19] = Ab[oF4]; L[20] = Ab[oF + 4];
-      if constexpr (!BIG) hold_all(L);
-      double bco[12];
-#pragma unroll
-      for (int psi = 0; psi < 12; ++psi) {
-        const int cp = psi % 3;
-        bco[psi] = (ph >= 9 || (isv && cp == ph - 6)) ? L[psi] : 0.0;
-      }
-      const double bfx = bdot_ln12(bco, vf, 0.0);
-      double dyn = L[12] * vX;
-      const double d1 = dyn + L[13] * L[14];
-      const double d2 = d1 + L[15] * L[16];
-      dyn = hp ? (isv ? d1 : d2) : dyn;
-      dyn = isv ? dyn + bfx : dyn;
-      const double q0 = qbc<0>(vf), q1 = qbc<1>(vf), q2 = qbc<2>(vf);
-      const double frA = L[17] * q2 + L[18] * (ta0 ? q0 : q1);
-      const double frB = L[19] * q2;
-      const double swg = L[20] * vf;
-      ax[0] = cl ? dyn : frA;
-      ax[1] = cl ? swg : frB;
-      ax[2] = cl ? frA : 0.0;
-    };
-    // A' w on the own columns for own-row values w, the next stage's dynamics-row w in W
-    auto colAt = [&](const double (&w)[3], const double* W, double& atf, double& atX)
-        __attribute__((always_inline)) {
-      MPCQ_LANE_OFFS(true);
-      const double* wn = W + 12 * (k < N - 1 ? k + 1 : k);
-      // the force column's ten coefficients, then the state column's and the next stage's
-      // duals: one batch of loads (up to 32 stages, hold_all)
-      double L[15];
-#pragma unroll
-      for (int i = 0; i < 10; ++i) L[i] = Ab[fo + i];
-      L[10] = Ab[oXd]; L[11] = Ab[oXd + 1]; L[12] = Ab[oXd + 2];
-      L[13] = wn[isv ? ph - 6 : ph]; L[14] = wn[ph];
-      if constexpr (!BIG) hold_all(L);
-      const double A[10] = {L[0], L[1], L[2], L[3], L[4], L[5], L[6], L[7], L[8], L[9]};
-      atf = colF_c(A, w);
-      const double sXv = L[10] * w[0];
-      const double x1 = sXv + L[11] * L[13];
-      const double x2 = x1 + L[12] * L[14];
-      atX = k < N - 1 ? (isv ? x2 : x1) : sXv;
-    };
-    // OSQP 0.6's infeasibility tests (auxil.c is_primal_infeasible / is_dual_infeasible)
-    // on the last iteration's delta_y (dy, own rows) and delta_x (dxf, dxX, own
-    // columns), evaluated the way osqp evaluates them: the cheap conditions first
-    // (||E dy||, u'dy+ + l'dy-, ||D dx||, ||D^-1 P dx||), the products A' dy / A dx
-    // only where those hold.  infeas_cheap runs right after the update, while the
-    // deltas are live: it publishes them (na / nb, free between the sweeps) with
-    // update_info's states / duals under one barrier and leaves the per-wave partials
-    // of the cheap quantities in red[32 wv + 16 ..]; update_info(INF) combines them
-    // into uniform flags (each test only where its residual test fails, as osqp's
-    // check_termination); infeas_products, only when a flag holds, adds the products
-    // (two more barriers).  On MPC.py's QPs the dual side never reaches its product
-    // and the primal side does at ~40 % of the checks (oracle counts, C2 batch), so
-    // the product pass is skipped at most checks -- with identical outcomes.
-    // outcome bits (one uniform int: the loop carries it): 1 primal, 2 dual infeasible
-    // at the check's tolerances, 4 / 8 at the approximate (x10) ones
-    int inf_bits = 0;
-    int inf_need = 0;  // cheap-condition bits (same layout) awaiting the products
+    // ---- 7. scaling: the check's constants, then (status == 0) the Ruiz passes and the start ----
     // The termination check's scaling constants (fixed once the Ruiz scaling is done):
     // D, D^-1 of the own columns, E^-1 of the own rows, the scaled P diagonal, c and
     // 1/c.  Held across the ADMM loop, which does not use them, they were spilled and
@@ -1968,284 +1013,10 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
         for (int i = 0; i < CK_COUNT; ++i) cv[i] = q[i];
       }
     };
-    // The check's lane ids, re-derived from a laundered thread index: the red[] addresses
-    // built from them would otherwise be hoisted out of the ADMM loop and spilled too.
-#define MPCQ_CHECK_IDS()                                           \
-  int tl_ = t;                                                     \
-  asm volatile("" : "+v"(tl_));                                    \
-  [[maybe_unused]] const int wv = tl_ >> 6, lane = tl_ & 63, s = tl_ & 15
-    // The bounds as the check sees them: lo_of / hi_of from the row scaling E and the
-    // dynamics bound in the check's constant block (ck, read with the others in one
-    // batch).  Formed from the loop's own E / bnd, the products (-inf E, -fz_max E) were
-    // hoisted out of the ADMM loop and spilled, and each came back in the check as a
-    // scratch reload waited for on its own.  Same expressions, same values.
-    auto chk_bounds = [&](const double (&cv)[CK_COUNT], double (&lo)[3], double (&hi)[3])
-        __attribute__((always_inline)) {
-      if constexpr (FUSED) {
-        const double e0 = cv[CK_E0], e1 = cv[CK_E1], e2 = cv[CK_E2], bd = cv[CK_BND];
-        double fz = fz_max();
-        asm volatile("" : "+v"(fz));
-        lo[0] = cl ? bd : -kInf * e0;
-        lo[1] = cl ? 0.0 : -fz * e1;
-        lo[2] = cl ? -kInf * e2 : -kInf;
-        hi[0] = cl ? bd : 0.0;
-        hi[1] = 0.0;
-        hi[2] = cl ? 0.0 : kInf;
-      } else {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) { lo[j] = lo_of(j); hi[j] = hi_of(j); }
-      }
-    };
-    // the infeasibility tolerances, laundered for the same reason (10 eps, hoisted, was
-    // spilled)
-    auto chk_eps = [&](double& epi0, double& edi0) __attribute__((always_inline)) {
-      epi0 = p.eps_prim_inf;
-      edi0 = p.eps_dual_inf;
-      asm volatile("" : "+v"(epi0), "+v"(edi0));
-    };
-    double dyp[3];     // delta_y projected onto the polar of the recession cone of [l, u]
-    // The cheap part of OSQP's infeasibility tests on the last iteration's deltas, own
-    // data only: dyp, and this wave's maxima ||E dy|| / ||D dx|| / ||D^-1 P dx|| and sum
-    // u'dy+ + l'dy- into P[PS wv + 16 + {0, 2, 3, 6}] (red for the blocking check, dcp
-    // for the deferred one).  cv: the constant block, read ahead of the check (ck_all).
-    auto cheap_partials = [&](const double (&dy)[3], double dxf, double dxX, const double (&cv)[CK_COUNT],
-                              double* const P, int PS) __attribute__((always_inline)) {
-      MPCQ_CHECK_IDS();
-      double lob[3], hib[3];
-      chk_bounds(cv, lob, hib);
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        const bool uinf = hib[j] > kInf * kMinScaling, linf = lob[j] < -kInf * kMinScaling;
-        dyp[j] = uinf ? (linf ? 0.0 : fmin(dy[j], 0.0)) : (linf ? fmax(dy[j], 0.0) : dy[j]);
-      }
-      double ndy = 0.0, ineq = 0.0;
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        const double lj = lob[j], hj = hib[j];
-        ndy = fmax(ndy, fabs(cv[CK_E0 + j] * dyp[j]));
-        ineq += hj * fmax(dyp[j], 0.0) + lj * fmin(dyp[j], 0.0);
-      }
-      if (phantom) ineq = 0.0;  // a sum: stage N-1 counts once
-      double q3[2] = {0.0, 0.0};
-      {
-        const double df = cv[CK_DF], dx = cv[CK_DX], dif = 1.0 / df, diX = 1.0 / dx;
-        const double pbf = cv[CK_PBF], pbx = cv[CK_PBX];
-        if (cl) {
-          q3[0] = fmax(fabs(df * dxf), fabs(dx * dxX));                // ||D dx||
-          q3[1] = fmax(fabs(pbf * dxf * dif), fabs(pbx * dxX * diX));  // ||D^-1 P dx||
-        }
-      }
-      // maxima over the wave (lanes 0 / 4 / 8 keep ||E dy|| / ||D dx|| / ||D^-1 P dx||,
-      // published in slots 0 / 2 / 3), the sum by xor butterflies
-      const double mine = pair_max(row_pair_max(tred3(ndy, q3[0], q3[1], s)));
-      ineq += dppd<0xB1>(ineq);
-      ineq += dppd<0x4E>(ineq);
-      ineq += dppd<0x124>(ineq);
-      ineq += dppd<0x128>(ineq);
-      ineq = row_pair_sum(ineq);
-      {
-        const long long bb = __double_as_longlong(ineq);
-        const auto lo_ = __builtin_amdgcn_permlane32_swap((unsigned)bb, (unsigned)bb, false, false);
-        const auto hi_ = __builtin_amdgcn_permlane32_swap((unsigned)(bb >> 32), (unsigned)(bb >> 32), false, false);
-        ineq = __longlong_as_double(((long long)hi_[0] << 32) | lo_[0]) +
-               __longlong_as_double(((long long)hi_[1] << 32) | lo_[1]);
-      }
-      if (lane == 0 || lane == 4 || lane == 8) P[PS * wv + 16 + (lane == 0 ? 0 : 2 + (lane >> 3))] = mine;
-      if (lane == 6) P[PS * wv + 16 + 6] = ineq;
-    };
-    auto infeas_cheap = [&](const double (&dy)[3], double dxf, double dxX, const double (&cv)[CK_COUNT])
-        __attribute__((always_inline)) {
-      cheap_partials(dy, dxf, dxX, cv, sh.red, 32);
-      // published together with update_info's states / duals, one barrier for both
-      if (cl) {
-        sh.u.it.na[k][ph] = dxX;
-        sh.u.it.nb[k][ph] = dyp[0];
-        sh.u.it.yv[k][ph] = xX;
-        sh.u.it.bo[k][ph] = y[0];
-      }
-      sync_all();  // (update_info(INF) relies on this barrier for its own publication)
-    };
-    // the products, where a cheap condition holds (inf_need != 0, uniform): A' dy for
-    // the primal test, A dx for the dual one, on the deltas infeas_cheap published
-    auto infeas_products = [&](double dxf, double dxX, const double (&cv)[CK_COUNT])
-        __attribute__((always_inline)) {
-      MPCQ_CHECK_IDS();
-      launder_p();
-      double vu = -INFINITY, vl = -INFINITY;
-      {
-        double adx[3], lob[3], hib[3];
-        rowA(dxf, dxX, (lds_cd*)&sh.u.it.na[0][0], adx);
-        chk_bounds(cv, lob, hib);
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-          const double lj = lob[j], hj = hib[j], v = adx[j] / cv[CK_E0 + j];
-          if (hj < kInf * kMinScaling) vu = fmax(vu, v);
-          if (lj > -kInf * kMinScaling) vl = fmax(vl, -v);
-        }
-      }
-      double naty = 0.0;
-      {
-        double dtf, dtX;
-        colAt(dyp, &sh.u.it.nb[0][0], dtf, dtX);
-        const double dif = 1.0 / cv[CK_DF], diX = 1.0 / cv[CK_DX];
-        if (cl) naty = fmax(fabs(dtf * dif), fabs(dtX * diX));  // ||D^-1 A' dy||
-      }
-      // lanes 0 / 4 / 8 keep ||D^-1 A' dy|| / vu / vl, published in slots 1 / 4 / 5
-      const double mine = pair_max(row_pair_max(tred3(naty, vu, vl, s)));
-      if (lane == 0 || lane == 4 || lane == 8) sh.red[32 * wv + 16 + (lane == 0 ? 1 : 4 + (lane >> 3))] = mine;
-      sync_all();
-      const int e = s < 6 ? s : 0;  // slots 16..21 are all maxima (0 / 2 / 3 from infeas_cheap)
-      double v = sh.red[16 + e];
-#pragma unroll
-      for (int w = 1; w < NW; ++w) v = fmax_hw(v, sh.red[32 * w + 16 + e]);
-      const double ndy = rbc<0>(v), ndx = rbc<2>(v);  // (the cheap maxima, kept in slots 0 / 2)
-      const double naty_ = rbc<1>(v), vu_ = rbc<4>(v), vl_ = rbc<5>(v);
-      double epi0, edi0;
-      chk_eps(epi0, edi0);
-      int bits = 0;
-#pragma unroll
-      for (int fi = 0; fi < 2; ++fi) {
-        const double f = fi == 0 ? 1.0 : 10.0, epi = f * epi0, edi = f * edi0;
-        const bool pi = ((inf_need >> (2 * fi)) & 1) && naty_ < epi * ndy;
-        const bool di = ((inf_need >> (2 * fi)) & 2) && !(vu_ > edi * ndx) && !(vl_ > edi * ndx);
-        bits |= (pi ? 1 : 0) << (2 * fi);
-        bits |= (di ? 2 : 0) << (2 * fi);
-      }
-      inf_bits = __builtin_amdgcn_readfirstlane(bits);
-      sync_all();
-    };
-    // The states and dynamics-row duals are published in yv / bo, which the sweeps
-    // no longer need (xs still feeds the force recovery of slower waves); lane s
-    // of each row then owns residual quantity s, reduced over the wave's rows by
-    // permlane swaps and over the waves through red[].  INF: also combine the
-    // cheap partials of infeas_cheap into inf_need.
-    // info_terms: this wave's 16 residual maxima into D[DS wv + 0..15], from the own
-    // rows / columns and the published states XP (X_{k'} of stage k' at 12 (k' - 1))
-    // and duals WD (y of stage k' at 12 k')
-    auto info_terms = [&](const double (&cv)[CK_COUNT], lds_cd* const XP, const double* WD, double* const D,
-                          int DS) __attribute__((always_inline)) {
-      MPCQ_CHECK_IDS();
-      const double ei3[3] = {1.0 / cv[CK_E0], 1.0 / cv[CK_E1], 1.0 / cv[CK_E2]};
-      const double dif = 1.0 / cv[CK_DF], diX = 1.0 / cv[CK_DX], pbf = cv[CK_PBF], pbx = cv[CK_PBX];
-      double mine, pmine;  // this lane's row maxima (tred6: primal quantity 3 b3 + (b2 ? 2 : b1))
-      {  // primal side: A x - z on the own rows
-        double ax[3], q6[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        rowA(xf, xX, XP, ax);
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-          const double ei = ei3[j], d = ax[j] - z[j];
-          q6[0] = fmax(q6[0], fabs(ei * d));
-          q6[1] = fmax(q6[1], fabs(ei * ax[j]));
-          q6[2] = fmax(q6[2], fabs(ei * z[j]));
-          q6[3] = fmax(q6[3], fabs(d));
-          q6[4] = fmax(q6[4], fabs(ax[j]));
-          q6[5] = fmax(q6[5], fabs(z[j]));
-        }
-        pmine = tred6(q6, s);
-      }
-      STAMP(5);
-      {  // dual side: P x + A' y on the own columns
-        double q6[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        double atf, atX;
-        colAt(y, WD, atf, atX);
-        const double pxf = pbf * xf, pxX = pbx * xX;
-        const double df_ = pxf + atf, dX_ = pxX + atX;
-        if (cl) {
-          q6[0] = fmax(fabs(dif * df_), fabs(diX * dX_));
-          q6[1] = fmax(fabs(dif * pxf), fabs(diX * pxX));
-          q6[2] = fmax(fabs(dif * atf), fabs(diX * atX));
-          q6[3] = fmax(fabs(df_), fabs(dX_));
-          q6[4] = fmax(fabs(pxf), fabs(pxX));
-          q6[5] = fmax(fabs(atf), fabs(atX));
-        }
-        // the last step of the butterfly joins the sides: primal quantity e on lane
-        // 2 e (e < 3) / 2 e + 2 (e >= 3), the dual's on the lane after it
-        mine = tstep(kXor1{}, pmine, tred6(q6, s), s & 1);
-      }
-      mine = pair_max(row_pair_max(mine));  // the wave's four rows
-      if (lane < 16) D[DS * wv + lane] = mine;
-    };
-    // info_combine: the residuals and tolerances (uniform) from every wave's partials in
-    // D (stride DS); INF: the cheap infeasibility partials (slots 16..) into inf_need
-    auto info_combine = [&](auto inf_tag, const double (&cv)[CK_COUNT], const double* const D, int DS)
-        __attribute__((always_inline)) {
-      constexpr bool INF = decltype(inf_tag)::value;
-      MPCQ_CHECK_IDS();
-      const double csc = cv[CK_C], cinv = 1.0 / csc;
-      double qv[12];
-      {
-        double v = D[s];
-#pragma unroll
-        for (int w = 1; w < NW; ++w) v = fmax_hw(v, D[DS * w + s]);
-        qv[0] = rbc<0>(v); qv[1] = rbc<2>(v); qv[2] = rbc<4>(v);
-        qv[3] = rbc<8>(v); qv[4] = rbc<10>(v); qv[5] = rbc<12>(v);
-        qv[6] = rbc<1>(v); qv[7] = rbc<3>(v); qv[8] = rbc<5>(v);
-        qv[9] = rbc<9>(v); qv[10] = rbc<11>(v); qv[11] = rbc<13>(v);
-      }
-      pri_res = qv[0];
-      dua_res = cinv * qv[6];
-      eps_pri = p.eps_abs + p.eps_rel * fmax(qv[1], qv[2]);
-      eps_dua = p.eps_abs + p.eps_rel * cinv * fmax(qv[7], qv[8]);
-      s_pri = qv[3] / (fmax(qv[4], qv[5]) + kDivTol);
-      s_dua = qv[9] / (fmax(qv[10], qv[11]) + kDivTol);
-      // uniform by construction; readfirstlane lets the compiler see it
-      pri_res = uni(pri_res); dua_res = uni(dua_res); eps_pri = uni(eps_pri);
-      eps_dua = uni(eps_dua); s_pri = uni(s_pri); s_dua = uni(s_dua);
-
-      if constexpr (INF) {
-        // the cheap conditions of infeas_cheap: slots 0 ||E dy||, 2 ||D dx||, 3 ||D^-1 P dx||, 6 u'dy+ + l'dy-
-        const int e = s == 2 || s == 3 || s == 6 ? s : 0;
-        // (every wave's partial read first, up to 32 stages in one batch: the select between the
-        // sum and the maximum is a branch, and each read sat inside it behind its own wait)
-        double tv[NW];
-#pragma unroll
-        for (int w = 0; w < NW; ++w) tv[w] = D[DS * w + 16 + e];
-        if constexpr (!BIG) hold_all(tv);
-        double v = tv[0];
-#pragma unroll
-        for (int w = 1; w < NW; ++w) v = s == 6 ? v + tv[w] : fmax_hw(v, tv[w]);
-        // kept in VGPRs (every lane holds the same values) and folded into one uniform
-        // int at the end: SGPRs here would push loop-carried scalars into VGPR lanes
-        // (v_readlane on the hot path, measured)
-        const double ndy = rbc<0>(v), ndx = rbc<2>(v), npdx = rbc<3>(v), ineq = rbc<6>(v);
-        double epi0, edi0;
-        chk_eps(epi0, edi0);
-        int need = 0;
-#pragma unroll
-        for (int fi = 0; fi < 2; ++fi) {
-          const double f = fi == 0 ? 1.0 : 10.0, epi = f * epi0, edi = f * edi0;
-          const bool pi = !(pri_res < f * eps_pri) && ndy > kDivTol && ineq < epi * ndy;
-          const bool di = !(dua_res < f * eps_dua) && ndx > kDivTol && 0.0 < csc * edi * ndx &&
-                          npdx < csc * edi * ndx;
-          need |= (pi ? 1 : 0) << (2 * fi);
-          need |= (di ? 2 : 0) << (2 * fi);
-        }
-        inf_need = __builtin_amdgcn_readfirstlane(need);
-        inf_bits = 0;
-      }
-    };
-    // INF: after infeas_cheap, which has published the states / duals with its deltas
-    auto update_info = [&](auto inf_tag, const double (&cv)[CK_COUNT]) __attribute__((always_inline)) {
-      constexpr bool INF = decltype(inf_tag)::value;
-      if constexpr (!INF) {
-        if (cl) { sh.u.it.yv[k][ph] = xX; sh.u.it.bo[k][ph] = y[0]; }
-        sync_all();
-      }
-      STAMP(4);
-      launder_p();
-      info_terms(cv, (lds_cd*)&sh.u.it.yv[0][0], &sh.u.it.bo[0][0], sh.red, 32);
-      sync_all();
-      STAMP(8);
-      info_combine(inf_tag, cv, sh.red, 32);
-      sync_all();
-    };
-    auto converged = [&](double fac) __attribute__((always_inline)) {
-      return pri_res < fac * eps_pri && dua_res < fac * eps_dua;
-    };
 
     if (status == 0) {
       STAMP(0);
-      // ------------------------------------------------------------ Ruiz scaling
+      // Ruiz scaling
       {
         double Pf = P0f, PX = P0X;
         double* Ex = gh0;  // row factors of this pass: Ex[48 k + 3 s + slot]
@@ -2401,6 +1172,7 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
       sync_all();
       STAMP(1);
 
+      // ---- 8. the loop phases: ph_rhs, ph_sweep (lag / split), ph_recover -----------------------
       // The phases of one KKT solve (K w = b, K = P + sigma I + A'RA as factored):
       // ph_rhs publishes the sweep right-hand sides of b = xc + A' w (P1-P4), ph_sweep
       // runs the state sweeps (P5-P7), ph_recover the forces and A w on the own rows
@@ -2539,6 +1311,189 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
           }
           // (the barrier that publishes bo / na / nb opens ph_sweep)
       };
+      auto ph_sweep_lag = [&]() __attribute__((always_inline)) {
+          // P5-P7: the state solve on wave 0 alone (no block barrier inside), up to 32
+          // stages (beyond: ph_sweep_split).
+          // Inward step j = 1..MID: top kk(j) = j, bottom kk(j) = N-1-j.  Half 0 (rows
+          // 0 top / 1 bottom) runs the recurrence y_kk = b_kk - G_kk y_kk(j-1) (G_kk of
+          // the top in GH[kk], H_kk of the bottom in GH[kk+1], stored negated), one
+          // full 12-term row per lane.  Half 1 (rows 2 / 3) runs the same instruction
+          // stream on S^{-1} rows two stages behind: w_kk(j-2) = S^{-1} y_kk(j-2), its y
+          // handed over by permlane32_swap.  Step MID+1 is the meeting stage: half 0
+          // solves x_m = M^{-1} (y_m + v_m - b_m) (top and bottom rows joined by
+          // permlane16_swap), half 1 the last top w.  Then the outward sweeps.
+          const int half = (t >> 5) & 1;
+#pragma nounroll
+          for (int rep_ = 0; rep_ < MPCQ_REP_SWEEP; ++rep_) {  // > 1: timing experiments only
+          double xp = 0.0;
+          // Step-ordered bases (SIG): step j's rows / right-hand sides / w / X are at
+          // base + j * stride for every lane, an immediate offset.  Half 0: G_j (top,
+          // slot j) / H_{N-1-j} (bottom, slot MID+j); half 1: S^{-1} of stage kk(j-2),
+          // top slot j-2 / bottom slot MID-1+j.  Step 1's rows are iteration-invariant:
+          // wave 0 reads them before the barrier that publishes the right-hand sides.
+          // (N > 32: S^{-1} is global, so the row pointer is a generic one)
+          using swp = lds_cd;
+          using swp2 = lds_cd2;
+          swp* const GHs = GHr;
+          // (the bottom chain's slots are past N/2: +2, SLOT)
+          swp* const Mb = half == 0 ? GHs + (GS * (cr == 0 ? 0 : MID) + (cr == 0 ? 0 : kSlotPad<N>) + RS * rr_)
+                                    : (swp*)&sh.Sm[0][0] + (GS * (cr == 0 ? -2 : MID - 1) + (cr == 0 ? 0 : kSlotPad<N>) + RS * rr_);
+          double g[12];
+          auto row12 = [&](swp* q) __attribute__((always_inline)) {  // 16-B aligned row: 6 ds_read_b128
+#pragma unroll
+            for (int i = 0; i < 6; ++i) {
+              const dbl2 v = ((swp2*)q)[i];
+              g[2 * i] = v.x;
+              g[2 * i + 1] = v.y;
+            }
+          };
+          // the rows of step j (j a constant after unrolling): every lane reads a slot the
+          // factorisation wrote -- the steps a chain does not take (half 1's first step,
+          // the bottom chain's steps past its BOT stages at even N) re-read a row of the
+          // chain's own, and their products are discarded by the hand-off select / the sink
+          auto rowp = [&](int j) __attribute__((always_inline)) -> swp* {
+            if (j >= 2 && j <= BOT) return Mb + GS * j;
+            const int jj = half == 0 ? (cr == 0 ? j : (j < BOT ? j : BOT))
+                                     : (cr == 0 ? (j > 2 ? j : 2) : (j < BOT + 1 ? j : BOT + 1));
+            return Mb + GS * jj;
+          };
+          STAMP(15);  // (diagnostic builds: as in ph_sweep_split)
+          if (t < 64) row12(rowp(1));
+          sync_all();
+          STAMP(3);
+          // outward step j reads G_{MID-j+1}' (top, slot MID+1-j) / H_{MID+j-1}'
+          // (bottom, slot N-j) columns: Ob + (MID - j) GS (LDS offsets are unsigned,
+          // so the bases sit at the lowest slot a chain reaches)
+          lds_cd* const Ob = GHr + (GS * (cr == 0 ? 1 : N - MID) + (cr == 0 ? 0 : kSlotPad<N>) + rr_);
+          if (t < 64) {
+            // the sweeps are every wave's critical path (the other waves of the
+            // instance wait at the barrier): issue them ahead of a co-resident
+            // instance's stage-parallel phases
+            __builtin_amdgcn_s_setprio(3);
+            // right-hand side of step j: top stage j (slot j), bottom stage N-1-j (slot
+            // MID+1+j, except the meeting stage MID at the bottom's last step BOT, slot
+            // MID, which the bottom re-reads in the steps it does not take); na at +12N
+            lds_cd* const Bb = (lds_cd*)&sh.u.it.bo[0][0] + (12 * (cr == 0 ? 0 : MID + 1) + rr_);
+            lds_cd* const Bm = (lds_cd*)&sh.u.it.bo[0][0] + (12 * MID + rr_);
+            auto rhs = [&](int j) __attribute__((always_inline)) -> lds_cd* {  // j: a constant
+              return (j >= BOT && cr != 0) ? Bm : Bb + 12 * j;
+            };
+            // w of stage kk(j-2) (half 1): top slot j-2, bottom slot MID-1+j; the other
+            // lanes store into the sink with the same stride
+            lds_d* const sink = (lds_d*)&sh.red[0] + (t & 31);
+            lds_d* const Yb = (half == 1 && s < 12) ? (lds_d*)&sh.u.it.yv[0][0] + (12 * (cr == 0 ? -2 : MID - 1) + rr_)
+                                                    : sink;
+            // step MID+1's store: every lane has one target, so it is one store and no branch
+            lds_d* const Ym = ((N & 1) || cr == 0) ? Yb + 12 * (MID + 1) : sink;
+            lds_d* const Pm = (half == 0 && cr == 0 && s < 12)
+                                  ? (lds_d*)&sh.u.it.xs[0][0] + (12 * SIGX<N>(MID + 1) + rr_) : Ym;
+            // right-hand sides run two steps ahead: step j sums the one of step j+1
+            // (loaded during step j-1) and loads the one of step j+2; half 1 (the w
+            // products) starts its chain from 0.  The first two (y_kk(0) and step 1's)
+            // are loaded together and waited for once: they were published by the
+            // barrier just passed, so this round trip is on the critical path.
+            const double m0 = half == 0 ? 1.0 : 0.0;
+            double s0 = rhs(0)[0], s1 = rhs(0)[12 * N];
+            double c0 = rhs(1)[0], c1 = rhs(1)[12 * N];
+            double src = half == 0 ? s0 + s1 : 0.0;  // y_kk(0) (half 0)
+            double bcn = add_mul_here(c0, c1, m0);
+            double b0 = rhs(2)[0], b1 = rhs(2)[12 * N];
+#pragma unroll
+            for (int j = 1; j <= MID + 1; ++j) {
+              asm volatile("" : : : "memory");
+              double gc[12];
+#pragma unroll
+              for (int i = 0; i < 12; ++i) gc[i] = g[i];
+              const double bc = j <= MID ? bcn : 0.0;
+              if (j < MID) {  // prefetch the next step's rows
+                row12(rowp(j + 1));
+              } else if (j == MID) {  // the meeting step: M^{-1} rows (half 0), the S walk (half 1)
+                row12(half == 0 ? GHs + RS * rr_ : rowp(MID + 1));
+                lds_cd* qb = (lds_cd*)&sh.u.it.bo[0][0] + (12 * MID + rr_);
+                b0 = qb[0]; b1 = qb[12 * N];
+              } else {  // the last step: the first outward step's columns
+#pragma unroll
+                for (int i = 0; i < 12; ++i) g[i] = Ob[RS * i + GS * (MID - 1)];
+              }
+              asm volatile("" : : : "memory");  // the prefetch is issued here, not sunk to its use
+              double s_in = src;
+              if (j == MID + 1) s_in = half == 0 ? row_pair_sum(src) - (b0 + b1) : src;
+              const double acc = bdot12(gc, s_in, bc);
+              // the next right-hand side is summed after the chain: its loads were
+              // issued at the end of the previous step, and summing them ahead of the
+              // chain would put their LDS latency on the critical path
+              // (the sum and its mask as a volatile asm, which keeps its place behind the chain's
+              // block: an empty-asm launder of b0 / b1 did too, but it redefines them, and the
+              // compiler then copied the first pair and put a wait state in front of every sum)
+              if (j < MID) bcn = add_mul_here(b0, b1, m0);
+              if (j + 2 <= MID) {
+                b0 = rhs(j + 2)[0]; b1 = rhs(j + 2)[12 * N];
+              }
+              if (j >= 2 && j <= MID) {  // half 1: w of stage kk(j-2)
+                Yb[12 * j] = acc;
+              } else if (j == MID + 1) {
+                // the last step's one store: x_m from row 0's state lanes, half 1's last w
+                // (even N: the bottom's kk(MID-1) is the meeting stage, no w), else the sink
+                *Pm = acc;
+              }
+              if (j <= MID) {
+                // half 0 continues with y_kk(j) (the bottom chain stops after step BOT), half 1
+                // receives y_kk(j-1) from half 0
+                const bool adv = j <= BOT || cr == 0;
+                src = keep_lo_take_lo(adv ? acc : src, src);
+                // (the hand-off stays ahead of the next step's row reads: with the reads
+                // between it and the chain, the chain's opening s_nop is dropped, nop_elide.py)
+                asm volatile("" : "+v"(src));
+              } else {
+                xp = acc;
+              }
+            }
+            STAMP(6);
+          }
+          if (t < 64) {
+            // Outward step j: top kk = MID-j: X_kk = w_kk - G_{kk+1}' X_{kk+1}; bottom
+            // kk = MID+j: X_kk = w_kk - H_{kk-1}' X_{kk-1} (columns from Ob - j GS).  Lane
+            // rr reads column rr (a full 12-term product per lane; half 1 repeats half 0).
+            // w of stage kk: top slot MID-j, bottom slot N-j (Wb - 12 j); X_kk = xs[kk+1]:
+            // top slot MID+1-j, bottom slot N-j (SIGX; Xb - 12 j).  The bottom row's last
+            // step (kk = N) is idle: its store goes to the sink.
+            // (bases at step MID's slot: step j at base + 12 (MID - j))
+            lds_cd* const Wb = (lds_cd*)&sh.u.it.yv[0][0] + (12 * (cr == 0 ? 0 : N - MID) + rr_);
+            lds_d* const sinkO = (lds_d*)&sh.red[0] + (t & 31);
+            lds_d* const Xb = (half == 0 && s < 12) ? (lds_d*)&sh.u.it.xs[0][0] + (12 * (cr == 0 ? 1 : N - MID) + rr_)
+                                                    : sinkO;
+            wave_sync();  // the w written by half 1
+            double bq = Wb[12 * (MID - 1)];
+#pragma unroll
+            for (int j = 1; j <= MID; ++j) {
+              asm volatile("" : : : "memory");
+              double gc[12];
+#pragma unroll
+              for (int i = 0; i < 12; ++i) gc[i] = g[i];
+              const double bc = bq;
+              if (j < MID) {
+#pragma unroll
+                for (int i = 0; i < 12; ++i) g[i] = Ob[RS * i + GS * (MID - j - 1)];
+                // (even N: the bottom chain has no step MID; it re-reads its last w)
+                if (j + 1 <= BOT) bq = Wb[12 * (MID - j - 1)];
+                else bq = Wb[12 * (MID - (cr == 0 ? j + 1 : BOT))];
+              }
+              asm volatile("" : : : "memory");
+              const double acc = bdot12(gc, xp, bc);  // x = w - G' x_next with -G stored
+              if (j < MID) {
+                xp = acc;
+                Xb[12 * (MID - j)] = acc;
+              } else if constexpr (N & 1) {
+                *Xb = acc;
+              } else {  // even N: the bottom chain has no step MID
+                *(cr == 0 ? Xb : sinkO) = acc;
+              }
+            }
+            __builtin_amdgcn_s_setprio(0);
+          }
+          wave_sync();
+          }  // MPCQ_REP_SWEEP
+      };
       auto ph_sweep_split = [&]() __attribute__((always_inline)) {
           // P5-P7: the state solve.  The two chains run on wave 0, each on a pair of rows
           // that splits every 12-term row product in two: rows 0 / 1 (top / bottom chain)
@@ -2560,9 +1515,6 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
           asm volatile("" : "+v"(tl_));
           const int hi = (tl_ >> 5) & 1;  // rows 2 / 3: the second six terms
           const int h6 = 6 * hi;
-#ifndef MPCQ_REP_SWEEP
-#define MPCQ_REP_SWEEP 1
-#endif
 #pragma nounroll
           for (int rep_ = 0; rep_ < MPCQ_REP_SWEEP; ++rep_) {  // > 1: timing experiments only
           double xp = 0.0;
@@ -2837,13 +1789,299 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
       };
       const double kNoW[3] = {0.0, 0.0, 0.0};
 
-      // ------------------------------------------------------------ ADMM
+      // ---- 9. residuals (OSQP update_info, uniform results), termination, infeasibility ---------
+      double pri_res = 0.0, dua_res = 0.0, eps_pri = 0.0, eps_dua = 0.0, s_pri = 0.0, s_dua = 0.0;
+      // OSQP 0.6's infeasibility tests (auxil.c is_primal_infeasible / is_dual_infeasible)
+      // on the last iteration's delta_y (dy, own rows) and delta_x (dxf, dxX, own
+      // columns), evaluated the way osqp evaluates them: the cheap conditions first
+      // (||E dy||, u'dy+ + l'dy-, ||D dx||, ||D^-1 P dx||), the products A' dy / A dx
+      // only where those hold.  infeas_cheap runs right after the update, while the
+      // deltas are live: it publishes them (na / nb, free between the sweeps) with
+      // update_info's states / duals under one barrier and leaves the per-wave partials
+      // of the cheap quantities in red[32 wv + 16 ..]; update_info(INF) combines them
+      // into uniform flags (each test only where its residual test fails, as osqp's
+      // check_termination); infeas_products, only when a flag holds, adds the products
+      // (two more barriers).  On MPC.py's QPs the dual side never reaches its product
+      // and the primal side does at ~40 % of the checks (oracle counts, C2 batch), so
+      // the product pass is skipped at most checks -- with identical outcomes.
+      // outcome bits (one uniform int: the loop carries it): 1 primal, 2 dual infeasible
+      // at the check's tolerances, 4 / 8 at the approximate (x10) ones
+      int inf_bits = 0;
+      int inf_need = 0;  // cheap-condition bits (same layout) awaiting the products
+      // The bounds as the check sees them: lo_of / hi_of from the row scaling E and the
+      // dynamics bound in the check's constant block (ck, read with the others in one
+      // batch).  Formed from the loop's own E / bnd, the products (-inf E, -fz_max E) were
+      // hoisted out of the ADMM loop and spilled, and each came back in the check as a
+      // scratch reload waited for on its own.  Same expressions, same values.
+      auto chk_bounds = [&](const double (&cv)[CK_COUNT], double (&lo)[3], double (&hi)[3])
+          __attribute__((always_inline)) {
+        if constexpr (FUSED) {
+          const double e0 = cv[CK_E0], e1 = cv[CK_E1], e2 = cv[CK_E2], bd = cv[CK_BND];
+          double fz = fz_max();
+          asm volatile("" : "+v"(fz));
+          lo[0] = cl ? bd : -kInf * e0;
+          lo[1] = cl ? 0.0 : -fz * e1;
+          lo[2] = cl ? -kInf * e2 : -kInf;
+          hi[0] = cl ? bd : 0.0;
+          hi[1] = 0.0;
+          hi[2] = cl ? 0.0 : kInf;
+        } else {
+#pragma unroll
+          for (int j = 0; j < 3; ++j) { lo[j] = lo_of(j); hi[j] = hi_of(j); }
+        }
+      };
+      // the infeasibility tolerances, laundered for the same reason (10 eps, hoisted, was
+      // spilled)
+      auto chk_eps = [&](double& epi0, double& edi0) __attribute__((always_inline)) {
+        epi0 = p.eps_prim_inf;
+        edi0 = p.eps_dual_inf;
+        asm volatile("" : "+v"(epi0), "+v"(edi0));
+      };
+      double dyp[3];     // delta_y projected onto the polar of the recession cone of [l, u]
+      // The cheap part of OSQP's infeasibility tests on the last iteration's deltas, own
+      // data only: dyp, and this wave's maxima ||E dy|| / ||D dx|| / ||D^-1 P dx|| and sum
+      // u'dy+ + l'dy- into P[PS wv + 16 + {0, 2, 3, 6}] (red for the blocking check, dcp
+      // for the deferred one).  cv: the constant block, read ahead of the check (ck_all).
+      auto cheap_partials = [&](const double (&dy)[3], double dxf, double dxX, const double (&cv)[CK_COUNT],
+                                double* const P, int PS) __attribute__((always_inline)) {
+        MPCQ_CHECK_IDS();
+        double lob[3], hib[3];
+        chk_bounds(cv, lob, hib);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+          const bool uinf = hib[j] > kInf * kMinScaling, linf = lob[j] < -kInf * kMinScaling;
+          dyp[j] = uinf ? (linf ? 0.0 : fmin(dy[j], 0.0)) : (linf ? fmax(dy[j], 0.0) : dy[j]);
+        }
+        double ndy = 0.0, ineq = 0.0;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+          const double lj = lob[j], hj = hib[j];
+          ndy = fmax(ndy, fabs(cv[CK_E0 + j] * dyp[j]));
+          ineq += hj * fmax(dyp[j], 0.0) + lj * fmin(dyp[j], 0.0);
+        }
+        if (phantom) ineq = 0.0;  // a sum: stage N-1 counts once
+        double q3[2] = {0.0, 0.0};
+        {
+          const double df = cv[CK_DF], dx = cv[CK_DX], dif = 1.0 / df, diX = 1.0 / dx;
+          const double pbf = cv[CK_PBF], pbx = cv[CK_PBX];
+          if (cl) {
+            q3[0] = fmax(fabs(df * dxf), fabs(dx * dxX));                // ||D dx||
+            q3[1] = fmax(fabs(pbf * dxf * dif), fabs(pbx * dxX * diX));  // ||D^-1 P dx||
+          }
+        }
+        // maxima over the wave (lanes 0 / 4 / 8 keep ||E dy|| / ||D dx|| / ||D^-1 P dx||,
+        // published in slots 0 / 2 / 3), the sum by xor butterflies
+        const double mine = pair_max(row_pair_max(tred3(ndy, q3[0], q3[1], s)));
+        ineq += dppd<0xB1>(ineq);
+        ineq += dppd<0x4E>(ineq);
+        ineq += dppd<0x124>(ineq);
+        ineq += dppd<0x128>(ineq);
+        ineq = row_pair_sum(ineq);
+        {
+          const long long bb = __double_as_longlong(ineq);
+          const auto lo_ = __builtin_amdgcn_permlane32_swap((unsigned)bb, (unsigned)bb, false, false);
+          const auto hi_ = __builtin_amdgcn_permlane32_swap((unsigned)(bb >> 32), (unsigned)(bb >> 32), false, false);
+          ineq = __longlong_as_double(((long long)hi_[0] << 32) | lo_[0]) +
+                 __longlong_as_double(((long long)hi_[1] << 32) | lo_[1]);
+        }
+        if (lane == 0 || lane == 4 || lane == 8) P[PS * wv + 16 + (lane == 0 ? 0 : 2 + (lane >> 3))] = mine;
+        if (lane == 6) P[PS * wv + 16 + 6] = ineq;
+      };
+      auto infeas_cheap = [&](const double (&dy)[3], double dxf, double dxX, const double (&cv)[CK_COUNT])
+          __attribute__((always_inline)) {
+        cheap_partials(dy, dxf, dxX, cv, sh.red, 32);
+        // published together with update_info's states / duals, one barrier for both
+        if (cl) {
+          sh.u.it.na[k][ph] = dxX;
+          sh.u.it.nb[k][ph] = dyp[0];
+          sh.u.it.yv[k][ph] = xX;
+          sh.u.it.bo[k][ph] = y[0];
+        }
+        sync_all();  // (update_info(INF) relies on this barrier for its own publication)
+      };
+      // the products, where a cheap condition holds (inf_need != 0, uniform): A' dy for
+      // the primal test, A dx for the dual one, on the deltas infeas_cheap published
+      auto infeas_products = [&](double dxf, double dxX, const double (&cv)[CK_COUNT])
+          __attribute__((always_inline)) {
+        MPCQ_CHECK_IDS();
+        launder_p();
+        double vu = -INFINITY, vl = -INFINITY;
+        {
+          double adx[3], lob[3], hib[3];
+          rowA(dxf, dxX, (lds_cd*)&sh.u.it.na[0][0], adx);
+          chk_bounds(cv, lob, hib);
+#pragma unroll
+          for (int j = 0; j < 3; ++j) {
+            const double lj = lob[j], hj = hib[j], v = adx[j] / cv[CK_E0 + j];
+            if (hj < kInf * kMinScaling) vu = fmax(vu, v);
+            if (lj > -kInf * kMinScaling) vl = fmax(vl, -v);
+          }
+        }
+        double naty = 0.0;
+        {
+          double dtf, dtX;
+          colAt(dyp, &sh.u.it.nb[0][0], dtf, dtX);
+          const double dif = 1.0 / cv[CK_DF], diX = 1.0 / cv[CK_DX];
+          if (cl) naty = fmax(fabs(dtf * dif), fabs(dtX * diX));  // ||D^-1 A' dy||
+        }
+        // lanes 0 / 4 / 8 keep ||D^-1 A' dy|| / vu / vl, published in slots 1 / 4 / 5
+        const double mine = pair_max(row_pair_max(tred3(naty, vu, vl, s)));
+        if (lane == 0 || lane == 4 || lane == 8) sh.red[32 * wv + 16 + (lane == 0 ? 1 : 4 + (lane >> 3))] = mine;
+        sync_all();
+        const int e = s < 6 ? s : 0;  // slots 16..21 are all maxima (0 / 2 / 3 from infeas_cheap)
+        double v = sh.red[16 + e];
+#pragma unroll
+        for (int w = 1; w < NW; ++w) v = fmax_hw(v, sh.red[32 * w + 16 + e]);
+        const double ndy = rbc<0>(v), ndx = rbc<2>(v);  // (the cheap maxima, kept in slots 0 / 2)
+        const double naty_ = rbc<1>(v), vu_ = rbc<4>(v), vl_ = rbc<5>(v);
+        double epi0, edi0;
+        chk_eps(epi0, edi0);
+        int bits = 0;
+#pragma unroll
+        for (int fi = 0; fi < 2; ++fi) {
+          const double f = fi == 0 ? 1.0 : 10.0, epi = f * epi0, edi = f * edi0;
+          const bool pi = ((inf_need >> (2 * fi)) & 1) && naty_ < epi * ndy;
+          const bool di = ((inf_need >> (2 * fi)) & 2) && !(vu_ > edi * ndx) && !(vl_ > edi * ndx);
+          bits |= (pi ? 1 : 0) << (2 * fi);
+          bits |= (di ? 2 : 0) << (2 * fi);
+        }
+        inf_bits = __builtin_amdgcn_readfirstlane(bits);
+        sync_all();
+      };
+      // The states and dynamics-row duals are published in yv / bo, which the sweeps
+      // no longer need (xs still feeds the force recovery of slower waves); lane s
+      // of each row then owns residual quantity s, reduced over the wave's rows by
+      // permlane swaps and over the waves through red[].  INF: also combine the
+      // cheap partials of infeas_cheap into inf_need.
+      // info_terms: this wave's 16 residual maxima into D[DS wv + 0..15], from the own
+      // rows / columns and the published states XP (X_{k'} of stage k' at 12 (k' - 1))
+      // and duals WD (y of stage k' at 12 k')
+      auto info_terms = [&](const double (&cv)[CK_COUNT], lds_cd* const XP, const double* WD, double* const D,
+                            int DS) __attribute__((always_inline)) {
+        MPCQ_CHECK_IDS();
+        const double ei3[3] = {1.0 / cv[CK_E0], 1.0 / cv[CK_E1], 1.0 / cv[CK_E2]};
+        const double dif = 1.0 / cv[CK_DF], diX = 1.0 / cv[CK_DX], pbf = cv[CK_PBF], pbx = cv[CK_PBX];
+        double mine, pmine;  // this lane's row maxima (tred6: primal quantity 3 b3 + (b2 ? 2 : b1))
+        {  // primal side: A x - z on the own rows
+          double ax[3], q6[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+          rowA(xf, xX, XP, ax);
+#pragma unroll
+          for (int j = 0; j < 3; ++j) {
+            const double ei = ei3[j], d = ax[j] - z[j];
+            q6[0] = fmax(q6[0], fabs(ei * d));
+            q6[1] = fmax(q6[1], fabs(ei * ax[j]));
+            q6[2] = fmax(q6[2], fabs(ei * z[j]));
+            q6[3] = fmax(q6[3], fabs(d));
+            q6[4] = fmax(q6[4], fabs(ax[j]));
+            q6[5] = fmax(q6[5], fabs(z[j]));
+          }
+          pmine = tred6(q6, s);
+        }
+        STAMP(5);
+        {  // dual side: P x + A' y on the own columns
+          double q6[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+          double atf, atX;
+          colAt(y, WD, atf, atX);
+          const double pxf = pbf * xf, pxX = pbx * xX;
+          const double df_ = pxf + atf, dX_ = pxX + atX;
+          if (cl) {
+            q6[0] = fmax(fabs(dif * df_), fabs(diX * dX_));
+            q6[1] = fmax(fabs(dif * pxf), fabs(diX * pxX));
+            q6[2] = fmax(fabs(dif * atf), fabs(diX * atX));
+            q6[3] = fmax(fabs(df_), fabs(dX_));
+            q6[4] = fmax(fabs(pxf), fabs(pxX));
+            q6[5] = fmax(fabs(atf), fabs(atX));
+          }
+          // the last step of the butterfly joins the sides: primal quantity e on lane
+          // 2 e (e < 3) / 2 e + 2 (e >= 3), the dual's on the lane after it
+          mine = tstep(kXor1{}, pmine, tred6(q6, s), s & 1);
+        }
+        mine = pair_max(row_pair_max(mine));  // the wave's four rows
+        if (lane < 16) D[DS * wv + lane] = mine;
+      };
+      // info_combine: the residuals and tolerances (uniform) from every wave's partials in
+      // D (stride DS); INF: the cheap infeasibility partials (slots 16..) into inf_need
+      auto info_combine = [&](auto inf_tag, const double (&cv)[CK_COUNT], const double* const D, int DS)
+          __attribute__((always_inline)) {
+        constexpr bool INF = decltype(inf_tag)::value;
+        MPCQ_CHECK_IDS();
+        const double csc = cv[CK_C], cinv = 1.0 / csc;
+        double qv[12];
+        {
+          double v = D[s];
+#pragma unroll
+          for (int w = 1; w < NW; ++w) v = fmax_hw(v, D[DS * w + s]);
+          qv[0] = rbc<0>(v); qv[1] = rbc<2>(v); qv[2] = rbc<4>(v);
+          qv[3] = rbc<8>(v); qv[4] = rbc<10>(v); qv[5] = rbc<12>(v);
+          qv[6] = rbc<1>(v); qv[7] = rbc<3>(v); qv[8] = rbc<5>(v);
+          qv[9] = rbc<9>(v); qv[10] = rbc<11>(v); qv[11] = rbc<13>(v);
+        }
+        pri_res = qv[0];
+        dua_res = cinv * qv[6];
+        eps_pri = p.eps_abs + p.eps_rel * fmax(qv[1], qv[2]);
+        eps_dua = p.eps_abs + p.eps_rel * cinv * fmax(qv[7], qv[8]);
+        s_pri = qv[3] / (fmax(qv[4], qv[5]) + kDivTol);
+        s_dua = qv[9] / (fmax(qv[10], qv[11]) + kDivTol);
+        // uniform by construction; readfirstlane lets the compiler see it
+        pri_res = uni(pri_res); dua_res = uni(dua_res); eps_pri = uni(eps_pri);
+        eps_dua = uni(eps_dua); s_pri = uni(s_pri); s_dua = uni(s_dua);
+
+        if constexpr (INF) {
+          // the cheap conditions of infeas_cheap: slots 0 ||E dy||, 2 ||D dx||, 3 ||D^-1 P dx||, 6 u'dy+ + l'dy-
+          const int e = s == 2 || s == 3 || s == 6 ? s : 0;
+          // (every wave's partial read first, up to 32 stages in one batch: the select between the
+          // sum and the maximum is a branch, and each read sat inside it behind its own wait)
+          double tv[NW];
+#pragma unroll
+          for (int w = 0; w < NW; ++w) tv[w] = D[DS * w + 16 + e];
+          if constexpr (!BIG) hold_all(tv);
+          double v = tv[0];
+#pragma unroll
+          for (int w = 1; w < NW; ++w) v = s == 6 ? v + tv[w] : fmax_hw(v, tv[w]);
+          // kept in VGPRs (every lane holds the same values) and folded into one uniform
+          // int at the end: SGPRs here would push loop-carried scalars into VGPR lanes
+          // (v_readlane on the hot path, measured)
+          const double ndy = rbc<0>(v), ndx = rbc<2>(v), npdx = rbc<3>(v), ineq = rbc<6>(v);
+          double epi0, edi0;
+          chk_eps(epi0, edi0);
+          int need = 0;
+#pragma unroll
+          for (int fi = 0; fi < 2; ++fi) {
+            const double f = fi == 0 ? 1.0 : 10.0, epi = f * epi0, edi = f * edi0;
+            const bool pi = !(pri_res < f * eps_pri) && ndy > kDivTol && ineq < epi * ndy;
+            const bool di = !(dua_res < f * eps_dua) && ndx > kDivTol && 0.0 < csc * edi * ndx &&
+                            npdx < csc * edi * ndx;
+            need |= (pi ? 1 : 0) << (2 * fi);
+            need |= (di ? 2 : 0) << (2 * fi);
+          }
+          inf_need = __builtin_amdgcn_readfirstlane(need);
+          inf_bits = 0;
+        }
+      };
+      // INF: after infeas_cheap, which has published the states / duals with its deltas
+      auto update_info = [&](auto inf_tag, const double (&cv)[CK_COUNT]) __attribute__((always_inline)) {
+        constexpr bool INF = decltype(inf_tag)::value;
+        if constexpr (!INF) {
+          if (cl) { sh.u.it.yv[k][ph] = xX; sh.u.it.bo[k][ph] = y[0]; }
+          sync_all();
+        }
+        STAMP(4);
+        launder_p();
+        info_terms(cv, (lds_cd*)&sh.u.it.yv[0][0], &sh.u.it.bo[0][0], sh.red, 32);
+        sync_all();
+        STAMP(8);
+        info_combine(inf_tag, cv, sh.red, 32);
+        sync_all();
+      };
+      auto converged = [&](double fac) __attribute__((always_inline)) {
+        return pri_res < fac * eps_pri && dua_res < fac * eps_dua;
+      };
+
+      // ---- 10. the ADMM loop --------------------------------------------------------------------
       // The factorisation sits outside the hot loop: the outer loop factors,
       // the inner loop iterates until convergence, max_iter or a rho update.
       bool last_checked = false;
       int iter = 1;
-      // the loop's exit status: LDS (kXstLds; read after the loop's closing barrier) or status
-#define MPCQ_SET_XST(v_) do { if constexpr (kXstLds<N>) { if (t == 0) sh.flag[4] = (v_); } else if constexpr (!kXstRe<N>) { status = (v_); } } while (0)
       if constexpr (kXstLds<N>) MPCQ_SET_XST(0);
       int to_check = p.check_termination, to_adapt = p.adaptive_rho_interval;
       // a resumed slice continues the saved loop counters; slice_iters > 0 suspends at the
@@ -2859,9 +2097,6 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
       // the bounds are re-derived where used (lo_of / hi_of: a select on the lane's
       // class and its row scaling in the fused path) rather than held in 6 registers
       for (;;) {
-#ifndef MPCQ_REP_FACTOR
-#define MPCQ_REP_FACTOR 1
-#endif
         bool fac_ok = true;
 #ifdef MPCQ_FACTIME
         const uint64_t ft0_ = __builtin_amdgcn_s_memtime();
@@ -3038,7 +2273,6 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
           else if (inf_bits & 2) status = MPCQ_STATUS_DUAL_INFEASIBLE;
         }
       }
-#undef MPCQ_SET_XST
       it_done = iter > p.max_iter ? p.max_iter : iter;
       if (status == 0) {
         if (!last_checked) {  // the information of the last (unchecked) iteration
@@ -3054,7 +2288,7 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
       }
 
       admm_st = status;
-      // ------------------------------------------------------------ polish
+      // ---- 11. polish ---------------------------------------------------------------------------
       // OSQP 0.6 polish (polish.c): guess the active set from (z, y), solve the
       // equality-constrained QP  min 1/2 x'Px  s.t. A_act x = b_act,  project
       // (A x, y) onto the normal cone and keep the point if it lowers the
@@ -3230,7 +2464,7 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
         }
       }
     }
-    // ------------------------------------------------------------ outputs
+    // ---- 12. outputs ----------------------------------------------------------------------------
     // osqp store_solution: no solution (x = y = NaN) for the infeasibility statuses
     const bool nan_out = status == MPCQ_STATUS_NONFINITE || status == MPCQ_STATUS_FACTOR_FAILED ||
                          status == MPCQ_STATUS_BAD_GAIT || status == MPCQ_STATUS_BAD_BOUNDS ||
@@ -3274,6 +2508,10 @@ void engine_kernel(mpcq_params p, LaunchArgs a) {
   }
 }
 
+#undef MPCQ_LANE_OFFS
+#undef MPCQ_CHECK_IDS
+#undef MPCQ_SET_XST
+
 template <int N>
 hipError_t launch_t(bool fused, bool solve, const mpcq_params& p, const LaunchArgs& a,
                     hipStream_t s) {
@@ -3305,12 +2543,10 @@ hipError_t launch_t(bool fused, bool solve, const mpcq_params& p, const LaunchAr
 #ifndef MPCQ_ENGINE_N
 #error "compile mpcq_engine.hip with -DMPCQ_ENGINE_N=<horizon> (see the Makefile)"
 #endif
-static_assert(MPCQ_ENGINE_N >= 4 && kRows<MPCQ_ENGINE_N> <= 64, "horizons 4..64 (1024 threads at most)");
-static_assert(sizeof(Smem<MPCQ_ENGINE_N>) <= 160 * 1024, "Smem<N> exceeds the CU's LDS");
+// (here, where both headers are seen; the unit's other layout checks end mpcq_engine_layout.h, and
+// tests/host/engine_layout_check.cpp runs them all for every horizon at once)
 static_assert(!kBig<MPCQ_ENGINE_N> || Work<MPCQ_ENGINE_N>::SIZE == work_doubles(MPCQ_ENGINE_N),
               "work_doubles(N) (mpcq_internal.h) and Work<N> disagree");
-static_assert(kRows<MPCQ_ENGINE_N> > 16 || sizeof(Smem<MPCQ_ENGINE_N>) <= 80 * 1024,
-              "Smem<N> must fit twice in a CU for N <= 16");
 
 #define MPCQ_CAT_(a, b) a##b
 #define MPCQ_CAT(a, b) MPCQ_CAT_(a, b)

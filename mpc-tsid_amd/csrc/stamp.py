@@ -7,7 +7,9 @@ First 16 hex digits of sha256 over every input that changes the shipped code: th
 sources (csrc/*.hip, name order), the assembly pass (asmpass/hipcc_elide.py, nop_elide.py,
 dpp_hazards.py), the Makefile, the headers (mpcq_internal.h: LaunchArgs and the workspace
 layout; mpcq_virtual.h: the tick's tail; mpcq_philox.h: the scenario's and the channel's
-generator; mpcq_model.h: the plant's, the estimator's and the disturbance stage's model step; mpcq_stage16.h: the sixteen-lane stages' shape; mpcq_host.h: what the two API units share; mpcq_session_layout.h: the session's parts and the blob's header; include/mpcq.h), the C++ units
+generator; mpcq_model.h: the plant's, the estimator's and the disturbance stage's model step; mpcq_stage16.h: the sixteen-lane stages' shape; mpcq_host.h: what the two API units share; mpcq_session_layout.h: the session's parts and the blob's header;
+mpcq_engine_layout.h, mpcq_engine_lanes.h, mpcq_engine_gj.h, mpcq_engine_form.h: the engine's layout, lane
+primitives, factorisation steps and formulation pieces; include/mpcq.h), the C++ units
 (csrc/*.cpp, name order), then the effective compiler flags as one string.  Without an argument the flags are the Makefile's defaults,
 so mpcq.source_sha() (mpcq/_lib.py) and a default `make` agree; a build with overridden
 flags carries another stamp, and bench.py then drops PMC figures profiled on the default
@@ -24,7 +26,8 @@ ELIDE_PASS = ("hipcc_elide.py", "nop_elide.py", "dpp_hazards.py")
 def inputs(csrc: str = HERE):
     names = sorted(n for n in os.listdir(csrc) if n.endswith(".hip"))
     names += [os.path.join("asmpass", n) for n in ELIDE_PASS]
-    names += ["Makefile", "mpcq_internal.h", "mpcq_virtual.h", "mpcq_philox.h", "mpcq_model.h", "mpcq_stage16.h", "mpcq_host.h", "mpcq_session_layout.h", os.path.join("..", "..", "include", "mpcq.h")]
+    names += ["Makefile", "mpcq_internal.h", "mpcq_virtual.h", "mpcq_philox.h", "mpcq_model.h", "mpcq_stage16.h", "mpcq_host.h", "mpcq_session_layout.h",
+              "mpcq_engine_layout.h", "mpcq_engine_lanes.h", "mpcq_engine_gj.h", "mpcq_engine_form.h", os.path.join("..", "..", "include", "mpcq.h")]
     names += sorted(n for n in os.listdir(csrc) if n.endswith(".cpp"))
     return [os.path.join(csrc, n) for n in names]
 

@@ -1,4 +1,4 @@
-"""CPU: the factorisation's Gauss-Jordan inverse with lazy pivot rows (mpcq_engine.hip
+"""CPU: the factorisation's Gauss-Jordan inverse with lazy pivot rows (mpcq_engine_gj.h
 gj_step / gj12, kGjLazy, round 5) restated in numpy next to the normalised form it replaced.
 
 The engine keeps one row of the 12 x 12 SPD block per lane; a pivot step updates every other

@@ -9,6 +9,10 @@ group_segment_fixed_size / LDSByteSize lines.  lds_bytes lists every distinct si
 unit's kernels.  Two checkouts whose columns agree have the same device code:
 
   tools/engine_asm_digest.py 16 32 48 [-DMPCQ_STAMPS] [--src other/csrc/mpcq_engine.hip]
+
+"Another checkout's engine source" means that checkout's csrc/: the engine's quoted includes
+(mpcq_internal.h, mpcq_engine_layout.h, _lanes.h, _gj.h, _form.h) resolve next to the source
+given, so --src takes the other checkout's headers with it; the flags stay this checkout's.
 """
 import argparse
 import hashlib
@@ -49,7 +53,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("horizons", nargs="*", type=int, default=list(range(4, 65)))
     ap.add_argument("-D", dest="defs", action="append", default=[], help="extra -D switch (MPCQ_STAMPS ...)")
-    ap.add_argument("--src", default=os.path.join(CSRC, "mpcq_engine.hip"), help="another checkout's engine source")
+    ap.add_argument("--src", default=os.path.join(CSRC, "mpcq_engine.hip"), help="another checkout's engine source (its csrc/ supplies the headers)")
     ap.add_argument("--hipcc", default=os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"))
     ap.add_argument("-j", type=int, default=min(16, os.cpu_count() or 1))
     a = ap.parse_args()
